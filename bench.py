@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
-"""bench.py -- sequence-pairs/s identity-scored on MI355X (BASELINE.json metric), with the pair kernel's HBM roofline
-and the CPU path timed beside it.
+"""bench.py -- sequence-pairs/s identity-scored on MI355X (BASELINE.json metric), with the pair kernel's HBM roofline;
+--full adds the CPU path timed beside it and the other measurements (secondary legs, the product kernel on one stream).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--nseq 100000] [--k 9] [--dtype 32] [--queries 64] [--scaling strong|weak]
+                  [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (ms_per_step = wall time of one timed step);
+--dump-outputs DIR also writes what the last timed step returned (dump_outputs) -- the inputs depend on the arguments only.
 
 Workload (BASELINE.json configs[1], "cfg2"): `nseq` synthetic 1 kb sequences IN TOTAL (families of 20, 3 % substitutions,
 0.5 % indels, SplitMix64 seed 20260002; sequence g is the same whatever the number of ranks), k = 9, --datatype 32 -> 1 MiB
@@ -72,15 +76,21 @@ def parse():
                     help="sparse: the same workload on sorted (bin, value) lists (DESIGN 3b; single GPU only) -- algorithmic bytes are then the list bytes")
     ap.add_argument("--weights", default=None, help="weights file (default: tests/golden/weights_k9_u32.txt, the 9-feature `fast` model of cfg2); e.g. "
                                                     "tests/golden/weights_cfg5_k9.txt for a `--feat slow` model with jensen_shannon")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline leg (0 disables it)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline leg of --full (0 disables it)")
     ap.add_argument("--cpu-cands", type=int, default=16384, help="candidates per CPU get_close pass: enough for every host thread of a 256-thread box to get 64")
     ap.add_argument("--repeats", type=float, default=0.0, help="fraction of the sequences that carry a 400-base run (a homopolymer or a dinucleotide repeat, alternating): "
                                                                 "counts of ~390 / ~196 among counts of 1 .. 8, as ordinary FASTA has them (microsatellites, poly-A tails); 0.01 = VERDICT r03's case")
-    ap.add_argument("--no-secondary", dest="secondary", action="store_false", help="skip the three short 1 x M legs behind the timed region (dense get_close, "
-                                                                                   "sparse k = 9, sparse k = 13 / 64-bit / 20 kb) that go under `secondary` in the line")
+    ap.add_argument("--no-secondary", dest="secondary", action="store_false", help="--full without the short legs behind the timed region (dense get_close, "
+                                                                                   "sparse k = 9, sparse k = 13 / 64-bit / 20 kb, ...) that go under `secondary` in the line")
     ap.add_argument("--check", action="store_true", help="add `check` to the line: per timed step, the number of close candidates of every query of the block (all ranks "
                                                          "summed) -- what two runs with different numbers of ranks must agree on")
     ap.add_argument("--check-world", type=int, default=0, help="single-rank run: choose each step's query block as a run over this many ranks would (with --check)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: the steady-state histogram build, the product kernel "
+                                                        "on one stream (roofline.one_stream), the `secondary` legs and the CPU baseline (off by default: a "
+                                                        "plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path returned in its last step "
+                                                                        "as DIR/<name>.npy (float32 / float64; a seeded sample of the close flags "
+                                                                        "where the whole matrix would pass 64 MB)")
     return ap.parse_args()
 
 
@@ -147,10 +157,10 @@ def build_resident_set(api, synth, ctx, args, plan, rank, build=True, tail=None)
     if not build:
         return None, time.time() - t0, None, (seq_rows, one_rows)
     # Between chunks the host spends ~1 s generating sequences, so every chunk above starts on an idle GPU (and the first ones
-    # allocate the library's scratch buffers). Steady state = the last chunk rebuilt in place three times back to back (same
+    # allocate the library's scratch buffers). Steady state (--full) = the last chunk rebuilt in place three times back to back (same
     # bytes into the same slots). Dense only: a sparse set's entry arena is append-only, a rebuilt slot reserves its entries again.
     steady = []
-    for _ in range(3 if args.layout == "dense" and M else 0):
+    for _ in range(3 if args.full and args.layout == "dense" and M else 0):
         first, n, b = last
         t1 = time.perf_counter()
         hs.build_packed(first, n, b["packed"], b["n_bases"], b["seg_seq"], b["seg_start"], b["seg_end"], b["eff_len"], b["one_mers"])
@@ -484,6 +494,40 @@ def pmc_traffic(kernel_prefix, config_key):
     return best, busy
 
 
+DUMP_CLOSE_CAP = 12 << 20          # close flags written at most (48 MiB as float32): the rest of the 64 MB goes to the small arrays
+
+
+def dump_outputs(path, last):
+    """--dump-outputs: what the timed path returned to its caller in the last timed step, one float32 / float64 .npy per array.
+    close.npy = the close flags (rows = queries, columns = candidates; one row in --mode get_close), sampled by a fixed seed to at most
+    DUMP_CLOSE_CAP entries where the whole matrix is larger -- close_rows.npy / close_cols.npy hold the row and column indices kept;
+    counts.npy = close candidates per query (all ranks summed); queries.npy = the query slots (global indices) of the step; best.npy
+    (--mode get_close) = best position and best similarity of the last pass."""
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    if last.get("close") is not None:
+        close = np.asarray(last["close"])
+        close = close.reshape(1, -1) if close.ndim == 1 else close
+        rng = np.random.default_rng(20260002)
+        n_r, n_c = close.shape
+        rows, cols = np.arange(n_r), np.arange(n_c)
+        r = min(n_r, max(1, DUMP_CLOSE_CAP // max(1, n_c)))
+        if r < n_r:
+            rows = np.sort(rng.choice(n_r, r, replace=False))
+        c = min(n_c, DUMP_CLOSE_CAP // r)
+        if c < n_c:
+            cols = np.sort(rng.choice(n_c, c, replace=False))
+        out["close"] = close[np.ix_(rows, cols)].astype(np.float32)
+        out["close_rows"] = rows.astype(np.float64)
+        out["close_cols"] = cols.astype(np.float64)
+    for name in ("counts", "queries", "best"):
+        if last.get(name) is not None:
+            out[name] = np.asarray(last[name], dtype=np.float64).reshape(-1)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(out)
+
+
 def main():
     args = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -684,6 +728,7 @@ def main():
     qpr = Q // world                # queries every rank contributes per step (--shard candidates) / scores per step (--shard rows)
     out_close = {"close": api.pinned_array(ctx, (qpr if rows_job else Q, M), np.uint8)} if args.mode == "allpairs" and (world == 1 or rows_job) else None
     step_no = [0]
+    last = {}                       # what the step handed back to its caller, the last step's after the loop (--dump-outputs)
     pending = [None, None]          # RCCL work handles of the query block in flight per buffer half (N > 1, allpairs)
     if rows_job is not None:
         def score_rows(globals_):
@@ -705,6 +750,7 @@ def main():
                 # candidates; the counts' all-gather is issued here and read one step later
                 qs = [((st * Q + j) * 7919) % n_total for j in range(Q)]
                 totals.append(rows_job.score(qs, defer=True))
+                last.update(close=out_close["close"], queries=rows_job.rows_of(qs), counts=None)
                 if len(totals) > 1:
                     done = totals.pop(0).total()
                     if args.check:
@@ -722,8 +768,9 @@ def main():
                 pending[nxt] = block.begin_packed(block_first(st + 1), qpr, base=nxt * Q)
                 # the per-query close counts of the block (all ranks summed) are the step's result; their all-gather is issued here and
                 # waited for one step later (or at the end): nothing in this step needs them
-                _, total = block.score(Q, base=cur * Q, defer=True)
+                close, total = block.score(Q, base=cur * Q, defer=True)
                 totals.append(total)
+                last.update(close=close, queries=block.packed_globals(block_first(st), qpr), counts=None)
                 if len(totals) > 1:
                     done = totals.pop(0).total()
                     if args.check:
@@ -735,6 +782,7 @@ def main():
                 else:
                     qs = np.array([((st * Q + j) * 7919) % M for j in range(Q)], dtype=np.uint32)
                 res = api.score_multi(ctx, feat, hs, None, hs, qs, m=M, want=("close", "counts"), out=out_close)
+                last.update(close=res["close"], queries=qs, counts=res["counts"])
                 if args.check:
                     checks.append([int(x) for x in res["counts"]])
             tiles_ms.append(ctx.last_kernel_ms()[0])
@@ -743,9 +791,10 @@ def main():
             for j in range(Q):
                 g = ((st * Q + j) * 7919) % n_total
                 if sharded is not None:
-                    sharded.get_close(g)
+                    flags, bp, bs, _, _ = sharded.get_close(g)
                 else:
-                    trn.get_close(hs, None, hs, g, m=M)
+                    flags, bp, bs, _ = trn.get_close(hs, None, hs, g, m=M)
+                last.update(close=flags, queries=[g], best=[bp, bs])
                 tiles_ms.append(ctx.last_kernel_ms()[0])
                 launches.append(ctx.last_kernel_launches())
 
@@ -772,6 +821,7 @@ def main():
             w.wait()
     for tt in totals:                # the counts of the last step
         done = tt.total()
+        last["counts"] = done
         if args.check:
             checks.append([int(x) for x in done])
     totals.clear()
@@ -781,6 +831,8 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
 
     pairs = args.steps * Q * n_total
     esz = args.dtype // 8
@@ -841,8 +893,8 @@ def main():
                    "hist_build": {"seq_per_s": round(build_dev_s["median_chunk"]), "GBps_written": round(build_dev_s["median_chunk"] * (4 ** args.k) * esz / 1e9, 1),
                                   "seq_per_s_all_chunks": round(build_dev_s["all"]),
                                   "note": "msc_hist_build_packed only (2-bit bases over PCIe + build kernel): the last chunk rebuilt in place back to "
-                                          "back; all_chunks = the chunks as first built, each after ~1 s of host-side sequence generation on an idle GPU; "
-                                          "untimed setup"},
+                                          "back (--full; without it the same as all_chunks); all_chunks = the chunks as first built, each after ~1 s of "
+                                          "host-side sequence generation on an idle GPU; untimed setup"},
                    "sharding": ("query rows: every rank holds all %d candidates (set-up: one RCCL all-gather of the 2-bit sequences + one of their 1-mer / length records, "
                                 "each rank builds every histogram) and scores %d of each step's %d query rows against all of them; no collective on the data path, "
                                 "the per-query close counts are all-gathered one step late" % (n_total, qpr, Q)) if rows_job is not None else
@@ -876,7 +928,7 @@ def main():
                                          "product of two set presence bits is exactly 1.0), exact sums in f32 (< 2^24)") if on_fp4 else
                                         "int8 multiply-adds counted as 2 operations each (v_mfma_i32_32x32x32_i8), exact int32 sums",
                                  "algorithmic_ops_per_launch": ops})
-    if on_mfma and args.mode == "allpairs" and world == 1 and not args.check:
+    if args.full and on_mfma and args.mode == "allpairs" and world == 1 and not args.check:
         # the same kernel without a neighbour on the chip: in the timed region above three streams share the CUs, and a kernel's launch time
         # there includes what the others took from it
         try:
@@ -890,13 +942,13 @@ def main():
         line["roofline"]["traffic_source"] = "profiles/*_pmc_hbm.json: the committed rocprofv3 --pmc passes of this command (not measured in this run)"
     if args.check:
         line["check"] = checks
-    if world == 1 and args.secondary and args.mode == "allpairs" and args.layout == "dense":
+    if args.full and world == 1 and args.secondary and args.mode == "allpairs" and args.layout == "dense":
         try:
             line["secondary"] = secondary_legs(api, synth, ctx, args, hs, M, seq_rows, one_rows, wtext)
         except Exception as e:      # noqa: BLE001 -- the main line must not depend on the extra legs
             line["secondary"] = [{"workload": "failed", "error": repr(e)}]
     if rank == 0:
-        if args.cpu_seconds > 0 and world == 1:
+        if args.full and args.cpu_seconds > 0 and world == 1:
             try:
                 line["cpu_baseline"] = cpu_baseline(args, synth, wtext, wpath)
             except Exception as e:      # noqa: BLE001

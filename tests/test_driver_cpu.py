@@ -79,7 +79,7 @@ def test_length_bins_match_the_reference_bvec(ref, seed):
     by hand (cluster/bvec.cpp:52-147). Same ranges, same windows, same removal order, same layouts -- including lengths outside
     every bin, empty bins in the middle and at the ends, and runs of equal lengths."""
     rng = np.random.default_rng(1000 + seed)
-    ref.lib().ref_set_threads(1)          # remove_available pushes under `omp critical`: one thread = the canonical order (SURVEY Q10)
+    ref.set_threads(1)          # remove_available pushes under `omp critical`: one thread = the canonical order (SURVEY Q10)
     n = int(rng.integers(1, 400))
     style = seed % 4
     if style == 0:
@@ -92,7 +92,7 @@ def test_length_bins_match_the_reference_bvec(ref, seed):
         lengths = rng.choice([10, 500, 501, 502, 9000], size=n)
     lengths = [int(x) for x in lengths]
     per_bin = int(rng.choice([1, 2, 3, 7, 50, 1000]))
-    mine, theirs = _Bins(_driver.load_library(), "msc_", lengths, per_bin), _Bins(ref.lib(), "ref_", lengths, per_bin)
+    mine, theirs = _Bins(_driver.load_library(), "msc_", lengths, per_bin), ref.new("bins", lambda: _Bins(ref.lib(), "ref_", lengths, per_bin), lengths, per_bin)
     assert mine.layout() == theirs.layout()
     lo, hi = min(lengths), max(lengths)
     for step in range(120):
@@ -140,8 +140,14 @@ def test_host_inverse_matches_the_reference_matrix(ref):
     bit for bit: random well-conditioned matrices, normal-equation matrices X^T X, exact-zero pivots that need a row swap,
     unit pivots, and singular matrices (both hand the input back)."""
     rng = np.random.default_rng(77)
-    mine, theirs = _driver.load_library().msc_host_inverse, ref.lib().ref_host_inverse
-    theirs.restype, theirs.argtypes = None, [C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    mine = _driver.load_library().msc_host_inverse
+
+    def theirs(n, a):
+        f = ref.lib().ref_host_inverse
+        f.restype, f.argtypes = None, [C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        o = np.zeros_like(a)
+        f(n, a.ctypes.data_as(C.POINTER(C.c_double)), o.ctypes.data_as(C.POINTER(C.c_double)))
+        return o
     swapped = singular = 0
     for trial in range(600):
         n = int(rng.integers(1, 6))
@@ -162,9 +168,9 @@ def test_host_inverse_matches_the_reference_matrix(ref):
         else:
             a = np.eye(n) + np.triu(rng.integers(0, 3, size=(n, n)), 1).astype(np.float64)
         a = np.ascontiguousarray(a, dtype=np.float64)
-        o1, o2 = np.zeros_like(a), np.zeros_like(a)
+        o1 = np.zeros_like(a)
         mine(n, a.ctypes.data_as(C.POINTER(C.c_double)), o1.ctypes.data_as(C.POINTER(C.c_double)))
-        theirs(n, a.ctypes.data_as(C.POINTER(C.c_double)), o2.ctypes.data_as(C.POINTER(C.c_double)))
+        o2 = ref.call("host_inverse", theirs, n, a)
         assert np.array_equal(o1.view(np.uint64), o2.view(np.uint64)), (trial, n, kind, a)
         swapped += kind == 3 and n > 1
         singular += bool(np.array_equal(o1, a) and not np.allclose(a @ a, np.eye(n)))

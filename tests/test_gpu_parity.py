@@ -1801,7 +1801,8 @@ def test_find_k_reproduces_the_reference_rule(tmp_path):
                     for a in range(0, len(s), 70):
                         f.write(s[a:a + 70] + "\n")
             names.append(name)
-        r = subprocess.run([exe] + names + ["--id", "0.9", "--output", str(tmp_path / "o.clstr")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
+        r = subprocess.run([exe] + names + ["--id", "0.9", "--output", str(tmp_path / "o.clstr")], cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                           timeout=300)          # (in tmp_path: a run that trains leaves weights.txt where it runs)
         out = r.stdout.decode(errors="replace")          # too few sequences to train on: the run stops after printing its choice of k
         assert "avg length: %d\n" % avg in out and "Recommended K: %d\n" % k in out, (ci, out[-400:])
 

@@ -1,5 +1,6 @@
-"""Pins oracle/msc_oracle.c (the travelling CPU restatement) against the REAL reference compiled from
-/root/reference (oracle/_ref/libmsc_ref.so). Runs only where that build exists (this container)."""
+"""Pins oracle/msc_oracle.c (the travelling CPU restatement) against the REAL reference compiled from its sources
+(oracle/_ref/libmsc_ref.so), through the `ref` fixture: replayed from tests/golden/ref_tapes/ where that build does not exist
+(tests/ref_tape.py)."""
 import os
 
 import numpy as np
@@ -158,7 +159,7 @@ def test_training_fixture_is_what_the_reference_writes(ref):
     fx = json.load(open(os.path.join(GOLDEN, "train_k5_u16.json")))
     seqs, pairs = training_set(fx["seed"], fx["n_templates"], fx["per_template"], fx["length"])
     assert [[a, b, v] for a, b, v in pairs] == fx["pairs"]
-    ref.lib().ref_set_threads(1)
+    ref.set_threads(1)
     pts = [ref.Point(fx["dtype"], s, fx["k"]) for s in seqs]
     text, atr, ate = ref.train_class(fx["dtype"], fx["k"], [pts[a] for a, b, v in pairs], [pts[b] for a, b, v in pairs], [v for a, b, v in pairs], fx["n_train"],
                                      fx["feat_flags"], fx["min_feat"], fx["max_feat"], fx["id"])

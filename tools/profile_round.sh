@@ -12,7 +12,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/prof
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py > $O/bench_plain.json 2> $O/bench_plain.err
+python3 $R/bench.py --full > $O/bench_plain.json 2> $O/bench_plain.err
 echo "plain done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_piped -o stats -- python3 $R/bench.py --cpu-seconds 0 --no-secondary --steps 6 --warmup 2 > $O/bench_stats_piped.json 2> $O/bench_stats_piped.err
 echo "piped stats done"
