@@ -402,7 +402,8 @@ int msc_hist_import_done(msc_ctx* ctx, msc_hist_set* set, uint64_t first_slot, u
  * a Trainer::get_close step (cluster/ClusterFactory.cpp:566) and all-gathers as the new centres of an update round (:328,331).
  *   msc_hist_packed_bytes: size of slot's range (a multiple of 16; known on the host).
  *   msc_hist_pack:   slots[i] -> dev_dst + offsets[i] (offsets: multiples of 16, ranges disjoint).
- *   msc_hist_unpack: dev_src + offsets[i] -> slots[i] of `set` (same k, bin type and layout), an exact copy -- stale magnitude
+ *   msc_hist_unpack: dev_src + offsets[i] -> slots[i] of `set` (same k, bin type and layout: the packed head records them,
+ *                    MSC_ERR_INVALID_ARG otherwise), an exact copy -- stale magnitude
  *                    included; clone / assign semantics come from msc_hist_clone / msc_hist_assign(_batch) out of a staging set. A
  *                    sparse destination appends the lists to its arena (MSC_ERR_OOM when full).
  *   msc_hist_set_reset: a sparse set forgets every list (its arena is append-only otherwise): what a one-slot staging set does

@@ -67,6 +67,26 @@ class Context:
         """msc_score_multi's blocks on three streams (default) or every kernel of a block on one: same results, unstretched kernel timings"""
         self.check(self.lib.msc_set_block_pipe(self.h, 1 if on else 0))
 
+    def device_malloc(self, nbytes):
+        """plain device memory of this context's GPU (msc_device_malloc) -> integer device address; release with device_free"""
+        p = C.c_void_p()
+        self.check(self.lib.msc_device_malloc(self.h, int(nbytes), C.byref(p)))
+        return p.value
+
+    def device_free(self, dev_ptr):
+        self.check(self.lib.msc_device_free(self.h, C.c_void_p(dev_ptr)))
+
+    def memcpy_to_host(self, dev_src, nbytes):
+        """nbytes of device memory at dev_src -> a new uint8 host array (waits for the ctx stream)"""
+        out = np.zeros(int(nbytes), dtype=np.uint8)
+        self.check(self.lib.msc_memcpy_to_host(self.h, _ptr(out), C.c_void_p(dev_src), int(nbytes)))
+        return out
+
+    def memcpy_to_device(self, dev_dst, host):
+        """a host array's bytes -> device memory at dev_dst (waits for the ctx stream)"""
+        a = np.ascontiguousarray(host)
+        self.check(self.lib.msc_memcpy_to_device(self.h, C.c_void_p(dev_dst), _ptr(a), a.nbytes))
+
     def last_kernel_launches(self):
         return self.lib.msc_last_kernel_launches(self.h)
 
@@ -227,6 +247,28 @@ class HistogramSet:
 
     def import_done(self, first_slot, n):
         self.ctx.check(self.ctx.lib.msc_hist_import_done(self.ctx.h, self.h, first_slot, n))
+
+    def packed_bytes(self, slot):
+        """size of slot's packed byte range (msc_hist_packed_bytes; a multiple of 16)"""
+        return self.ctx.lib.msc_hist_packed_bytes(self.h, int(slot))
+
+    def pack(self, slots, dev_dst, offsets):
+        """slots[i] -> device memory dev_dst + offsets[i] (offsets: multiples of 16, ranges disjoint)"""
+        sl = np.ascontiguousarray(slots, dtype=np.uint32)
+        of = np.ascontiguousarray(offsets, dtype=np.uint64)
+        assert sl.size == of.size
+        self.ctx.check(self.ctx.lib.msc_hist_pack(self.ctx.h, self.h, _ptr(sl), sl.size, C.c_void_p(dev_dst), _ptr(of)))
+
+    def unpack(self, slots, dev_src, offsets):
+        """device memory dev_src + offsets[i] -> slots[i]: an exact copy of the packed slot (stale magnitude included)"""
+        sl = np.ascontiguousarray(slots, dtype=np.uint32)
+        of = np.ascontiguousarray(offsets, dtype=np.uint64)
+        assert sl.size == of.size
+        self.ctx.check(self.ctx.lib.msc_hist_unpack(self.ctx.h, self.h, _ptr(sl), sl.size, C.c_void_p(dev_src), _ptr(of)))
+
+    def reset(self):
+        """msc_hist_set_reset: a sparse set forgets every list (no-op on dense sets)"""
+        self.ctx.check(self.ctx.lib.msc_hist_set_reset(self.ctx.h, self.h))
 
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):
@@ -414,14 +456,22 @@ class Trainer:
         """mean_shift_update for many centres: lists[c] = point slots of centre c's neighbourhood.
         -> (nearest_pos[n] (position inside lists[c], -1 if nothing survives the filter), n_kept[n])"""
         cs = np.ascontiguousarray(centre_slots, dtype=np.uint32)
-        offsets = np.zeros(cs.size + 1, dtype=np.uint64)
-        offsets[1:] = np.cumsum([len(x) for x in lists])
-        flat = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.uint32) for x in lists]) if len(lists) else np.zeros(0), dtype=np.uint32)
+        flat, offsets = _flat_lists(lists)
         nearest = np.zeros(cs.size, dtype=np.int64)
         kept = np.zeros(cs.size, dtype=np.uint64)
         self.ctx.check(self.ctx.lib.msc_update_centres(self.ctx.h, self.feat.h, self.cutoff, centres.h, _ptr(cs), cs.size, points.h, _ptr(flat), _ptr(offsets),
                                                        _ptr(nearest), _ptr(kept)))
         return nearest, kept
+
+    def filter_batch(self, centres, centre_slots, points, lists):
+        """Trainer::filter of centre c against lists[c] for every c in one pass (msc_filter_batch) -> keep, one uint8 array per list"""
+        cs = np.ascontiguousarray(centre_slots, dtype=np.uint32)
+        assert cs.size == len(lists)
+        flat, offsets = _flat_lists(lists)
+        keep = np.zeros(max(flat.size, 1), dtype=np.uint8)
+        self.ctx.check(self.ctx.lib.msc_filter_batch(self.ctx.h, self.feat.h, self.cutoff, centres.h, _ptr(cs), cs.size, points.h, _ptr(flat), _ptr(offsets),
+                                                     _ptr(keep)))
+        return [keep[offsets[c]:offsets[c + 1]] for c in range(cs.size)]
 
     def closest(self, points, member_slots, m=None, want_mean=False):
         """get_mean / closest: -> (nearest_pos, dists[m], mean or None)"""
@@ -499,6 +549,37 @@ def train_regr(ctx, points, first_slots, second_slots, vals, n_train, feat_flags
 
 def mean_nearest(ctx, points, member_slots, m=None, want_mean=False):
     return Trainer(ctx, None, 1.0).closest(points, member_slots, m, want_mean)
+
+
+def _flat_lists(lists):
+    """lists of slots -> (flat uint32 slots, uint64 offsets[len(lists) + 1])"""
+    offsets = np.zeros(len(lists) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(x) for x in lists])
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.uint32) for x in lists]) if len(lists) else np.zeros(0), dtype=np.uint32)
+    return flat, offsets
+
+
+def colsum_partial(ctx, points, lists):
+    """msc_colsum_partial: this rank's integer column sums of lists[c] (slots of `points`) -> a host copy of the payload (uint8).
+    Dense sets: uint64 [n][padded bins] then uint64 [n] member counts, to be summed across ranks; sparse sets: a table and packed
+    sparse slots, to be gathered across ranks. (The library's buffer is only valid until its next call: it is copied out here.)"""
+    flat, offsets = _flat_lists(lists)
+    p, nb = C.c_void_p(), C.c_uint64()
+    ctx.check(ctx.lib.msc_colsum_partial(ctx.h, points.h, _ptr(flat), _ptr(offsets), len(lists), C.byref(p), C.byref(nb)))
+    return ctx.memcpy_to_host(p.value, nb.value)
+
+
+def colsum_nearest(ctx, points, lists, dev_global, bytes_per_rank, world):
+    """msc_colsum_nearest over the reduced (dense) or gathered (sparse, bytes_per_rank apart) payloads at device address dev_global
+    -> (pos[n] inside this rank's lists[c] or -1, dist[n], m_total[n] members of list c over all ranks)"""
+    flat, offsets = _flat_lists(lists)
+    n = len(lists)
+    pos = np.zeros(n, dtype=np.int64)
+    dist = np.zeros(n)
+    m_total = np.zeros(n, dtype=np.uint64)
+    ctx.check(ctx.lib.msc_colsum_nearest(ctx.h, points.h, _ptr(flat), _ptr(offsets), n, C.c_void_p(dev_global), int(bytes_per_rank), int(world),
+                                         _ptr(pos), _ptr(dist), _ptr(m_total)))
+    return pos, dist, m_total
 
 
 class Predictor:

@@ -18,11 +18,29 @@
 
 namespace {
 
-constexpr uint32_t kPackDense = 0x4d534431u, kPackSparse = 0x4d534332u;      // "MSD1" / "MSC2"
+constexpr uint16_t kPackDense = 0x4431u, kPackSparse = 0x5332u;              // "1D" / "2S"
 constexpr uint64_t kSplitBytes = 80;                                          // split[17] padded to a multiple of 16
 
-struct PackHead { uint32_t kind, nnz; uint64_t bytes; };                      // first 16 bytes of a packed slot
+// first 16 bytes of a packed slot; k and bin type travel with it: a sparse list of another shape has the same layout and size
+struct PackHead { uint16_t kind; uint8_t k, dtype; uint32_t nnz; uint64_t bytes; };
 static_assert(sizeof(PackHead) == 16, "packed slot header");
+
+PackHead head_of(const msc_hist_set* s, uint64_t slot, uint64_t bytes) {
+	PackHead ph;
+	ph.kind = s->sparse ? kPackSparse : kPackDense;
+	ph.k = (uint8_t)s->k;
+	ph.dtype = (uint8_t)s->dtype;
+	ph.nnz = s->sparse ? s->hdr_host[slot].nnz : 0;
+	ph.bytes = bytes;
+	return ph;
+}
+
+// what msc_hist_unpack checks of a head before it copies anything
+int check_head(msc_ctx* ctx, const msc_hist_set* s, const PackHead& ph, uint64_t i) {
+	if (ph.kind != (s->sparse ? kPackSparse : kPackDense)) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_hist_unpack: packed slot %llu is not of this set's layout", (unsigned long long)i);
+	if (ph.k != s->k || ph.dtype != s->dtype) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_hist_unpack: packed slot %llu is of another k or bin type (k=%d, dtype=%d)", (unsigned long long)i, ph.k, ph.dtype);
+	return MSC_OK;
+}
 
 inline uint64_t up16(uint64_t v) { return (v + 15) & ~15ull; }
 
@@ -149,10 +167,7 @@ extern "C" int msc_hist_pack(msc_ctx* ctx, const msc_hist_set* set, const uint32
 		if (slot >= set->capacity) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_hist_pack: slot out of range");
 		if (offsets[0] & 15) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_hist_pack: offsets must be multiples of 16");
 		uint8_t* o = dst + offsets[0];
-		PackHead ph;
-		ph.bytes = packed_bytes(set, slot);
-		ph.kind = set->sparse ? kPackSparse : kPackDense;
-		ph.nnz = set->sparse ? set->hdr_host[slot].nnz : 0;
+		const PackHead ph = head_of(set, slot, packed_bytes(set, slot));
 		uint4 w;
 		memcpy(&w, &ph, sizeof w);
 		k_write_words<<<dim3(1), dim3(1), 0, ctx->stream>>>((uint32_t*)o, w);
@@ -177,14 +192,12 @@ extern "C" int msc_hist_pack(msc_ctx* ctx, const msc_hist_set* set, const uint32
 		if (slot >= set->capacity) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_hist_pack: slot out of range");
 		if (offsets[i] & 15) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_hist_pack: offsets must be multiples of 16");
 		uint8_t* o = dst + offsets[i];
-		heads[i].bytes = packed_bytes(set, slot);
+		heads[i] = head_of(set, slot, packed_bytes(set, slot));
 		segs.push_back(CopySeg{set->scalars + (uint64_t)slot * set->scalar_stride, o + sizeof(PackHead), set->scalar_stride});
 		if (!set->sparse) {
-			heads[i].kind = kPackDense; heads[i].nnz = 0;
 			segs.push_back(CopySeg{set->bins + (uint64_t)slot * set->L.slot_bytes, o + sizeof(PackHead) + sc, set->L.slot_bytes});
 		} else {
 			const MscSparseHdr& h = set->hdr_host[slot];
-			heads[i].kind = kPackSparse; heads[i].nnz = h.nnz;
 			uint8_t* p = o + sizeof(PackHead) + sc;
 			segs.push_back(CopySeg{(const uint8_t*)(set->hdr + slot) + offsetof(MscSparseHdr, split), p, sizeof(uint32_t) * (MSC_SPARSE_SUB + 1)});
 			p += kSplitBytes;
@@ -230,7 +243,7 @@ extern "C" int msc_hist_unpack(msc_ctx* ctx, msc_hist_set* set, const uint32_t* 
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 		PackHead ph;
 		memcpy(&ph, hh.data(), sizeof ph);
-		if (ph.kind != (set->sparse ? kPackSparse : kPackDense)) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_hist_unpack: the packed slot is not of this set's layout");
+		if ((r = check_head(ctx, set, ph, 0))) return r;
 		const uint32_t slot = slots[0];
 		HIP_TRY(ctx, hipMemcpyAsync(set->scalars + (uint64_t)slot * set->scalar_stride, o + sizeof(PackHead), set->scalar_stride, hipMemcpyDeviceToDevice, ctx->stream));
 		if (!set->sparse) {
@@ -285,7 +298,7 @@ extern "C" int msc_hist_unpack(msc_ctx* ctx, msc_hist_set* set, const uint32_t* 
 	for (uint64_t i = 0; i < n; i++) {
 		PackHead ph;
 		memcpy(&ph, hh.data() + i * hb, sizeof ph);
-		if (ph.kind != (set->sparse ? kPackSparse : kPackDense)) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_hist_unpack: packed slot %llu is not of this set's layout", (unsigned long long)i);
+		if ((r = check_head(ctx, set, ph, i))) return r;
 		const uint8_t* o = src + offsets[i];
 		segs.push_back(CopySeg{o + sizeof(PackHead), set->scalars + (uint64_t)slots[i] * set->scalar_stride, set->scalar_stride});
 		if (!set->sparse) {
