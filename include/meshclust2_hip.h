@@ -312,6 +312,33 @@ int msc_search(msc_ctx* ctx, const msc_model* cls, const msc_model* reg,
                const msc_hist_set* db, const uint32_t* db_slots, uint64_t m,
                const msc_hist_set* qset, uint64_t q_slot, uint8_t* close_out, double* sim_out);
 
+/* fastcar's work() (fastcar/FC_Runner.cpp:426-471) for n_q queries against one candidate list, with only the CLOSE pairs as output: what a
+ * search asks (which pairs are close, and their identity) at a size that follows the close pairs instead of n_q x m.
+ * Pair (q, i) is listed iff win_lo[q] <= i < win_hi[q] (both NULL: every i < m; win_hi is clamped to m) and, when cls != NULL,
+ * p_close(db[db_slots[i]], query q) (MSC_ORDER_CAND_FIRST, as msc_search). Its similarity is clamp(p_predict, 0, 1) with reg, 1 without
+ * it -- bit for bit what msc_search gives for that pair; pairs of similarity 0 are listed too. cls == reg == NULL is MSC_ERR_INVALID_ARG.
+ * Pairs are ordered by query, then by ascending i. offsets[n_q + 1] is filled on return (offsets[0] = 0; query q's pairs are
+ * [offsets[q], offsets[q + 1])). The pairs of each block of queries are evaluated over the union of its members' windows, so the error
+ * statuses (zero length, NaN) are those msc_score_multi returns for those pairs. The list stays on the device until the next
+ * msc_search_pairs call on ctx or msc_destroy; msc_search_pairs_fetch copies a range of it (either output may be NULL).
+ * info (nullable): n_pairs; route = MSC_PAIRS_ROUTE_MATRIX when the product on the matrix cores served the call (dense sets of whole
+ * 4 KiB tiles, n_q >= 2, no divergence or group statistic in either model), MSC_PAIRS_ROUTE_FALLBACK when msc_score_multi's other routes
+ * did, one block of queries at a time; fp64_pairs = pairs evaluated in FP64 (regression evaluations plus classification pairs the f32
+ * screen left undecided, or every classification pair where there is no screen). */
+#define MSC_PAIRS_ROUTE_MATRIX   1
+#define MSC_PAIRS_ROUTE_FALLBACK 2
+typedef struct {
+	uint64_t n_pairs;
+	int32_t  route;
+	int32_t  pad_;
+	uint64_t fp64_pairs;
+} msc_pairs_info;
+int msc_search_pairs(msc_ctx* ctx, const msc_model* cls, const msc_model* reg,
+                     const msc_hist_set* db, const uint32_t* db_slots, uint64_t m,
+                     const msc_hist_set* qset, const uint32_t* q_slots, uint64_t n_q,
+                     const uint64_t* win_lo, const uint64_t* win_hi, uint64_t* offsets, msc_pairs_info* info);
+int msc_search_pairs_fetch(msc_ctx* ctx, uint64_t first, uint64_t n, uint32_t* cand_idx, double* sim);
+
 /* ------------------------------------------------------------------ a8 over a device-resident window
  * The accumulate loop (cluster/ClusterFactory.cpp:553-610) hands Trainer::get_close an iterator range of the length-sorted store
  * (bvec::get_range, cluster/bvec.cpp:261-330; the loop `for (i = istart; i < iend; ++i)` of cluster/Trainer.cpp:41-48). A

@@ -24,6 +24,7 @@ FEAT_FAST = sum(FEAT[n] for n in ("euclidean", "manhattan", "intersection", "kul
 FEAT_DIV = FEAT["jefferey_divergence"] | FEAT["jensen_shannon"]
 FEAT_SLOW = FEAT_FAST | FEAT_DIV
 ORDER_CAND_FIRST, ORDER_QUERY_FIRST = 0, 1
+PAIRS_ROUTE_MATRIX, PAIRS_ROUTE_FALLBACK = 1, 2          # msc_pairs_info.route
 COMBO_XY, COMBO_XY2, COMBO_X2Y, COMBO_X2Y2 = 0, 1, 2, 3
 
 
@@ -34,6 +35,11 @@ class HistInfo(C.Structure):
 
 
 # name -> (restype, argtypes); every symbol include/meshclust2_hip.h declares
+class PairsInfo(C.Structure):
+    """msc_pairs_info of include/meshclust2_hip.h"""
+    _fields_ = [("n_pairs", C.c_uint64), ("route", C.c_int32), ("pad_", C.c_int32), ("fp64_pairs", C.c_uint64)]
+
+
 _vp, _u64, _i64, _int, _dbl = C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_double
 _pu8, _pu32, _pu64, _pi64, _pdbl = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_double)
 PROTOTYPES = {
@@ -90,6 +96,8 @@ PROTOTYPES = {
     "msc_filter": (_int, [_vp, _vp, _dbl, _vp, _u64, _vp, _vp, _u64, _vp, _pu64]),
     "msc_merge": (_int, [_vp, _vp, _dbl, _vp, _vp, _u64, _i64, _i64, _i64, _pi64]),
     "msc_search": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp]),
+    "msc_search_pairs": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "msc_search_pairs_fetch": (_int, [_vp, _u64, _u64, _vp, _vp]),
     "msc_mean_nearest": (_int, [_vp, _vp, _vp, _u64, _pi64, _vp, _vp]),
     "msc_update_centres": (_int, [_vp, _vp, C.c_double, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "msc_merge_all": (_int, [_vp, _vp, C.c_double, _vp, _vp, C.c_uint64, _int, _vp]),

@@ -11,7 +11,7 @@ import weakref
 import numpy as np
 
 from . import _capi
-from ._capi import FEAT, FEAT_FAST, FEAT_SLOW, MscError, ORDER_CAND_FIRST, ORDER_QUERY_FIRST  # noqa: F401
+from ._capi import FEAT, FEAT_FAST, FEAT_SLOW, MscError, ORDER_CAND_FIRST, ORDER_QUERY_FIRST, PAIRS_ROUTE_FALLBACK, PAIRS_ROUTE_MATRIX  # noqa: F401
 
 NP_T = {8: np.uint8, 16: np.uint16, 32: np.uint32, 64: np.uint64}
 
@@ -612,3 +612,28 @@ class Predictor:
         self.ctx.check(self.ctx.lib.msc_search(self.ctx.h, self.cls.h if self.cls else None, self.reg.h if self.reg else None, db.h, _ptr(sl), m,
                                                qset.h, q_slot, _ptr(close), _ptr(sim)))
         return close[:m], sim[:m]
+
+    def search_pairs(self, db, db_slots, qset, q_slots, win_lo=None, win_hi=None, m=None):
+        """work() for every query of q_slots against the candidate list, the CLOSE pairs only (msc_search_pairs). Pair (q, i) is listed when
+        win_lo[q] <= i < win_hi[q] (no windows: every i) and the classification block calls it close; its similarity is clamp(p_predict, 0, 1)
+        (1 without a regression block). -> (offsets [n_q + 1] uint64, cand_idx uint32, sim float64, info): query q's pairs are
+        [offsets[q], offsets[q + 1]) of cand_idx / sim, ascending i; info = dict(n_pairs, route (PAIRS_ROUTE_MATRIX / _FALLBACK), fp64_pairs)."""
+        sl, m = _slots(db_slots, m)
+        qs = np.ascontiguousarray(q_slots, dtype=np.uint32)
+        nq = qs.size
+        if (win_lo is None) != (win_hi is None):
+            raise ValueError("win_lo and win_hi are given together or not at all")
+        lo = None if win_lo is None else np.ascontiguousarray(win_lo, dtype=np.uint64)
+        hi = None if win_hi is None else np.ascontiguousarray(win_hi, dtype=np.uint64)
+        if lo is not None and (lo.size != nq or hi.size != nq):
+            raise ValueError("one window per query")
+        offsets = np.zeros(nq + 1, dtype=np.uint64)
+        info = _capi.PairsInfo()
+        lib, h = self.ctx.lib, self.ctx.h
+        self.ctx.check(lib.msc_search_pairs(h, self.cls.h if self.cls else None, self.reg.h if self.reg else None, db.h, _ptr(sl), m, qset.h, _ptr(qs), nq,
+                                            _ptr(lo), _ptr(hi), _ptr(offsets), C.byref(info)))
+        n = int(info.n_pairs)
+        idx = np.zeros(max(n, 1), dtype=np.uint32)
+        sim = np.zeros(max(n, 1))
+        self.ctx.check(lib.msc_search_pairs_fetch(h, 0, n, _ptr(idx), _ptr(sim)))
+        return offsets, idx[:n], sim[:n], dict(n_pairs=n, route=int(info.route), fp64_pairs=int(info.fp64_pairs))

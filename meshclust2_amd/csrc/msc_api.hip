@@ -160,6 +160,20 @@ extern "C" void msc_destroy(msc_ctx* ctx) {
 	release(ctx->rk_items);
 	release(ctx->rk_big);
 	release(ctx->kb_qT);
+	release(ctx->pl_idx);
+	release(ctx->pl_sim);
+	release(ctx->pl_stage_idx);
+	release(ctx->pl_stage_sim);
+	release(ctx->pl_flags);
+	release(ctx->pl_counts);
+	release(ctx->pl_offsets);
+	release(ctx->pl_seg);
+	release(ctx->pl_dst);
+	release(ctx->pl_qslots);
+	release(ctx->pl_win);
+	release(ctx->pl_qcount);
+	release(ctx->pl_words);
+	if (ctx->pl_pin.p) (void)hipHostFree(ctx->pl_pin.p);
 	release(ctx->kb_hot);
 	release(ctx->kb_hot_idx);
 	release(ctx->kb_min);

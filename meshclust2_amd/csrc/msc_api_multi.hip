@@ -45,7 +45,7 @@ static int ensure_digest(msc_ctx* ctx, const msc_hist_set* set) {
 
 // The presence-bit mirror of a dense set and its lists of large bins (msc_pair_gemm.hip): the operands of the int8 product that takes the
 // Q x M pass. MSC_OK with set->kb == nullptr when it cannot be had (no memory): the older routes then run.
-static int ensure_kb(msc_ctx* ctx, const msc_hist_set* set) {
+int ensure_kb(msc_ctx* ctx, const msc_hist_set* set) {
 	if (set->sparse || set->kb_unavailable || set->dtype == 64) return MSC_OK;
 	auto give_up = [&] {
 		(void)hipGetLastError();
@@ -107,7 +107,7 @@ static int ensure_kb(msc_ctx* ctx, const msc_hist_set* set) {
 
 // The ranks mirror of a dense set (msc_emd_ranks.hip), from its bins. MSC_OK with set->ranks == nullptr when it cannot be had (no
 // memory, or a slot holds a zero count): the digest kernel then keeps the prefixes.
-static int ensure_ranks(msc_ctx* ctx, const msc_hist_set* set) {
+int ensure_ranks(msc_ctx* ctx, const msc_hist_set* set) {
 	if (set->sparse || set->dtype == 64 || !msc_digest_supported(set->L) || set->ranks_unavailable || set->max_sum < set->L.nbins) return MSC_OK;
 	const uint64_t pitch = msc_ranks_pitch(set->max_sum - set->L.nbins);
 	if (set->ranks && pitch > set->rk_pitch) {          // a longer list than any before: lay the mirror out again
@@ -172,7 +172,7 @@ static int ensure_ranks(msc_ctx* ctx, const msc_hist_set* set) {
 // Whether the pass on the matrix cores (msc_pair_gemm.hip) can take a Q x M call over these sets -- host-side bounds only: dense 8/16/32-bit
 // sets of the narrow range whose histograms are whole 4 KiB tiles, P1 / P2 within int32 and, when
 // the earth mover's distance is wanted, lists short enough for the ranks mirror (msc_emd_ranks.hip).
-static bool kb_route_fits(const msc_hist_set* cands, const msc_hist_set* qset, bool need_emd) {
+bool kb_route_fits(const msc_hist_set* cands, const msc_hist_set* qset, bool need_emd) {
 	static const bool off = getenv("MSC_MULTI_NO_GEMM") != nullptr;
 	static const bool no_ranks = getenv("MSC_MULTI_NO_RANKS") != nullptr;
 	const MscLayout& L = cands->L;
@@ -188,7 +188,7 @@ static int score_multi_impl(msc_ctx* ctx, const msc_model* model, const msc_hist
                             uint8_t* close_out, uint64_t feat_mask, double* raw_out);
 
 // the epilogue's error word (the stream is idle): the first failing pair's status
-static int read_error_word(msc_ctx* ctx) {
+int read_error_word(msc_ctx* ctx) {
 	int32_t first_err = 0;
 	HIP_TRY(ctx, hipMemcpy(&first_err, ctx->err_word.p, sizeof first_err, hipMemcpyDeviceToHost));
 	if (first_err == MSC_ERR_ZERO_LENGTH) return fail(ctx, first_err, "length_difference: a point has length 0 (the reference throws 123, predict/Feature.cpp:878-886)");

@@ -1,0 +1,370 @@
+// msc_api_pairs.hip -- msc_search_pairs: fastcar's work() (fastcar/FC_Runner.cpp:426-471) for many queries, with the close pairs and their
+// similarity as the only output. Two routes:
+//   matrix   -- msc_score_multi's pass on the matrix cores (msc_pair_gemm.hip) per block of up to 128 queries, the classification flags left on
+//               the device, then the list kernels of pair_features.hip (k_pair_list_count / _scan / _write): the regression model is
+//               evaluated in FP64 for the listed pairs only, and nothing of size n_q x m crosses to the host.
+//   fallback -- every other case: msc_score_multi one block of queries at a time (dense flags and sums of that block on the host), compacted
+//               there and copied up, so that msc_search_pairs_fetch reads one list whichever route ran.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "msc_internal.h"
+
+#include "msc_objects.h"
+#include "msc_api_private.h"
+
+namespace {
+
+struct PairsBlock {
+	uint64_t q0, nq;          // queries [q0, q0 + nq)
+	uint64_t lo, hi;          // the union of their windows: the candidates the block is evaluated over
+};
+
+// the list (idx, sim) holds `keep` pairs; make room for `need`
+int grow_list(msc_ctx* ctx, DevBuf& idx, DevBuf& sim, uint64_t keep, uint64_t need) {
+	if (need * sizeof(double) <= sim.cap && need * sizeof(uint32_t) <= idx.cap) return MSC_OK;
+	const uint64_t n = std::max<uint64_t>(std::max<uint64_t>(need, sim.cap / sizeof(double) * 3 / 2), 4096);
+	void *pi = nullptr, *ps = nullptr;
+	if (hipMalloc(&pi, n * sizeof(uint32_t)) != hipSuccess || hipMalloc(&ps, n * sizeof(double)) != hipSuccess) {
+		(void)hipGetLastError();
+		if (pi) (void)hipFree(pi);
+		return fail(ctx, MSC_ERR_OOM, "msc_search_pairs: no device memory for a list of %llu pairs", (unsigned long long)need);
+	}
+	if (keep) {
+		HIP_TRY(ctx, hipMemcpyAsync(pi, idx.p, keep * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+		HIP_TRY(ctx, hipMemcpyAsync(ps, sim.p, keep * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+	}
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	release(idx);
+	release(sim);
+	idx.p = pi; idx.cap = n * sizeof(uint32_t);
+	sim.p = ps; sim.cap = n * sizeof(double);
+	return MSC_OK;
+}
+
+// a 64-bit word of the device read back (the stream is waited for)
+int read_word(msc_ctx* ctx, const uint64_t* d, uint64_t* out) {
+	int r;
+	if ((r = ensure_pinned(ctx, ctx->pl_pin, 64))) return r;
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->pl_pin.p, d, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	*out = *(const uint64_t*)ctx->pl_pin.p;
+	return MSC_OK;
+}
+
+struct PairsCall {
+	msc_ctx* ctx;
+	const msc_model *cls, *reg;
+	const msc_hist_set* cands;
+	const uint32_t* cand_slots;
+	uint64_t m;
+	const msc_hist_set* qset;
+	const uint32_t* q_slots;
+	uint64_t n_q;
+	bool windows;
+	std::vector<uint64_t> win;          // [0, n_q): lo, [n_q, 2 n_q): hi (clamped to m, lo <= hi)
+	std::vector<PairsBlock> blocks;
+	std::vector<uint64_t> qcount;       // pairs per query
+	uint64_t fp64 = 0;
+	bool need_emd = false;
+};
+
+// blocks of up to blk queries (none of one query when there are more: the product pass takes two and up), each with its union window;
+// a block whose members' windows are all empty is left out
+void plan_blocks(PairsCall& c, uint64_t blk) {
+	c.blocks.clear();
+	for (uint64_t q0 = 0; q0 < c.n_q;) {
+		uint64_t nq = std::min(blk, c.n_q - q0);
+		if (c.n_q - q0 - nq == 1 && nq > 2) nq--;
+		PairsBlock b{q0, nq, 0, c.m};
+		if (c.windows) {
+			b.lo = c.m; b.hi = 0;
+			for (uint64_t q = q0; q < q0 + nq; q++)
+				if (c.win[q] < c.win[c.n_q + q]) { b.lo = std::min(b.lo, c.win[q]); b.hi = std::max(b.hi, c.win[c.n_q + q]); }
+		}
+		if (b.lo < b.hi) c.blocks.push_back(b);
+		q0 += nq;
+	}
+}
+
+int run_matrix(PairsCall& c) {
+	msc_ctx* ctx = c.ctx;
+	const msc_hist_set *cands = c.cands, *qset = c.qset;
+	const MscLayout& L = cands->L;
+	hipStream_t st = ctx->stream;
+	const uint64_t n_q = c.n_q;
+	int r;
+	// the call's query slots, windows, per-query counts and running totals {list, staging list, pairs the screen left open}
+	if ((r = ensure(ctx, ctx->pl_qslots, n_q * sizeof(uint32_t))) || (r = ensure(ctx, ctx->pl_qcount, n_q * sizeof(uint64_t))) ||
+	    (r = ensure(ctx, ctx->pl_words, 4 * sizeof(uint64_t))) || (r = ensure(ctx, ctx->err_word, sizeof(int32_t))))
+		return r;
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->pl_qslots.p, c.q_slots, n_q * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+	HIP_TRY(ctx, hipMemsetAsync(ctx->pl_qcount.p, 0, n_q * sizeof(uint64_t), st));
+	HIP_TRY(ctx, hipMemsetAsync(ctx->pl_words.p, 0, 4 * sizeof(uint64_t), st));
+	HIP_TRY(ctx, hipMemsetAsync(ctx->err_word.p, 0, sizeof(int32_t), st));
+	if (c.windows) {
+		if ((r = ensure(ctx, ctx->pl_win, 2 * n_q * sizeof(uint64_t)))) return r;
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->pl_win.p, c.win.data(), 2 * n_q * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+	}
+	if (c.cand_slots) {
+		if ((r = ensure(ctx, ctx->slots, c.m * sizeof(uint32_t)))) return r;
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->slots.p, c.cand_slots, c.m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+	}
+	uint64_t* words = (uint64_t*)ctx->pl_words.p;
+	uint64_t total = 0;          // pairs in the list so far
+	const bool screen = c.cls && c.cls->h.screen_ok;
+	const bool emd16 = c.need_emd && cands->ranks16 && qset->ranks16 && cands->rk_pitch == qset->rk_pitch;
+	uint32_t last_qn = 0;
+	for (const PairsBlock& b : c.blocks) {
+		const uint32_t nb = (uint32_t)b.nq;
+		const uint64_t mall = b.hi - b.lo;
+		const uint32_t kb_qn = msc_pair_gemm_rows(nb);
+		last_qn = kb_qn;
+		uint64_t n_hot = 0;
+		for (uint64_t q = b.q0; q < b.q0 + nb; q++) n_hot += std::min(qset->mb_n_host[c.q_slots[q]], qset->mb_pitch);
+		// candidate chunks as msc_score_multi cuts them: the product array [slices][chunk][rows] int32 within 2 GiB
+		uint64_t chunk = (2048ull << 20) / ((uint64_t)msc_pair_gemm_slices(L.nbins, (uint32_t)std::min<uint64_t>(mall, 1u << 30), kb_qn, ctx->num_cus) * kb_qn * sizeof(int32_t));
+		chunk = std::min(std::max<uint64_t>(chunk, 256), mall);
+		chunk = (mall + (mall + chunk - 1) / chunk - 1) / ((mall + chunk - 1) / chunk);
+		const uint32_t n_chunks = (uint32_t)((mall + chunk - 1) / chunk);
+		const uint32_t slices = msc_pair_gemm_slices(L.nbins, (uint32_t)chunk, kb_qn, ctx->num_cus);
+		const uint32_t tiles = msc_pair_list_tiles((uint32_t)chunk);
+		const uint64_t nsteps = L.nbins / 128;
+		if ((r = ensure(ctx, ctx->kb_anib, msc_pair_gemm_anib_bytes(L.nbins, kb_qn))) || (r = ensure(ctx, ctx->kb_qT, msc_pair_gemm_qt_bytes(L.nbins, kb_qn))) ||
+		    (r = ensure(ctx, ctx->kb_min, (size_t)slices * chunk * kb_qn * sizeof(int32_t))) ||
+		    (r = ensure(ctx, ctx->pl_counts, (size_t)nb * tiles * sizeof(uint32_t))) || (r = ensure(ctx, ctx->pl_offsets, ((size_t)nb * tiles + 1) * sizeof(uint64_t))))
+			return r;
+		uint32_t *hot_ptr = nullptr, *hot_cursor = nullptr, *hot_cnt = nullptr;
+		if (n_hot) {
+			if ((r = ensure(ctx, ctx->kb_hot, n_hot * 8)) || (r = ensure(ctx, ctx->kb_hot_idx, 3 * (nsteps + 1) * sizeof(uint32_t))) ||
+			    (r = ensure(ctx, ctx->kb_diff, chunk * kb_qn * sizeof(int32_t))))
+				return r;
+			hot_ptr = (uint32_t*)ctx->kb_hot_idx.p;
+			hot_cursor = hot_ptr + (nsteps + 1);
+			hot_cnt = hot_cursor + (nsteps + 1);
+		}
+		if (c.need_emd && (r = ensure(ctx, ctx->emd_out, chunk * kb_qn * sizeof(uint64_t)))) return r;
+		if (c.cls && (r = ensure(ctx, ctx->pl_flags, (size_t)nb * chunk))) return r;
+		if (n_chunks > 1) {
+			if ((r = ensure(ctx, ctx->pl_seg, (size_t)n_chunks * nb * 2 * sizeof(uint64_t))) || (r = ensure(ctx, ctx->pl_dst, (size_t)n_chunks * nb * sizeof(uint64_t)))) return r;
+			HIP_TRY(ctx, hipMemsetAsync(words + 1, 0, sizeof(uint64_t), st));
+		}
+		const uint32_t* dq = (const uint32_t*)ctx->pl_qslots.p + b.q0;
+		const uint64_t* dwl = c.windows ? (const uint64_t*)ctx->pl_win.p + b.q0 : nullptr;
+		const uint64_t* dwh = c.windows ? (const uint64_t*)ctx->pl_win.p + n_q + b.q0 : nullptr;
+		uint8_t* flags = c.cls ? (uint8_t*)ctx->pl_flags.p : nullptr;
+		// the queries' side of the block, once for all chunks of candidates
+		HIP_TRY(ctx, msc_launch_pair_gemm_queries(st, L.nbins, qset->kb, qset->mb, qset->mb_n, qset->mb_pitch, dq, nb, kb_qn, (uint8_t*)ctx->kb_qT.p, n_hot, ctx->kb_hot.p,
+		                                          hot_ptr, hot_cursor, hot_cnt, (uint8_t*)ctx->kb_anib.p));
+		uint64_t staged = 0;
+		uint32_t ci = 0;
+		for (uint64_t off = b.lo; off < b.hi; off += chunk, ci++) {
+			const uint32_t mc = (uint32_t)std::min(chunk, b.hi - off);
+			const uint32_t* d_slots = c.cand_slots ? (const uint32_t*)ctx->slots.p + off : nullptr;
+			HIP_TRY(ctx, msc_launch_pair_gemm(st, L.nbins, cands->kb, d_slots, off, mc, kb_qn, slices, hot_ptr, ctx->kb_hot.p, (int32_t*)ctx->kb_min.p,
+			                                  (int32_t*)ctx->kb_diff.p, (const uint8_t*)ctx->kb_anib.p));
+			if (emd16)
+				HIP_TRY(ctx, msc_launch_emd_ranks16(st, L.nbins, cands->ranks16, cands->rk_pitch, cands->rk_n, d_slots, off, mc, qset->ranks16, qset->rk_n, dq, nb,
+				                                    (uint64_t*)ctx->emd_out.p, kb_qn));
+			else if (c.need_emd)
+				HIP_TRY(ctx, msc_launch_emd_ranks(st, L.nbins, cands->ranks, cands->rk_pitch, cands->rk_n, d_slots, off, mc, qset->ranks, qset->rk_pitch, qset->rk_n, dq, nb,
+				                                  (uint64_t*)ctx->emd_out.p, kb_qn));
+			MscEpilogueArgs ea;
+			memset(&ea, 0, sizeof ea);
+			ea.kb_min = (const int32_t*)ctx->kb_min.p;
+			ea.kb_diff = n_hot ? (const int32_t*)ctx->kb_diff.p : nullptr;
+			ea.kb_slices = slices;
+			ea.kb_qn = kb_qn;
+			ea.kb_first = c.cand_slots ? 0 : off;
+			ea.kb_c_mb = cands->mb; ea.kb_c_mb_n = cands->mb_n; ea.kb_c_pitch = cands->mb_pitch;
+			ea.kb_q_mb = qset->mb; ea.kb_q_mb_n = qset->mb_n; ea.kb_q_pitch = qset->mb_pitch;
+			ea.kb_qT = (const uint8_t*)ctx->kb_qT.p;
+			ea.emd_stride = kb_qn;
+			if (c.need_emd) ea.emd_ranks = (const uint64_t*)ctx->emd_out.p;
+			ea.S = slices;
+			ea.m = nb * mc;
+			ea.cand_scalars = cands->scalars + (c.cand_slots ? 0 : off * cands->scalar_stride);
+			ea.cand_scalar_stride = cands->scalar_stride;
+			ea.cand_slots = d_slots;
+			ea.n_queries = nb;
+			ea.m_per_query = mc;
+			ea.q_slots = dq;
+			ea.qset_scalars = qset->scalars;
+			ea.q_scalar_stride = qset->scalar_stride;
+			ea.q_scalars = qset->scalars + (uint64_t)c.q_slots[b.q0] * qset->scalar_stride;
+			ea.nbins = L.nbins;
+			ea.dtype = cands->dtype;
+			ea.order = MSC_ORDER_CAND_FIRST;
+			ea.error_word = (int32_t*)ctx->err_word.p;
+			if (c.cls) {          // the flags, as msc_score_multi decides them, kept here
+				ea.model = c.cls->d;
+				ea.close_soa = flags;
+				ea.screen = screen;
+				HIP_TRY(ctx, msc_launch_pair_list_flags(st, ea, (unsigned long long*)(words + 2)));
+				if (!screen) c.fp64 += (uint64_t)nb * mc;
+			}
+			HIP_TRY(ctx, msc_launch_pair_list_count(st, flags, nb, mc, off, dwl, dwh, (uint32_t*)ctx->pl_counts.p));
+			uint64_t* base = n_chunks == 1 ? words : words + 1;
+			HIP_TRY(ctx, msc_launch_pair_list_scan(st, (const uint32_t*)ctx->pl_counts.p, nb, msc_pair_list_tiles(mc), base, (uint64_t*)ctx->pl_offsets.p,
+			                                       (uint64_t*)ctx->pl_qcount.p + b.q0, n_chunks > 1 ? (uint64_t*)ctx->pl_seg.p + (uint64_t)ci * nb * 2 : nullptr));
+			uint64_t now = 0;
+			if ((r = read_word(ctx, base, &now))) return r;          // the list grows before the write: no block runs past its end
+			DevBuf& out_idx = n_chunks == 1 ? ctx->pl_idx : ctx->pl_stage_idx;
+			DevBuf& out_sim = n_chunks == 1 ? ctx->pl_sim : ctx->pl_stage_sim;
+			if ((r = grow_list(ctx, out_idx, out_sim, n_chunks == 1 ? total : staged, now))) return r;
+			if (n_chunks == 1) total = now; else staged = now;
+			ea.model = c.reg ? c.reg->d : nullptr;
+			ea.close_soa = nullptr;
+			ea.screen = 0;
+			HIP_TRY(ctx, msc_launch_pair_list_write(st, ea, flags, off, dwl, dwh, (const uint64_t*)ctx->pl_offsets.p, (uint32_t*)out_idx.p, (double*)out_sim.p));
+		}
+		if (n_chunks > 1) {          // the block's chunks were staged chunk by chunk: into the list query by query
+			if ((r = grow_list(ctx, ctx->pl_idx, ctx->pl_sim, total, total + staged))) return r;
+			HIP_TRY(ctx, msc_launch_pair_list_gather(st, (const uint64_t*)ctx->pl_seg.p, n_chunks, nb, words, (uint64_t*)ctx->pl_dst.p, (const uint32_t*)ctx->pl_stage_idx.p,
+			                                         (const double*)ctx->pl_stage_sim.p, (uint32_t*)ctx->pl_idx.p, (double*)ctx->pl_sim.p));
+			total += staged;
+		}
+	}
+	HIP_TRY(ctx, hipStreamSynchronize(st));
+	if ((r = read_error_word(ctx))) return r;
+	HIP_TRY(ctx, hipMemcpy(c.qcount.data(), ctx->pl_qcount.p, n_q * sizeof(uint64_t), hipMemcpyDeviceToHost));
+	uint64_t open = 0;
+	if ((r = read_word(ctx, words + 2, &open))) return r;
+	c.fp64 += open + (c.reg ? total : 0);
+	ctx->pl_n = total;
+	if (last_qn) {          // msc_last_kernel_info names the product kernel, as msc_score_multi does
+		snprintf(ctx->last_kernel_buf, sizeof ctx->last_kernel_buf, "%s<%u query rows, one matrix product per tile of presence bits%s>", msc_pair_gemm_kernel_name(), last_qn,
+		         c.need_emd ? ", emd by ranks" : ", no emd");
+		ctx->last_kernel = ctx->last_kernel_buf;
+		ctx->last_query_tile = (int)c.blocks.back().nq;
+		ctx->have_timing = false;
+	}
+	return MSC_OK;
+}
+
+int run_fallback(PairsCall& c) {
+	msc_ctx* ctx = c.ctx;
+	int r;
+	std::vector<uint32_t> idx;
+	std::vector<double> sim;
+	std::vector<uint8_t> bclose;
+	std::vector<double> bsim;
+	std::vector<uint32_t> ids;
+	for (const PairsBlock& b : c.blocks) {
+		const uint64_t mw = b.hi - b.lo;
+		const uint32_t* sl = c.cand_slots ? c.cand_slots + b.lo : nullptr;
+		if (!c.cand_slots && b.lo) {          // (the candidates [lo, hi) of the set: a slot list of them)
+			ids.resize(mw);
+			for (uint64_t i = 0; i < mw; i++) ids[i] = (uint32_t)(b.lo + i);
+			sl = ids.data();
+		}
+		bclose.assign(b.nq * mw, 1);
+		bsim.assign(b.nq * mw, 1.0);
+		if (c.cls) {
+			if ((r = msc_score_multi(ctx, c.cls, c.cands, sl, mw, c.qset, c.q_slots + b.q0, b.nq, MSC_ORDER_CAND_FIRST, nullptr, nullptr, bclose.data(), 0, nullptr))) return r;
+			c.fp64 += b.nq * mw;
+		}
+		if (c.reg) {
+			if ((r = msc_score_multi(ctx, c.reg, c.cands, sl, mw, c.qset, c.q_slots + b.q0, b.nq, MSC_ORDER_CAND_FIRST, bsim.data(), nullptr, nullptr, 0, nullptr))) return r;
+			c.fp64 += b.nq * mw;
+			for (double& v : bsim) v = v < 0 ? 0 : (v > 1 ? 1 : v);      // p_predict clamps to [0,1], predict/Predictor.cpp:293-298
+		}
+		for (uint64_t j = 0; j < b.nq; j++) {
+			const uint64_t q = b.q0 + j;
+			const uint64_t lo = c.windows ? c.win[q] : 0, hi = c.windows ? c.win[c.n_q + q] : c.m;
+			for (uint64_t i = lo; i < hi; i++) {
+				const uint64_t at = j * mw + (i - b.lo);
+				if (!bclose[at]) continue;
+				idx.push_back((uint32_t)i);
+				sim.push_back(bsim[at]);
+				c.qcount[q]++;
+			}
+		}
+	}
+	if ((r = grow_list(ctx, ctx->pl_idx, ctx->pl_sim, 0, idx.size()))) return r;
+	if (!idx.empty()) {
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->pl_idx.p, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->pl_sim.p, sim.data(), sim.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	}
+	ctx->pl_n = idx.size();
+	return MSC_OK;
+}
+
+}  // namespace
+
+extern "C" int msc_search_pairs(msc_ctx* ctx, const msc_model* cls, const msc_model* reg, const msc_hist_set* db, const uint32_t* db_slots, uint64_t m,
+                                const msc_hist_set* qset, const uint32_t* q_slots, uint64_t n_q, const uint64_t* win_lo, const uint64_t* win_hi, uint64_t* offsets,
+                                msc_pairs_info* info) {
+	if (!ctx || !db || !qset || !offsets || (n_q && !q_slots)) return MSC_ERR_INVALID_ARG;
+	if ((cls && cls->ctx != ctx) || (reg && reg->ctx != ctx)) return MSC_ERR_INVALID_ARG;
+	if (info) memset(info, 0, sizeof *info);
+	ctx->pl_n = 0;          // (the list of the call before is gone whatever happens next)
+	if (!cls && !reg) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_search_pairs needs a classification or a regression model");
+	if (!win_lo != !win_hi) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_search_pairs: win_lo and win_hi are given together or not at all");
+	if (m > 0xffffffffull) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_search_pairs: candidate indices are 32-bit");
+	memset(offsets, 0, (n_q + 1) * sizeof(uint64_t));
+	if (n_q == 0 || m == 0) return MSC_OK;
+	for (uint64_t i = 0; i < n_q; i++) if (q_slots[i] >= qset->capacity) return fail(ctx, MSC_ERR_INVALID_ARG, "query slot out of range");
+	int r = validate_pair(ctx, db, qset, q_slots[0], db_slots, m);
+	if (r) return r;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	PairsCall c;
+	c.ctx = ctx; c.cls = cls; c.reg = reg; c.cands = db; c.cand_slots = db_slots; c.m = m; c.qset = qset; c.q_slots = q_slots; c.n_q = n_q;
+	c.windows = win_lo != nullptr;
+	if (c.windows) {
+		c.win.resize(2 * n_q);
+		for (uint64_t q = 0; q < n_q; q++) {
+			c.win[n_q + q] = std::min(win_hi[q], m);
+			c.win[q] = std::min(win_lo[q], c.win[n_q + q]);
+		}
+	}
+	c.qcount.assign(n_q, 0);
+	uint64_t want = 0;
+	for (const msc_model* md : {cls, reg})
+		if (md) for (int i = 0; i < md->h.n_singles; i++) want |= md->h.single_flag[i];
+	c.need_emd = (want & MSC_FEAT_EMD) != 0;
+	// the matrix-core route: where msc_score_multi would put every block of this call on the product kernel, for both models at once
+	bool matrix = n_q >= 2 && !(want & (MSC_FEAT_DIV | MSC_FEAT_GROUPS)) && kb_route_fits(db, qset, c.need_emd);
+	if (matrix) {
+		if ((r = ensure_kb(ctx, db)) || (r = ensure_kb(ctx, qset))) return r;
+		matrix = db->kb && qset->kb && !db->kb_has_zero && !qset->kb_has_zero;
+	}
+	if (matrix) {
+		plan_blocks(c, 128);
+		for (const PairsBlock& b : c.blocks) {          // (a block whose queries' hot list would be too long goes to the older routes there)
+			uint64_t n_hot = 0;
+			for (uint64_t q = b.q0; q < b.q0 + b.nq; q++) n_hot += std::min(qset->mb_n_host[q_slots[q]], qset->mb_pitch);
+			if (n_hot > 64 * (db->L.nbins / 128)) matrix = false;
+		}
+	}
+	if (matrix && c.need_emd) {
+		if ((r = ensure_ranks(ctx, db)) || (r = ensure_ranks(ctx, qset))) return r;
+		matrix = db->ranks && qset->ranks;
+	}
+	if (!matrix) plan_blocks(c, 128);
+	r = matrix ? run_matrix(c) : run_fallback(c);
+	if (r) { ctx->pl_n = 0; return r; }
+	for (uint64_t q = 0; q < n_q; q++) offsets[q + 1] = offsets[q] + c.qcount[q];
+	if (offsets[n_q] != ctx->pl_n) { ctx->pl_n = 0; return fail(ctx, MSC_ERR_HIP, "msc_search_pairs: %llu pairs listed, %llu counted", (unsigned long long)ctx->pl_n, (unsigned long long)offsets[n_q]); }
+	if (info) {
+		info->n_pairs = ctx->pl_n;
+		info->route = matrix ? MSC_PAIRS_ROUTE_MATRIX : MSC_PAIRS_ROUTE_FALLBACK;
+		info->fp64_pairs = c.fp64;
+	}
+	return MSC_OK;
+}
+
+extern "C" int msc_search_pairs_fetch(msc_ctx* ctx, uint64_t first, uint64_t n, uint32_t* cand_idx, double* sim) {
+	if (!ctx) return MSC_ERR_INVALID_ARG;
+	if (first > ctx->pl_n || n > ctx->pl_n - first)
+		return fail(ctx, MSC_ERR_INVALID_ARG, "msc_search_pairs_fetch: pairs [%llu, %llu) outside the list of %llu", (unsigned long long)first,
+		            (unsigned long long)(first + n), (unsigned long long)ctx->pl_n);
+	if (n == 0) return MSC_OK;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if (cand_idx) HIP_TRY(ctx, hipMemcpyAsync(cand_idx, (const uint32_t*)ctx->pl_idx.p + first, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+	if (sim) HIP_TRY(ctx, hipMemcpyAsync(sim, (const double*)ctx->pl_sim.p + first, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return MSC_OK;
+}

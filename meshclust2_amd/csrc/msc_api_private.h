@@ -42,3 +42,9 @@ hipError_t launch_sparse_pass(msc_ctx* ctx, SparseKernel k, const msc_hist_set* 
                               uint64_t off, uint32_t mc, const msc_hist_set* q_sp, uint64_t q_slot, const uint8_t* q_scal, uint64_t nbins, int use_window,
                               uint64_t min_len, uint64_t max_len, MscPartial* partials, void* div_tables, void* div_partials, int order, uint32_t parts = 1,
                               uint32_t div_stride = 1);
+
+// ---- msc_api_multi.hip (shared with msc_api_pairs.hip)
+int ensure_kb(msc_ctx* ctx, const msc_hist_set* set);          // the presence-bit mirror and lists of large bins of a dense set (set->kb null: unavailable)
+int ensure_ranks(msc_ctx* ctx, const msc_hist_set* set);       // the ranks mirror (set->ranks null: unavailable)
+bool kb_route_fits(const msc_hist_set* cands, const msc_hist_set* qset, bool need_emd);          // host-side bounds of the matrix-core pass
+int read_error_word(msc_ctx* ctx);                             // the epilogue's error word as a status (the stream is idle)

@@ -247,6 +247,16 @@ hipError_t msc_launch_pair_gemm(hipStream_t st, uint64_t nbins, const uint8_t* c
                                 uint32_t k_slices, const uint32_t* hot_ptr, const void* hot, int32_t* out_min, int32_t* out_diff, const uint8_t* anib);
 hipError_t msc_launch_epilogue(hipStream_t st, const MscEpilogueArgs& a);
 hipError_t msc_launch_close_counts(hipStream_t st, const uint8_t* flags, uint32_t n_q, uint32_t m, uint64_t* counts);
+// the list of close pairs of msc_search_pairs (pair_features.hip): records of (query, tile of candidates), counted, scanned, written
+uint32_t msc_pair_list_tiles(uint32_t mc);
+hipError_t msc_launch_pair_list_flags(hipStream_t st, const MscEpilogueArgs& a, unsigned long long* open);
+hipError_t msc_launch_pair_list_count(hipStream_t st, const uint8_t* flags, uint32_t n_q, uint32_t mc, uint64_t first, const uint64_t* win_lo, const uint64_t* win_hi,
+                                      uint32_t* counts);
+hipError_t msc_launch_pair_list_scan(hipStream_t st, const uint32_t* counts, uint32_t n_q, uint32_t tiles, uint64_t* base, uint64_t* offsets, uint64_t* qcount, uint64_t* seg);
+hipError_t msc_launch_pair_list_write(hipStream_t st, const MscEpilogueArgs& a, const uint8_t* flags, uint64_t first, const uint64_t* win_lo, const uint64_t* win_hi,
+                                      const uint64_t* offsets, uint32_t* out_idx, double* out_sim);
+hipError_t msc_launch_pair_list_gather(hipStream_t st, const uint64_t* seg, uint32_t n_chunks, uint32_t n_q, uint64_t* base, uint64_t* dst, const uint32_t* s_idx,
+                                       const double* s_sim, uint32_t* out_idx, double* out_sim);
 // the window bookkeeping the fused epilogue + reduce kernels do for msc_get_close_window (msc_window.hip): pos[i] = position of candidate i,
 // alive[] = the window's flags, counter / out = the host-visible list of closed positions (out[0] = best position + 1, out[2 ..] = the list)
 struct MscCloseList {

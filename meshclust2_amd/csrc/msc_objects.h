@@ -67,6 +67,12 @@ struct msc_ctx {
 	bool packed_on_device = false;         // msc_hist_build_packed_dev: the 2-bit stream of the build in progress is device memory
 	bool no_kb_now = false;                // msc_score_multi: this block is taken by the older routes (its hot list would be too long)
 	DevBuf close_counts;                   // msc_score_multi: close candidates per query of the call in progress / the last call (msc_last_close_counts)
+	// msc_search_pairs (msc_api_pairs.hip): the list of the last call (candidate index, similarity), kept until the next call, and its scratch
+	DevBuf pl_idx, pl_sim;
+	uint64_t pl_n = 0;                     // pairs in the list
+	DevBuf pl_stage_idx, pl_stage_sim;     // a block's pairs chunk by chunk, when its candidates take several chunks
+	DevBuf pl_flags, pl_counts, pl_offsets, pl_seg, pl_dst, pl_qslots, pl_win, pl_qcount, pl_words;
+	DevBuf pl_pin;                         // page-locked: the running totals read back before a list grows
 	uint64_t close_counts_n = 0, close_counts_base = 0;
 	bool in_score_multi = false;
 	// msc_score_multi queues the blocks of its matrix-core pass without waiting between them: 0 = off, 1 = the next queued block clears

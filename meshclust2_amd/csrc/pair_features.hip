@@ -2485,3 +2485,213 @@ hipError_t msc_launch_distance_batch(hipStream_t st, const MscPartial* partials,
 	k_distance_batch<<<dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st>>>(partials, S, n, scalars, scalar_stride, member_slots, pair_seg, r_scalars, r_stride, floor_sum, dist_out);
 	return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------- the list of close pairs (msc_search_pairs)
+// A Q x M search that returns only the close pairs: the product, the rank walk and the classification flags of a block run as for
+// msc_score_multi and the flags stay on the device. k_pair_list_count counts, per (query, tile of kListTile candidates), the flags inside
+// the query's window; k_pair_list_scan turns the counts into each record's first position (query-major, tiles ascending) behind a running
+// total kept on the device; k_pair_list_write lays out the pairs of each record in candidate order (a wave's ballot gives a lane its rank)
+// and evaluates the regression model in FP64 for those pairs only. Positions come from the scan alone: no atomic decides the order.
+namespace {
+constexpr uint32_t kListTile = 1024;          // candidates per (query, tile) record: sixteen steps of a wave
+
+// the window of query q in the coordinates of a chunk whose candidate 0 is index `first` of the call's list: [lo, hi) within [0, mc)
+__device__ __forceinline__ void list_window(const uint64_t* win_lo, const uint64_t* win_hi, uint32_t q, uint64_t first, uint32_t mc, uint32_t& lo, uint32_t& hi) {
+	lo = 0;
+	hi = mc;
+	if (!win_lo) return;
+	const uint64_t a = win_lo[q], b = win_hi[q];
+	lo = a <= first ? 0 : (a - first >= mc ? mc : (uint32_t)(a - first));
+	hi = b <= first ? 0 : (b - first >= mc ? mc : (uint32_t)(b - first));
+}
+
+// one wave per (query, tile): the number of listed pairs -- flag set (every pair when flags is null) and inside the window
+__global__ void __launch_bounds__(kBlock) k_pair_list_count(const uint8_t* __restrict__ flags, uint32_t n_q, uint32_t mc, uint64_t first,
+                                                            const uint64_t* __restrict__ win_lo, const uint64_t* __restrict__ win_hi, uint32_t* __restrict__ counts) {
+	const uint32_t lane = threadIdx.x & 63;
+	const uint32_t tiles = (mc + kListTile - 1) / kListTile;
+	const uint32_t w = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+	if (w >= n_q * tiles) return;
+	const uint32_t q = w / tiles, t = w % tiles;
+	uint32_t lo, hi;
+	list_window(win_lo, win_hi, q, first, mc, lo, hi);
+	uint32_t n = 0;
+	for (uint32_t s = 0; s < kListTile; s += 64) {
+		const uint32_t c = t * kListTile + s + lane;
+		const bool f = c >= lo && c < hi && (!flags || flags[(uint64_t)q * mc + c] != 0);
+		n += (uint32_t)__popcll(__ballot(f));
+	}
+	if (lane == 0) counts[w] = n;
+}
+
+// counts [n_q][tiles] -> offsets [n_q * tiles + 1], exclusive, starting at *base; *base becomes the new total. qcount[q] += query q's
+// pairs; seg (nullable) = {first position, pairs} of each query. One workgroup: a block has at most 128 x 4096 records.
+__global__ void __launch_bounds__(1024) k_pair_list_scan(const uint32_t* __restrict__ counts, uint32_t n_q, uint32_t tiles, unsigned long long* __restrict__ base,
+                                                         unsigned long long* __restrict__ offsets, unsigned long long* __restrict__ qcount,
+                                                         unsigned long long* __restrict__ seg) {
+	__shared__ unsigned long long part[1024];
+	const uint32_t n = n_q * tiles, per = (n + 1023) / 1024, i0 = threadIdx.x * per;
+	const uint32_t i1 = i0 + per < n ? i0 + per : n;
+	unsigned long long s = 0;
+	for (uint32_t i = i0; i < i1; i++) s += counts[i];
+	part[threadIdx.x] = s;
+	__syncthreads();
+	for (uint32_t d = 1; d < 1024; d <<= 1) {
+		const unsigned long long v = threadIdx.x >= d ? part[threadIdx.x - d] : 0ull;
+		__syncthreads();
+		part[threadIdx.x] += v;
+		__syncthreads();
+	}
+	const unsigned long long b = *base, total = b + part[1023];
+	unsigned long long run = b + part[threadIdx.x] - s;
+	for (uint32_t i = i0; i < i1; i++) { offsets[i] = run; run += counts[i]; }
+	if (threadIdx.x == 0) offsets[n] = total;
+	__syncthreads();          // (every offset is written and every thread has read *base)
+	for (uint32_t q = threadIdx.x; q < n_q; q += 1024) {
+		const unsigned long long a = offsets[q * tiles], e = offsets[(q + 1) * tiles];
+		qcount[q] += e - a;
+		if (seg) { seg[2 * q] = a; seg[2 * q + 1] = e - a; }
+	}
+	if (threadIdx.x == 0) *base = total;
+}
+
+// One wave per (query, tile), the lanes over 64 consecutive candidates at a time: a listed pair's position is its record's offset plus the
+// listed pairs of the lanes below it and of the steps before. With REG, the pair's integer reductions are formed again as
+// k_pair_epilogue_bits_open forms them and epilogue_eval (the FP64 path of every route) gives the regression model's weighted sum, clamped to
+// [0, 1] as p_predict does (predict/Predictor.cpp:293-298). Few pairs are listed (one in thousands): a separate launch keeps the FP64
+// evaluation's registers out of the flag kernels, and its lanes idle where nothing is listed. (Four waves per SIMD asked of the compiler:
+// unbounded, the evaluation took 200 registers and two waves per SIMD for a kernel that mostly reads flags.)
+template <bool REG>
+__global__ void __launch_bounds__(kBlock, 4) k_pair_list_write(const MscEpilogueArgs a, const uint8_t* __restrict__ flags, uint64_t first,
+                                                            const uint64_t* __restrict__ win_lo, const uint64_t* __restrict__ win_hi,
+                                                            const unsigned long long* __restrict__ offsets, uint32_t* __restrict__ out_idx,
+                                                            double* __restrict__ out_sim) {
+	const uint32_t lane = threadIdx.x & 63;
+	const uint32_t n_q = a.n_queries, mc = a.m_per_query;
+	const uint32_t tiles = (mc + kListTile - 1) / kListTile;
+	const uint32_t w = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+	if (w >= n_q * tiles) return;
+	const uint32_t q = w / tiles, t = w % tiles;
+	uint32_t lo, hi;
+	list_window(win_lo, win_hi, q, first, mc, lo, hi);
+	unsigned long long at = offsets[w];
+	const uint64_t below = (1ull << lane) - 1ull;
+	for (uint32_t s = 0; s < kListTile; s += 64) {
+		const uint32_t c = t * kListTile + s + lane;
+		const bool f = c >= lo && c < hi && (!flags || flags[(uint64_t)q * mc + c] != 0);
+		const uint64_t mask = __ballot(f);
+		if (f) {
+			const unsigned long long pos = at + (unsigned long long)__popcll(mask & below);
+			double sim = 1.0;
+			if (REG) {
+				const uint32_t q_slot = a.q_slots[q];
+				const uint32_t slot_rel = a.cand_slots ? a.cand_slots[c] : c;
+				const uint64_t slot = a.cand_slots ? (uint64_t)slot_rel : a.kb_first + c;
+				const uint2* cmb = reinterpret_cast<const uint2*>(a.kb_c_mb) + slot * a.kb_c_pitch;
+				const uint32_t c_n = a.kb_c_mb_n[slot] < a.kb_c_pitch ? a.kb_c_mb_n[slot] : a.kb_c_pitch;
+				const MscSlotScalars* cs = reinterpret_cast<const MscSlotScalars*>(a.cand_scalars + (uint64_t)slot_rel * a.cand_scalar_stride);
+				const MscSlotScalars* qs = reinterpret_cast<const MscSlotScalars*>(a.qset_scalars + (uint64_t)q_slot * a.q_scalar_stride);
+				const Side cand{cs->mag, cs->length, cs->sum, cs->sum_sq}, qry{qs->mag, qs->length, qs->sum, qs->sum_sq};
+				int64_t min_e = 0;
+				for (uint32_t s_ = 0; s_ < a.kb_slices; s_++) min_e += a.kb_min[((uint64_t)s_ * mc + c) * a.kb_qn + q];
+				const int64_t diff_e = a.kb_diff ? a.kb_diff[(uint64_t)c * a.kb_qn + q] : 0;
+				const uint64_t emd = a.emd_ranks ? a.emd_ranks[(uint64_t)c * (a.emd_stride ? a.emd_stride : 64) + q] : 0;
+				PairTotals tt{0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+				bits_pair_totals(a, c, cmb, c_n, q, q_slot, min_e, diff_e, emd, cand, qry, tt);
+				MscPairOut po;
+				epilogue_eval(a, q * mc + c, c, q, cand, qry, a.min_len, a.max_len, tt, &po);
+				sim = po.sum < 0 ? 0.0 : (po.sum > 1 ? 1.0 : po.sum);
+			}
+			out_idx[pos] = (uint32_t)(first + c);
+			out_sim[pos] = sim;
+		}
+		at += (unsigned long long)__popcll(mask);
+	}
+}
+
+// the flag bytes the screen left open (kScreenOpen), before k_pair_epilogue_bits_open resolves them: what fp64_pairs reports
+__global__ void __launch_bounds__(kBlock) k_pair_list_open_count(const uint8_t* __restrict__ flags, uint64_t n, unsigned long long* __restrict__ open) {
+	const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	const bool o = i < n && flags[i] == kScreenOpen;
+	const uint64_t mask = __ballot(o);
+	if ((threadIdx.x & 63) == 0 && mask) atomicAdd(open, (unsigned long long)__popcll(mask));
+}
+
+// several chunks of candidates in one block: chunk c's pairs of query q were written to the staging list at seg[c][q] = {first, n};
+// their final positions run query by query, chunk after chunk, from *base (one thread: a block has at most 128 x a few segments)
+__global__ void k_pair_list_plan(const unsigned long long* __restrict__ seg, uint32_t n_chunks, uint32_t n_q, unsigned long long* __restrict__ base,
+                                 unsigned long long* __restrict__ dst) {
+	if (threadIdx.x != 0 || blockIdx.x != 0) return;
+	unsigned long long run = *base;
+	for (uint32_t q = 0; q < n_q; q++)
+		for (uint32_t c = 0; c < n_chunks; c++) {
+			dst[(uint64_t)c * n_q + q] = run;
+			run += seg[2 * ((uint64_t)c * n_q + q) + 1];
+		}
+	*base = run;
+}
+
+__global__ void __launch_bounds__(kBlock) k_pair_list_gather(const unsigned long long* __restrict__ seg, const unsigned long long* __restrict__ dst,
+                                                             const uint32_t* __restrict__ s_idx, const double* __restrict__ s_sim, uint32_t* __restrict__ out_idx,
+                                                             double* __restrict__ out_sim) {
+	const uint64_t k = blockIdx.x;
+	const unsigned long long from = seg[2 * k], n = seg[2 * k + 1], to = dst[k];
+	for (unsigned long long i = threadIdx.x; i < n; i += blockDim.x) {
+		out_idx[to + i] = s_idx[from + i];
+		out_sim[to + i] = s_sim[from + i];
+	}
+}
+}  // namespace
+
+uint32_t msc_pair_list_tiles(uint32_t mc) { return (mc + kListTile - 1) / kListTile; }
+
+// the classification flags of a block on the matrix-core route, left on the device (a.close_soa): the f32 screen and the FP64 pass over the
+// pairs it left open when a.screen is set (counted into *open), k_pair_epilogue_bits otherwise
+hipError_t msc_launch_pair_list_flags(hipStream_t st, const MscEpilogueArgs& a, unsigned long long* open) {
+	if (!a.screen || !a.kb_min || !a.model || !a.close_soa || a.sum_soa || a.csum_soa || a.raw_out || a.pair_out) return msc_launch_epilogue(st, a);
+	if (a.n_queries < 2 || a.n_queries > a.kb_qn || !a.kb_c_mb || !a.kb_q_mb || !a.kb_qT) return hipErrorInvalidValue;
+	constexpr uint32_t chunk = 4;          // (as msc_launch_epilogue takes it)
+	const uint64_t cw = (uint64_t)((a.m_per_query + chunk - 1) / chunk) * ((a.n_queries + 63) / 64);
+	hipLaunchKernelGGL(k_pair_epilogue_bits_screen<chunk>, dim3((unsigned)((cw + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, st, a);
+	const uint64_t pairs = (uint64_t)a.n_queries * a.m_per_query;
+	hipLaunchKernelGGL(k_pair_list_open_count, dim3((unsigned)((pairs + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a.close_soa, pairs, open);
+	const uint64_t threads = (pairs + 15) / 16;
+	hipLaunchKernelGGL(k_pair_epilogue_bits_open, dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a);
+	return hipGetLastError();
+}
+
+hipError_t msc_launch_pair_list_count(hipStream_t st, const uint8_t* flags, uint32_t n_q, uint32_t mc, uint64_t first, const uint64_t* win_lo, const uint64_t* win_hi,
+                                      uint32_t* counts) {
+	const uint64_t waves = (uint64_t)n_q * msc_pair_list_tiles(mc);
+	if (waves == 0) return hipSuccess;
+	hipLaunchKernelGGL(k_pair_list_count, dim3((unsigned)((waves + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, st, flags, n_q, mc, first, win_lo, win_hi, counts);
+	return hipGetLastError();
+}
+
+hipError_t msc_launch_pair_list_scan(hipStream_t st, const uint32_t* counts, uint32_t n_q, uint32_t tiles, uint64_t* base, uint64_t* offsets, uint64_t* qcount, uint64_t* seg) {
+	if ((uint64_t)n_q * tiles > (1ull << 31)) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(k_pair_list_scan, dim3(1), dim3(1024), 0, st, counts, n_q, tiles, (unsigned long long*)base, (unsigned long long*)offsets,
+	                   (unsigned long long*)qcount, (unsigned long long*)seg);
+	return hipGetLastError();
+}
+
+// a.model = the regression model (its device image) or null: similarity 1
+hipError_t msc_launch_pair_list_write(hipStream_t st, const MscEpilogueArgs& a, const uint8_t* flags, uint64_t first, const uint64_t* win_lo, const uint64_t* win_hi,
+                                      const uint64_t* offsets, uint32_t* out_idx, double* out_sim) {
+	const uint64_t waves = (uint64_t)a.n_queries * msc_pair_list_tiles(a.m_per_query);
+	if (waves == 0) return hipSuccess;
+	if (a.model && (a.n_queries > a.kb_qn || !a.kb_min || !a.kb_c_mb || !a.kb_q_mb || !a.kb_qT)) return hipErrorInvalidValue;
+	const dim3 grid((unsigned)((waves + kWavesPerBlock - 1) / kWavesPerBlock));
+	if (a.model) hipLaunchKernelGGL(k_pair_list_write<true>, grid, dim3(kBlock), 0, st, a, flags, first, win_lo, win_hi, (const unsigned long long*)offsets, out_idx, out_sim);
+	else hipLaunchKernelGGL(k_pair_list_write<false>, grid, dim3(kBlock), 0, st, a, flags, first, win_lo, win_hi, (const unsigned long long*)offsets, out_idx, out_sim);
+	return hipGetLastError();
+}
+
+hipError_t msc_launch_pair_list_gather(hipStream_t st, const uint64_t* seg, uint32_t n_chunks, uint32_t n_q, uint64_t* base, uint64_t* dst, const uint32_t* s_idx,
+                                       const double* s_sim, uint32_t* out_idx, double* out_sim) {
+	if ((uint64_t)n_chunks * n_q == 0) return hipSuccess;
+	hipLaunchKernelGGL(k_pair_list_plan, dim3(1), dim3(64), 0, st, (const unsigned long long*)seg, n_chunks, n_q, (unsigned long long*)base, (unsigned long long*)dst);
+	hipLaunchKernelGGL(k_pair_list_gather, dim3(n_chunks * n_q), dim3(kBlock), 0, st, (const unsigned long long*)seg, (const unsigned long long*)dst, s_idx, s_sim,
+	                   out_idx, out_sim);
+	return hipGetLastError();
+}

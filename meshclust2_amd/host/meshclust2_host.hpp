@@ -215,6 +215,22 @@ public:
 			for (double& v : similarity) v = v < 0 ? 0 : (v > 1 ? 1 : v);      // p_predict clamps to [0,1], predict/Predictor.cpp:293-298
 		}
 	}
+	// the same block with only the close pairs as output (msc_search_pairs): pair (q, i) is listed when win_lo[q] <= i < win_hi[q] and close;
+	// query q's pairs are [offsets[q], offsets[q + 1]) of cand_idx (index into slots, ascending) and similarity -- the values of search()
+	std::vector<uint64_t> search_pairs(const PointSet& db, const std::vector<uint32_t>& slots, const PointSet& q, const std::vector<uint32_t>& q_slots,
+	                                   const std::vector<uint64_t>& win_lo, const std::vector<uint64_t>& win_hi, std::vector<uint32_t>& cand_idx,
+	                                   std::vector<double>& similarity, msc_pairs_info* info = nullptr) const {
+		if (win_lo.size() != q_slots.size() || win_hi.size() != q_slots.size()) throw Error(MSC_ERR_INVALID_ARG, "search_pairs: one window per query");
+		std::vector<uint64_t> offsets(q_slots.size() + 1, 0);
+		msc_pairs_info inf;
+		ctx_.check(msc_search_pairs(ctx_.get(), cls_ ? cls_->get() : nullptr, reg_ ? reg_->get() : nullptr, db.get(), slots.data(), slots.size(), q.get(), q_slots.data(),
+		                            q_slots.size(), win_lo.data(), win_hi.data(), offsets.data(), &inf));
+		cand_idx.resize(inf.n_pairs);
+		similarity.resize(inf.n_pairs);
+		ctx_.check(msc_search_pairs_fetch(ctx_.get(), 0, inf.n_pairs, cand_idx.data(), similarity.data()));
+		if (info) *info = inf;
+		return offsets;
+	}
 private:
 	Context& ctx_;
 	std::unique_ptr<Feature> cls_, reg_;

@@ -195,19 +195,24 @@ int main(int argc, char** argv) {
 					if (members.empty()) continue;
 					std::vector<uint32_t> window;
 					for (size_t i = lo; i < hi; i++) window.push_back(pts[i]->slot);
-					std::vector<uint8_t> close;
-					std::vector<double> sim;
-					if (members.size() == 1) pred.search(dset, window, qset, q_slots[0], close, sim);      // pred->close / similarity, one query
-					else pred.search_block(dset, window, qset, q_slots, close, sim);
-					note_kernel();
-					for (size_t j = 0; j < members.size(); j++) {
-						const size_t qi = members[j];
-						for (size_t i = win_start[qi]; i < win_end[qi]; i++) {
-							const size_t at = j * window.size() + (i - lo);
-							if (!close[at]) continue;
-							hits[qi].push_back(Hit{i, sim[at]});
-						}
+					if (members.size() == 1) {          // pred->close / similarity, one query
+						std::vector<uint8_t> close;
+						std::vector<double> sim;
+						pred.search(dset, window, qset, q_slots[0], close, sim);
+						note_kernel();
+						for (size_t i = win_start[members[0]]; i < win_end[members[0]]; i++)
+							if (close[i - lo]) hits[members[0]].push_back(Hit{i, sim[i - lo]});
+						continue;
 					}
+					// the block in one pass over the union window, each member's own window given: only its close pairs come back
+					std::vector<uint64_t> wl(members.size()), wh(members.size());
+					for (size_t j = 0; j < members.size(); j++) { wl[j] = win_start[members[j]] - lo; wh[j] = win_end[members[j]] - lo; }
+					std::vector<uint32_t> idx;
+					std::vector<double> sim;
+					const std::vector<uint64_t> offsets = pred.search_pairs(dset, window, qset, q_slots, wl, wh, idx, sim);
+					note_kernel();
+					for (size_t j = 0; j < members.size(); j++)
+						for (uint64_t p = offsets[j]; p < offsets[j + 1]; p++) hits[members[j]].push_back(Hit{lo + idx[p], sim[p]});
 				}
 				for (size_t qi = 0; qi < qp.size(); qi++) {
 					const Pt& query = qp[qi];
