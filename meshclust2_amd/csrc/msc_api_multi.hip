@@ -347,7 +347,11 @@ static int score_multi_impl(msc_ctx* ctx, const msc_model* model, const msc_hist
 		ctx->tiles_ms_accum = 0.f;
 		ctx->tiles_launches = 0;
 		ctx->have_timing = false;
-		ctx->last_kernel = "k_pair_sparse_mp";
+		// (msc_launch_pair_sparse_mp hands a pass whose lists fit LDS whole to k_pair_sparse_wl: the name says which of the two the
+		// queries' passes ran, "k_pair_sparse_mp+wl" when some queries fit and some do not)
+		uint64_t n_wl = 0;
+		for (uint64_t q = 0; q < n_q; q++) n_wl += msc_sparse_wl_fits(qset->hdr_host[q_slots[q]].nnz, cands->max_nnz) ? 1 : 0;
+		ctx->last_kernel = n_wl == n_q ? "k_pair_sparse_wl" : n_wl ? "k_pair_sparse_mp+wl" : "k_pair_sparse_mp";
 		ctx->last_query_tile = 1;
 		ctx->last_partial_stride = 1;
 		if ((r = ensure(ctx, ctx->err_word, sizeof(int32_t)))) return r;

@@ -6,7 +6,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from golden_util import EXACT, FEATS, VECTOR_SETS, cfg4_sequences, dense_bins, kat, load_vectors, weights_text
+from golden_util import EXACT, FEATS, VECTOR_SETS, _divergence_longdouble, cfg4_sequences, dense_bins, kat, load_vectors, weights_text
 from meshclust2_amd import api, synth
 
 pytestmark = pytest.mark.gpu
@@ -843,23 +843,6 @@ def test_sparse_k13_against_the_oracle(ctx, oracle):
 
 CFG4_WEIGHTS = weights_text("weights_cfg4_k13.txt")      # hand-written model (the reference cannot train at this size here)
 _cfg4_sequences = cfg4_sequences
-
-
-def _divergence_longdouble(name, a, b):
-    """jefferey_divergence / jensen_shannon (predict/Feature.cpp:1231-1263,984-1009) of two oracle histograms in extended
-    precision: the bins where either count differs from the pseudocount one by one, the (1, 1) term times its count"""
-    p, q = a.array(), b.array()
-    ld = np.longdouble
-    mp_, mq_ = ld(int(a.mag)), ld(int(b.mag))
-    idx = np.nonzero((p != 1) | (q != 1))[0]
-
-    def term(pp, pq):
-        if name == "jefferey_divergence":
-            return (pp - pq) * np.log(pp / pq)
-        avg = (pp + pq) / 2
-        return (pp * np.log(pp / avg) + pq * np.log(pq / avg)) / 2
-    total = np.sum(term(p[idx].astype(ld) / mp_, q[idx].astype(ld) / mq_)) + (p.size - idx.size) * term(ld(1) / mp_, ld(1) / mq_)
-    return float(total)
 
 
 @pytest.mark.parametrize("route", ["k_pair_sparse_mp", "k_pair_sparse"])
