@@ -130,6 +130,15 @@ int         msc_set_mirror_pass(msc_ctx* ctx, int on);
  * not stretched by a neighbour -- what the roofline of the product kernel is measured on. Default: on (off at start with
  * MSC_GEMM_NO_PIPE in the environment). */
 int         msc_set_block_pipe(msc_ctx* ctx, int on);
+/* msc_search_pairs sends a model that holds jefferey_divergence or jensen_shannon (every --feat slow model) through msc_score_multi block by
+ * block, whose divergence sums come from the sparse merge kernels. on = 1 keeps such a call on the matrix-core route instead (where that
+ * route's other conditions hold; a model with sim_mm or rre_k_r still takes the fallback): the two sums are evaluated per pair from exact
+ * (count, count) cell counts and the lists of large bins, in one fixed order, so a pair's value does not depend on blocks, chunks, the slot
+ * list or the windows. That order is not the merge kernels': the similarities agree with the fallback's to rounding (1e-9 relative), NOT bit
+ * for bit, and a pair whose weighted sum sits within rounding of the threshold may be listed by one route only. msc_pairs_info.route reports
+ * MSC_PAIRS_ROUTE_MATRIX, and msc_last_kernel_info's name says that the sums came from cells. msc_score_multi and every other call are
+ * unaffected. Default: off. */
+int         msc_set_pairs_div_cells(msc_ctx* ctx, int on);
 /* Number of streaming-kernel launches that pair_tiles_ms sums over (large calls are chunked). */
 int         msc_last_kernel_launches(const msc_ctx* ctx);
 /* Which streaming kernel the LAST scoring call ran (its name is copied to buf) and how many queries one HBM read of a

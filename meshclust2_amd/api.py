@@ -67,6 +67,11 @@ class Context:
         """msc_score_multi's blocks on three streams (default) or every kernel of a block on one: same results, unstretched kernel timings"""
         self.check(self.lib.msc_set_block_pipe(self.h, 1 if on else 0))
 
+    def set_pairs_div_cells(self, on):
+        """search_pairs with a divergence-statistic (--feat slow) model: the matrix-core route with the two sums from cells (on) or the
+        fallback through score_multi (default); similarities agree to rounding (1e-9 relative), not bit for bit"""
+        self.check(self.lib.msc_set_pairs_div_cells(self.h, 1 if on else 0))
+
     def device_malloc(self, nbytes):
         """plain device memory of this context's GPU (msc_device_malloc) -> integer device address; release with device_free"""
         p = C.c_void_p()
@@ -92,9 +97,9 @@ class Context:
 
     def last_kernel_info(self):
         """-> (name of the streaming kernel the last scoring call ran, queries served per HBM read of a candidate tile)"""
-        buf = C.create_string_buffer(128)
+        buf = C.create_string_buffer(256)
         n = C.c_int()
-        self.check(self.lib.msc_last_kernel_info(self.h, buf, 128, C.byref(n)))
+        self.check(self.lib.msc_last_kernel_info(self.h, buf, 256, C.byref(n)))
         return buf.value.decode(), n.value
 
     def close(self):

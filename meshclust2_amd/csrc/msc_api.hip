@@ -249,6 +249,12 @@ extern "C" int msc_set_block_pipe(msc_ctx* ctx, int on) {
 	return MSC_OK;
 }
 
+extern "C" int msc_set_pairs_div_cells(msc_ctx* ctx, int on) {
+	if (!ctx) return MSC_ERR_INVALID_ARG;
+	ctx->pairs_div_cells = on != 0;
+	return MSC_OK;
+}
+
 extern "C" int msc_set_mirror_pass(msc_ctx* ctx, int on) {
 	if (!ctx) return MSC_ERR_INVALID_ARG;
 	ctx->mirror_pass = on != 0;

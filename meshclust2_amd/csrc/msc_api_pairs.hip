@@ -2,7 +2,9 @@
 // similarity as the only output. Two routes:
 //   matrix   -- msc_score_multi's pass on the matrix cores (msc_pair_gemm.hip) per block of up to 128 queries, the classification flags left on
 //               the device, then the list kernels of pair_features.hip (k_pair_list_count / _scan / _write): the regression model is
-//               evaluated in FP64 for the listed pairs only, and nothing of size n_q x m crosses to the host.
+//               evaluated in FP64 for the listed pairs only, and nothing of size n_q x m crosses to the host. A model that holds
+//               jefferey_divergence or jensen_shannon takes it only with msc_set_pairs_div_cells: the two sums then come from (count, count)
+//               cells (k_pair_epilogue_bits_div) and agree with the fallback's to rounding, not bit for bit.
 //   fallback -- every other case: msc_score_multi one block of queries at a time (dense flags and sums of that block on the host), compacted
 //               there and copied up, so that msc_search_pairs_fetch reads one list whichever route ran.
 #include <algorithm>
@@ -68,6 +70,7 @@ struct PairsCall {
 	std::vector<uint64_t> qcount;       // pairs per query
 	uint64_t fp64 = 0;
 	bool need_emd = false;
+	bool cls_div = false, reg_div = false;          // msc_set_pairs_div_cells: the model holds a divergence statistic, its sums come from cells
 };
 
 // blocks of up to blk queries (none of one query when there are more: the product pass takes two and up), each with its union window;
@@ -197,12 +200,14 @@ int run_matrix(PairsCall& c) {
 			ea.dtype = cands->dtype;
 			ea.order = MSC_ORDER_CAND_FIRST;
 			ea.error_word = (int32_t*)ctx->err_word.p;
+			ea.kb_c_bits = cands->kb;
 			if (c.cls) {          // the flags, as msc_score_multi decides them, kept here
 				ea.model = c.cls->d;
 				ea.close_soa = flags;
-				ea.screen = screen;
+				ea.screen = screen && !c.cls_div;
+				ea.div_cells = c.cls_div;
 				HIP_TRY(ctx, msc_launch_pair_list_flags(st, ea, (unsigned long long*)(words + 2)));
-				if (!screen) c.fp64 += (uint64_t)nb * mc;
+				if (!ea.screen) c.fp64 += (uint64_t)nb * mc;
 			}
 			HIP_TRY(ctx, msc_launch_pair_list_count(st, flags, nb, mc, off, dwl, dwh, (uint32_t*)ctx->pl_counts.p));
 			uint64_t* base = n_chunks == 1 ? words : words + 1;
@@ -217,6 +222,7 @@ int run_matrix(PairsCall& c) {
 			ea.model = c.reg ? c.reg->d : nullptr;
 			ea.close_soa = nullptr;
 			ea.screen = 0;
+			ea.div_cells = c.reg_div;
 			HIP_TRY(ctx, msc_launch_pair_list_write(st, ea, flags, off, dwl, dwh, (const uint64_t*)ctx->pl_offsets.p, (uint32_t*)out_idx.p, (double*)out_sim.p));
 		}
 		if (n_chunks > 1) {          // the block's chunks were staged chunk by chunk: into the list query by query
@@ -234,8 +240,8 @@ int run_matrix(PairsCall& c) {
 	c.fp64 += open + (c.reg ? total : 0);
 	ctx->pl_n = total;
 	if (last_qn) {          // msc_last_kernel_info names the product kernel, as msc_score_multi does
-		snprintf(ctx->last_kernel_buf, sizeof ctx->last_kernel_buf, "%s<%u query rows, one matrix product per tile of presence bits%s>", msc_pair_gemm_kernel_name(), last_qn,
-		         c.need_emd ? ", emd by ranks" : ", no emd");
+		snprintf(ctx->last_kernel_buf, sizeof ctx->last_kernel_buf, "%s<%u query rows, one matrix product per tile of presence bits%s%s>", msc_pair_gemm_kernel_name(), last_qn,
+		         c.need_emd ? ", emd by ranks" : ", no emd", c.cls_div || c.reg_div ? ", divergence sums from cells" : "");
 		ctx->last_kernel = ctx->last_kernel_buf;
 		ctx->last_query_tile = (int)c.blocks.back().nq;
 		ctx->have_timing = false;
@@ -326,7 +332,9 @@ extern "C" int msc_search_pairs(msc_ctx* ctx, const msc_model* cls, const msc_mo
 		if (md) for (int i = 0; i < md->h.n_singles; i++) want |= md->h.single_flag[i];
 	c.need_emd = (want & MSC_FEAT_EMD) != 0;
 	// the matrix-core route: where msc_score_multi would put every block of this call on the product kernel, for both models at once
-	bool matrix = n_q >= 2 && !(want & (MSC_FEAT_DIV | MSC_FEAT_GROUPS)) && kb_route_fits(db, qset, c.need_emd);
+	// (a divergence statistic leaves it unless msc_set_pairs_div_cells asks for the sums from cells; the 4-bin group statistics always do)
+	const uint64_t declines = ctx->pairs_div_cells ? MSC_FEAT_GROUPS : MSC_FEAT_DIV | MSC_FEAT_GROUPS;
+	bool matrix = n_q >= 2 && !(want & declines) && kb_route_fits(db, qset, c.need_emd);
 	if (matrix) {
 		if ((r = ensure_kb(ctx, db)) || (r = ensure_kb(ctx, qset))) return r;
 		matrix = db->kb && qset->kb && !db->kb_has_zero && !qset->kb_has_zero;
@@ -343,6 +351,13 @@ extern "C" int msc_search_pairs(msc_ctx* ctx, const msc_model* cls, const msc_mo
 		if ((r = ensure_ranks(ctx, db)) || (r = ensure_ranks(ctx, qset))) return r;
 		matrix = db->ranks && qset->ranks;
 	}
+	if (matrix)
+		for (int i = 0; i < 2; i++) {
+			const msc_model* md = i ? reg : cls;
+			uint64_t w = 0;
+			if (md) for (int j = 0; j < md->h.n_singles; j++) w |= md->h.single_flag[j];
+			(i ? c.reg_div : c.cls_div) = (w & MSC_FEAT_DIV) != 0;
+		}
 	if (!matrix) plan_blocks(c, 128);
 	r = matrix ? run_matrix(c) : run_fallback(c);
 	if (r) { ctx->pl_n = 0; return r; }

@@ -23,7 +23,7 @@ struct msc_ctx {
 	float tiles_ms_accum = 0.f;
 	int tiles_launches = 0;
 	const char* last_kernel = "";            // streaming kernel of the last scoring call
-	char last_kernel_buf[96] = "";           // (where the Q x M pass composes the name of the form it ran)
+	char last_kernel_buf[160] = "";          // (where the Q x M pass composes the name of the form it ran)
 	int last_query_tile = 1;                 // queries one HBM read of a candidate tile served in it
 	std::string err;
 	char dev_name[128] = {0};
@@ -63,6 +63,7 @@ struct msc_ctx {
 	int close_pp_next = 0;
 	bool copy_pending = false;
 	bool block_pipe = true;                // msc_set_block_pipe: the blocks of msc_score_multi on three streams
+	bool pairs_div_cells = false;          // msc_set_pairs_div_cells: msc_search_pairs keeps divergence-statistic models on the matrix-core route
 	bool mirror_pass = true;               // msc_set_mirror_pass: a dense set's 1 x M passes merge the lists of its sparse mirror
 	bool packed_on_device = false;         // msc_hist_build_packed_dev: the 2-bit stream of the build in progress is device memory
 	bool no_kb_now = false;                // msc_score_multi: this block is taken by the older routes (its hot list would be too long)
@@ -129,7 +130,7 @@ struct msc_hist_set {
 	mutable bool digest_unavailable = false;      // allocation failed once: do not retry every pass
 	// presence-bit mirror (msc_pair_gemm.hip, msc_kbits.h): one BIT per bin = [count >= 2], slots blocked by 32 -- the B operand of the
 	// int8 product of the Q x M pass -- and beside it the lists of large bins (count - 1 >= 2) that make the pass exact for any counts:
-	// mb[slot][mb_pitch] = (bin, count - 1), unordered; mb_n = entries per slot (also on the host: the size of a query block's hot list is
+	// mb[slot][mb_pitch] = (bin, count - 1), sorted by bin; mb_n = entries per slot (also on the host: the size of a query block's hot list is
 	// known without a read-back). slots [kb_lo, kb_hi) are stale (mark_stale)
 	mutable uint8_t* kb = nullptr;
 	mutable uint64_t kb_lo = 0, kb_hi = 0;

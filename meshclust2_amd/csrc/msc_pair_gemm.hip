@@ -19,7 +19,7 @@
 // bits of that step sit in its registers (P2: one atomic add per (entry, candidate that holds the k-mer) -- 0.4 % of the candidates at
 // k = 9). Exact in integers for any counts of the narrow range (<= 8191).
 //
-//   kb mirror            msc_kbits.h: a bit per bin, slots blocked by 32; + the lists of large bins (mb, pitch entries per slot, unordered)
+//   kb mirror            msc_kbits.h: a bit per bin, slots blocked by 32; + the lists of large bins (mb, pitch entries per slot, sorted by bin)
 //   k_kb_gather          the queries' side of a block of <= QN queries: their bits as the nibble tiles the product copies into LDS, and
 //                        transposed as two bit planes per bin ("the query holds this k-mer", "... more than once") for the epilogue
 //   k_hot_*              the queries' large bins bucketed by 128-bin step: (bin, query row, e - 1); the fill also sets the second plane
@@ -78,6 +78,24 @@ __global__ void __launch_bounds__(256) k_kb_build(const T* __restrict__ bins, ui
 	}
 	*reinterpret_cast<uint16_t*>(kb + msc_kb_offset(slot, at, nbins)) = (uint16_t)hw;
 	if (zero) atomicOr(&flags[0], 1);
+}
+
+// The lists of the slots just built, sorted by bin (one thread per slot, insertion sort: ~2 entries per 1 kb sequence at k = 9). The integer
+// corrections do not care about the order; the divergence sums of msc_search_pairs (bits_pair_div in pair_features.hip) add their FP64 terms
+// in list order, and k_kb_build's atomics hand the positions out in whatever order the threads arrive -- sorted, a pair's value is the
+// same from build to build.
+__global__ void __launch_bounds__(256) k_kb_sort(uint2* __restrict__ mb, const uint32_t* __restrict__ mb_n, uint32_t pitch, uint64_t first_slot, uint64_t n_slots) {
+	const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n_slots) return;
+	const uint64_t slot = first_slot + i;
+	uint2* l = mb + slot * pitch;
+	const uint32_t n = mb_n[slot] < pitch ? mb_n[slot] : pitch;
+	for (uint32_t j = 1; j < n; j++) {
+		const uint2 v = l[j];
+		uint32_t k = j;
+		while (k > 0 && l[k - 1].x > v.x) { l[k] = l[k - 1]; k--; }
+		l[k] = v;
+	}
 }
 
 // ------------------------------------------------------------------------------------------------ the queries' side of a block
@@ -366,6 +384,7 @@ hipError_t msc_launch_kb_build(hipStream_t st, const MscLayout& L, int dtype, co
 	else if (dtype == 16) k_kb_build<uint16_t><<<grid, dim3(256), 0, st>>>((const uint16_t*)bins, L.padded_bins, kb, first_slot, n_slots, (uint2*)mb, mb_n, pitch, flags);
 	else if (dtype == 32) k_kb_build<uint32_t><<<grid, dim3(256), 0, st>>>((const uint32_t*)bins, L.padded_bins, kb, first_slot, n_slots, (uint2*)mb, mb_n, pitch, flags);
 	else return hipErrorInvalidValue;
+	k_kb_sort<<<dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, st>>>((uint2*)mb, mb_n, pitch, first_slot, n_slots);
 	return hipGetLastError();
 }
 

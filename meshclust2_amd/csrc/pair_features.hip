@@ -1217,6 +1217,154 @@ __device__ __forceinline__ void bits_pair_totals(const MscEpilogueArgs& a, uint3
 	t.emd = emd;
 }
 
+// ---------------------------------------------------------------------------------------- the divergence statistics from cells
+// msc_search_pairs with msc_set_pairs_div_cells: jefferey_divergence / jensen_shannon (predict/Feature.cpp:1235-1262, 988-1008) of a pair on
+// the matrix-core route, without a walk of the bins. With term(a, b) the bin's term for the counts a (candidate) and b (query) -- rk_div_term
+// of msc_ranks_pass.hip --, T11 = term(1, 1) and F(a, b) = term(a, b) - T11:
+//     statistic = 4^k T11 + sum over the bins either sequence holds of F(a_i, b_i)
+// Outside the two lists of large bins (count >= 3) every count is 1 or 2, so three integer cell counts cover those bins:
+//     n22 = P1 - #{i in L_c : b_i >= 2} - #{i in L_q \ L_c : a_i = 2}                  P1 = the product's output: the shared k-mers
+//     n21 = (D_c - |L_c|) - n22 - #{i in L_q \ L_c : a_i = 2}                          D = the distinct k-mers of a sequence
+//     n12 = (D_q - |L_q|) - n22 - #{i in L_c : b_i = 2}                                  = (sum - 4^k) - sum over its list of (e - 1)
+// and the bins of the lists get their F(a_i, b_i) on the spot: b_i of a candidate's large bin from the queries' two bit planes (and the
+// query's list where the second is set), a_i of a query's large bin from the candidate's bit of the mirror (msc_kbits.h). term(2, 2) =
+// 2 T11, so F(2, 2) = T11. The counts are exact integers. The FP64 part runs in ONE order per pair -- the candidate's list, then the query's
+// entries the candidate's list does not hold, both in bin order (k_kb_sort keeps the lists sorted), then the three cells, then 4^k T11 --,
+// so a pair's value does not depend on its block, its chunk of candidates, the slot list or the windows. It is NOT the merge kernels' order
+// (sparse.hip: the union of the two lists of stored bins): the two agree to rounding, not bit for bit.
+//
+// A term in the form evaluated here, with x = 1 / magnitude of the reference call's first argument, y = of its second, pp = p x, pq = q y,
+// r = pq / pp and log(pp / pq) = log(p / q) + log(x / y) (the second logarithm once per pair, the first a constant for the cells):
+//     jd = (pp - pq) log(pp / pq)        js = pp log(pp / avg) + pq log(pq / avg) = pp ((1 + r) log(2 / (1 + r)) - r log(pp / pq))
+// -- one division and one logarithm per term where the textbook form takes three of each.
+struct DivPair {
+	double x, y, lam;          // lam = log(x / y)
+};
+__device__ __forceinline__ void div_cell_term(const DivPair& d, double p, double q, double log_p_over_q, double& jd, double& js) {
+	const double pp = p * d.x, pq = q * d.y, l = log_p_over_q + d.lam, r = pq / pp;
+	jd = (pp - pq) * l;
+	js = pp * ((1.0 + r) * log(2.0 / (1.0 + r)) - r * l);
+}
+
+// t.jd / t.js of one (candidate, query) pair. Wave-uniform: slot (the candidate's slot in its set), cmb, c_n; per lane: qq (its query row),
+// qmb / q_n (its query's list), q_twos = D_q - |L_q| (the query's bins of count 2), p1 = the product's output summed over the slices
+__device__ __forceinline__ void bits_pair_div(const MscEpilogueArgs& a, uint64_t slot, const uint2* cmb, uint32_t c_n, uint32_t qq, const uint2* qmb, uint32_t q_n, int64_t q_twos,
+                                              int64_t p1, const Side& cand, const Side& qry, PairTotals& t) {
+	const bool cf = a.order == MSC_ORDER_CAND_FIRST;
+	const double mag_c = (double)cand.mag, mag_q = (double)qry.mag;
+	DivPair d;
+	d.x = 1.0 / (cf ? mag_c : mag_q);
+	d.y = 1.0 / (cf ? mag_q : mag_c);
+	d.lam = log(cf ? mag_q / mag_c : mag_c / mag_q);
+	double t11_jd, t11_js;
+	div_cell_term(d, 1.0, 1.0, 0.0, t11_jd, t11_js);
+	double jd = 0.0, js = 0.0;
+	auto spot = [&](uint32_t count_c, uint32_t count_q) {
+		const double p = (double)(cf ? count_c : count_q), q = (double)(cf ? count_q : count_c);
+		double tj, ts;
+		div_cell_term(d, p, q, log(p / q), tj, ts);
+		jd += tj - t11_jd;
+		js += ts - t11_js;
+	};
+	const uint32_t* qt = reinterpret_cast<const uint32_t*>(a.kb_qT);
+	int64_t c_extra = 0, b_ge2 = 0, b_eq2 = 0;
+	for (uint32_t i = 0; i < c_n; i++) {          // the candidate's large bins: the query's count from its bit planes and its list
+		const uint2 en = cmb[i];
+		c_extra += (int64_t)en.y - 1;
+		const uint32_t present = (qt[msc_qt_word(en.x, 0, qq, a.kb_qn)] >> (qq & 31)) & 1u, large = (qt[msc_qt_word(en.x, 1, qq, a.kb_qn)] >> (qq & 31)) & 1u;
+		uint32_t b = 1 + present;
+		if (large)
+			for (uint32_t t_ = 0; t_ < q_n; t_++) if (qmb[t_].x == en.x) { b = qmb[t_].y + 1; break; }
+		b_ge2 += b >= 2;
+		b_eq2 += b == 2;
+		spot(en.y + 1, b);
+	}
+	int64_t a_eq2 = 0;
+	uint32_t cj = 0;
+	for (uint32_t t_ = 0; t_ < q_n; t_++) {          // the query's large bins the candidate's list does not hold (both sorted by bin: a merge)
+		const uint2 en = qmb[t_];
+		while (cj < c_n && cmb[cj].x < en.x) cj++;
+		if (cj < c_n && cmb[cj].x == en.x) continue;
+		const uint32_t bit = (*reinterpret_cast<const uint16_t*>(a.kb_c_bits + msc_kb_offset(slot, en.x, a.nbins)) >> (en.x & 15)) & 1u;
+		a_eq2 += bit;
+		spot(1 + bit, en.y + 1);
+	}
+	const int64_t c_twos = (int64_t)(cand.sum - a.nbins) - c_extra - (int64_t)c_n;          // D_c - |L_c|
+	const int64_t n22 = p1 - b_ge2 - a_eq2, n21 = c_twos - n22 - a_eq2, n12 = q_twos - n22 - b_eq2;
+	constexpr double kLn2 = 0.693147180559945309417;
+	double f21_jd, f21_js, f12_jd, f12_js;          // (candidate 2, query 1) and (candidate 1, query 2)
+	div_cell_term(d, cf ? 2.0 : 1.0, cf ? 1.0 : 2.0, cf ? kLn2 : -kLn2, f21_jd, f21_js);
+	div_cell_term(d, cf ? 1.0 : 2.0, cf ? 2.0 : 1.0, cf ? -kLn2 : kLn2, f12_jd, f12_js);
+	const double N = (double)a.nbins;
+	t.jd = jd + (double)n22 * t11_jd + (double)n21 * (f21_jd - t11_jd) + (double)n12 * (f12_jd - t11_jd) + N * t11_jd;
+	t.js = js + (double)n22 * t11_js + (double)n21 * (f21_js - t11_js) + (double)n12 * (f12_js - t11_js) + N * t11_js;
+}
+
+// what depends on the query alone: its list of large bins and D_q - |L_q|
+__device__ __forceinline__ void bits_div_query(const MscEpilogueArgs& a, uint32_t q_slot, const Side& qry, const uint2*& qmb, uint32_t& q_n, int64_t& q_twos) {
+	qmb = reinterpret_cast<const uint2*>(a.kb_q_mb) + (uint64_t)q_slot * a.kb_q_pitch;
+	q_n = a.kb_q_mb_n[q_slot] < a.kb_q_pitch ? a.kb_q_mb_n[q_slot] : a.kb_q_pitch;
+	int64_t extra = 0;
+	for (uint32_t t_ = 0; t_ < q_n; t_++) extra += (int64_t)qmb[t_].y - 1;
+	q_twos = (int64_t)(qry.sum - a.nbins) - extra - (int64_t)q_n;
+}
+
+// The flags of a block of msc_search_pairs whose classification model holds a divergence statistic (msc_set_pairs_div_cells): the integer
+// reductions as k_pair_epilogue_bits forms them, the two sums from cells (bits_pair_div) and the model in FP64 -- such a model has no f32
+// image, so every pair is an FP64 evaluation. The layout of k_pair_epilogue_bits_screen: a wave takes kDivChunk consecutive candidates x 64
+// queries, lane = query, the candidate's record and list wave-uniform (scalar cache), the queries' side -- slot, scalar record, list,
+// D_q - |L_q| -- fetched once per chunk.
+// -Rpass-analysis=kernel-resource-usage (gfx950, two waves per SIMD asked of the compiler): 165 VGPRs, no AGPRs, 104 SGPRs with 75 more
+// spilled into VGPR lanes, no VGPR spill, no LDS: 3 waves per SIMD. (k_pair_epilogue_bits with the FP64 evaluation alone: 116 VGPRs, 4 waves;
+// the difference is the list walks and the logarithms of bits_pair_div kept live beside epilogue_eval's statistics.)
+template <uint32_t kDivChunk>
+__global__ void __launch_bounds__(kBlock, 2) k_pair_epilogue_bits_div(const MscEpilogueArgs a) {
+	const uint32_t lane = threadIdx.x & 63;
+	const uint32_t groups = (a.n_queries + 63) / 64;
+	const uint32_t chunks = (a.m_per_query + kDivChunk - 1) / kDivChunk;
+	const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
+	if (w >= chunks * groups) return;
+	const uint32_t c0 = (w / groups) * kDivChunk, q = (w % groups) * 64 + lane;
+	const uint32_t nc = a.m_per_query - c0 < kDivChunk ? a.m_per_query - c0 : kDivChunk;
+	const bool live = q < a.n_queries;
+	const uint32_t qq = live ? q : 0;
+	const uint32_t q_slot = a.q_slots[qq];
+	const MscSlotScalars* qs = reinterpret_cast<const MscSlotScalars*>(a.qset_scalars + (uint64_t)q_slot * a.q_scalar_stride);
+	const Side qry{qs->mag, qs->length, qs->sum, qs->sum_sq};
+	const uint2* qmb;
+	uint32_t q_n;
+	int64_t q_twos;
+	bits_div_query(a, q_slot, qry, qmb, q_n, q_twos);
+	const uint32_t ns = a.kb_slices, estride = a.emd_stride ? a.emd_stride : 64;
+	int64_t p1[kDivChunk], diff[kDivChunk];          // the chunk's loads in flight together
+	uint64_t emd[kDivChunk];
+#pragma unroll
+	for (uint32_t j = 0; j < kDivChunk; j++) {
+		const uint32_t ci = c0 + (j < nc ? j : nc - 1);
+		int64_t v = a.kb_min[(uint64_t)ci * a.kb_qn + qq];
+		for (uint32_t s_ = 1; s_ < ns; s_++) v += a.kb_min[((uint64_t)s_ * a.m_per_query + ci) * a.kb_qn + qq];
+		p1[j] = v;
+		diff[j] = a.kb_diff ? a.kb_diff[(uint64_t)ci * a.kb_qn + qq] : 0;
+		emd[j] = a.emd_ranks ? a.emd_ranks[(uint64_t)ci * estride + qq] : 0;
+	}
+#pragma unroll
+	for (uint32_t j = 0; j < kDivChunk; j++) {
+		if (j >= nc) break;
+		const uint32_t ci = c0 + j;
+		const uint32_t slot_rel = a.cand_slots ? a.cand_slots[ci] : ci;
+		const uint64_t slot = a.cand_slots ? (uint64_t)slot_rel : a.kb_first + ci;
+		const uint2* cmb = reinterpret_cast<const uint2*>(a.kb_c_mb) + slot * a.kb_c_pitch;
+		const uint32_t c_n = a.kb_c_mb_n[slot] < a.kb_c_pitch ? a.kb_c_mb_n[slot] : a.kb_c_pitch;
+		const MscSlotScalars* cs = reinterpret_cast<const MscSlotScalars*>(a.cand_scalars + (uint64_t)slot_rel * a.cand_scalar_stride);
+		const Side cand{cs->mag, cs->length, cs->sum, cs->sum_sq};
+		PairTotals t{0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+		bits_pair_totals(a, ci, cmb, c_n, qq, q_slot, p1[j], diff[j], emd[j], cand, qry, t);
+		bits_pair_div(a, slot, cmb, c_n, qq, qmb, q_n, q_twos, p1[j], cand, qry, t);
+		if (live) epilogue_eval(a, q * a.m_per_query + ci, ci, q, cand, qry, a.min_len, a.max_len, t);
+		__builtin_amdgcn_sched_barrier(0);          // (one candidate's evaluation at a time)
+	}
+}
+
 __global__ void __launch_bounds__(kBlock) k_pair_epilogue_bits(const MscEpilogueArgs a) {
 	const uint32_t lane = threadIdx.x & 63;
 	const uint32_t groups = (a.n_queries + 63) / 64;
@@ -2561,8 +2709,11 @@ __global__ void __launch_bounds__(1024) k_pair_list_scan(const uint32_t* __restr
 // [0, 1] as p_predict does (predict/Predictor.cpp:293-298). Few pairs are listed (one in thousands): a separate launch keeps the FP64
 // evaluation's registers out of the flag kernels, and its lanes idle where nothing is listed. (Four waves per SIMD asked of the compiler:
 // unbounded, the evaluation took 200 registers and two waves per SIMD for a kernel that mostly reads flags.)
-template <bool REG>
-__global__ void __launch_bounds__(kBlock, 4) k_pair_list_write(const MscEpilogueArgs a, const uint8_t* __restrict__ flags, uint64_t first,
+// DIV (msc_set_pairs_div_cells, a regression model with a divergence statistic): the two sums from cells as k_pair_epilogue_bits_div forms them.
+// Bounded to four waves like the others it took 128 registers and spilled 77 more (312 bytes of scratch per lane); asked for two it takes 210 VGPRs without a spill (2 waves
+// per SIMD) -- its lanes idle where nothing is listed, and every listed pair is a whole FP64 evaluation.
+template <bool REG, bool DIV = false>
+__global__ void __launch_bounds__(kBlock, DIV ? 2 : 4) k_pair_list_write(const MscEpilogueArgs a, const uint8_t* __restrict__ flags, uint64_t first,
                                                             const uint64_t* __restrict__ win_lo, const uint64_t* __restrict__ win_hi,
                                                             const unsigned long long* __restrict__ offsets, uint32_t* __restrict__ out_idx,
                                                             double* __restrict__ out_sim) {
@@ -2598,6 +2749,13 @@ __global__ void __launch_bounds__(kBlock, 4) k_pair_list_write(const MscEpilogue
 				const uint64_t emd = a.emd_ranks ? a.emd_ranks[(uint64_t)c * (a.emd_stride ? a.emd_stride : 64) + q] : 0;
 				PairTotals tt{0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 				bits_pair_totals(a, c, cmb, c_n, q, q_slot, min_e, diff_e, emd, cand, qry, tt);
+				if constexpr (DIV) {
+					const uint2* qmb;
+					uint32_t q_n;
+					int64_t q_twos;
+					bits_div_query(a, q_slot, qry, qmb, q_n, q_twos);
+					bits_pair_div(a, slot, cmb, c_n, q, qmb, q_n, q_twos, min_e, cand, qry, tt);
+				}
 				MscPairOut po;
 				epilogue_eval(a, q * mc + c, c, q, cand, qry, a.min_len, a.max_len, tt, &po);
 				sim = po.sum < 0 ? 0.0 : (po.sum > 1 ? 1.0 : po.sum);
@@ -2648,6 +2806,13 @@ uint32_t msc_pair_list_tiles(uint32_t mc) { return (mc + kListTile - 1) / kListT
 // the classification flags of a block on the matrix-core route, left on the device (a.close_soa): the f32 screen and the FP64 pass over the
 // pairs it left open when a.screen is set (counted into *open), k_pair_epilogue_bits otherwise
 hipError_t msc_launch_pair_list_flags(hipStream_t st, const MscEpilogueArgs& a, unsigned long long* open) {
+	if (a.div_cells) {          // a model with a divergence statistic: the sums from cells, every pair in FP64
+		if (!a.kb_min || !a.model || !a.close_soa || !a.kb_c_bits || a.n_queries < 2 || a.n_queries > a.kb_qn || !a.kb_c_mb || !a.kb_q_mb || !a.kb_qT) return hipErrorInvalidValue;
+		constexpr uint32_t chunk = 4;
+		const uint64_t cw = (uint64_t)((a.m_per_query + chunk - 1) / chunk) * ((a.n_queries + 63) / 64);
+		hipLaunchKernelGGL(k_pair_epilogue_bits_div<chunk>, dim3((unsigned)((cw + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, st, a);
+		return hipGetLastError();
+	}
 	if (!a.screen || !a.kb_min || !a.model || !a.close_soa || a.sum_soa || a.csum_soa || a.raw_out || a.pair_out) return msc_launch_epilogue(st, a);
 	if (a.n_queries < 2 || a.n_queries > a.kb_qn || !a.kb_c_mb || !a.kb_q_mb || !a.kb_qT) return hipErrorInvalidValue;
 	constexpr uint32_t chunk = 4;          // (as msc_launch_epilogue takes it)
@@ -2682,7 +2847,10 @@ hipError_t msc_launch_pair_list_write(hipStream_t st, const MscEpilogueArgs& a, 
 	if (waves == 0) return hipSuccess;
 	if (a.model && (a.n_queries > a.kb_qn || !a.kb_min || !a.kb_c_mb || !a.kb_q_mb || !a.kb_qT)) return hipErrorInvalidValue;
 	const dim3 grid((unsigned)((waves + kWavesPerBlock - 1) / kWavesPerBlock));
-	if (a.model) hipLaunchKernelGGL(k_pair_list_write<true>, grid, dim3(kBlock), 0, st, a, flags, first, win_lo, win_hi, (const unsigned long long*)offsets, out_idx, out_sim);
+	if (a.model && a.div_cells) {
+		if (!a.kb_c_bits) return hipErrorInvalidValue;
+		hipLaunchKernelGGL((k_pair_list_write<true, true>), grid, dim3(kBlock), 0, st, a, flags, first, win_lo, win_hi, (const unsigned long long*)offsets, out_idx, out_sim);
+	} else if (a.model) hipLaunchKernelGGL(k_pair_list_write<true>, grid, dim3(kBlock), 0, st, a, flags, first, win_lo, win_hi, (const unsigned long long*)offsets, out_idx, out_sim);
 	else hipLaunchKernelGGL(k_pair_list_write<false>, grid, dim3(kBlock), 0, st, a, flags, first, win_lo, win_hi, (const unsigned long long*)offsets, out_idx, out_sim);
 	return hipGetLastError();
 }

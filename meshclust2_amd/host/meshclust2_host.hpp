@@ -39,6 +39,8 @@ public:
 	Context& operator=(const Context&) = delete;
 	msc_ctx* get() const { return h_; }
 	void set_kernel_timing(bool on) { check(msc_set_kernel_timing(h_, on ? 1 : 0)); }
+	// search_pairs with a divergence-statistic model on the matrix-core route (sums from cells; agrees with the default to rounding, not bit for bit)
+	void set_pairs_div_cells(bool on) { check(msc_set_pairs_div_cells(h_, on ? 1 : 0)); }
 	void check(int rc) const { if (rc != MSC_OK) throw Error(rc, msc_last_error(h_)); }
 private:
 	msc_ctx* h_ = nullptr;

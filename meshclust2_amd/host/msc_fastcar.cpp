@@ -6,7 +6,7 @@
 // std::sort by length, bin_search, format_header and the output formatting follow fastcar/FC_Runner.cpp:389-471,
 // 560-611 at one thread (one output file "<prefix>0"); training is out of scope, a two-block weights file is required.
 //
-//   msc_fastcar <db.fa> --query <q.fa> --recover weights.txt [--output output] [--chunk 10000] [--no-format] [--device 0]
+//   msc_fastcar <db.fa> --query <q.fa> --recover weights.txt [--output output] [--chunk 10000] [--no-format] [--device 0] [--div-cells]
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -91,7 +91,7 @@ int main(int argc, char** argv) {
 	std::vector<std::string> files, qfiles;
 	std::string weights, output = "output";
 	size_t chunk = 10000, qblock = 16;
-	bool format = true, sparse = false, report_kernels = false;
+	bool format = true, sparse = false, report_kernels = false, div_cells = false;
 	int device = 0;
 	for (int i = 1; i < argc; i++) {
 		std::string a = argv[i];
@@ -105,11 +105,12 @@ int main(int argc, char** argv) {
 		else if (a == "--threads" || a == "-t") need("--threads");
 		else if (a == "--kernels") report_kernels = true;   // after the run: the streaming kernels the library picked for the scoring passes, on stderr
 		else if (a == "--sparse") sparse = true;        // sparse histogram layout (required for k >= 13; also the faster one for --feat slow models)
+		else if (a == "--div-cells") div_cells = true;  // msc_set_pairs_div_cells: a --feat slow model's query blocks on the matrix-core route
 		else if (a == "--device") device = std::atoi(need("--device").c_str());
 		else files.push_back(a);
 	}
 	if (files.empty() || qfiles.empty() || weights.empty()) {
-		std::fprintf(stderr, "usage: %s <db.fa> --query <q.fa> --recover weights.txt [--output prefix] [--chunk 10000] [--no-format] [--sparse]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s <db.fa> --query <q.fa> --recover weights.txt [--output prefix] [--chunk 10000] [--no-format] [--sparse] [--div-cells]\n", argv[0]);
 		return 1;
 	}
 	try {
@@ -126,6 +127,7 @@ int main(int argc, char** argv) {
 			}
 		}
 		msc::Context ctx(device);
+		ctx.set_pairs_div_cells(div_cells);
 		msc::Predictor pred(ctx, weights);
 		std::vector<Rec> db, queries;
 		for (const auto& f : files) { auto r = read_fasta(f); db.insert(db.end(), r.begin(), r.end()); }
