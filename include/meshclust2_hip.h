@@ -207,6 +207,22 @@ int msc_hist_build_packed_dev(msc_ctx* ctx, msc_hist_set* set, uint64_t first_sl
                               const uint32_t* seg_seq, const uint64_t* seg_start, const uint64_t* seg_end, uint64_t n_segs,
                               const uint64_t* eff_len, const uint64_t* one_mers);
 
+/* Diagnostics of the builders (tests, profiling): which builder the LAST msc_hist_build* call on this set ran, and the set's current
+ * bounds. `builder` (nullable) receives one of these fixed names, "" before the first build:
+ *   "k_build_lds"                  dense, 4^k <= 16384 bins: the whole histogram counted in LDS
+ *   "k_build_sort"                 dense, larger histograms, <= 32768 k-mers per sequence: the k-mer indices sorted in LDS
+ *   "k_count"                      dense, everything else: k_fill + k_count + k_finalize + k_prefix
+ *   "k_sparse_build_sort"          sparse, <= 32768 k-mers per sequence: the lists straight from the sorted k-mer indices
+ *   "k_count+k_sparse_write"       sparse, everything else: dense scratch slots (built by k_count) compacted by k_sparse_count / k_sparse_write
+ *   "k_build_sort+k_sparse_write", "k_build_lds+k_sparse_write"
+ *                                  the same where the dense rule gives the scratch slots to another builder (short
+ *                                  sequences under MSC_NO_SORT_BUILD, the switch that turns k_sparse_build_sort off)
+ * A call that is refused before anything is launched leaves the name as it was. max_count / max_sum (nullable): the largest bin and the
+ * largest sum of bins over every slot ever written -- what selects the count width and the wide kernels of the scoring calls; never
+ * below the true maxima of the set's slots. max_nnz: the longest list ever stored in a sparse set, 0 for a dense set. */
+int msc_hist_set_build_info(const msc_hist_set* set, char* builder, size_t cap,
+                            uint64_t* max_count, uint64_t* max_sum, uint64_t* max_nnz);
+
 /* Debug / parity: bins in NATURAL k-mer order (first base most significant), 4^k * dtype/8 bytes. */
 int msc_hist_download(msc_ctx* ctx, const msc_hist_set* set, uint64_t slot, void* bins_out);
 int msc_hist_upload(msc_ctx* ctx, msc_hist_set* set, uint64_t slot, const void* bins, uint64_t length,

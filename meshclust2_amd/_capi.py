@@ -70,6 +70,7 @@ PROTOTYPES = {
     "msc_hist_build": (_int, [_vp, _vp, _u64, _u64, C.POINTER(C.c_char_p), _pu64, _int]),
     "msc_hist_build_packed": (_int, [_vp, _vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp]),
     "msc_hist_build_packed_dev": (_int, [_vp, _vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp]),
+    "msc_hist_set_build_info": (_int, [_vp, C.c_char_p, C.c_size_t, _pu64, _pu64, _pu64]),
     "msc_hist_download": (_int, [_vp, _vp, _u64, _vp]),
     "msc_hist_upload": (_int, [_vp, _vp, _u64, _vp, _u64, _pu64]),
     "msc_hist_info_get": (_int, [_vp, _vp, _u64, C.POINTER(HistInfo)]),

@@ -191,6 +191,13 @@ class HistogramSet:
         self.ctx.check(self.ctx.lib.msc_hist_build_packed_dev(self.ctx.h, self.h, first_slot, n_seqs, C.c_void_p(int(packed_dev_ptr)), int(n_bases), _ptr(seg_seq),
                                                               _ptr(seg_start), _ptr(seg_end), len(seg_seq), _ptr(eff_len), _ptr(one_mers)))
 
+    def build_info(self):
+        """-> (name of the builder the last build* call on this set ran, max_count, max_sum, max_nnz): msc_hist_set_build_info"""
+        buf = C.create_string_buffer(64)
+        mc, ms, mn = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self.ctx.check(self.ctx.lib.msc_hist_set_build_info(self.h, buf, 64, C.byref(mc), C.byref(ms), C.byref(mn)))
+        return buf.value.decode(), mc.value, ms.value, mn.value
+
     def download(self, slot):
         out = np.zeros(self.nbins, dtype=NP_T[self.dtype])
         self.ctx.check(self.ctx.lib.msc_hist_download(self.ctx.h, self.h, slot, _ptr(out)))

@@ -61,66 +61,97 @@ __device__ __forceinline__ uint32_t rev2(uint32_t x) {
 	return ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
 }
 
-template <typename T, bool SAT>
-__device__ __forceinline__ void bump(T* bins, uint64_t elem, uint64_t* overflow_word) {
+// one occurrence, no saturation possible (no sequence of the batch has max(T) - 1 k-mers)
+template <typename T>
+__device__ __forceinline__ void bump(T* bins, uint64_t elem) {
+	if constexpr (sizeof(T) == 8) {
+		atomicAdd(reinterpret_cast<unsigned long long*>(bins) + elem, 1ull);
+	} else {
+		// 8/16/32-bit bins live inside a 32-bit word; counts cannot carry into a neighbour unless they saturate
+		const uint64_t byte_off = elem * sizeof(T);
+		atomicAdd(reinterpret_cast<uint32_t*>(bins) + (byte_off >> 2), 1u << ((uint32_t)(byte_off & 3) * 8));
+	}
+}
+
+// cnt occurrences of one bin, stopping at max(T) exactly as cnt saturating increments one after the other would
+// (wholesaleIncrementNoOverflow): a compare-and-swap, so that a full bin never carries into its neighbour
+template <typename T>
+__device__ __forceinline__ void bump_sat(T* bins, uint64_t elem, uint32_t cnt, uint64_t* overflow_word) {
 	if constexpr (sizeof(T) == 8) {
 		unsigned long long* a = reinterpret_cast<unsigned long long*>(bins) + elem;
-		if constexpr (SAT) {
-			unsigned long long old = *a;
-			while (true) {
-				if (old == ~0ull) { *overflow_word = 1; return; }
-				unsigned long long prev = atomicCAS(a, old, old + 1);
-				if (prev == old) return;
-				old = prev;
-			}
-		} else {
-			atomicAdd(a, 1ull);
+		unsigned long long old = *a;
+		while (true) {
+			const unsigned long long room = ~0ull - old, add = cnt < room ? cnt : room;
+			if (add < cnt) *overflow_word = 1;           // (bins only grow: what does not fit now never will)
+			if (add == 0) return;
+			const unsigned long long prev = atomicCAS(a, old, old + add);
+			if (prev == old) return;
+			old = prev;
 		}
 	} else {
-		// 8/16/32-bit bins live inside a 32-bit word; counts cannot carry into a neighbour unless they
-		// saturate, which the SAT variant excludes with a compare-and-swap.
 		const uint64_t byte_off = elem * sizeof(T);
 		uint32_t* a = reinterpret_cast<uint32_t*>(bins) + (byte_off >> 2);
 		const uint32_t shift = (uint32_t)(byte_off & 3) * 8;
 		const uint32_t mask = sizeof(T) == 4 ? 0xffffffffu : ((1u << (8 * sizeof(T))) - 1u);
-		if constexpr (SAT) {
-			uint32_t old = *a;
-			while (true) {
-				if (((old >> shift) & mask) == mask) { *overflow_word = 1; return; }
-				uint32_t prev = atomicCAS(a, old, old + (1u << shift));
-				if (prev == old) return;
-				old = prev;
-			}
-		} else {
-			atomicAdd(a, 1u << shift);
+		uint32_t old = *a;
+		while (true) {
+			const uint32_t room = mask - ((old >> shift) & mask), add = cnt < room ? cnt : room;
+			if (add < cnt) *overflow_word = 1;
+			if (add == 0) return;
+			const uint32_t prev = atomicCAS(a, old, old + (add << shift));
+			if (prev == old) return;
+			old = prev;
 		}
 	}
 }
 
+// SAT: consecutive k-mers of a wave that fall into the same bin (a homopolymer, a tandem repeat) are added by the first of their lanes
+// in one compare-and-swap. One swap per k-mer made 65 535 lanes retry against each other on the bin of a 65 kb homopolymer: 5.4 s for
+// that one sequence; the result is the same, increment by increment.
 template <typename T, bool SAT>
 __global__ void __launch_bounds__(kBlock) k_count(T* __restrict__ bins, uint8_t* __restrict__ scalars, uint64_t scalar_stride,
                                                   uint64_t slot_elems, uint64_t first_slot, int k, uint32_t E, uint32_t R,
                                                   const uint32_t* __restrict__ packed, const uint32_t* __restrict__ seg_seq,
                                                   const uint64_t* __restrict__ seg_start, const uint64_t* __restrict__ kmer_off,
                                                   uint64_t n_segs, uint64_t total_kmers) {
-	for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total_kmers; g += (uint64_t)gridDim.x * blockDim.x) {
-		// segment j with kmer_off[j] <= g < kmer_off[j+1]
-		uint64_t lo = 0, hi = n_segs;
-		while (hi - lo > 1) {
-			uint64_t mid = (lo + hi) >> 1;
-			if (kmer_off[mid] <= g) lo = mid; else hi = mid;
+	const uint32_t lane = threadIdx.x & 63;
+	// (SAT: the lanes of a wave leave the loop together, the ones past the last k-mer idle)
+	for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; (SAT ? g - lane : g) < total_kmers; g += (uint64_t)gridDim.x * blockDim.x) {
+		const bool valid = g < total_kmers;
+		uint64_t slot = 0, elem = 0, key = ~0ull;
+		if (valid) {
+			// segment j with kmer_off[j] <= g < kmer_off[j+1]
+			uint64_t lo = 0, hi = n_segs;
+			while (hi - lo > 1) {
+				uint64_t mid = (lo + hi) >> 1;
+				if (kmer_off[mid] <= g) lo = mid; else hi = mid;
+			}
+			const uint64_t pos = seg_start[lo] + (g - kmer_off[lo]);     // global base offset of the k-mer's first base
+			const uint64_t w = pos >> 4;
+			const uint32_t sh = (uint32_t)(pos & 15) * 2;
+			uint64_t window = (uint64_t)packed[w] | ((uint64_t)packed[w + 1] << 32);
+			uint32_t bits = (uint32_t)(window >> sh);
+			if (2 * k < 32) bits &= (1u << (2 * k)) - 1u;
+			// base i sits at bits [2i, 2i+1]; the reference index has base 0 most significant (KmerHashTable.cpp:108-131)
+			const uint32_t idx = rev2(bits) >> (32 - 2 * k);
+			slot = first_slot + seg_seq[lo];
+			elem = msc_phys_index(idx, E, R);
+			key = slot * slot_elems + elem;
 		}
-		const uint64_t pos = seg_start[lo] + (g - kmer_off[lo]);     // global base offset of the k-mer's first base
-		const uint64_t w = pos >> 4;
-		const uint32_t sh = (uint32_t)(pos & 15) * 2;
-		uint64_t window = (uint64_t)packed[w] | ((uint64_t)packed[w + 1] << 32);
-		uint32_t bits = (uint32_t)(window >> sh);
-		if (2 * k < 32) bits &= (1u << (2 * k)) - 1u;
-		// base i sits at bits [2i, 2i+1]; the reference index has base 0 most significant (KmerHashTable.cpp:108-131)
-		const uint32_t idx = rev2(bits) >> (32 - 2 * k);
-		const uint64_t slot = first_slot + seg_seq[lo];
-		MscSlotScalars* sc = reinterpret_cast<MscSlotScalars*>(scalars + slot * scalar_stride);
-		bump<T, SAT>(bins + slot * slot_elems, msc_phys_index(idx, E, R), &sc->overflow);
+		if constexpr (!SAT) {
+			bump<T>(bins + slot * slot_elems, elem);
+		} else {
+			const uint64_t before = __shfl_up(key, 1, 64);
+			const bool head = valid && (lane == 0 || key != before);
+			const uint64_t heads = __ballot(head);
+			const uint32_t n_valid = (uint32_t)__popcll(__ballot(valid));      // (the valid lanes are the first n_valid)
+			if (head) {
+				const uint64_t later = lane == 63 ? 0ull : heads >> (lane + 1);
+				const uint32_t next = later ? lane + (uint32_t)__ffsll((long long)later) : n_valid;
+				MscSlotScalars* sc = reinterpret_cast<MscSlotScalars*>(scalars + slot * scalar_stride);
+				bump_sat<T>(bins + slot * slot_elems, elem, next - lane, &sc->overflow);
+			}
+		}
 	}
 }
 

@@ -529,6 +529,15 @@ extern "C" uint64_t msc_hist_set_bytes(const msc_hist_set* s) {
 	return (s->L.slot_bytes + (s->digest ? msc_digest_slot_bytes(s->L) : 0) + (s->kb ? s->L.padded_bins / 8 + 32 + (uint64_t)s->mb_pitch * 8 + 4 : 0) + (s->ranks ? (s->rk_pitch + 1) * 4 : 0) + s->scalar_stride) * s->capacity;
 }
 
+extern "C" int msc_hist_set_build_info(const msc_hist_set* s, char* builder, size_t cap, uint64_t* max_count, uint64_t* max_sum, uint64_t* max_nnz) {
+	if (!s) return MSC_ERR_INVALID_ARG;
+	if (builder && cap) snprintf(builder, cap, "%s", s->last_builder);
+	if (max_count) *max_count = s->max_count;
+	if (max_sum) *max_sum = s->max_sum;
+	if (max_nnz) *max_nnz = s->sparse ? s->max_nnz : 0;
+	return MSC_OK;
+}
+
 // every writer of slots ends here: both mirrors of a dense set (digest, sparse lists) are stale for [first, first + n)
 static void mark_stale(msc_hist_set* s, uint64_t first, uint64_t n) {
 	if (s->sparse || n == 0) return;
@@ -745,6 +754,7 @@ static int build_sparse_sort(msc_ctx* ctx, msc_hist_set* set, uint64_t first_slo
 	HIP_TRY(ctx, msc_launch_sparse_build_sort(ctx->stream, k, set->dtype, set->L.nbins, first_slot, (uint32_t)n_seqs, (const uint32_t*)ctx->packed.p,
 	                                          (const uint64_t*)ctx->seg_start.p, (const uint64_t*)ctx->kmer_off.p, (const uint64_t*)ctx->seq_seg.p,
 	                                          (const uint64_t*)ctx->sp_cumbase.p, P, set->scalars, set->scalar_stride, set->hdr, set->ent, set->cum));
+	set->last_builder = "k_sparse_build_sort";
 	set->ent_used += need;
 	set->list_epoch++;
 	HIP_TRY(ctx, hipMemcpyAsync(set->hdr_host.data() + first_slot, set->hdr + first_slot, n_seqs * sizeof(MscSparseHdr), hipMemcpyDeviceToHost, ctx->stream));
@@ -782,6 +792,8 @@ static int build_sparse(msc_ctx* ctx, msc_hist_set* set, uint64_t first_slot, ui
 		if ((r = msc_hist_build_packed(ctx, sc, 0, nb, packed, n_bases, sseq.data(), seg_start + s0, seg_end + s0, s1 - s0, eff_len + b0,
 		                               one_mers ? one_mers + 4 * b0 : nullptr)))
 			return r;
+		set->last_builder = strcmp(sc->last_builder, "k_build_sort") == 0 ? "k_build_sort+k_sparse_write"
+		                    : strcmp(sc->last_builder, "k_build_lds") == 0 ? "k_build_lds+k_sparse_write" : "k_count+k_sparse_write";
 		if ((r = sparsify_slots(ctx, sc, 0, set, first_slot + b0, nb, nullptr))) return r;
 		// the scalar record (mag, length, sums, max, 1-mers, stddev, overflow) is the dense slot's
 		HIP_TRY(ctx, hipMemcpy2DAsync(set->scalars + (first_slot + b0) * set->scalar_stride, set->scalar_stride, sc->scalars, sc->scalar_stride,
@@ -873,6 +885,7 @@ extern "C" int msc_hist_build_packed(msc_ctx* ctx, msc_hist_set* set, uint64_t f
 			if ((r = ensure(ctx, ctx->kmer_off, 8)) != MSC_OK) return r;
 		}
 		HIP_TRY(ctx, hipMemcpyAsync(ctx->seq_seg.p, sbeg.data(), (n_seqs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+		set->last_builder = "k_build_lds";
 		HIP_TRY(ctx, msc_launch_build_lds(ctx->stream, set->bins, set->scalars, L, k, set->dtype, first_slot, n_seqs, (const uint32_t*)ctx->packed.p,
 		                                  (const uint64_t*)ctx->seg_start.p, (const uint64_t*)ctx->kmer_off.p, (const uint64_t*)ctx->seq_seg.p));
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // sbeg lives on this stack frame
@@ -910,6 +923,7 @@ extern "C" int msc_hist_build_packed(msc_ctx* ctx, msc_hist_set* set, uint64_t f
 		HIP_TRY(ctx, hipMemcpyAsync(ctx->seq_seg.p, sbeg.data(), (n_seqs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
 		HIP_TRY(ctx, hipMemcpyAsync(ctx->seq_ids.p, ids.data(), n_seqs * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
 		HIP_TRY(ctx, hipMemcpyAsync(ctx->seq_meta.p, meta.data(), meta.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+		set->last_builder = "k_build_sort";
 		for (int c = 0; c < 4; c++)
 			HIP_TRY(ctx, msc_launch_build_sort(ctx->stream, set->bins, set->scalars, L, k, set->dtype, first_slot, (const uint32_t*)ctx->seq_ids.p + class_begin[c],
 			                                   class_begin[c + 1] - class_begin[c], classes[c], (const uint32_t*)ctx->packed.p, (const uint64_t*)ctx->seg_start.p,
@@ -923,6 +937,7 @@ extern "C" int msc_hist_build_packed(msc_ctx* ctx, msc_hist_set* set, uint64_t f
 		for (uint64_t i = 0; i < n_seqs; i++) learn_length(set, first_slot + i, eff_len[i]);
 		return MSC_OK;
 	}
+	set->last_builder = "k_count";
 	HIP_TRY(ctx, msc_launch_fill(ctx->stream, set->bins, L, first_slot, n_seqs));
 	HIP_TRY(ctx, msc_launch_count(ctx->stream, set->bins, set->scalars, L, k, set->dtype, first_slot, (const uint32_t*)ctx->packed.p,
 	                              (const uint32_t*)ctx->seg_seq.p, (const uint64_t*)ctx->seg_start.p, (const uint64_t*)ctx->kmer_off.p,

@@ -124,6 +124,7 @@ struct msc_hist_set {
 	uint8_t* scalars = nullptr;
 	// host-side bounds over every slot ever written (monotone; used to pick the kernels' integer range)
 	uint64_t max_count = 0, max_sum = 0;
+	const char* last_builder = "";        // what the last msc_hist_build* call on this set ran (msc_hist_set_build_info)
 	// digest mirror (pair_digest.hip), allocated on the first Q x M pass that can use it; slots [dg_lo, dg_hi) are stale
 	mutable uint8_t* digest = nullptr;    // a cache: maintained through const handles
 	mutable uint64_t dg_lo = 0, dg_hi = 0;
