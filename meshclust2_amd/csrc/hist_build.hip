@@ -590,21 +590,11 @@ inline int grid_for(uint64_t work_items, int cap) {
 
 }  // namespace
 
-template <typename F>
-static inline void by_dtype(int dtype, F&& f) {
-	switch (dtype) {
-	case 8: f(uint8_t{}); break;
-	case 16: f(uint16_t{}); break;
-	case 32: f(uint32_t{}); break;
-	default: f(uint64_t{}); break;
-	}
-}
-
 hipError_t msc_launch_fill(hipStream_t st, void* bins, const MscLayout& L, uint64_t first_slot, uint64_t n_slots) {
 	if (n_slots == 0) return hipSuccess;
 	const uint64_t chunks = n_slots * (L.padded_bins / L.E);
 	const int grid = grid_for(chunks, 256 * 16);
-	by_dtype((int)L.esz * 8, [&](auto tag) {
+	msc_by_dtype((int)L.esz * 8, [&](auto tag) {
 		using T = decltype(tag);
 		k_fill<T><<<dim3(grid), dim3(kBlock), 0, st>>>((T*)bins, first_slot, n_slots, L.padded_bins, L.nbins, L.E, L.R);
 	});
@@ -618,7 +608,7 @@ hipError_t msc_launch_count(hipStream_t st, void* bins, uint8_t* scalars, const 
 	if (total_kmers == 0 || n_segs == 0) return hipSuccess;
 	const int grid = grid_for(total_kmers, 256 * 16);
 	const uint64_t stride = msc_scalar_stride(L.S);
-	by_dtype(dtype, [&](auto tag) {
+	msc_by_dtype(dtype, [&](auto tag) {
 		using T = decltype(tag);
 		if (saturating)
 			k_count<T, true><<<dim3(grid), dim3(kBlock), 0, st>>>((T*)bins, scalars, stride, L.padded_bins, first_slot, k, L.E, L.R,
@@ -637,7 +627,7 @@ hipError_t msc_launch_build_lds(hipStream_t st, void* bins, uint8_t* scalars, co
                                 const uint64_t* seq_seg_begin) {
 	if (n_seqs == 0) return hipSuccess;
 	const uint64_t stride = msc_scalar_stride(L.S);
-	by_dtype(dtype, [&](auto tag) {
+	msc_by_dtype(dtype, [&](auto tag) {
 		using T = decltype(tag);
 		k_build_lds<T><<<dim3((unsigned)n_seqs), dim3(kBlock), L.nbins * sizeof(uint32_t), st>>>((T*)bins, scalars, stride, L.padded_bins, first_slot, k,
 		                                                                                         L.E, L.R, L.S, L.nbins, packed_words, seg_start, kmer_off,
@@ -660,7 +650,7 @@ hipError_t msc_launch_build_sort(hipStream_t st, void* bins, uint8_t* scalars, c
 	const uint64_t stride = msc_scalar_stride(L.S);
 	const size_t lds = ((size_t)(kBlock / 64) * kStageWords + P) * sizeof(uint32_t);
 	hipError_t e = hipSuccess;
-	by_dtype(dtype, [&](auto tag) {
+	msc_by_dtype(dtype, [&](auto tag) {
 		using T = decltype(tag);
 		if (lds > 48 * 1024) e = hipFuncSetAttribute((const void*)k_build_sort<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 		if (e != hipSuccess) return;
@@ -678,7 +668,7 @@ hipError_t msc_launch_finalize(hipStream_t st, const void* bins, uint8_t* scalar
 	const uint64_t stride = msc_scalar_stride(L.S);
 	if (tile_scratch) {
 		const uint64_t waves = n_slots * L.S;
-		by_dtype(dtype, [&](auto tag) {
+		msc_by_dtype(dtype, [&](auto tag) {
 			using T = decltype(tag);
 			k_finalize_tiles<T><<<dim3((unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, st>>>((const T*)bins, scalars, stride, L.padded_bins, first_slot,
 			                                                                                                          n_slots, L.S, L.tile_bins, tile_scratch);
@@ -688,7 +678,7 @@ hipError_t msc_launch_finalize(hipStream_t st, const void* bins, uint8_t* scalar
 		k_prefix_record<<<dim3((unsigned)n_slots), dim3(64), 0, st>>>(scalars, stride, first_slot, L.S, L.nbins, keep_mag ? 1 : 0, tile_scratch);
 		return hipGetLastError();
 	}
-	by_dtype(dtype, [&](auto tag) {
+	msc_by_dtype(dtype, [&](auto tag) {
 		using T = decltype(tag);
 		k_finalize<T><<<dim3((unsigned)n_slots), dim3(kBlock), 0, st>>>((const T*)bins, scalars, stride, L.padded_bins, first_slot, L.S,
 		                                                                 L.tile_bins, L.nbins, keep_mag ? 1 : 0);
@@ -701,7 +691,7 @@ hipError_t msc_launch_finalize(hipStream_t st, const void* bins, uint8_t* scalar
 
 hipError_t msc_launch_permute(hipStream_t st, const void* src, void* dst, const MscLayout& L, int dtype, bool to_physical) {
 	const int grid = grid_for(L.padded_bins, 256 * 4);
-	by_dtype(dtype, [&](auto tag) {
+	msc_by_dtype(dtype, [&](auto tag) {
 		using T = decltype(tag);
 		k_permute<T><<<dim3(grid), dim3(kBlock), 0, st>>>((const T*)src, (T*)dst, L.nbins, L.padded_bins, L.E, L.R, to_physical ? 1 : 0);
 	});

@@ -101,9 +101,8 @@ int sparse_acc_scatter(msc_ctx* ctx, const msc_hist_set* src, const uint32_t* sl
 }
 
 // (c) the accumulators of nc lists are swept into the sparse slots 0 .. nc-1 of ctx->sparse_mean_batch: list c's rounded mean over
-// m_of[c] members (value_bits = the set's bin type), or -- m_of[c] = 1 and value_bits = 32 -- its summed excesses + 1, the column sums
-// a rank sends to the others (msc_colsum_partial). floor_sum_out[c] = sum of floor(mean) (nullable). The accumulators are zero again.
-int sparse_acc_sweep(msc_ctx* ctx, const msc_hist_set* pts, uint32_t nc, const uint32_t* m_of, int value_bits, uint32_t* touched, uint64_t* floor_sum_out) {
+// m_of[c] members, or -- m_of[c] = 1 -- its summed excesses + 1, the column sums a rank sends to the others (msc_colsum_partial). floor_sum_out[c] = sum of floor(mean) (nullable). The accumulators are zero again.
+int sparse_acc_sweep(msc_ctx* ctx, const msc_hist_set* pts, uint32_t nc, const uint32_t* m_of, uint32_t* touched, uint64_t* floor_sum_out) {
 	const MscLayout& L = pts->L;
 	int r;
 	// a wave per (list, chunk of bins): many lists bring their own parallelism, and every chunk costs 24 bytes of counts to the host and
@@ -118,8 +117,8 @@ int sparse_acc_sweep(msc_ctx* ctx, const msc_hist_set* pts, uint32_t nc, const u
 	    (r = ensure(ctx, ctx->floor_sum, nc * sizeof(uint64_t))))
 		return r;
 	HIP_TRY(ctx, hipMemcpyAsync(ctx->qslots.p, m_of, nc * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-	HIP_TRY(ctx, msc_launch_sparse_mean_count_batch(ctx->stream, value_bits, (const uint32_t*)ctx->sp_acc_batch.p, L.nbins, n_chunks, chunk_bins, nc,
-	                                                (const uint32_t*)ctx->qslots.p, (uint64_t*)ctx->sp_counts.p, touched));
+	HIP_TRY(ctx, msc_launch_sparse_mean_count_batch(ctx->stream, (const uint32_t*)ctx->sp_acc_batch.p, L.nbins, n_chunks, chunk_bins, nc,
+	                                                (const uint32_t*)ctx->qslots.p, 0, (uint64_t*)ctx->sp_counts.p, touched));
 	std::vector<uint64_t> counts((size_t)nc * n_chunks * 3);
 	HIP_TRY(ctx, hipMemcpyAsync(counts.data(), ctx->sp_counts.p, counts.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -170,7 +169,7 @@ int sparse_acc_sweep(msc_ctx* ctx, const msc_hist_set* pts, uint32_t nc, const u
 	HIP_TRY(ctx, hipMemcpyAsync(ctx->floor_sum.p, floor_sum.data(), nc * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
 	HIP_TRY(ctx, hipMemcpyAsync(ctx->sp_chunk_off.p, off.data(), off.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
 	HIP_TRY(ctx, hipMemcpyAsync(ctx->sp_chunk_cum.p, cb.data(), cb.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-	HIP_TRY(ctx, msc_launch_sparse_mean_write_batch(ctx->stream, value_bits, (uint32_t*)ctx->sp_acc_batch.p, L.nbins, n_chunks, chunk_bins, nc, (const uint32_t*)ctx->qslots.p,
+	HIP_TRY(ctx, msc_launch_sparse_mean_write_batch(ctx->stream, (uint32_t*)ctx->sp_acc_batch.p, L.nbins, n_chunks, chunk_bins, nc, (const uint32_t*)ctx->qslots.p, 0,
 	                                                (const uint64_t*)ctx->sp_chunk_off.p, (const uint64_t*)ctx->sp_chunk_cum.p, ms->ent, ms->cum, touched));
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // hdr, sc, floor_sum, off, cb live on this frame
 	return MSC_OK;
@@ -207,7 +206,7 @@ static int sparse_means_and_distances(msc_ctx* ctx, const msc_hist_set* pts, con
 	if ((r = sparse_acc_scatter(ctx, pts, members.data(), pair_seg.data(), members.size(), touched))) return r;
 	std::vector<uint32_t> m_of(nc);
 	for (uint32_t c = 0; c < nc; c++) m_of[c] = segs[c].m;
-	if ((r = sparse_acc_sweep(ctx, pts, nc, m_of.data(), pts->dtype, touched, nullptr))) return r;
+	if ((r = sparse_acc_sweep(ctx, pts, nc, m_of.data(), touched, nullptr))) return r;
 	return sparse_distances_to_means(ctx, pts, segs, pair_seg, members, nc);
 }
 

@@ -696,27 +696,26 @@ static int mean_nearest_sparse(msc_ctx* ctx, const msc_hist_set* set, const uint
 	}
 	const uint32_t* d_slots = member_slots ? (const uint32_t*)ctx->slots.p : nullptr;
 	uint64_t* d_counts = (uint64_t*)(pin_d + pl.counts);
-	// k >= 11: the kernels of the batched form with one centre, whose sweeps visit touched 64-byte lines only
+	// the sweeps of the batched form with one centre of m members; k >= 11: the scatter of that form as well, which marks the 64-byte
+	// lines it touches for the sweeps to visit those only
 	static const bool no_groups = getenv("MSC_SPARSE_MEAN_NO_GROUPS") != nullptr;
 	const bool grouped = !no_groups && L.nbins >= msc_sparse_groups_min_bins() && chunk_bins % 512 == 0 && member_slots;
+	uint32_t* touched = nullptr;
 	if (grouped) {
 		const size_t tb = (size_t)(L.nbins >> 9) * sizeof(uint32_t);
 		if (tb > ctx->sp_touched.cap) {
 			if ((r = ensure(ctx, ctx->sp_touched, tb))) return r;
 			HIP_TRY(ctx, hipMemsetAsync(ctx->sp_touched.p, 0, ctx->sp_touched.cap, ctx->stream));
 		}
-		if ((r = ensure(ctx, ctx->pair_seg, m * sizeof(uint32_t))) || (r = ensure(ctx, ctx->qslots, sizeof(uint32_t)))) return r;
-		const uint32_t m32 = (uint32_t)m;
+		touched = (uint32_t*)ctx->sp_touched.p;
+		if ((r = ensure(ctx, ctx->pair_seg, m * sizeof(uint32_t)))) return r;
 		HIP_TRY(ctx, hipMemsetAsync(ctx->pair_seg.p, 0, m * sizeof(uint32_t), ctx->stream));
-		HIP_TRY(ctx, hipMemcpyAsync(ctx->qslots.p, &m32, sizeof m32, hipMemcpyHostToDevice, ctx->stream));
-		HIP_TRY(ctx, msc_launch_sparse_scatter_batch(ctx->stream, set->ent, set->hdr, d_slots, (const uint32_t*)ctx->pair_seg.p, m32, L.nbins, (uint32_t*)ctx->sp_acc.p,
-		                                             (uint32_t*)ctx->sp_touched.p));
-		HIP_TRY(ctx, msc_launch_sparse_mean_count_batch(ctx->stream, set->dtype, (const uint32_t*)ctx->sp_acc.p, L.nbins, n_chunks, chunk_bins, 1, (const uint32_t*)ctx->qslots.p,
-		                                                d_counts, (const uint32_t*)ctx->sp_touched.p));
+		HIP_TRY(ctx, msc_launch_sparse_scatter_batch(ctx->stream, set->ent, set->hdr, d_slots, (const uint32_t*)ctx->pair_seg.p, (uint32_t)m, L.nbins, (uint32_t*)ctx->sp_acc.p,
+		                                             touched));
 	} else {
-	HIP_TRY(ctx, msc_launch_sparse_scatter(ctx->stream, set->ent, set->hdr, d_slots, (uint32_t)m, (uint32_t*)ctx->sp_acc.p));
-	HIP_TRY(ctx, msc_launch_sparse_mean_count(ctx->stream, set->dtype, (const uint32_t*)ctx->sp_acc.p, n_chunks, chunk_bins, (uint32_t)m, d_counts));
+		HIP_TRY(ctx, msc_launch_sparse_scatter(ctx->stream, set->ent, set->hdr, d_slots, (uint32_t)m, (uint32_t*)ctx->sp_acc.p));
 	}
+	HIP_TRY(ctx, msc_launch_sparse_mean_count_batch(ctx->stream, (const uint32_t*)ctx->sp_acc.p, L.nbins, n_chunks, chunk_bins, 1, nullptr, (uint32_t)m, d_counts, touched));
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	const uint64_t* counts = (const uint64_t*)(pin_h + pl.counts);
 	uint64_t *off = (uint64_t*)(pin_h + pl.off), *cb = (uint64_t*)(pin_h + pl.cb);
@@ -752,12 +751,8 @@ static int mean_nearest_sparse(msc_ctx* ctx, const msc_hist_set* set, const uint
 	                                                  (const uint32_t*)(pin_d + pl.sc), (uint32_t)(sizeof sc / 4));
 	HIP_TRY(ctx, hipGetLastError());
 	const uint64_t *d_off = (const uint64_t*)(pin_d + pl.off), *d_cb = (const uint64_t*)(pin_d + pl.cb), *d_floor = (const uint64_t*)(pin_d + pl.floor_sum);
-	if (grouped)
-		HIP_TRY(ctx, msc_launch_sparse_mean_write_batch(ctx->stream, set->dtype, (uint32_t*)ctx->sp_acc.p, L.nbins, n_chunks, chunk_bins, 1, (const uint32_t*)ctx->qslots.p,
-		                                                d_off, d_cb, rs->ent, rs->cum, (uint32_t*)ctx->sp_touched.p));
-	else
-	HIP_TRY(ctx, msc_launch_sparse_mean_write(ctx->stream, set->dtype, (uint32_t*)ctx->sp_acc.p, n_chunks, chunk_bins, (uint32_t)m, d_off,
-	                                          d_cb, rs->ent, rs->cum));
+	HIP_TRY(ctx, msc_launch_sparse_mean_write_batch(ctx->stream, (uint32_t*)ctx->sp_acc.p, L.nbins, n_chunks, chunk_bins, 1, nullptr, (uint32_t)m, d_off, d_cb, rs->ent, rs->cum,
+	                                                touched));
 	// members vs the rounded mean: only the |p - r| reduction of the merge kernel is used
 	if ((r = run_score_fwd(ctx, set, member_slots, m, rs))) return r;
 	if ((r = ensure(ctx, ctx->raw, m * sizeof(double)))) return r;

@@ -149,6 +149,17 @@ struct MscEpilogueArgs {
 };
 
 // ---------------------------------------------------------------- launchers (defined in the .hip kernel files)
+// f(T{}) for the bin type T of `dtype` bits (8, 16, 32, otherwise 64); returns what f returns
+template <typename F>
+static inline auto msc_by_dtype(int dtype, F&& f) {
+	switch (dtype) {
+	case 8: return f(uint8_t{});
+	case 16: return f(uint16_t{});
+	case 32: return f(uint32_t{});
+	default: return f(uint64_t{});
+	}
+}
+
 hipError_t msc_launch_fill(hipStream_t st, void* bins, const MscLayout& L, uint64_t first_slot, uint64_t n_slots);
 hipError_t msc_launch_count(hipStream_t st, void* bins, uint8_t* scalars, const MscLayout& L, int k, int dtype,
                             uint64_t first_slot, const uint32_t* packed_words, const uint32_t* seg_seq,
@@ -306,9 +317,6 @@ hipError_t msc_launch_sparse_build_sort(hipStream_t st, int k, int dtype, uint64
                                         const uint64_t* seg_start, const uint64_t* kmer_off, const uint64_t* seq_seg_begin, const uint64_t* seq_arena_off,
                                         uint32_t P, uint8_t* scalars, uint64_t scalar_stride, MscSparseHdr* hdr, void* ent, uint32_t* cum);
 hipError_t msc_launch_sparse_scatter(hipStream_t st, const void* ent, const MscSparseHdr* hdr, const uint32_t* slots, uint32_t m, uint32_t* acc);
-hipError_t msc_launch_sparse_mean_count(hipStream_t st, int dtype, const uint32_t* acc, uint32_t n_chunks, uint64_t chunk_bins, uint32_t m, uint64_t* counts);
-hipError_t msc_launch_sparse_mean_write(hipStream_t st, int dtype, uint32_t* acc, uint32_t n_chunks, uint64_t chunk_bins, uint32_t m,
-                                        const uint64_t* chunk_off, const uint64_t* chunk_cum, void* ent, uint32_t* cum);
 hipError_t msc_launch_pair_sparse_mp_pairs(hipStream_t st, const void* c_ent, const uint32_t* c_cum, const MscSparseHdr* c_hdr, const uint8_t* cand_scalars,
                                            uint64_t scalar_stride, const uint32_t* cand_slots, uint32_t m, const void* q_ent, const uint32_t* q_cum,
                                            const MscSparseHdr* q_hdr, uint64_t nbins, int use_window, const MscBatchSeg* segs, const uint32_t* pair_seg,
@@ -316,10 +324,12 @@ hipError_t msc_launch_pair_sparse_mp_pairs(hipStream_t st, const void* c_ent, co
                                            void* div_tables = nullptr, void* div_partials = nullptr, uint32_t div_stride = 1);
 hipError_t msc_launch_sparse_scatter_batch(hipStream_t st, const void* ent, const MscSparseHdr* hdr, const uint32_t* slots, const uint32_t* seg, uint32_t n_members,
                                            uint64_t nbins, uint32_t* acc, uint32_t* touched = nullptr);
-hipError_t msc_launch_sparse_mean_count_batch(hipStream_t st, int dtype, const uint32_t* acc, uint64_t nbins, uint32_t n_chunks, uint64_t chunk_bins, uint32_t n_centres,
-                                              const uint32_t* m_of, uint64_t* counts, const uint32_t* touched = nullptr);
-hipError_t msc_launch_sparse_mean_write_batch(hipStream_t st, int dtype, uint32_t* acc, uint64_t nbins, uint32_t n_chunks, uint64_t chunk_bins, uint32_t n_centres,
-                                              const uint32_t* m_of, const uint64_t* chunk_off, const uint64_t* chunk_cum, void* ent, uint32_t* cum, uint32_t* touched = nullptr);
+// (m_of == nullptr: one centre of m_one members; touched == nullptr: the sweeps over all bins)
+hipError_t msc_launch_sparse_mean_count_batch(hipStream_t st, const uint32_t* acc, uint64_t nbins, uint32_t n_chunks, uint64_t chunk_bins, uint32_t n_centres,
+                                              const uint32_t* m_of, uint32_t m_one, uint64_t* counts, const uint32_t* touched);
+hipError_t msc_launch_sparse_mean_write_batch(hipStream_t st, uint32_t* acc, uint64_t nbins, uint32_t n_chunks, uint64_t chunk_bins, uint32_t n_centres,
+                                              const uint32_t* m_of, uint32_t m_one, const uint64_t* chunk_off, const uint64_t* chunk_cum, void* ent, uint32_t* cum,
+                                              uint32_t* touched);
 hipError_t msc_launch_sparse_assign_batch(hipStream_t st, void* d_ent, uint32_t* d_cum, MscSparseHdr* d_hdr, const void* s_ent, const uint32_t* s_cum, const MscSparseHdr* s_hdr,
                                           const uint32_t* ds, const uint32_t* ss, const uint64_t* dst_off, uint32_t n);
 hipError_t msc_launch_assign_scalars(hipStream_t st, uint8_t* dst_scalars, const uint8_t* src_scalars, uint64_t stride_bytes, const uint32_t* dst_slots,

@@ -222,7 +222,7 @@ int ensure_sparse_mirror(msc_ctx* ctx, const msc_hist_set* set, const msc_hist_s
 // the stages of the batched sparse mean (msc_api_batch.hip; msc_shard.hip puts an exchange between them)
 int sparse_acc_prepare(msc_ctx* ctx, const MscLayout& L, uint32_t nc, uint32_t** touched_out);
 int sparse_acc_scatter(msc_ctx* ctx, const msc_hist_set* src, const uint32_t* slots, const uint32_t* seg, uint64_t P, uint32_t* touched);
-int sparse_acc_sweep(msc_ctx* ctx, const msc_hist_set* pts, uint32_t nc, const uint32_t* m_of, int value_bits, uint32_t* touched, uint64_t* floor_sum_out);
+int sparse_acc_sweep(msc_ctx* ctx, const msc_hist_set* pts, uint32_t nc, const uint32_t* m_of, uint32_t* touched, uint64_t* floor_sum_out);
 int sparse_distances_to_means(msc_ctx* ctx, const msc_hist_set* pts, const std::vector<MscBatchSeg>& segs, const std::vector<uint32_t>& pair_seg,
                               const std::vector<uint32_t>& members, uint32_t nc);
 bool needs_wide(const msc_hist_set* a, const msc_hist_set* b);

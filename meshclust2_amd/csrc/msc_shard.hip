@@ -409,7 +409,7 @@ extern "C" int msc_colsum_partial(msc_ctx* ctx, const msc_hist_set* set, const u
 	if ((r = sparse_acc_prepare(ctx, L, (uint32_t)n, &touched))) return r;
 	if ((r = sparse_acc_scatter(ctx, set, member_slots, pair_seg.data(), total, touched))) return r;
 	std::vector<uint32_t> ones(n, 1);
-	if ((r = sparse_acc_sweep(ctx, set, (uint32_t)n, ones.data(), 32, touched, nullptr))) return r;
+	if ((r = sparse_acc_sweep(ctx, set, (uint32_t)n, ones.data(), touched, nullptr))) return r;
 	const msc_hist_set* ms = ctx->sparse_mean_batch;
 	std::vector<uint64_t> table(2 + 2 * n), offs(n);
 	uint64_t at = blob_head_bytes(n);
@@ -508,7 +508,7 @@ extern "C" int msc_colsum_nearest(msc_ctx* ctx, const msc_hist_set* set, const u
 			m32[c] = (uint32_t)m_total[c];
 		}
 		// (every rank sweeps, members of its own or not: the accumulators must be zero again)
-		if ((r = sparse_acc_sweep(ctx, set, (uint32_t)n, m32.data(), set->dtype, touched, nullptr))) return r;
+		if ((r = sparse_acc_sweep(ctx, set, (uint32_t)n, m32.data(), touched, nullptr))) return r;
 		if (total == 0) return MSC_OK;
 		if ((r = sparse_distances_to_means(ctx, set, segs, pair_seg, members, (uint32_t)n))) return r;
 	}

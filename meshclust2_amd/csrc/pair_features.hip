@@ -2127,12 +2127,7 @@ hipError_t msc_launch_pair_tiles_wide(hipStream_t st, const MscLayout& L, int dt
                                       int use_window, uint64_t min_len, uint64_t max_len, MscPartial* partials, int num_cus,
                                       void* div_partials, int order) {
 	if (m == 0) return hipSuccess;
-	switch (dtype) {
-	case 8: return launch_wide_t<uint8_t>(st, L, cand_bins, cand_scalars, cand_slots, m, q_bins_slot, q_scalars_slot, use_window, min_len, max_len, partials, num_cus, div_partials, order);
-	case 16: return launch_wide_t<uint16_t>(st, L, cand_bins, cand_scalars, cand_slots, m, q_bins_slot, q_scalars_slot, use_window, min_len, max_len, partials, num_cus, div_partials, order);
-	case 32: return launch_wide_t<uint32_t>(st, L, cand_bins, cand_scalars, cand_slots, m, q_bins_slot, q_scalars_slot, use_window, min_len, max_len, partials, num_cus, div_partials, order);
-	default: return launch_wide_t<uint64_t>(st, L, cand_bins, cand_scalars, cand_slots, m, q_bins_slot, q_scalars_slot, use_window, min_len, max_len, partials, num_cus, div_partials, order);
-	}
+	return msc_by_dtype(dtype, [&](auto tag) { return launch_wide_t<decltype(tag)>(st, L, cand_bins, cand_scalars, cand_slots, m, q_bins_slot, q_scalars_slot, use_window, min_len, max_len, partials, num_cus, div_partials, order); });
 }
 
 int msc_div_table_dim(const MscLayout& L) { return (L.LPT == 4 && L.S >= 4) ? 8 : 16; }
@@ -2143,12 +2138,7 @@ hipError_t msc_launch_pair_tiles(hipStream_t st, const MscLayout& L, int dtype, 
                                  void* div_tables, void* div_partials, int order) {
 	if (m == 0) return hipSuccess;
 	const int tb = div_tables ? msc_div_table_dim(L) : 0;
-	switch (dtype) {
-	case 8: return launch_tiles_lpt<uint8_t>(st, L, cand_bins, cand_scalars, cand_slots, m, q_bins_slot, q_scalars_slot, use_window, min_len, max_len, partials, num_cus, tb, div_tables, div_partials, order);
-	case 16: return launch_tiles_lpt<uint16_t>(st, L, cand_bins, cand_scalars, cand_slots, m, q_bins_slot, q_scalars_slot, use_window, min_len, max_len, partials, num_cus, tb, div_tables, div_partials, order);
-	case 32: return launch_tiles_lpt<uint32_t>(st, L, cand_bins, cand_scalars, cand_slots, m, q_bins_slot, q_scalars_slot, use_window, min_len, max_len, partials, num_cus, tb, div_tables, div_partials, order);
-	default: return launch_tiles_lpt<uint64_t>(st, L, cand_bins, cand_scalars, cand_slots, m, q_bins_slot, q_scalars_slot, use_window, min_len, max_len, partials, num_cus, tb, div_tables, div_partials, order);
-	}
+	return msc_by_dtype(dtype, [&](auto tag) { return launch_tiles_lpt<decltype(tag)>(st, L, cand_bins, cand_scalars, cand_slots, m, q_bins_slot, q_scalars_slot, use_window, min_len, max_len, partials, num_cus, tb, div_tables, div_partials, order); });
 }
 
 template <typename T, int TQ, bool COMPACT>
@@ -2203,12 +2193,7 @@ hipError_t msc_launch_pair_tiles_multi(hipStream_t st, const MscLayout& L, int d
 	     ? (compact ? launch_multi_t<T, 8, true>(MSC_MULTI_ARGS) : launch_multi_t<T, 8, false>(MSC_MULTI_ARGS))  \
 	 : tq >= 4 ? (compact ? launch_multi_t<T, 4, true>(MSC_MULTI_ARGS) : launch_multi_t<T, 4, false>(MSC_MULTI_ARGS)) \
 	           : (compact ? launch_multi_t<T, 2, true>(MSC_MULTI_ARGS) : launch_multi_t<T, 2, false>(MSC_MULTI_ARGS)))
-	switch (dtype) {
-	case 8: return MSC_MULTI(uint8_t);
-	case 16: return MSC_MULTI(uint16_t);
-	case 32: return MSC_MULTI(uint32_t);
-	default: return MSC_MULTI(uint64_t);
-	}
+	return msc_by_dtype(dtype, [&](auto tag) { using T = decltype(tag); return MSC_MULTI(T); });
 #undef MSC_MULTI
 #undef MSC_MULTI_ARGS
 }
@@ -2364,12 +2349,10 @@ hipError_t msc_launch_colsum(hipStream_t st, const MscLayout& L, int dtype, cons
 	if (e != hipSuccess) return e;
 	const uint64_t chunks = L.padded_bins / L.E;
 	const unsigned blocks = (unsigned)((chunks + kBlock - 1) / kBlock);
-	switch (dtype) {
-	case 8: hipLaunchKernelGGL(k_colsum<uint8_t>, dim3(blocks), dim3(kBlock), 0, st, (const uint8_t*)bins, L.padded_bins, member_slots, m, L.padded_bins, L.nbins, L.R, (uint8_t*)rounded_out, mean_out, (unsigned long long*)floor_sum_out); break;
-	case 16: hipLaunchKernelGGL(k_colsum<uint16_t>, dim3(blocks), dim3(kBlock), 0, st, (const uint16_t*)bins, L.padded_bins, member_slots, m, L.padded_bins, L.nbins, L.R, (uint16_t*)rounded_out, mean_out, (unsigned long long*)floor_sum_out); break;
-	case 32: hipLaunchKernelGGL(k_colsum<uint32_t>, dim3(blocks), dim3(kBlock), 0, st, (const uint32_t*)bins, L.padded_bins, member_slots, m, L.padded_bins, L.nbins, L.R, (uint32_t*)rounded_out, mean_out, (unsigned long long*)floor_sum_out); break;
-	default: hipLaunchKernelGGL(k_colsum<uint64_t>, dim3(blocks), dim3(kBlock), 0, st, (const uint64_t*)bins, L.padded_bins, member_slots, m, L.padded_bins, L.nbins, L.R, (uint64_t*)rounded_out, mean_out, (unsigned long long*)floor_sum_out); break;
-	}
+	msc_by_dtype(dtype, [&](auto tag) {
+		using T = decltype(tag);
+		hipLaunchKernelGGL(k_colsum<T>, dim3(blocks), dim3(kBlock), 0, st, (const T*)bins, L.padded_bins, member_slots, m, L.padded_bins, L.nbins, L.R, (T*)rounded_out, mean_out, (unsigned long long*)floor_sum_out);
+	});
 	return hipGetLastError();
 }
 
@@ -2509,14 +2492,7 @@ hipError_t msc_launch_pair_groups_dense(hipStream_t st, const MscLayout& L, int 
                                         const uint32_t* cand_slots, uint32_t m, const uint8_t* q_bins, int use_window, uint64_t min_len, uint64_t max_len, double* out) {
 	if (m == 0) return hipSuccess;
 	const dim3 grid((unsigned)(((uint64_t)m * 16 + 255) / 256));
-#define MSC_GD(TT) k_pair_groups_dense<TT><<<grid, dim3(256), 0, st>>>(c_bins, L.slot_bytes, cand_scalars, scalar_stride, cand_slots, m, q_bins, L.E, L.R, L.nbins, use_window, min_len, max_len, out)
-	switch (dtype) {
-	case 8: MSC_GD(uint8_t); break;
-	case 16: MSC_GD(uint16_t); break;
-	case 32: MSC_GD(uint32_t); break;
-	default: MSC_GD(uint64_t); break;
-	}
-#undef MSC_GD
+	msc_by_dtype(dtype, [&](auto tag) { k_pair_groups_dense<decltype(tag)><<<grid, dim3(256), 0, st>>>(c_bins, L.slot_bytes, cand_scalars, scalar_stride, cand_slots, m, q_bins, L.E, L.R, L.nbins, use_window, min_len, max_len, out); });
 	return hipGetLastError();
 }
 // bins: base of the set; the slots are slots[c] or first_slot + c
@@ -2524,14 +2500,7 @@ hipError_t msc_launch_self_markov_dense(hipStream_t st, const MscLayout& L, int 
                                         double* out) {
 	if (m == 0) return hipSuccess;
 	const dim3 grid((unsigned)(((uint64_t)m * 16 + 255) / 256));
-#define MSC_SD(TT) k_self_markov_dense<TT><<<grid, dim3(256), 0, st>>>(bins, L.slot_bytes, slots, first_slot, m, L.E, L.R, L.nbins, out)
-	switch (dtype) {
-	case 8: MSC_SD(uint8_t); break;
-	case 16: MSC_SD(uint16_t); break;
-	case 32: MSC_SD(uint32_t); break;
-	default: MSC_SD(uint64_t); break;
-	}
-#undef MSC_SD
+	msc_by_dtype(dtype, [&](auto tag) { k_self_markov_dense<decltype(tag)><<<grid, dim3(256), 0, st>>>(bins, L.slot_bytes, slots, first_slot, m, L.E, L.R, L.nbins, out); });
 	return hipGetLastError();
 }
 
@@ -2565,12 +2534,7 @@ hipError_t msc_launch_pair_tiles_batch(hipStream_t st, const MscLayout& L, int d
                                        uint64_t q_slot_bytes, const uint8_t* qset_scalars, uint64_t q_scalar_stride, int use_window, MscPartial* partials,
                                        int order) {
 	if (n_segs == 0) return hipSuccess;
-	switch (dtype) {
-	case 8: return launch_tiles_batch_t<uint8_t>(st, L, cand_bins, cand_scalars, cand_slots, segs, n_segs, max_m, qset_bins, q_slot_bytes, qset_scalars, q_scalar_stride, use_window, partials, order);
-	case 16: return launch_tiles_batch_t<uint16_t>(st, L, cand_bins, cand_scalars, cand_slots, segs, n_segs, max_m, qset_bins, q_slot_bytes, qset_scalars, q_scalar_stride, use_window, partials, order);
-	case 32: return launch_tiles_batch_t<uint32_t>(st, L, cand_bins, cand_scalars, cand_slots, segs, n_segs, max_m, qset_bins, q_slot_bytes, qset_scalars, q_scalar_stride, use_window, partials, order);
-	default: return launch_tiles_batch_t<uint64_t>(st, L, cand_bins, cand_scalars, cand_slots, segs, n_segs, max_m, qset_bins, q_slot_bytes, qset_scalars, q_scalar_stride, use_window, partials, order);
-	}
+	return msc_by_dtype(dtype, [&](auto tag) { return launch_tiles_batch_t<decltype(tag)>(st, L, cand_bins, cand_scalars, cand_slots, segs, n_segs, max_m, qset_bins, q_slot_bytes, qset_scalars, q_scalar_stride, use_window, partials, order); });
 }
 
 hipError_t msc_launch_colsum_batch(hipStream_t st, const MscLayout& L, int dtype, const uint8_t* bins, const uint32_t* member_slots, const MscBatchSeg* segs,
@@ -2582,12 +2546,10 @@ hipError_t msc_launch_colsum_batch(hipStream_t st, const MscLayout& L, int dtype
 	const uint32_t cpb = (uint32_t)((chunks + kBlock - 1) / kBlock);
 	const dim3 grid((unsigned)((uint64_t)n_segs * cpb));
 	unsigned long long* fs = reinterpret_cast<unsigned long long*>(floor_sum_out);
-	switch (dtype) {
-	case 8: k_colsum_batch<uint8_t><<<grid, dim3(kBlock), 0, st>>>((const uint8_t*)bins, L.padded_bins, member_slots, segs, cpb, L.padded_bins, L.nbins, L.R, (uint8_t*)rounded_out, fs); break;
-	case 16: k_colsum_batch<uint16_t><<<grid, dim3(kBlock), 0, st>>>((const uint16_t*)bins, L.padded_bins, member_slots, segs, cpb, L.padded_bins, L.nbins, L.R, (uint16_t*)rounded_out, fs); break;
-	case 32: k_colsum_batch<uint32_t><<<grid, dim3(kBlock), 0, st>>>((const uint32_t*)bins, L.padded_bins, member_slots, segs, cpb, L.padded_bins, L.nbins, L.R, (uint32_t*)rounded_out, fs); break;
-	default: k_colsum_batch<uint64_t><<<grid, dim3(kBlock), 0, st>>>((const uint64_t*)bins, L.padded_bins, member_slots, segs, cpb, L.padded_bins, L.nbins, L.R, (uint64_t*)rounded_out, fs); break;
-	}
+	msc_by_dtype(dtype, [&](auto tag) {
+		using T = decltype(tag);
+		k_colsum_batch<T><<<grid, dim3(kBlock), 0, st>>>((const T*)bins, L.padded_bins, member_slots, segs, cpb, L.padded_bins, L.nbins, L.R, (T*)rounded_out, fs);
+	});
 	return hipGetLastError();
 }
 
@@ -2597,12 +2559,10 @@ hipError_t msc_launch_colsum_sums(hipStream_t st, const MscLayout& L, int dtype,
 	const uint64_t chunks = L.padded_bins / L.E;
 	const uint32_t cpb = (uint32_t)((chunks + kBlock - 1) / kBlock);
 	const dim3 grid(n_segs * cpb);
-	switch (dtype) {
-	case 8: k_colsum_sums<uint8_t><<<grid, dim3(kBlock), 0, st>>>((const uint8_t*)bins, L.padded_bins, member_slots, segs, cpb, L.padded_bins, (unsigned long long*)sums_out); break;
-	case 16: k_colsum_sums<uint16_t><<<grid, dim3(kBlock), 0, st>>>((const uint16_t*)bins, L.padded_bins, member_slots, segs, cpb, L.padded_bins, (unsigned long long*)sums_out); break;
-	case 32: k_colsum_sums<uint32_t><<<grid, dim3(kBlock), 0, st>>>((const uint32_t*)bins, L.padded_bins, member_slots, segs, cpb, L.padded_bins, (unsigned long long*)sums_out); break;
-	default: k_colsum_sums<uint64_t><<<grid, dim3(kBlock), 0, st>>>((const uint64_t*)bins, L.padded_bins, member_slots, segs, cpb, L.padded_bins, (unsigned long long*)sums_out); break;
-	}
+	msc_by_dtype(dtype, [&](auto tag) {
+		using T = decltype(tag);
+		k_colsum_sums<T><<<grid, dim3(kBlock), 0, st>>>((const T*)bins, L.padded_bins, member_slots, segs, cpb, L.padded_bins, (unsigned long long*)sums_out);
+	});
 	return hipGetLastError();
 }
 // sums[n_segs][padded] of m_total[si] members -> rounded mean slots 0 .. n_segs-1 behind rounded_out and floor_sum_out[si] (zeroed here)
@@ -2617,12 +2577,10 @@ hipError_t msc_launch_mean_from_sums(hipStream_t st, const MscLayout& L, int dty
 	const unsigned long long* su = (const unsigned long long*)sums;
 	const unsigned long long* mt = (const unsigned long long*)m_total;
 	unsigned long long* fs = (unsigned long long*)floor_sum_out;
-	switch (dtype) {
-	case 8: k_mean_from_sums<uint8_t><<<grid, dim3(kBlock), 0, st>>>(su, mt, cpb, L.padded_bins, L.nbins, L.R, L.padded_bins, (uint8_t*)rounded_out, fs); break;
-	case 16: k_mean_from_sums<uint16_t><<<grid, dim3(kBlock), 0, st>>>(su, mt, cpb, L.padded_bins, L.nbins, L.R, L.padded_bins, (uint16_t*)rounded_out, fs); break;
-	case 32: k_mean_from_sums<uint32_t><<<grid, dim3(kBlock), 0, st>>>(su, mt, cpb, L.padded_bins, L.nbins, L.R, L.padded_bins, (uint32_t*)rounded_out, fs); break;
-	default: k_mean_from_sums<uint64_t><<<grid, dim3(kBlock), 0, st>>>(su, mt, cpb, L.padded_bins, L.nbins, L.R, L.padded_bins, (uint64_t*)rounded_out, fs); break;
-	}
+	msc_by_dtype(dtype, [&](auto tag) {
+		using T = decltype(tag);
+		k_mean_from_sums<T><<<grid, dim3(kBlock), 0, st>>>(su, mt, cpb, L.padded_bins, L.nbins, L.R, L.padded_bins, (T*)rounded_out, fs);
+	});
 	return hipGetLastError();
 }
 

@@ -16,13 +16,19 @@
 // boundaries, and the lanes' shares inside a chunk, come from merge-path co-rank searches (see the kernel).
 // k_pair_sparse (wide arithmetic range): one LANE per (candidate, index sub-range): a branch-light two-pointer merge of the two
 // sorted lists restricted to the sub-range, straight from global memory; the prefix difference at a sub-range start comes from the
-// stored cum arrays. k_pair_sparse_lds: the whole-list LDS variant the merge-path kernel replaced (MSC_SPARSE_LDS=1).
+// stored cum arrays. k_pair_sparse_lds: the whole-list LDS variant the merge-path kernel replaced (MSC_SPARSE_LDS=1). These two and
+// k_pair_sparse_groups share one two-pointer walk (merge_walk); k_pair_sparse_wl: short lists whole in LDS, one merge-path split.
 // Bytes per pair: 8 B per stored bin of the candidate list instead of 4^k * sizeof(T) per histogram.
 //
 // Build: the dense builder (hist_build.hip) fills a scratch slot per sequence of the batch, then k_sparse_count /
 // k_sparse_write compact it IN INDEX ORDER: in the tile-permuted layout every lane already holds a logically consecutive
-// run, so one wave scan per tile yields ordered output with coalesced reads.
+// run (lane_run), so one wave scan per tile yields ordered output with coalesced reads.
+//
+// Mean: the members' excesses are scatter-added into a dense u32 accumulator per centre, which k_sparse_mean_count_batch /
+// _write_batch (all bins) or _count_groups / _write_groups (touched 64-byte lines only) sweep into the rounded mean as a sparse slot;
+// one centre (msc_mean_nearest) is the same sweeps with a grid of one.
 #include <algorithm>
+#include <type_traits>
 
 #include "msc_groups.h"
 #include "msc_internal.h"
@@ -39,79 +45,65 @@ __device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
 	return v;
 }
 
-// ------------------------------------------------------------------------------------------------ compaction, pass 1
-// counts[seq][w] = {entries, excess sum} of index sub-range w (wave w streams tiles [w*S/16, (w+1)*S/16))
+// ------------------------------------------------------------------------------------------------ compaction
+// this lane's logically consecutive run of R bins of tile t of the tile-permuted slot h, 16 bytes per load (coalesced across the
+// wave): visit(position in the run, value)
+template <typename T, typename V>
+__device__ __forceinline__ void lane_run(const T* __restrict__ h, uint32_t t, uint32_t R, uint32_t lane, V visit) {
+	constexpr uint32_t E = 16 / sizeof(T);
+	const uint32_t loads = R / E, tile_bins = 64 * R;
+	for (uint32_t l = 0; l < loads; l++) {
+		const uint4 v = *reinterpret_cast<const uint4*>(h + (uint64_t)t * tile_bins + (uint64_t)l * 64 * E + lane * E);
+		const T* e = reinterpret_cast<const T*>(&v);
+#pragma unroll
+		for (uint32_t j = 0; j < E; j++) visit(l * E + j, (uint64_t)e[j]);
+	}
+}
+
+// pass 1: counts[seq][w] = {entries, excess sum} of index sub-range w (wave w streams tiles [w*S/16, (w+1)*S/16))
 template <typename T>
 __global__ void __launch_bounds__(kBlockC) k_sparse_count(const T* __restrict__ bins, uint64_t slot_elems, uint32_t S, uint32_t R,
                                                          uint64_t* __restrict__ counts /* [n][16][2] */) {
-	constexpr uint32_t E = 16 / sizeof(T);
 	const uint32_t seq = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-	const uint32_t loads = R / E, tile_bins = 64 * R;
 	const T* h = bins + (uint64_t)seq * slot_elems;
 	const uint32_t t0 = (uint32_t)((uint64_t)wave * S / kSub), t1 = (uint32_t)((uint64_t)(wave + 1) * S / kSub);
 	uint64_t n = 0, ex = 0;
-	for (uint32_t t = t0; t < t1; t++) {
-		for (uint32_t l = 0; l < loads; l++) {
-			const uint4 v = *reinterpret_cast<const uint4*>(h + (uint64_t)t * tile_bins + (uint64_t)l * 64 * E + lane * E);
-			const T* e = reinterpret_cast<const T*>(&v);
-#pragma unroll
-			for (uint32_t j = 0; j < E; j++) {
-				const uint64_t p = e[j];
-				if (p > 1) { n++; ex += p - 1; }
-			}
-		}
-	}
+	for (uint32_t t = t0; t < t1; t++)
+		lane_run(h, t, R, lane, [&](uint32_t, uint64_t p) { if (p > 1) { n++; ex += p - 1; } });
 	n = wave_sum_u64(n);
 	ex = wave_sum_u64(ex);
 	if (lane == 0) { counts[((uint64_t)seq * kSub + wave) * 2] = n; counts[((uint64_t)seq * kSub + wave) * 2 + 1] = ex; }
 }
 
-// ------------------------------------------------------------------------------------------------ compaction, pass 2
-// wave w writes its sub-range's entries at hdr.off + hdr.split[w], ordered by index, with the running excess prefix
+// pass 2: wave w writes its sub-range's entries at hdr.off + hdr.split[w], ordered by index, with the running excess prefix
 template <typename T>
 __global__ void __launch_bounds__(kBlockC) k_sparse_write(const T* __restrict__ bins, uint64_t slot_elems, uint32_t S, uint32_t R,
                                                          const MscSparseHdr* __restrict__ hdr, uint64_t first_slot,
                                                          const uint64_t* __restrict__ cum_base /* [n][16] */, uint2* __restrict__ ent,
                                                          uint32_t* __restrict__ cum) {
-	constexpr uint32_t E = 16 / sizeof(T);
 	const uint32_t seq = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-	const uint32_t loads = R / E, tile_bins = 64 * R;
 	const T* h = bins + (uint64_t)seq * slot_elems;
 	const MscSparseHdr& hd = hdr[first_slot + seq];
 	uint64_t o = hd.off + hd.split[wave];
 	uint32_t run = (uint32_t)cum_base[(uint64_t)seq * kSub + wave];
 	const uint32_t t0 = (uint32_t)((uint64_t)wave * S / kSub), t1 = (uint32_t)((uint64_t)(wave + 1) * S / kSub);
 	for (uint32_t t = t0; t < t1; t++) {
-		// this lane's logically consecutive run of R bins
 		uint32_t cnt = 0, ex = 0;
-		for (uint32_t l = 0; l < loads; l++) {
-			const uint4 v = *reinterpret_cast<const uint4*>(h + (uint64_t)t * tile_bins + (uint64_t)l * 64 * E + lane * E);
-			const T* e = reinterpret_cast<const T*>(&v);
-#pragma unroll
-			for (uint32_t j = 0; j < E; j++) { const uint64_t p = e[j]; if (p > 1) { cnt++; ex += (uint32_t)(p - 1); } }
-		}
+		lane_run(h, t, R, lane, [&](uint32_t, uint64_t p) { if (p > 1) { cnt++; ex += (uint32_t)(p - 1); } });
 		const uint32_t cnt_incl = wave_incl_scan(cnt), ex_incl = wave_incl_scan(ex);
 		const uint32_t tile_cnt = (uint32_t)__builtin_amdgcn_readlane((int)cnt_incl, 63);
 		const uint32_t tile_ex = (uint32_t)__builtin_amdgcn_readlane((int)ex_incl, 63);
-		if (tile_cnt) {
+		if (tile_cnt && cnt) {
 			uint64_t w = o + (cnt_incl - cnt);
 			uint32_t c = run + (ex_incl - ex);
-			if (cnt) {
-				for (uint32_t l = 0; l < loads; l++) {
-					const uint4 v = *reinterpret_cast<const uint4*>(h + (uint64_t)t * tile_bins + (uint64_t)l * 64 * E + lane * E);
-					const T* e = reinterpret_cast<const T*>(&v);
-#pragma unroll
-					for (uint32_t j = 0; j < E; j++) {
-						const uint64_t p = e[j];
-						if (p > 1) {
-							c += (uint32_t)(p - 1);
-							ent[w] = make_uint2(t * tile_bins + lane * R + l * E + j, (uint32_t)p);
-							cum[w] = c;
-							w++;
-						}
-					}
+			lane_run(h, t, R, lane, [&](uint32_t at, uint64_t p) {
+				if (p > 1) {
+					c += (uint32_t)(p - 1);
+					ent[w] = make_uint2(t * 64 * R + lane * R + at, (uint32_t)p);
+					cum[w] = c;
+					w++;
 				}
-			}
+			});
 		}
 		o += tile_cnt;
 		run += tile_ex;
@@ -284,6 +276,22 @@ __global__ void __launch_bounds__(256) k_sparse_div_tables(const uint8_t* __rest
 	tables[(uint64_t)c * 256 + j] = t;
 }
 
+// the two-pointer merge of entries [i, iend) of list P and [j, jend) of list Q, both sorted by bin: visit(bin, pv, qv) once per bin
+// stored in either list, in ascending order, with 1 -- the value of an unstored bin -- for the list that does not hold it
+template <typename V>
+__device__ __forceinline__ void merge_walk(const uint2* P, uint32_t i, uint32_t iend, const uint2* Q, uint32_t j, uint32_t jend, V visit) {
+	const uint32_t kInf = 0xffffffffu;
+	uint2 a = i < iend ? P[i] : make_uint2(kInf, 1u);
+	uint2 b = j < jend ? Q[j] : make_uint2(kInf, 1u);
+	while (i < iend || j < jend) {
+		const uint32_t e = a.x < b.x ? a.x : b.x;
+		const bool ta = a.x == e, tb = b.x == e;
+		visit(e, ta ? a.y : 1u, tb ? b.y : 1u);
+		if (ta) { i++; a = i < iend ? P[i] : make_uint2(kInf, 1u); }
+		if (tb) { j++; b = j < jend ? Q[j] : make_uint2(kInf, 1u); }
+	}
+}
+
 template <bool DIV>
 __global__ void __launch_bounds__(256) k_pair_sparse(
     const uint2* __restrict__ c_ent, const uint32_t* __restrict__ c_cum, const MscSparseHdr* __restrict__ c_hdr,
@@ -303,8 +311,8 @@ __global__ void __launch_bounds__(256) k_pair_sparse(
 	const uint32_t* CP = c_cum + ch.off;
 	const uint2* Q = q_ent + qh.off;
 	const uint32_t* CQ = q_cum + qh.off;
-	uint32_t i = ch.split[r], iend = ch.split[r + 1];
-	uint32_t j = qh.split[r], jend = qh.split[r + 1];
+	const uint32_t i = ch.split[r], iend = ch.split[r + 1];
+	const uint32_t j = qh.split[r], jend = qh.split[r + 1];
 	const uint64_t range_begin = nbins / kSub * r, range_end = nbins / kSub * (r + 1);
 	int64_t D = (int64_t)(i ? CP[i - 1] : 0u) - (int64_t)(j ? CQ[j - 1] : 0u);     // prefix difference entering the sub-range
 	uint64_t pos = range_begin, manh = 0, dotx = 0, emd = 0;
@@ -316,15 +324,9 @@ __global__ void __launch_bounds__(256) k_pair_sparse(
 		qm = (double)reinterpret_cast<const MscSlotScalars*>(q_scalars)->mag;
 		t11 = div_term_sp(1, 1, cm, qm, order);
 	}
-	const uint32_t kInf = 0xffffffffu;
-	uint2 a = i < iend ? P[i] : make_uint2(kInf, 1u);
-	uint2 b = j < jend ? Q[j] : make_uint2(kInf, 1u);
-	while (i < iend || j < jend) {
-		const uint32_t e = a.x < b.x ? a.x : b.x;
-		const bool ta = a.x == e, tb = b.x == e;
+	merge_walk(P, i, iend, Q, j, jend, [&](uint32_t e, uint32_t pv, uint32_t qv) {
 		const uint64_t absD = (uint64_t)(D < 0 ? -D : D);
 		emd += absD * ((uint64_t)e - pos);                 // bins [pos, e) all carry the prefix difference D
-		const uint32_t pv = ta ? a.y : 1u, qv = tb ? b.y : 1u;
 		manh += pv > qv ? pv - qv : qv - pv;
 		dotx += (uint64_t)pv * qv - 1;
 		D += (int64_t)pv - (int64_t)qv;
@@ -336,9 +338,7 @@ __global__ void __launch_bounds__(256) k_pair_sparse(
 			js += tt.js - t11.js;
 		}
 		pos = e;
-		if (ta) { i++; a = i < iend ? P[i] : make_uint2(kInf, 1u); }
-		if (tb) { j++; b = j < jend ? Q[j] : make_uint2(kInf, 1u); }
-	}
+	});
 	{
 		const uint64_t absD = (uint64_t)(D < 0 ? -D : D);
 		emd += absD * (range_end - pos);
@@ -396,20 +396,9 @@ __global__ void __launch_bounds__(256) k_pair_sparse_groups(
 	const MscSparseHdr qh = *q_hdr_p;
 	const uint2* P = c_ent + ch.off;
 	const uint2* Q = q_ent + qh.off;
-	uint32_t i = ch.split[r], iend = ch.split[r + 1];
-	uint32_t j = qh.split[r], jend = qh.split[r + 1];
 	GroupState st;
 	st.g = 0xffffffffu; st.markov = 0.0; st.rre = 0.0;
-	const uint32_t kInf = 0xffffffffu;
-	uint2 a = i < iend ? P[i] : make_uint2(kInf, 1u);
-	uint2 b = j < jend ? Q[j] : make_uint2(kInf, 1u);
-	while (i < iend || j < jend) {
-		const uint32_t e = a.x < b.x ? a.x : b.x;
-		const bool ta = a.x == e, tb = b.x == e;
-		group_put(st, e, ta ? a.y : 1u, tb ? b.y : 1u);
-		if (ta) { i++; a = i < iend ? P[i] : make_uint2(kInf, 1u); }
-		if (tb) { j++; b = j < jend ? Q[j] : make_uint2(kInf, 1u); }
-	}
+	merge_walk(P, ch.split[r], ch.split[r + 1], Q, qh.split[r], qh.split[r + 1], [&](uint32_t bin, uint32_t pv, uint32_t qv) { group_put(st, bin, pv, qv); });
 	group_close(st);
 	out[((uint64_t)c * kSub + r) * 2] = st.markov;
 	out[((uint64_t)c * kSub + r) * 2 + 1] = st.rre;
@@ -501,63 +490,63 @@ __global__ void __launch_bounds__(256) k_sparse_scatter(const uint2* __restrict_
 	}
 }
 
+// Rounding needs no bin type: every stored value is min(1 + occurrences, max(T)) <= max(T) by construction, so is every mean of
+// stored values (and every all-rank sum divided by the all-rank count), and (T)round(mean) never truncates. The one caller whose
+// result may exceed max(T) sweeps column SUMS (m = 1, msc_colsum_partial) and wants all 32 bits of them.
 struct MeanBin { uint32_t r; uint64_t fl; };
-template <typename T>
 __device__ __forceinline__ MeanBin mean_bin(uint32_t E, uint32_t m) {
 	MeanBin b;
 	const double mean = (double)((uint64_t)m + E) / (double)m;       // (sum of the m bins) / m, cluster/ClusterFactory.cpp:349-357
-	b.r = (uint32_t)(T)round(mean);                                   // (T)round(c.points[i]), clutil/DivergencePoint.cpp:61
+	b.r = (uint32_t)(uint64_t)round(mean);                            // (T)round(c.points[i]), clutil/DivergencePoint.cpp:61
 	b.fl = (uint64_t)floor(mean);                                     // uint64 += double truncates every step (:62)
 	return b;
 }
 
-// one wave per chunk of bins; counts[chunk] = {entries with r >= 2, sum (r-1), sum (floor-1)}
-template <typename T>
-__global__ void __launch_bounds__(64) k_sparse_mean_count(const uint32_t* __restrict__ acc, uint64_t chunk_bins, uint32_t m,
-                                                          uint64_t* __restrict__ counts) {
-	const uint64_t base = (uint64_t)blockIdx.x * chunk_bins;
-	uint64_t n = 0, ex = 0, fl = 0;
-	for (uint64_t i = threadIdx.x; i < chunk_bins; i += 64) {
-		const uint32_t E = acc[base + i];
-		if (E) {
-			const MeanBin b = mean_bin<T>(E, m);
-			if (b.r >= 2) { n++; ex += b.r - 1; }
-			fl += b.fl - 1;
-		}
-	}
-	n = wave_sum_u64(n); ex = wave_sum_u64(ex); fl = wave_sum_u64(fl);
-	if (threadIdx.x == 0) { counts[blockIdx.x * 3ull] = n; counts[blockIdx.x * 3ull + 1] = ex; counts[blockIdx.x * 3ull + 2] = fl; }
-}
-
-template <typename T>
-__global__ void __launch_bounds__(64) k_sparse_mean_write(uint32_t* __restrict__ acc, uint64_t chunk_bins, uint32_t m,
-                                                          const uint64_t* __restrict__ chunk_off, const uint64_t* __restrict__ chunk_cum,
-                                                          uint2* __restrict__ ent, uint32_t* __restrict__ cum) {
-	const uint64_t base = (uint64_t)blockIdx.x * chunk_bins;
-	uint64_t o = chunk_off[blockIdx.x];
-	uint32_t run = (uint32_t)chunk_cum[blockIdx.x];
-	const uint32_t lane = threadIdx.x;
-	for (uint64_t i0 = 0; i0 < chunk_bins; i0 += 64) {
-		const uint64_t i = i0 + lane;
-		uint32_t E = 0;
-		if (i < chunk_bins) { E = acc[base + i]; if (E) acc[base + i] = 0; }       // leave the accumulator clean for the next call
-		uint32_t r = 1;
-		if (E) r = mean_bin<T>(E, m).r;
-		const bool emit = r >= 2;
-		const unsigned long long mask = __ballot(emit);
-		const uint32_t ex = emit ? r - 1 : 0;
-		const uint32_t ex_incl = wave_incl_scan(ex);
-		if (emit) {
-			const uint32_t rank = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-			ent[o + rank] = make_uint2((uint32_t)(base + i), r);
-			cum[o + rank] = run + ex_incl;
-		}
-		o += (uint64_t)__popcll(mask);
-		run += (uint32_t)__builtin_amdgcn_readlane((int)ex_incl, 63);
+// The count step of a sweep: what the bin with summed excess E adds to a chunk's {entries with r >= 2, sum (r-1), sum (floor-1)} ...
+struct MeanCounts { uint64_t n = 0, ex = 0, fl = 0; };
+__device__ __forceinline__ void mean_count_bin(MeanCounts& k, uint32_t E, uint32_t m) {
+	if (E) {
+		const MeanBin b = mean_bin(E, m);
+		if (b.r >= 2) { k.n++; k.ex += b.r - 1; }
+		k.fl += b.fl - 1;
 	}
 }
+// ... and the wave's record of them
+__device__ __forceinline__ void mean_counts_store(MeanCounts k, uint64_t* __restrict__ rec) {
+	k.n = wave_sum_u64(k.n); k.ex = wave_sum_u64(k.ex); k.fl = wave_sum_u64(k.fl);
+	if ((threadIdx.x & 63) == 0) { rec[0] = k.n; rec[1] = k.ex; rec[2] = k.fl; }
+}
 
-// ---- the same three steps for MANY centres at once (the update stage of a mean-shift round on sparse sets): member j belongs to
+// The ordered emit of a sweep: every lane holds the summed excesses E[0 .. N) of N consecutive bins from bin0 (zeros for a lane
+// without bins), lanes in bin order. The entries leave in bin order = lane order, then the order inside the lane: one wave scan of
+// the lanes' entry counts and excess sums places them behind entry o / running excess `run`, which move on by the wave's totals.
+template <int N>
+__device__ __forceinline__ void mean_emit(const uint32_t (&E)[N], uint32_t m, uint32_t bin0, uint64_t& o, uint32_t& run, uint2* __restrict__ ent,
+                                          uint32_t* __restrict__ cum) {
+	uint32_t r[N], cnt = 0, exs = 0;
+#pragma unroll
+	for (int j = 0; j < N; j++) {
+		r[j] = E[j] ? mean_bin(E[j], m).r : 1u;
+		if (r[j] >= 2) { cnt++; exs += r[j] - 1; }
+	}
+	const uint32_t cnt_incl = wave_incl_scan(cnt), ex_incl = wave_incl_scan(exs);
+	if (cnt) {
+		uint64_t at = o + (cnt_incl - cnt);
+		uint32_t c = run + (ex_incl - exs);
+#pragma unroll
+		for (int j = 0; j < N; j++)
+			if (r[j] >= 2) {
+				c += r[j] - 1;
+				ent[at] = make_uint2(bin0 + (uint32_t)j, r[j]);
+				cum[at] = c;
+				at++;
+			}
+	}
+	o += (uint64_t)__builtin_amdgcn_readlane((int)cnt_incl, 63);
+	run += (uint32_t)__builtin_amdgcn_readlane((int)ex_incl, 63);
+}
+
+// ---- scatter and the two sweeps for MANY centres at once (the update stage of a mean-shift round on sparse sets): member j belongs to
 // centre seg[j] of the chunk; accumulator, counts and offsets carry a centre dimension (acc[centre][bin]); m differs per centre.
 // touched (optional): one bit per group of 16 bins and centre, word w of a centre = groups 32 w .. 32 w + 31 (the grouped sweeps below)
 __global__ void __launch_bounds__(256) k_sparse_scatter_batch(const uint2* __restrict__ ent, const MscSparseHdr* __restrict__ hdr,
@@ -578,99 +567,45 @@ __global__ void __launch_bounds__(256) k_sparse_scatter_batch(const uint2* __res
 	}
 }
 
-// (Both sweeps read four bins per lane and instruction: almost every group of 256 bins of an accumulator is zero -- a centre's
+// One wave per (centre, chunk of bins); m = m_of[centre], or m_one for the one centre of a call without a list (msc_mean_nearest).
+// Both sweeps read four bins per lane and instruction: almost every group of 256 bins of an accumulator is zero -- a centre's
 // neighbourhood touches a per cent or two of the 4^k bins --, so the common iteration is one 1 KiB load and a vote. With one bin per lane
-// the two sweeps ran at 0.43 TB/s and were half of the device time of the update stage of a 200 000-sequence run.)
-template <typename T>
+// the two sweeps ran at 0.43 TB/s and were half of the device time of the update stage of a 200 000-sequence run.
+// chunk_bins % 256 == 0 (host-checked).
 __global__ void __launch_bounds__(64) k_sparse_mean_count_batch(const uint32_t* __restrict__ acc, uint64_t nbins, uint64_t chunk_bins,
-                                                                const uint32_t* __restrict__ m_of, uint64_t* __restrict__ counts) {
+                                                                const uint32_t* __restrict__ m_of, uint32_t m_one, uint64_t* __restrict__ counts) {
 	const uint32_t ci = blockIdx.y, n_chunks = gridDim.x;
-	const uint32_t m = m_of[ci];
+	const uint32_t m = m_of ? m_of[ci] : m_one;
 	const uint64_t base = (uint64_t)ci * nbins + (uint64_t)blockIdx.x * chunk_bins;
-	uint64_t n = 0, ex = 0, fl = 0;
+	MeanCounts k;
 	if (m) {
-		auto one = [&](uint32_t E) {
-			if (E) {
-				const MeanBin b = mean_bin<T>(E, m);
-				if (b.r >= 2) { n++; ex += b.r - 1; }
-				fl += b.fl - 1;
-			}
-		};
-		if (chunk_bins % 256 == 0) {
-			const uint4* a4 = reinterpret_cast<const uint4*>(acc + base);
-			for (uint64_t i = threadIdx.x; i < chunk_bins / 4; i += 64) {
-				const uint4 E = a4[i];
-				if (E.x | E.y | E.z | E.w) { one(E.x); one(E.y); one(E.z); one(E.w); }
-			}
-		} else {
-			for (uint64_t i = threadIdx.x; i < chunk_bins; i += 64) one(acc[base + i]);
+		const uint4* a4 = reinterpret_cast<const uint4*>(acc + base);
+		for (uint64_t i = threadIdx.x; i < chunk_bins / 4; i += 64) {
+			const uint4 E = a4[i];
+			if (E.x | E.y | E.z | E.w) { mean_count_bin(k, E.x, m); mean_count_bin(k, E.y, m); mean_count_bin(k, E.z, m); mean_count_bin(k, E.w, m); }
 		}
 	}
-	n = wave_sum_u64(n); ex = wave_sum_u64(ex); fl = wave_sum_u64(fl);
-	if (threadIdx.x == 0) {
-		uint64_t* o = counts + ((uint64_t)ci * n_chunks + blockIdx.x) * 3;
-		o[0] = n; o[1] = ex; o[2] = fl;
-	}
+	mean_counts_store(k, counts + ((uint64_t)ci * n_chunks + blockIdx.x) * 3);
 }
 
-template <typename T>
 __global__ void __launch_bounds__(64) k_sparse_mean_write_batch(uint32_t* __restrict__ acc, uint64_t nbins, uint64_t chunk_bins, const uint32_t* __restrict__ m_of,
-                                                                const uint64_t* __restrict__ chunk_off, const uint64_t* __restrict__ chunk_cum,
+                                                                uint32_t m_one, const uint64_t* __restrict__ chunk_off, const uint64_t* __restrict__ chunk_cum,
                                                                 uint2* __restrict__ ent, uint32_t* __restrict__ cum) {
 	const uint32_t ci = blockIdx.y, n_chunks = gridDim.x;
-	const uint32_t m = m_of[ci];
+	const uint32_t m = m_of ? m_of[ci] : m_one;
 	if (m == 0) return;
 	const uint64_t bin0 = (uint64_t)blockIdx.x * chunk_bins, base = (uint64_t)ci * nbins + bin0;
 	uint64_t o = chunk_off[(uint64_t)ci * n_chunks + blockIdx.x];
 	uint32_t run = (uint32_t)chunk_cum[(uint64_t)ci * n_chunks + blockIdx.x];
 	const uint32_t lane = threadIdx.x;
-	if (chunk_bins % 256 == 0) {
-		// lane l holds bins i0 + 4 l .. + 3: entries leave in bin order = lane order, then the order inside the lane
-		uint4* a4 = reinterpret_cast<uint4*>(acc + base);
-		for (uint64_t i0 = 0; i0 < chunk_bins; i0 += 256) {
-			const uint4 E4 = a4[i0 / 4 + lane];
-			const bool any = (E4.x | E4.y | E4.z | E4.w) != 0;
-			if (__ballot(any) == 0) continue;
-			if (any) a4[i0 / 4 + lane] = make_uint4(0, 0, 0, 0);       // leave the accumulator clean for the next chunk of centres
-			const uint32_t E[4] = {E4.x, E4.y, E4.z, E4.w};
-			uint32_t r[4], cnt = 0, exs = 0;
-#pragma unroll
-			for (int j = 0; j < 4; j++) {
-				r[j] = E[j] ? mean_bin<T>(E[j], m).r : 1u;
-				if (r[j] >= 2) { cnt++; exs += r[j] - 1; }
-			}
-			const uint32_t cnt_incl = wave_incl_scan(cnt), ex_incl = wave_incl_scan(exs);
-			uint32_t at = cnt_incl - cnt, c = run + ex_incl - exs;
-#pragma unroll
-			for (int j = 0; j < 4; j++)
-				if (r[j] >= 2) {
-					c += r[j] - 1;
-					ent[o + at] = make_uint2((uint32_t)(bin0 + i0 + 4 * lane + j), r[j]);
-					cum[o + at] = c;
-					at++;
-				}
-			o += (uint64_t)__builtin_amdgcn_readlane((int)cnt_incl, 63);
-			run += (uint32_t)__builtin_amdgcn_readlane((int)ex_incl, 63);
-		}
-		return;
-	}
-	for (uint64_t i0 = 0; i0 < chunk_bins; i0 += 64) {
-		const uint64_t i = i0 + lane;
-		uint32_t E = 0;
-		if (i < chunk_bins) { E = acc[base + i]; if (E) acc[base + i] = 0; }
-		uint32_t r = 1;
-		if (E) r = mean_bin<T>(E, m).r;
-		const bool emit = r >= 2;
-		const unsigned long long mask = __ballot(emit);
-		const uint32_t ex = emit ? r - 1 : 0;
-		const uint32_t ex_incl = wave_incl_scan(ex);
-		if (emit) {
-			const uint32_t rank = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-			ent[o + rank] = make_uint2((uint32_t)(bin0 + i), r);
-			cum[o + rank] = run + ex_incl;
-		}
-		o += (uint64_t)__popcll(mask);
-		run += (uint32_t)__builtin_amdgcn_readlane((int)ex_incl, 63);
+	uint4* a4 = reinterpret_cast<uint4*>(acc + base);
+	for (uint64_t i0 = 0; i0 < chunk_bins; i0 += 256) {      // lane l holds bins i0 + 4 l .. + 3
+		const uint4 E4 = a4[i0 / 4 + lane];
+		const bool any = (E4.x | E4.y | E4.z | E4.w) != 0;
+		if (__ballot(any) == 0) continue;
+		if (any) a4[i0 / 4 + lane] = make_uint4(0, 0, 0, 0);       // leave the accumulator clean for the next call
+		const uint32_t E[4] = {E4.x, E4.y, E4.z, E4.w};
+		mean_emit(E, m, (uint32_t)(bin0 + i0 + 4 * lane), o, run, ent, cum);
 	}
 }
 
@@ -695,16 +630,15 @@ __device__ __forceinline__ uint32_t expand_touched(const uint32_t* __restrict__ 
 	return (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
 }
 
-template <typename T>
 __global__ void __launch_bounds__(64) k_sparse_mean_count_groups(const uint32_t* __restrict__ acc, const uint32_t* __restrict__ touched, uint64_t nbins,
-                                                                 uint64_t chunk_bins, const uint32_t* __restrict__ m_of, uint64_t* __restrict__ counts) {
+                                                                 uint64_t chunk_bins, const uint32_t* __restrict__ m_of, uint32_t m_one, uint64_t* __restrict__ counts) {
 	__shared__ uint32_t s_list[kGroupList];
 	const uint32_t ci = blockIdx.y, n_chunks = gridDim.x, lane = threadIdx.x;
-	const uint32_t m = m_of[ci];
+	const uint32_t m = m_of ? m_of[ci] : m_one;
 	const uint32_t* a = acc + (uint64_t)ci * nbins;
 	const uint32_t* words = touched + (uint64_t)ci * (nbins >> 9);
 	const uint32_t w_lo = (uint32_t)(((uint64_t)blockIdx.x * chunk_bins) >> 9), w_hi = (uint32_t)(((uint64_t)(blockIdx.x + 1) * chunk_bins) >> 9);
-	uint64_t n = 0, ex = 0, fl = 0;
+	MeanCounts k;
 	if (m) {
 		for (uint32_t w0 = w_lo; w0 < w_hi; w0 += 64) {
 			const uint32_t T_ = expand_touched(words, w0, w_hi - w0 < 64 ? w_hi - w0 : 64, lane, s_list);
@@ -715,31 +649,21 @@ __global__ void __launch_bounds__(64) k_sparse_mean_count_groups(const uint32_t*
 #pragma unroll
 					for (int q = 0; q < 4; q++) { const uint4 v = p[q]; E[4 * q] = v.x; E[4 * q + 1] = v.y; E[4 * q + 2] = v.z; E[4 * q + 3] = v.w; }
 #pragma unroll
-					for (int q = 0; q < 16; q++)
-						if (E[q]) {
-							const MeanBin b = mean_bin<T>(E[q], m);
-							if (b.r >= 2) { n++; ex += b.r - 1; }
-							fl += b.fl - 1;
-						}
+					for (int q = 0; q < 16; q++) mean_count_bin(k, E[q], m);
 				}
 			}
 			__builtin_amdgcn_wave_barrier();          // the list is rewritten by the next window
 		}
 	}
-	n = wave_sum_u64(n); ex = wave_sum_u64(ex); fl = wave_sum_u64(fl);
-	if (lane == 0) {
-		uint64_t* o = counts + ((uint64_t)ci * n_chunks + blockIdx.x) * 3;
-		o[0] = n; o[1] = ex; o[2] = fl;
-	}
+	mean_counts_store(k, counts + ((uint64_t)ci * n_chunks + blockIdx.x) * 3);
 }
 
-template <typename T>
 __global__ void __launch_bounds__(64) k_sparse_mean_write_groups(uint32_t* __restrict__ acc, uint32_t* __restrict__ touched, uint64_t nbins, uint64_t chunk_bins,
-                                                                 const uint32_t* __restrict__ m_of, const uint64_t* __restrict__ chunk_off,
+                                                                 const uint32_t* __restrict__ m_of, uint32_t m_one, const uint64_t* __restrict__ chunk_off,
                                                                  const uint64_t* __restrict__ chunk_cum, uint2* __restrict__ ent, uint32_t* __restrict__ cum) {
 	__shared__ uint32_t s_list[kGroupList];
 	const uint32_t ci = blockIdx.y, n_chunks = gridDim.x, lane = threadIdx.x;
-	const uint32_t m = m_of[ci];
+	const uint32_t m = m_of ? m_of[ci] : m_one;
 	if (m == 0) return;
 	uint32_t* a = acc + (uint64_t)ci * nbins;
 	uint32_t* words = touched + (uint64_t)ci * (nbins >> 9);
@@ -750,38 +674,18 @@ __global__ void __launch_bounds__(64) k_sparse_mean_write_groups(uint32_t* __res
 		const uint32_t nw = w_hi - w0 < 64 ? w_hi - w0 : 64;
 		const uint32_t T_ = expand_touched(words, w0, nw, lane, s_list);
 		for (uint32_t g0 = 0; g0 < T_; g0 += 64) {
-			uint32_t r[16], n_emit = 0, ex_sum = 0, grp = 0;
-			const bool have = g0 + lane < T_;
-			if (have) {
+			uint32_t E[16] = {}, grp = 0;
+			if (g0 + lane < T_) {
 				grp = s_list[g0 + lane];
 				uint4* p = reinterpret_cast<uint4*>(a + (uint64_t)grp * 16);
 #pragma unroll
 				for (int q = 0; q < 4; q++) {
 					const uint4 v = p[q];
-					r[4 * q] = v.x; r[4 * q + 1] = v.y; r[4 * q + 2] = v.z; r[4 * q + 3] = v.w;
+					E[4 * q] = v.x; E[4 * q + 1] = v.y; E[4 * q + 2] = v.z; E[4 * q + 3] = v.w;
 					p[q] = make_uint4(0u, 0u, 0u, 0u);          // leave the accumulator clean for the next chunk of centres
 				}
-#pragma unroll
-				for (int q = 0; q < 16; q++) {
-					r[q] = r[q] ? mean_bin<T>(r[q], m).r : 1u;
-					if (r[q] >= 2) { n_emit++; ex_sum += r[q] - 1u; }
-				}
 			}
-			const uint32_t e_incl = wave_incl_scan(n_emit), x_incl = wave_incl_scan(ex_sum);
-			if (n_emit) {
-				uint64_t at = o + (e_incl - n_emit);
-				uint32_t c_run = run + (x_incl - ex_sum);
-#pragma unroll
-				for (int q = 0; q < 16; q++)
-					if (r[q] >= 2) {
-						c_run += r[q] - 1u;
-						ent[at] = make_uint2(grp * 16u + (uint32_t)q, r[q]);
-						cum[at] = c_run;
-						at++;
-					}
-			}
-			o += (uint64_t)__builtin_amdgcn_readlane((int)e_incl, 63);
-			run += (uint32_t)__builtin_amdgcn_readlane((int)x_incl, 63);
+			mean_emit(E, m, grp * 16u, o, run, ent, cum);
 		}
 		__builtin_amdgcn_wave_barrier();
 		if (lane < nw && words[w0 + lane]) words[w0 + lane] = 0u;          // ... and the bitmap
@@ -839,22 +743,15 @@ __global__ void __launch_bounds__(256) k_pair_sparse_lds(
 		const uint32_t i0 = lower_bound_lds(clist, ch.nnz, lane * sub);
 		uint32_t i1 = __shfl_down(i0, 1, 64);
 		if (lane == 63) i1 = ch.nnz;
-		uint32_t i = i0, j = j0;
-		int32_t D = (int32_t)(i ? c_cum[ch.off + i - 1] : 0u) - (int32_t)cq0;           // prefix difference entering the sub-range
+		int32_t D = (int32_t)(i0 ? c_cum[ch.off + i0 - 1] : 0u) - (int32_t)cq0;         // prefix difference entering the sub-range
 		uint32_t pos = lane * sub, manh = 0;
 		uint64_t dotx = 0, emd = 0;
 		double jd = 0.0, js = 0.0, cm = 0.0;
 		DivTerm t11{0.0, 0.0};
 		if constexpr (DIV) { cm = (double)cs->mag; t11 = div_term_sp(1, 1, cm, qm, order); }
-		const uint32_t kInf = 0xffffffffu;
-		uint2 a = i < i1 ? clist[i] : make_uint2(kInf, 1u);
-		uint2 b = j < j1 ? qlist[j] : make_uint2(kInf, 1u);
-		while (i < i1 || j < j1) {
-			const uint32_t e = a.x < b.x ? a.x : b.x;
-			const bool ta = a.x == e, tb = b.x == e;
+		merge_walk(clist, i0, i1, qlist, j0, j1, [&](uint32_t e, uint32_t pv, uint32_t qv) {
 			const uint32_t absD = (uint32_t)(D < 0 ? -D : D);
 			emd += (uint64_t)absD * (e - pos);
-			const uint32_t pv = ta ? a.y : 1u, qv = tb ? b.y : 1u;
 			manh += pv > qv ? pv - qv : qv - pv;
 			dotx += (uint64_t)(pv * qv - 1u);               // counts < 2^16: the product fits 32 bits
 			D += (int32_t)pv - (int32_t)qv;
@@ -866,9 +763,7 @@ __global__ void __launch_bounds__(256) k_pair_sparse_lds(
 				js += tt.js - t11.js;
 			}
 			pos = e;
-			if (ta) { i++; a = i < i1 ? clist[i] : make_uint2(kInf, 1u); }
-			if (tb) { j++; b = j < j1 ? qlist[j] : make_uint2(kInf, 1u); }
-		}
+		});
 		{
 			const uint32_t absD = (uint32_t)(D < 0 ? -D : D);
 			emd += (uint64_t)absD * ((lane + 1) * sub - pos);
@@ -1287,24 +1182,20 @@ __global__ void __launch_bounds__(256) k_pair_sparse_wl(
 // ================================================================================================ launchers
 hipError_t msc_launch_sparse_count(hipStream_t st, const void* scratch_bins, const MscLayout& L, int dtype, uint32_t n, uint64_t* counts) {
 	if (n == 0) return hipSuccess;
-	switch (dtype) {
-	case 8: k_sparse_count<uint8_t><<<dim3(n), dim3(kBlockC), 0, st>>>((const uint8_t*)scratch_bins, L.padded_bins, L.S, L.R, counts); break;
-	case 16: k_sparse_count<uint16_t><<<dim3(n), dim3(kBlockC), 0, st>>>((const uint16_t*)scratch_bins, L.padded_bins, L.S, L.R, counts); break;
-	case 32: k_sparse_count<uint32_t><<<dim3(n), dim3(kBlockC), 0, st>>>((const uint32_t*)scratch_bins, L.padded_bins, L.S, L.R, counts); break;
-	default: k_sparse_count<uint64_t><<<dim3(n), dim3(kBlockC), 0, st>>>((const uint64_t*)scratch_bins, L.padded_bins, L.S, L.R, counts); break;
-	}
+	msc_by_dtype(dtype, [&](auto tag) {
+		using T = decltype(tag);
+		k_sparse_count<T><<<dim3(n), dim3(kBlockC), 0, st>>>((const T*)scratch_bins, L.padded_bins, L.S, L.R, counts);
+	});
 	return hipGetLastError();
 }
 
 hipError_t msc_launch_sparse_write(hipStream_t st, const void* scratch_bins, const MscLayout& L, int dtype, uint32_t n, const MscSparseHdr* hdr,
                                    uint64_t first_slot, const uint64_t* cum_base, void* ent, uint32_t* cum) {
 	if (n == 0) return hipSuccess;
-	switch (dtype) {
-	case 8: k_sparse_write<uint8_t><<<dim3(n), dim3(kBlockC), 0, st>>>((const uint8_t*)scratch_bins, L.padded_bins, L.S, L.R, hdr, first_slot, cum_base, (uint2*)ent, cum); break;
-	case 16: k_sparse_write<uint16_t><<<dim3(n), dim3(kBlockC), 0, st>>>((const uint16_t*)scratch_bins, L.padded_bins, L.S, L.R, hdr, first_slot, cum_base, (uint2*)ent, cum); break;
-	case 32: k_sparse_write<uint32_t><<<dim3(n), dim3(kBlockC), 0, st>>>((const uint32_t*)scratch_bins, L.padded_bins, L.S, L.R, hdr, first_slot, cum_base, (uint2*)ent, cum); break;
-	default: k_sparse_write<uint64_t><<<dim3(n), dim3(kBlockC), 0, st>>>((const uint64_t*)scratch_bins, L.padded_bins, L.S, L.R, hdr, first_slot, cum_base, (uint2*)ent, cum); break;
-	}
+	msc_by_dtype(dtype, [&](auto tag) {
+		using T = decltype(tag);
+		k_sparse_write<T><<<dim3(n), dim3(kBlockC), 0, st>>>((const T*)scratch_bins, L.padded_bins, L.S, L.R, hdr, first_slot, cum_base, (uint2*)ent, cum);
+	});
 	return hipGetLastError();
 }
 
@@ -1334,27 +1225,6 @@ hipError_t msc_launch_sparse_scatter(hipStream_t st, const void* ent, const MscS
 	if (m == 0) return hipSuccess;
 	const uint32_t parts = std::max<uint32_t>(1, std::min<uint32_t>(32, 512 / m));          // (about 512 workgroups: few members -> many parts each)
 	k_sparse_scatter<<<dim3(m, parts), dim3(256), 0, st>>>((const uint2*)ent, hdr, slots, m, acc);
-	return hipGetLastError();
-}
-
-hipError_t msc_launch_sparse_mean_count(hipStream_t st, int dtype, const uint32_t* acc, uint32_t n_chunks, uint64_t chunk_bins, uint32_t m, uint64_t* counts) {
-	switch (dtype) {
-	case 8: k_sparse_mean_count<uint8_t><<<dim3(n_chunks), dim3(64), 0, st>>>(acc, chunk_bins, m, counts); break;
-	case 16: k_sparse_mean_count<uint16_t><<<dim3(n_chunks), dim3(64), 0, st>>>(acc, chunk_bins, m, counts); break;
-	case 32: k_sparse_mean_count<uint32_t><<<dim3(n_chunks), dim3(64), 0, st>>>(acc, chunk_bins, m, counts); break;
-	default: k_sparse_mean_count<uint64_t><<<dim3(n_chunks), dim3(64), 0, st>>>(acc, chunk_bins, m, counts); break;
-	}
-	return hipGetLastError();
-}
-
-hipError_t msc_launch_sparse_mean_write(hipStream_t st, int dtype, uint32_t* acc, uint32_t n_chunks, uint64_t chunk_bins, uint32_t m,
-                                        const uint64_t* chunk_off, const uint64_t* chunk_cum, void* ent, uint32_t* cum) {
-	switch (dtype) {
-	case 8: k_sparse_mean_write<uint8_t><<<dim3(n_chunks), dim3(64), 0, st>>>(acc, chunk_bins, m, chunk_off, chunk_cum, (uint2*)ent, cum); break;
-	case 16: k_sparse_mean_write<uint16_t><<<dim3(n_chunks), dim3(64), 0, st>>>(acc, chunk_bins, m, chunk_off, chunk_cum, (uint2*)ent, cum); break;
-	case 32: k_sparse_mean_write<uint32_t><<<dim3(n_chunks), dim3(64), 0, st>>>(acc, chunk_bins, m, chunk_off, chunk_cum, (uint2*)ent, cum); break;
-	default: k_sparse_mean_write<uint64_t><<<dim3(n_chunks), dim3(64), 0, st>>>(acc, chunk_bins, m, chunk_off, chunk_cum, (uint2*)ent, cum); break;
-	}
 	return hipGetLastError();
 }
 
@@ -1410,8 +1280,6 @@ hipError_t msc_launch_pair_sparse_lds(hipStream_t st, const void* c_ent, const u
 	return hipGetLastError();
 }
 
-int msc_sparse_div_waves();
-bool msc_sparse_mp_pairs();
 // MSC_SPARSE_MP_DMA=1: the chunks of the merge-path kernel are staged by LDS-DMA instead of the load -> store loop. OFF by default:
 // measured r03 (k = 13, 20 kb lists, 8 000 candidates) 2.89 ms per launch against 0.78 ms for the loop, and results that differ -- list
 // pieces start on 8-byte, not 16-byte, boundaries of global memory, which global_load_lds_dwordx4 does not take (profiles/r03_notes.md).
@@ -1440,6 +1308,34 @@ static bool mp_wide(uint64_t nbins) {
 	return force == 575 ? true : force == 512 ? false : nbins <= (1ull << 22);
 }
 
+// waves per SIMD the divergence form of the merge-path kernel is compiled for and launched at (r03: 6 against 4 and 7)
+constexpr int kMpDivWaves = 6;
+int msc_sparse_div_waves() { return kMpDivWaves; }
+
+// every launch of k_pair_sparse_mp, with the kernel's own argument list: the divergence form when div_tables is given, the pair-list
+// form when segs is, the chunk of the set's 4^k
+template <bool DIV, bool PAIRS, typename... Args>
+static void launch_mp_t(hipStream_t st, uint32_t blocks, uint64_t nbins, Args... args) {
+	constexpr int kWaves = DIV ? kMpDivWaves : 1;
+	if (mp_wide(nbins)) k_pair_sparse_mp<DIV, kMpChunkWide, PAIRS, kWaves><<<dim3(blocks), dim3(256), 0, st>>>(args...);
+	else k_pair_sparse_mp<DIV, kMpChunk, PAIRS, kWaves><<<dim3(blocks), dim3(256), 0, st>>>(args...);
+}
+static hipError_t launch_mp(hipStream_t st, uint32_t blocks, const void* c_ent, const uint32_t* c_cum, const MscSparseHdr* c_hdr, const uint8_t* cand_scalars,
+                            uint64_t scalar_stride, const uint32_t* cand_slots, uint32_t m, const void* q_ent, const uint32_t* q_cum, const MscSparseHdr* q_hdr,
+                            const uint8_t* q_scalars, uint64_t nbins, int use_window, uint64_t min_len, uint64_t max_len, MscPartial* partials, void* div_tables,
+                            void* div_partials, int order, const MscBatchSeg* segs, const uint32_t* pair_seg, uint32_t parts, uint64_t q_scalar_stride,
+                            uint32_t div_stride) {
+	auto go = [&](auto div, auto pairs) {
+		launch_mp_t<decltype(div)::value, decltype(pairs)::value>(st, blocks, nbins, (const uint2*)c_ent, c_cum, c_hdr, cand_scalars, scalar_stride, cand_slots, m,
+		                                                           (const uint2*)q_ent, q_cum, q_hdr, q_scalars, nbins, use_window, min_len, max_len, partials,
+		                                                           (const DivTerm*)div_tables, (double*)div_partials, order, segs, pair_seg, parts, q_scalar_stride,
+		                                                           div_stride, msc_sparse_mp_dma(), msc_sparse_mp_pairs());
+	};
+	if (div_tables) { if (segs) go(std::true_type{}, std::true_type{}); else go(std::true_type{}, std::false_type{}); }
+	else { if (segs) go(std::false_type{}, std::true_type{}); else go(std::false_type{}, std::false_type{}); }
+	return hipGetLastError();
+}
+
 // lists of any length up to msc_sparse_mp_max_entries() together; same arithmetic range as the LDS kernel (caller checks).
 // parts (1 .. 16): waves per candidate, each writing its own record -- partials[c * parts + p]. The divergence form writes its two
 // FP64 sums once per granule of the merged order (div_partials[c][div_stride][2], zeroed by the caller; the epilogue adds a pair's
@@ -1462,29 +1358,12 @@ hipError_t msc_launch_pair_sparse_mp(hipStream_t st, const void* c_ent, const ui
 		                                                     c_max_nnz, nbins, use_window, min_len, max_len, partials);
 		return hipGetLastError();
 	}
-	const int wpe = msc_sparse_div_waves();
-	const bool wide = mp_wide(nbins);
-	const uint32_t per_cu = div_tables ? (uint32_t)wpe : std::min<uint32_t>(8, (160 * 1024) / (4 * (kMpChunkWide + 9) * 8 + 512));      // LDS-limited residency; every wave walks several candidates
+	const uint32_t per_cu = div_tables ? (uint32_t)kMpDivWaves : std::min<uint32_t>(8, (160 * 1024) / (4 * (kMpChunkWide + 9) * 8 + 512));      // LDS-limited residency; every wave walks several candidates
 	const uint64_t waves = (uint64_t)m * parts;
 	uint32_t blocks = (uint32_t)num_cus * per_cu;
 	if (blocks > (waves + 3) / 4) blocks = (uint32_t)((waves + 3) / 4);
-	if (div_tables) {
-#define MSC_MP_DIV(W) if (wide) MSC_MP_DIV_T(kMpChunkWide, W); else MSC_MP_DIV_T(kMpChunk, W)
-#define MSC_MP_DIV_T(T, W) k_pair_sparse_mp<true, T, false, W><<<dim3(blocks), dim3(256), 0, st>>>((const uint2*)c_ent, c_cum, c_hdr, cand_scalars, scalar_stride, cand_slots, m, \
-		(const uint2*)q_ent, q_cum, q_hdr, q_scalars, nbins, use_window, min_len, max_len, partials, (const DivTerm*)div_tables, (double*)div_partials, order, nullptr, nullptr, parts, 0, div_stride, msc_sparse_mp_dma(), msc_sparse_mp_pairs())
-		MSC_MP_DIV(6);
-#undef MSC_MP_DIV
-#undef MSC_MP_DIV_T
-	} else if (wide) {
-		k_pair_sparse_mp<false, kMpChunkWide><<<dim3(blocks), dim3(256), 0, st>>>((const uint2*)c_ent, c_cum, c_hdr, cand_scalars, scalar_stride, cand_slots, m, (const uint2*)q_ent,
-		                                                                          q_cum, q_hdr, q_scalars, nbins, use_window, min_len, max_len, partials, nullptr, nullptr, order,
-		                                                                          nullptr, nullptr, parts, 0, 1, msc_sparse_mp_dma(), msc_sparse_mp_pairs());
-	} else {
-		k_pair_sparse_mp<false, kMpChunk><<<dim3(blocks), dim3(256), 0, st>>>((const uint2*)c_ent, c_cum, c_hdr, cand_scalars, scalar_stride, cand_slots, m, (const uint2*)q_ent,
-		                                                                      q_cum, q_hdr, q_scalars, nbins, use_window, min_len, max_len, partials, nullptr, nullptr, order,
-		                                                                      nullptr, nullptr, parts, 0, 1, msc_sparse_mp_dma(), msc_sparse_mp_pairs());
-	}
-	return hipGetLastError();
+	return launch_mp(st, blocks, c_ent, c_cum, c_hdr, cand_scalars, scalar_stride, cand_slots, m, q_ent, q_cum, q_hdr, q_scalars, nbins, use_window, min_len, max_len, partials,
+	                 div_tables, div_partials, order, nullptr, nullptr, parts, 0, div_stride);
 }
 
 // how many waves should share a candidate of a window of m (about `entries` merged entries each): fill the resident wave slots, keep
@@ -1493,12 +1372,10 @@ bool msc_sparse_wl_fits(uint32_t q_nnz, uint32_t c_max_nnz) {
 	static const bool no_wl = getenv("MSC_SPARSE_NO_WL") != nullptr;
 	return !no_wl && c_max_nnz && (uint64_t)q_nnz + 4ull * c_max_nnz + 10 <= 8192;
 }
-// waves per SIMD the divergence form of the merge-path kernel is compiled for and launched at (r03: 6 against 4 and 7)
-int msc_sparse_div_waves() { return 6; }
 uint32_t msc_sparse_mp_parts(uint32_t m, uint64_t entries, int num_cus, bool div) {
 	static const bool off = getenv("MSC_SPARSE_MP_NO_PARTS") != nullptr;
 	if (off || m == 0) return 1;
-	const uint64_t slots = (uint64_t)num_cus * (div ? 4 * msc_sparse_div_waves() : 32), chunks = entries / kMpChunk;
+	const uint64_t slots = (uint64_t)num_cus * (div ? 4 * kMpDivWaves : 32), chunks = entries / kMpChunk;
 	uint32_t parts = 1;
 	if (div) {
 		// the divergence form cuts between granules, each pair by its OWN length (k_pair_sparse_mp): the launch only sets the most a
@@ -1552,31 +1429,13 @@ hipError_t msc_launch_pair_sparse_mp_pairs(hipStream_t st, const void* c_ent, co
                                            MscPartial* partials, int order, int num_cus, const uint8_t* q_scalars, uint64_t q_scalar_stride, void* div_tables,
                                            void* div_partials, uint32_t div_stride) {
 	if (m == 0) return hipSuccess;
-	const bool wide = mp_wide(nbins);
-	const uint32_t per_cu = std::min<uint32_t>(8, (160 * 1024) / (4 * (kMpChunkWide + 9) * 8 + 512));
+	if (div_tables && (!q_scalars || !div_partials)) return hipErrorInvalidValue;
+	// the divergence sums of every pair as well: the same walk, hence the same bits, as the 1 x M divergence form
+	const uint32_t per_cu = div_tables ? (uint32_t)kMpDivWaves : std::min<uint32_t>(8, (160 * 1024) / (4 * (kMpChunkWide + 9) * 8 + 512));
 	uint32_t blocks = (uint32_t)num_cus * per_cu;
 	if (blocks > (m + 3) / 4) blocks = (m + 3) / 4;
-	if (div_tables) {      // the divergence sums of every pair as well: the same walk, hence the same bits, as the 1 x M divergence form
-		if (!q_scalars || !div_partials) return hipErrorInvalidValue;
-		const int wpe = msc_sparse_div_waves();
-		blocks = (uint32_t)num_cus * (uint32_t)wpe;
-		if (blocks > (m + 3) / 4) blocks = (m + 3) / 4;
-#define MSC_MP_DIVP(W) if (wide) MSC_MP_DIVP_T(kMpChunkWide, W); else MSC_MP_DIVP_T(kMpChunk, W)
-#define MSC_MP_DIVP_T(T, W) k_pair_sparse_mp<true, T, true, W><<<dim3(blocks), dim3(256), 0, st>>>((const uint2*)c_ent, c_cum, c_hdr, cand_scalars, scalar_stride, cand_slots, m, (const uint2*)q_ent, \
-		q_cum, q_hdr, q_scalars, nbins, use_window, 0, ~0ull, partials, (const DivTerm*)div_tables, (double*)div_partials, order, segs, pair_seg, 1, q_scalar_stride, div_stride, msc_sparse_mp_dma(), msc_sparse_mp_pairs())
-		MSC_MP_DIVP(6);
-#undef MSC_MP_DIVP
-#undef MSC_MP_DIVP_T
-		return hipGetLastError();
-	}
-	if (wide) {
-		k_pair_sparse_mp<false, kMpChunkWide, true><<<dim3(blocks), dim3(256), 0, st>>>((const uint2*)c_ent, c_cum, c_hdr, cand_scalars, scalar_stride, cand_slots, m, (const uint2*)q_ent, q_cum,
-		                                                                               q_hdr, nullptr, nbins, use_window, 0, ~0ull, partials, nullptr, nullptr, order, segs, pair_seg, 1, 0, 1, msc_sparse_mp_dma(), msc_sparse_mp_pairs());
-		return hipGetLastError();
-	}
-	k_pair_sparse_mp<false, kMpChunk, true><<<dim3(blocks), dim3(256), 0, st>>>((const uint2*)c_ent, c_cum, c_hdr, cand_scalars, scalar_stride, cand_slots, m, (const uint2*)q_ent, q_cum,
-	                                                                    q_hdr, nullptr, nbins, use_window, 0, ~0ull, partials, nullptr, nullptr, order, segs, pair_seg, 1, 0, 1, msc_sparse_mp_dma(), msc_sparse_mp_pairs());
-	return hipGetLastError();
+	return launch_mp(st, blocks, c_ent, c_cum, c_hdr, cand_scalars, scalar_stride, cand_slots, m, q_ent, q_cum, q_hdr, q_scalars, nbins, use_window, 0, ~0ull, partials,
+	                 div_tables, div_partials, order, segs, pair_seg, 1, q_scalar_stride, div_stride);
 }
 
 hipError_t msc_launch_sparse_scatter_batch(hipStream_t st, const void* ent, const MscSparseHdr* hdr, const uint32_t* slots, const uint32_t* seg, uint32_t n_members,
@@ -1586,49 +1445,28 @@ hipError_t msc_launch_sparse_scatter_batch(hipStream_t st, const void* ent, cons
 	return hipGetLastError();
 }
 
-hipError_t msc_launch_sparse_mean_count_batch(hipStream_t st, int dtype, const uint32_t* acc, uint64_t nbins, uint32_t n_chunks, uint64_t chunk_bins, uint32_t n_centres,
-                                              const uint32_t* m_of, uint64_t* counts, const uint32_t* touched) {
+// The two sweeps of n_centres accumulators in n_chunks chunks of chunk_bins bins each; m_of == nullptr: one centre of m_one members.
+// touched != nullptr: the sweeps over touched groups. A chunk is whole 1 KiB loads of the full sweep (256 bins) / whole bitmap words
+// of the grouped one (512): sparse sets have 4^k >= 16384 bins and every caller cuts them into a power of two of at most 4^k / 256
+// chunks, so a chunk is a power of two >= 256 and the full sweep needs no form for a ragged one.
+hipError_t msc_launch_sparse_mean_count_batch(hipStream_t st, const uint32_t* acc, uint64_t nbins, uint32_t n_chunks, uint64_t chunk_bins, uint32_t n_centres,
+                                              const uint32_t* m_of, uint32_t m_one, uint64_t* counts, const uint32_t* touched) {
 	if (n_centres == 0) return hipSuccess;
+	if (chunk_bins % (touched ? 512 : 256)) return hipErrorInvalidValue;
 	const dim3 grid(n_chunks, n_centres);
-	if (touched) {
-		if (chunk_bins % 512) return hipErrorInvalidValue;
-		switch (dtype) {
-		case 8: k_sparse_mean_count_groups<uint8_t><<<grid, dim3(64), 0, st>>>(acc, touched, nbins, chunk_bins, m_of, counts); break;
-		case 16: k_sparse_mean_count_groups<uint16_t><<<grid, dim3(64), 0, st>>>(acc, touched, nbins, chunk_bins, m_of, counts); break;
-		case 32: k_sparse_mean_count_groups<uint32_t><<<grid, dim3(64), 0, st>>>(acc, touched, nbins, chunk_bins, m_of, counts); break;
-		default: k_sparse_mean_count_groups<uint64_t><<<grid, dim3(64), 0, st>>>(acc, touched, nbins, chunk_bins, m_of, counts); break;
-		}
-		return hipGetLastError();
-	}
-	switch (dtype) {
-	case 8: k_sparse_mean_count_batch<uint8_t><<<grid, dim3(64), 0, st>>>(acc, nbins, chunk_bins, m_of, counts); break;
-	case 16: k_sparse_mean_count_batch<uint16_t><<<grid, dim3(64), 0, st>>>(acc, nbins, chunk_bins, m_of, counts); break;
-	case 32: k_sparse_mean_count_batch<uint32_t><<<grid, dim3(64), 0, st>>>(acc, nbins, chunk_bins, m_of, counts); break;
-	default: k_sparse_mean_count_batch<uint64_t><<<grid, dim3(64), 0, st>>>(acc, nbins, chunk_bins, m_of, counts); break;
-	}
+	if (touched) k_sparse_mean_count_groups<<<grid, dim3(64), 0, st>>>(acc, touched, nbins, chunk_bins, m_of, m_one, counts);
+	else k_sparse_mean_count_batch<<<grid, dim3(64), 0, st>>>(acc, nbins, chunk_bins, m_of, m_one, counts);
 	return hipGetLastError();
 }
 
-hipError_t msc_launch_sparse_mean_write_batch(hipStream_t st, int dtype, uint32_t* acc, uint64_t nbins, uint32_t n_chunks, uint64_t chunk_bins, uint32_t n_centres,
-                                              const uint32_t* m_of, const uint64_t* chunk_off, const uint64_t* chunk_cum, void* ent, uint32_t* cum, uint32_t* touched) {
+hipError_t msc_launch_sparse_mean_write_batch(hipStream_t st, uint32_t* acc, uint64_t nbins, uint32_t n_chunks, uint64_t chunk_bins, uint32_t n_centres,
+                                              const uint32_t* m_of, uint32_t m_one, const uint64_t* chunk_off, const uint64_t* chunk_cum, void* ent, uint32_t* cum,
+                                              uint32_t* touched) {
 	if (n_centres == 0) return hipSuccess;
+	if (chunk_bins % (touched ? 512 : 256)) return hipErrorInvalidValue;
 	const dim3 grid(n_chunks, n_centres);
-	if (touched) {
-		if (chunk_bins % 512) return hipErrorInvalidValue;
-		switch (dtype) {
-		case 8: k_sparse_mean_write_groups<uint8_t><<<grid, dim3(64), 0, st>>>(acc, touched, nbins, chunk_bins, m_of, chunk_off, chunk_cum, (uint2*)ent, cum); break;
-		case 16: k_sparse_mean_write_groups<uint16_t><<<grid, dim3(64), 0, st>>>(acc, touched, nbins, chunk_bins, m_of, chunk_off, chunk_cum, (uint2*)ent, cum); break;
-		case 32: k_sparse_mean_write_groups<uint32_t><<<grid, dim3(64), 0, st>>>(acc, touched, nbins, chunk_bins, m_of, chunk_off, chunk_cum, (uint2*)ent, cum); break;
-		default: k_sparse_mean_write_groups<uint64_t><<<grid, dim3(64), 0, st>>>(acc, touched, nbins, chunk_bins, m_of, chunk_off, chunk_cum, (uint2*)ent, cum); break;
-		}
-		return hipGetLastError();
-	}
-	switch (dtype) {
-	case 8: k_sparse_mean_write_batch<uint8_t><<<grid, dim3(64), 0, st>>>(acc, nbins, chunk_bins, m_of, chunk_off, chunk_cum, (uint2*)ent, cum); break;
-	case 16: k_sparse_mean_write_batch<uint16_t><<<grid, dim3(64), 0, st>>>(acc, nbins, chunk_bins, m_of, chunk_off, chunk_cum, (uint2*)ent, cum); break;
-	case 32: k_sparse_mean_write_batch<uint32_t><<<grid, dim3(64), 0, st>>>(acc, nbins, chunk_bins, m_of, chunk_off, chunk_cum, (uint2*)ent, cum); break;
-	default: k_sparse_mean_write_batch<uint64_t><<<grid, dim3(64), 0, st>>>(acc, nbins, chunk_bins, m_of, chunk_off, chunk_cum, (uint2*)ent, cum); break;
-	}
+	if (touched) k_sparse_mean_write_groups<<<grid, dim3(64), 0, st>>>(acc, touched, nbins, chunk_bins, m_of, m_one, chunk_off, chunk_cum, (uint2*)ent, cum);
+	else k_sparse_mean_write_batch<<<grid, dim3(64), 0, st>>>(acc, nbins, chunk_bins, m_of, m_one, chunk_off, chunk_cum, (uint2*)ent, cum);
 	return hipGetLastError();
 }
 

@@ -571,8 +571,9 @@ class Check:
                     assert np.array_equal(rec_u[0], rec_b) and np.array_equal(raw_u[0], raw_b), (tag, "upload", slot)
 
     def long_lists(self):
-        """F. more than 32768 k-mers in one sparse list: the dense scratch slot (k = 13, u64: 512 MiB) and its compaction"""
-        for k, bits, n in ((11, 8, 40000), (13, 64, 33000)):
+        """F. more than 32768 k-mers in one sparse list: the dense scratch slot (k = 13, u64: 512 MiB) and its compaction; with A's
+        (9, 32) that is every bin type (k = 8, u16: 32769 k-mers, one past the sort builder's limit)"""
+        for k, bits, n in ((11, 8, 40000), (13, 64, 33000), (8, 16, 32769 + 8 - 1)):
             name = "F_sparse_k%d_u%d" % (k, bits)
             hs, refs, _ = self.build(name, k, bits, True, [rnd(n, 700 + k)])
             assert refs[0]["n_kmers"] == n - k + 1 > SORT_MAX and self.routes[name] == "k_count+k_sparse_write", name

@@ -414,6 +414,7 @@ class Check:
                 pos, d, _ = trn.closest(hs, lists[j])                # (a sparse set does not hand out its dense mean)
                 _, od, opos = exp["mean"][t]
                 assert pos == opos and np.allclose(d, od, rtol=1e-12, atol=0), ("mean_nearest", wts, j, pos, opos)
+                self.dump["mean_operators_%s_%d" % (wts[:-4], j)] = d
             self.qxm(hs, np.array([0, 3, 27, 28, 13, 29], dtype=np.uint32), np.array([c for c in range(n)] + [3, 3, 0], dtype=np.uint32), wts, (seqs, k, dt))
 
     def qxm(self, hs, qs, cands, wts, oracle_seqs, key=None):
@@ -452,7 +453,8 @@ class Check:
         """The sparse mean where the mean switches choose its sweep: get_mean / closest at k = 10 (chunks of 1 024 bins: the grouped sweep
         by default, the full one under MSC_SPARSE_MEAN_GROUPS_MIN_K=16 or MSC_SPARSE_MEAN_NO_GROUPS), and update_centres of 300 centres at
         k = 8 (the batched sweep in chunks of 512 bins: grouped only under MSC_SPARSE_MEAN_GROUPS_MIN_K <= 8). Lists of 0, 1 and a few
-        members, identical members among them; nearest member and kept count per centre, and the distances, against the oracle."""
+        members, identical members among them; nearest member and kept count per centre, and the distances, against the oracle. The
+        distances of every closest call go to the dump (mean_*): the grouped and the full sweep must give the same list."""
         wts, cutoff = "weights_k9_u32.txt", 0.9
         text = weights_text(wts)
         trn = api.Trainer(self.ctx, api.Feature.from_text(self.ctx, text, 0), cutoff)
@@ -475,9 +477,15 @@ class Check:
                     oracle_py.lib().orc_hist_free(h)
         exp = self.oracle.cached("means_k10", closest_oracle)
         self.routes["means_k10_grouped"] = mean_grouped(4 ** k, 4 ** k // min(1024, 4 ** k // 256))
-        for lst, (od, opos) in zip(lists, exp):
+        for t, (lst, (od, opos)) in enumerate(zip(lists, exp)):
             pos, d, _ = trn.closest(hs, lst)
             assert pos == opos and np.allclose(d, od, rtol=1e-12, atol=0), ("closest k10", list(lst), pos, opos)
+            self.dump["mean_k10_%d" % t] = d
+        # the first n slots without a slot list (the one route with a null list; always the full sweep) == the same slots listed
+        pos, d, _ = trn.closest(hs, None, m=n)
+        pos_l, d_l, _ = trn.closest(hs, np.arange(n, dtype=np.uint32))
+        assert pos == pos_l and np.array_equal(d, d_l), ("closest without a list", pos, pos_l)
+        self.dump["mean_k10_no_list"], self.dump["mean_k10_listed"] = d, d_l
         # k = 8: the batched update of 300 centres
         k, dt = 8, 16
         hs = api.HistogramSet(self.ctx, k, dt, n, sparse_entries=sum(len(s) for s in seqs) + 4096)
@@ -510,6 +518,33 @@ class Check:
         nearest, kept = trn.update_centres(cen, cslots, hs, lists)
         for j in range(nc):
             assert (int(nearest[j]), int(kept[j])) == exp[j], ("update_centres k8", j, nearest[j], kept[j], exp[j])
+        self.means_u8(seqs)
+
+    def means_u8(self, plain):
+        """k = 8, u8 (64 KiB: the smallest sparse u8 set), members with a bin saturated at 255 -- poly-A in all of them, poly-G in every
+        third: a mean bin of 255 is where a rounding narrower than the bin type's would show. closest, and update_centres of three centres."""
+        k, dt = 8, 8
+        text, cutoff = weights_text("weights_k8_u16.txt"), 0.9          # (a model that keeps members of the centre's family at k = 8)
+        trn = api.Trainer(self.ctx, api.Feature.from_text(self.ctx, text, 0), cutoff)
+        seqs = means_u8_seqs(plain, k)
+        n = len(seqs)
+        hs = api.HistogramSet(self.ctx, k, dt, n, sparse_entries=sum(len(s) for s in seqs) + 4096)
+        hs.build(seqs)
+        assert all(int(hs.download(i).max()) == 255 for i in range(n))
+        lists, owner, ulists = means_u8_lists(n)
+        exp = self.oracle.cached("means_k8_u8", lambda: means_u8_oracle(seqs, k, dt, text, cutoff))
+        assert all(c >= 1 for c in exp["bins_255"]) and exp["bins_255"][1] >= 2 and max(kept for _, kept in exp["update"]) >= 3, exp
+        for t, (lst, (od, opos)) in enumerate(zip(lists, exp["closest"])):
+            pos, d, _ = trn.closest(hs, lst)
+            assert pos == opos and np.allclose(d, od, rtol=1e-12, atol=0), ("closest k8 u8", list(lst), pos, opos)
+            self.dump["mean_k8_u8_%d" % t] = d
+        cen = api.HistogramSet(self.ctx, k, dt, len(owner), sparse_entries=len(owner) * 2500 + 4096)
+        cslots = np.arange(len(owner), dtype=np.uint32)[::-1].copy()
+        for j, o in enumerate(owner):
+            cen.clone_from(int(cslots[j]), hs, o)
+        nearest, kept = trn.update_centres(cen, cslots, hs, ulists)
+        for j in range(len(owner)):
+            assert (int(nearest[j]), int(kept[j])) == exp["update"][j], ("update_centres k8 u8", j, nearest[j], kept[j], exp["update"][j])
 
     def save(self):
         os.makedirs(self.out_dir, exist_ok=True)
@@ -517,6 +552,39 @@ class Check:
             np.save(os.path.join(self.out_dir, name + ".npy"), a)
         with open(os.path.join(self.out_dir, "routes.json"), "w") as f:
             json.dump(self.routes, f, sort_keys=True)
+
+
+def means_u8_seqs(plain, k):
+    """the members of Check.means_u8: every sequence with a run that saturates the u8 bin of poly-A, every third also that of poly-G"""
+    return [s[:300] + run_of(b"A", 300, k) + s[300:] + (run_of(b"G", 300, k) if i % 3 == 0 else b"") for i, s in enumerate(plain)]
+
+
+def means_u8_lists(n):
+    """-> (lists for closest: all members, members that all hold both saturated bins, members of which some do; the owner sequence of
+    each of three centres; their neighbourhoods: sequence 4 and its copies 30 .. 32 (30 with the poly-G run), the copies, everything)"""
+    lists = [np.arange(n, dtype=np.uint32), np.array([0, 3, 6, 9], dtype=np.uint32), np.array([1, 2, 3, 4, 5], dtype=np.uint32)]
+    return lists, [4, 31, 0], [np.array([4, 31, 32, 30, 5], dtype=np.uint32), np.array([30, 31, 32], dtype=np.uint32), np.arange(n, dtype=np.uint32)]
+
+
+def means_u8_oracle(seqs, k, dt, text, cutoff):
+    """oracle_py.mean_nearest of every list of means_u8_lists (distances, nearest, how many bins of the rounded mean are 255) and the
+    (nearest survivor, survivors) of the three centres"""
+    lists, owner, ulists = means_u8_lists(len(seqs))
+    pred = oracle_py.predictor(text)
+    oh = [oracle_py.hist(s, k, dt) for s in seqs]
+    try:
+        out = {"closest": [], "bins_255": [], "update": []}
+        for lst in lists:
+            mean, d, pos = oracle_py.mean_nearest([oh[int(s)] for s in lst])
+            out["closest"].append((d, pos))
+            out["bins_255"].append(int((np.round(mean) == 255).sum()))
+        for o, lst in zip(owner, ulists):
+            idx = np.flatnonzero(oracle_py.filter_(pred, cutoff, oh[o], [oh[int(s)] for s in lst]))
+            out["update"].append((int(idx[oracle_py.mean_nearest([oh[int(lst[i])] for i in idx])[2]]) if idx.size else -1, int(idx.size)))
+        return out
+    finally:
+        for h in oh:
+            oracle_py.lib().orc_hist_free(h)
 
 
 def batch_sweep_chunks(nbins, nc):

@@ -80,7 +80,8 @@ def test_sparse_route_variant(dumps, name, switches, kernel, timeout):
 
 
 def test_sparse_route_dumps_agree(dumps):
-    """the integer statistics of every variant are bit-identical; the divergence sums too wherever the kernel keeps its granule order.
+    """the integer statistics of every variant are bit-identical, and so are the distances to every rounded mean (mean_*: the grouped
+    and the full sweep write one list); the divergence sums too wherever the kernel keeps its granule order.
     Every chunk and mean variant takes another route than the default somewhere (routes.json: the library's rules per case)."""
     failed = []
     for v in VARIANTS:
@@ -94,12 +95,16 @@ def test_sparse_route_dumps_agree(dumps):
     assert not failed, "variants that ran and left no result: %s" % failed
     names = sorted(p.name for p in (dumps / "default").iterdir() if p.suffix == ".npy")
     assert len(names) >= 20, names
+    assert sum(f.startswith("mean_") for f in names) >= 20, names
     for f in names:
         base = np.load(dumps / "default" / f)
         same = SAME_DIV_BITS | ({"chunk512"} if f.startswith("k12_") else {"chunk575"})
         for v in VARIANTS[1:]:
             got = np.load(dumps / v[0] / f)
             assert got.shape == base.shape, (f, v[0])
+            if f.startswith("mean_"):          # distances to a rounded mean: one list whatever sweep wrote the mean, whatever kernel took |p - r|
+                assert np.array_equal(got, base), (f, v[0])
+                continue
             if f.startswith("parts_div"):
                 cols, int_cols = list(range(base.shape[1])), []
             elif f.startswith("parts_int"):
