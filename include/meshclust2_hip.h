@@ -139,6 +139,18 @@ int         msc_set_block_pipe(msc_ctx* ctx, int on);
  * MSC_PAIRS_ROUTE_MATRIX, and msc_last_kernel_info's name says that the sums came from cells. msc_score_multi and every other call are
  * unaffected. Default: off. */
 int         msc_set_pairs_div_cells(msc_ctx* ctx, int on);
+/* A Q x M call over two SPARSE sets (msc_score_multi, msc_search_pairs) runs one 1 x M pass per query over the lists: the matrix-core
+ * route reads a presence bit per bin, the lists of large bins and the sorted ranks of a set -- mirrors only dense sets used to carry.
+ * on = 1 lets two sparse sets of equal k and dtype take that route as well, under its usual conditions (8/16/32-bit bins of the narrow
+ * range, whole 4 KiB tiles, two queries and more) and up to k = 10: the three mirrors are built from the lists, byte for byte what a dense
+ * set of the same sequences builds from its bins, so the products, rank walks and epilogues run unchanged and every result -- statistics,
+ * sums, flags, close counts, the pair list -- equals both the switch-off call's and the dense sets'. The mirrors are allocated by the
+ * first call that takes the route (a bit per bin and slot, 8 bytes per large bin, 4 + 2 bytes per rank) and every writer of a slot's list
+ * makes that slot stale in them. A block whose queries' list of large bins is too long, a set whose mirrors cannot be allocated, and in
+ * msc_score_multi a model or feat_mask with a divergence or group statistic go on as without the switch, with the same kernels (in
+ * msc_search_pairs a divergence-statistic model takes the route where msc_set_pairs_div_cells is on as well). msc_last_kernel_info names
+ * the product kernel and adds "mirrors from lists". One dense and one sparse set are not affected. Default: off. */
+int         msc_set_sparse_matrix_pass(msc_ctx* ctx, int on);
 /* Number of streaming-kernel launches that pair_tiles_ms sums over (large calls are chunked). */
 int         msc_last_kernel_launches(const msc_ctx* ctx);
 /* Which streaming kernel the LAST scoring call ran (its name is copied to buf) and how many queries one HBM read of a
@@ -346,10 +358,11 @@ int msc_search(msc_ctx* ctx, const msc_model* cls, const msc_model* reg,
  * [offsets[q], offsets[q + 1])). The pairs of each block of queries are evaluated over the union of its members' windows, so the error
  * statuses (zero length, NaN) are those msc_score_multi returns for those pairs. The list stays on the device until the next
  * msc_search_pairs call on ctx or msc_destroy; msc_search_pairs_fetch copies a range of it (either output may be NULL).
- * info (nullable): n_pairs; route = MSC_PAIRS_ROUTE_MATRIX when the product on the matrix cores served the call (dense sets of whole
- * 4 KiB tiles, n_q >= 2, no divergence or group statistic in either model), MSC_PAIRS_ROUTE_FALLBACK when msc_score_multi's other routes
- * did, one block of queries at a time; fp64_pairs = pairs evaluated in FP64 (regression evaluations plus classification pairs the f32
- * screen left undecided, or every classification pair where there is no screen). */
+ * info (nullable): n_pairs; route = MSC_PAIRS_ROUTE_MATRIX when the product on the matrix cores served the call (dense sets -- with
+ * msc_set_sparse_matrix_pass two sparse sets as well -- of whole 4 KiB tiles, n_q >= 2, no divergence or group statistic in either
+ * model), MSC_PAIRS_ROUTE_FALLBACK when msc_score_multi's other routes did, one block of queries at a time; fp64_pairs = pairs evaluated
+ * in FP64 (regression evaluations plus classification pairs the f32 screen left undecided, or every classification pair where there is
+ * no screen). */
 #define MSC_PAIRS_ROUTE_MATRIX   1
 #define MSC_PAIRS_ROUTE_FALLBACK 2
 typedef struct {

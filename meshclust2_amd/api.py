@@ -72,6 +72,11 @@ class Context:
         fallback through score_multi (default); similarities agree to rounding (1e-9 relative), not bit for bit"""
         self.check(self.lib.msc_set_pairs_div_cells(self.h, 1 if on else 0))
 
+    def set_sparse_matrix_pass(self, on):
+        """score_multi / search_pairs over two sparse sets: the matrix-core route over mirrors built from the lists (on) or one 1 x M pass
+        per query (default); identical results"""
+        self.check(self.lib.msc_set_sparse_matrix_pass(self.h, 1 if on else 0))
+
     def device_malloc(self, nbytes):
         """plain device memory of this context's GPU (msc_device_malloc) -> integer device address; release with device_free"""
         p = C.c_void_p()

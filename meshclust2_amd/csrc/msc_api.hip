@@ -255,6 +255,12 @@ extern "C" int msc_set_pairs_div_cells(msc_ctx* ctx, int on) {
 	return MSC_OK;
 }
 
+extern "C" int msc_set_sparse_matrix_pass(msc_ctx* ctx, int on) {
+	if (!ctx) return MSC_ERR_INVALID_ARG;
+	ctx->sparse_matrix_pass = on != 0;
+	return MSC_OK;
+}
+
 extern "C" int msc_set_mirror_pass(msc_ctx* ctx, int on) {
 	if (!ctx) return MSC_ERR_INVALID_ARG;
 	ctx->mirror_pass = on != 0;
@@ -480,7 +486,7 @@ extern "C" int msc_hist_set_clear(msc_ctx* ctx, msc_hist_set* s) {
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	s->hdr_host.assign(s->capacity, MscSparseHdr{});
 	s->ent_used = 0;
-	s->list_epoch++;
+	lists_written(s, 0, s->capacity);
 	s->max_nnz = 0;
 	s->max_count = s->max_sum = 0;
 	forget_lengths(s, 0, s->capacity);
@@ -525,7 +531,9 @@ extern "C" int msc_hist_set_k(const msc_hist_set* s) { return s ? s->k : 0; }
 extern "C" int msc_hist_set_dtype(const msc_hist_set* s) { return s ? s->dtype : 0; }
 extern "C" uint64_t msc_hist_set_bytes(const msc_hist_set* s) {
 	if (!s) return 0;
-	if (s->sparse) return s->ent_capacity * 12 + (s->scalar_stride + sizeof(MscSparseHdr)) * s->capacity + (s->rkl ? s->rkl_entries * 4 + s->capacity * 12 : 0) + (s->rkm ? s->rkm_entries * 8 + s->capacity * 12 : 0);
+	if (s->sparse)
+		return s->ent_capacity * 12 + (s->scalar_stride + sizeof(MscSparseHdr)) * s->capacity + (s->rkl ? s->rkl_entries * 4 + s->capacity * 12 : 0) + (s->rkm ? s->rkm_entries * 8 + s->capacity * 12 : 0) +
+		       ((s->kb ? s->L.padded_bins / 8 + 32 + (uint64_t)s->mb_pitch * 8 + 4 : 0) + (s->ranks ? (s->rk_pitch + 1) * 4 : 0) + (s->ranks16 ? s->rk_pitch * 2 : 0)) * s->capacity;
 	return (s->L.slot_bytes + (s->digest ? msc_digest_slot_bytes(s->L) : 0) + (s->kb ? s->L.padded_bins / 8 + 32 + (uint64_t)s->mb_pitch * 8 + 4 : 0) + (s->ranks ? (s->rk_pitch + 1) * 4 : 0) + s->scalar_stride) * s->capacity;
 }
 
@@ -538,9 +546,10 @@ extern "C" int msc_hist_set_build_info(const msc_hist_set* s, char* builder, siz
 	return MSC_OK;
 }
 
-// every writer of slots ends here: both mirrors of a dense set (digest, sparse lists) are stale for [first, first + n)
+// every writer of slots ends here: the mirrors the set has (dense: digest, sparse lists, presence bits, ranks; sparse: presence bits,
+// ranks) are stale for [first, first + n)
 static void mark_stale(msc_hist_set* s, uint64_t first, uint64_t n) {
-	if (s->sparse || n == 0) return;
+	if (n == 0) return;
 	if (s->digest) {
 		if (s->dg_lo >= s->dg_hi) { s->dg_lo = first; s->dg_hi = first + n; }
 		else { s->dg_lo = std::min(s->dg_lo, first); s->dg_hi = std::max(s->dg_hi, first + n); }
@@ -566,6 +575,11 @@ void learn_length(const msc_hist_set* s, uint64_t slot, uint64_t len) {
 	if (s->len_known.size() < s->capacity) { s->len_known.resize(s->capacity, 0); s->len_host.resize(s->capacity, 0); }
 	s->len_host[slot] = len;
 	s->len_known[slot] = 1;
+}
+
+void lists_written(msc_hist_set* s, uint64_t first, uint64_t n) {
+	s->list_epoch++;
+	mark_stale(s, first, n);
 }
 
 void mark_written(msc_hist_set* s, uint64_t first, uint64_t n) {
@@ -633,7 +647,7 @@ static int sparsify_slots(msc_ctx* ctx, const msc_hist_set* dense, uint64_t d_fi
 			h.off = sp->ent_used;
 			sp->ent_used += cnt;
 			sp->hdr_host[s_first + b0 + i] = h;
-			sp->list_epoch++;
+			lists_written(sp, s_first + b0 + i, 1);
 			sp->max_nnz = std::max(sp->max_nnz, h.nnz);
 		}
 		HIP_TRY(ctx, hipMemcpyAsync(sp->hdr + s_first + b0, sp->hdr_host.data() + s_first + b0, nb * sizeof(MscSparseHdr), hipMemcpyHostToDevice, ctx->stream));
@@ -756,7 +770,7 @@ static int build_sparse_sort(msc_ctx* ctx, msc_hist_set* set, uint64_t first_slo
 	                                          (const uint64_t*)ctx->sp_cumbase.p, P, set->scalars, set->scalar_stride, set->hdr, set->ent, set->cum));
 	set->last_builder = "k_sparse_build_sort";
 	set->ent_used += need;
-	set->list_epoch++;
+	lists_written(set, first_slot, n_seqs);
 	HIP_TRY(ctx, hipMemcpyAsync(set->hdr_host.data() + first_slot, set->hdr + first_slot, n_seqs * sizeof(MscSparseHdr), hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	return refresh_bounds(ctx, set, first_slot, n_seqs);
@@ -1176,7 +1190,7 @@ static int copy_common(msc_ctx* ctx, msc_hist_set* dst, uint64_t ds, const msc_h
 			HIP_TRY(ctx, hipMemcpyAsync(dst->cum + dh.off, src->cum + sh.off, sh.nnz * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
 		}
 		dst->hdr_host[ds] = dh;
-		dst->list_epoch++;
+		lists_written(dst, ds, 1);
 		HIP_TRY(ctx, hipMemcpyAsync(dst->hdr + ds, &dst->hdr_host[ds], sizeof(MscSparseHdr), hipMemcpyHostToDevice, ctx->stream));
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 		return MSC_OK;
@@ -1280,7 +1294,7 @@ static int assign_or_copy_batch(msc_ctx* ctx, msc_hist_set* dst, const uint32_t*
 			else forget_lengths(dst, dst_slots[i], 1);
 		}
 		dst->ent_used = o;
-		dst->list_epoch++;
+		lists_written(dst, lo, (uint64_t)hi + 1 - lo);
 		dst->max_count = std::max(dst->max_count, src->max_count);
 		dst->max_sum = std::max(dst->max_sum, src->max_sum);
 		return MSC_OK;

@@ -160,7 +160,7 @@ int sparse_acc_sweep(msc_ctx* ctx, const msc_hist_set* pts, uint32_t nc, const u
 		if ((r = msc_hist_set_create_sparse(ctx, pts->k, pts->dtype, cap, arena, &ms))) return r;
 	}
 	ms->ent_used = used;
-	ms->list_epoch++;
+	lists_written(ms, 0, nc);
 	ms->max_nnz = std::max(ms->max_nnz, max_nnz);
 	ms->max_sum = std::max(ms->max_sum, max_mean_sum);          // (a rounded mean can hold more k-mers than any member: the bound travels with msc_hist_assign*)
 	for (uint32_t c = 0; c < nc; c++) ms->hdr_host[c] = hdr[c];

@@ -43,10 +43,12 @@ static int ensure_digest(msc_ctx* ctx, const msc_hist_set* set) {
 	return MSC_OK;
 }
 
-// The presence-bit mirror of a dense set and its lists of large bins (msc_pair_gemm.hip): the operands of the int8 product that takes the
-// Q x M pass. MSC_OK with set->kb == nullptr when it cannot be had (no memory): the older routes then run.
+// The presence-bit mirror of a set and its lists of large bins (msc_pair_gemm.hip): the operands of the int8 product that takes the
+// Q x M pass. A dense set's come from its bins, a sparse set's from its entry lists (the same bytes for the same sequences; every slot of
+// the stale range is rebuilt, a slot without a list as an all-zero image). MSC_OK with set->kb == nullptr when it cannot be had (no
+// memory): the older routes then run.
 int ensure_kb(msc_ctx* ctx, const msc_hist_set* set) {
-	if (set->sparse || set->kb_unavailable || set->dtype == 64) return MSC_OK;
+	if (set->kb_unavailable || set->dtype == 64) return MSC_OK;
 	auto give_up = [&] {
 		(void)hipGetLastError();
 		if (set->kb) (void)hipFree(set->kb);
@@ -76,13 +78,17 @@ int ensure_kb(msc_ctx* ctx, const msc_hist_set* set) {
 		int r;
 		if ((r = ensure(ctx, ctx->rk_bad, 2 * sizeof(int32_t)))) return r;
 		HIP_TRY(ctx, hipMemsetAsync(ctx->rk_bad.p, 0, 2 * sizeof(int32_t), ctx->stream));
-		const uint64_t lo = set->kb_lo, hi = std::min<uint64_t>(set->kb_hi, set->written.size());
-		for (uint64_t i = lo; i < hi;) {
-			if (!set->written[i]) { i++; continue; }
-			uint64_t j = i;
-			while (j < hi && set->written[j]) j++;
-			HIP_TRY(ctx, msc_launch_kb_build(ctx->stream, set->L, set->dtype, set->bins, set->kb, i, j - i, set->mb, set->mb_n, set->mb_pitch, (int32_t*)ctx->rk_bad.p));
-			i = j;
+		const uint64_t lo = set->kb_lo, hi = std::min<uint64_t>(set->kb_hi, set->sparse ? set->capacity : set->written.size());
+		if (set->sparse) {          // every slot of the range: one without a list gets an all-zero image and an empty list
+			if (hi > lo) HIP_TRY(ctx, msc_launch_kb_build_sparse(ctx->stream, set->L, set->ent, set->hdr, set->kb, lo, hi - lo, set->mb, set->mb_n, set->mb_pitch, (int32_t*)ctx->rk_bad.p));
+		} else {
+			for (uint64_t i = lo; i < hi;) {
+				if (!set->written[i]) { i++; continue; }
+				uint64_t j = i;
+				while (j < hi && set->written[j]) j++;
+				HIP_TRY(ctx, msc_launch_kb_build(ctx->stream, set->L, set->dtype, set->bins, set->kb, i, j - i, set->mb, set->mb_n, set->mb_pitch, (int32_t*)ctx->rk_bad.p));
+				i = j;
+			}
 		}
 		int32_t flags[2] = {0, 0};
 		HIP_TRY(ctx, hipMemcpyAsync(flags, ctx->rk_bad.p, sizeof flags, hipMemcpyDeviceToHost, ctx->stream));
@@ -105,10 +111,10 @@ int ensure_kb(msc_ctx* ctx, const msc_hist_set* set) {
 	return MSC_OK;
 }
 
-// The ranks mirror of a dense set (msc_emd_ranks.hip), from its bins. MSC_OK with set->ranks == nullptr when it cannot be had (no
-// memory, or a slot holds a zero count): the digest kernel then keeps the prefixes.
+// The ranks mirror of a set (msc_emd_ranks.hip), from a dense set's bins or a sparse set's lists. MSC_OK with set->ranks == nullptr when
+// it cannot be had (no memory, or a slot holds a zero count): the digest kernel then keeps the prefixes.
 int ensure_ranks(msc_ctx* ctx, const msc_hist_set* set) {
-	if (set->sparse || set->dtype == 64 || !msc_digest_supported(set->L) || set->ranks_unavailable || set->max_sum < set->L.nbins) return MSC_OK;
+	if (set->dtype == 64 || !msc_digest_supported(set->L) || set->ranks_unavailable || set->max_sum < set->L.nbins) return MSC_OK;
 	const uint64_t pitch = msc_ranks_pitch(set->max_sum - set->L.nbins);
 	if (set->ranks && pitch > set->rk_pitch) {          // a longer list than any before: lay the mirror out again
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -142,14 +148,29 @@ int ensure_ranks(msc_ctx* ctx, const msc_hist_set* set) {
 		if ((r = ensure(ctx, ctx->rk_bad, 2 * sizeof(int32_t)))) return r;
 		HIP_TRY(ctx, hipMemsetAsync(ctx->rk_bad.p, 0, 2 * sizeof(int32_t), ctx->stream));
 		// runs of slots that hold a histogram (an unwritten slot's digest is whatever the allocation held)
-		const uint64_t hi = std::min<uint64_t>(set->rk_hi, set->written.size());
-		for (uint64_t i = set->rk_lo; i < hi;) {
-			if (!set->written[i]) { i++; continue; }
-			uint64_t j = i;
-			while (j < hi && set->written[j]) j++;
-			HIP_TRY(ctx, msc_launch_ranks_build(ctx->stream, set->L, set->dtype, set->bins, set->scalars, set->ranks, set->rk_n, set->rk_pitch, i, j - i, (int32_t*)ctx->rk_bad.p));
-			if (set->ranks16) HIP_TRY(ctx, msc_launch_ranks16_build(ctx->stream, set->L.nbins, set->ranks, set->ranks16, set->rk_pitch, i, j - i, (int32_t*)ctx->rk_bad.p + 1));
-			i = j;
+		const uint64_t hi = std::min<uint64_t>(set->rk_hi, set->sparse ? set->capacity : set->written.size());
+		if (set->sparse) {
+			// the 32-bit ranks of every slot of the range from its list (one without a list: all padding, n = 0); the 16-bit form only of the
+			// runs that hold a list, as a dense set's unwritten slots are skipped: the ranks16 row of an empty slot is NOT maintained (all
+			// padding does not fit 16 bits and would switch the form off for the set; nothing reads a row past its rk_n = 0)
+			if (hi > set->rk_lo)
+				HIP_TRY(ctx, msc_launch_ranks_build_sparse(ctx->stream, set->L, set->ent, set->cum, set->hdr, set->ranks, set->rk_n, set->rk_pitch, set->rk_lo, hi - set->rk_lo, (int32_t*)ctx->rk_bad.p));
+			for (uint64_t i = set->rk_lo; i < hi && set->ranks16;) {
+				if (!set->hdr_host[i].nnz) { i++; continue; }
+				uint64_t j = i;
+				while (j < hi && set->hdr_host[j].nnz) j++;
+				HIP_TRY(ctx, msc_launch_ranks16_build(ctx->stream, set->L.nbins, set->ranks, set->ranks16, set->rk_pitch, i, j - i, (int32_t*)ctx->rk_bad.p + 1));
+				i = j;
+			}
+		} else {
+			for (uint64_t i = set->rk_lo; i < hi;) {
+				if (!set->written[i]) { i++; continue; }
+				uint64_t j = i;
+				while (j < hi && set->written[j]) j++;
+				HIP_TRY(ctx, msc_launch_ranks_build(ctx->stream, set->L, set->dtype, set->bins, set->scalars, set->ranks, set->rk_n, set->rk_pitch, i, j - i, (int32_t*)ctx->rk_bad.p));
+				if (set->ranks16) HIP_TRY(ctx, msc_launch_ranks16_build(ctx->stream, set->L.nbins, set->ranks, set->ranks16, set->rk_pitch, i, j - i, (int32_t*)ctx->rk_bad.p + 1));
+				i = j;
+			}
 		}
 		int32_t bad[2] = {0, 0};
 		HIP_TRY(ctx, hipMemcpyAsync(bad, ctx->rk_bad.p, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
@@ -171,12 +192,16 @@ int ensure_ranks(msc_ctx* ctx, const msc_hist_set* set) {
 
 // Whether the pass on the matrix cores (msc_pair_gemm.hip) can take a Q x M call over these sets -- host-side bounds only: dense 8/16/32-bit
 // sets of the narrow range whose histograms are whole 4 KiB tiles, P1 / P2 within int32 and, when
-// the earth mover's distance is wanted, lists short enough for the ranks mirror (msc_emd_ranks.hip).
+// the earth mover's distance is wanted, lists short enough for the ranks mirror (msc_emd_ranks.hip). Two sparse sets under the same
+// bounds with msc_set_sparse_matrix_pass on, up to 2^20 bins (their mirrors come from the lists); never one of each.
 bool kb_route_fits(const msc_hist_set* cands, const msc_hist_set* qset, bool need_emd) {
 	static const bool off = getenv("MSC_MULTI_NO_GEMM") != nullptr;
 	static const bool no_ranks = getenv("MSC_MULTI_NO_RANKS") != nullptr;
 	const MscLayout& L = cands->L;
-	if (off || cands->sparse || qset->sparse || cands->dtype == 64 || L.nbins != L.padded_bins || !msc_digest_supported(L) || needs_wide(cands, qset)) return false;
+	if (cands->sparse != qset->sparse || (cands->sparse && (!cands->ctx->sparse_matrix_pass || L.nbins > (1ull << 20)))) return false;
+	// (what msc_launch_kb_build_sparse asks of the layout, so that a set it cannot serve stays on the list passes instead of failing the call)
+	if (cands->sparse && !msc_kb_build_sparse_fits(L)) return false;
+	if (off || cands->dtype == 64 || L.nbins != L.padded_bins || !msc_digest_supported(L) || needs_wide(cands, qset)) return false;
 	const uint64_t ms_ = std::max(cands->max_sum, qset->max_sum);
 	if (ms_ < L.nbins || ms_ - L.nbins >= (1ull << 24)) return false;          // (P1 <= the k-mers of either sequence is summed in f32: exact below 2^24; the corrections stay within int32)
 	if (need_emd && (no_ranks || L.nbins > (1ull << 20) || (ms_ - L.nbins) * 4 > L.nbins)) return false;
@@ -260,6 +285,8 @@ static int score_multi_impl(msc_ctx* ctx, const msc_model* model, const msc_hist
 	const bool need_emd = (want & MSC_FEAT_EMD) != 0;           // Feature::compute evaluates only the model's singles too
 	// The pass on the matrix cores (msc_pair_gemm.hip) serves blocks of up to 128 queries per pass over the candidates' bits; the older routes 64
 	bool kb_fit = !ctx->no_kb_now && n_q >= 2 && kb_route_fits(cands, qset, need_emd);
+	// (two sparse sets, msc_set_sparse_matrix_pass: a divergence or group statistic keeps the call on the merge kernels, blocks of 64 and all)
+	if (kb_fit && cands->sparse && (want & (MSC_FEAT_DIV | MSC_FEAT_GROUPS))) kb_fit = false;
 	if (kb_fit) {
 		if ((r = ensure_kb(ctx, cands)) || (r = ensure_kb(ctx, qset))) return r;
 		kb_fit = cands->kb && qset->kb && !cands->kb_has_zero && !qset->kb_has_zero;
@@ -334,12 +361,45 @@ static int score_multi_impl(msc_ctx* ctx, const msc_model* model, const msc_hist
 		if (!c_sp || !q_sp) c_sp = q_sp = nullptr;
 	}
 	const bool grp_dense = want_grp && !c_sp;
+	static const bool no_digest = getenv("MSC_MULTI_NO_DIGEST") != nullptr;
+	const bool tuned_by_hand = getenv("MSC_MULTI_TQ") || getenv("MSC_DIGEST_SLOTS");          // A/B switches of the older kernels: keep to them
+	// EVERYTHING on the matrix cores (msc_pair_gemm.hip): one int8 product per tile of bins over the presence-bit mirrors + corrections from the
+	// lists of large bins -- exact for any counts of the narrow range; one read of a candidate byte per 256 queries, no partial records.
+	// The queries' large bins become this block's hot list: its size is known here (the lists' lengths are mirrored on the host), and
+	// a block whose list would average more than 64 entries per 128-bin step (long sequences in few bins: the walk over the list would
+	// then take several times the step's product) is left to the older routes.
+	bool manh_gemm = false, emd_ranks = false;
+	uint64_t n_hot = 0;
+	auto pick_matrix = [&]() -> int {
+		for (uint64_t q = 0; q < n_q; q++) n_hot += std::min(qset->mb_n_host[q_slots[q]], qset->mb_pitch);
+		manh_gemm = n_hot <= 64 * (L.nbins / 128);
+		if (manh_gemm && need_emd) {
+			int e;
+			if ((e = ensure_ranks(ctx, cands)) || (e = ensure_ranks(ctx, qset))) return e;
+			manh_gemm = emd_ranks = cands->ranks && qset->ranks;
+		}
+		return MSC_OK;
+	};
+	// Two sparse sets whose mirrors stand (kb_fit): the block is decided here, ahead of the sparse branch below. One that declines -- hot
+	// list too long, no ranks mirror -- goes on exactly as without the switch: the merge / rank-list passes, in blocks of 64.
+	if (kb_fit && cands->sparse) {
+		if (!tuned_by_hand && !no_digest && (r = pick_matrix())) return r;
+		if (!manh_gemm) {
+			if (ctx->defer == 2 && (r = flush_deferred(ctx))) return r;
+			if (n_q > 64) {
+				ctx->no_kb_now = true;
+				r = score_multi_impl(ctx, model, cands, cand_slots, m, qset, q_slots, n_q, order, sum_out, csum_out, close_out, feat_mask, raw_out);
+				ctx->no_kb_now = false;
+				return r;
+			}
+		}
+	}
 	const bool simple = (!grp_dense || std::max(cands->max_count, qset->max_count) <= 0xffffffffull) && (!want_div || c_sp) && L.nbins == L.padded_bins && n_q > 1 &&
-	                    !needs_wide(cands, qset) && !cands->sparse;
+	                    !needs_wide(cands, qset) && (!cands->sparse || manh_gemm);
 	// Sparse sets: one merge-path pass per query, but queued back to back into one [n_q][m] record array with ONE epilogue and one
 	// copy back -- no host round trip between the passes.
 	static const bool no_sp_multi = getenv("MSC_SPARSE_NO_MULTI") != nullptr;
-	const bool sparse_multi = cands->sparse && qset->sparse && !no_sp_multi && !(want & (MSC_FEAT_DIV | MSC_FEAT_GROUPS)) && n_q > 1 && !needs_wide(cands, qset) &&
+	const bool sparse_multi = cands->sparse && qset->sparse && !manh_gemm && !no_sp_multi && !(want & (MSC_FEAT_DIV | MSC_FEAT_GROUPS)) && n_q > 1 && !needs_wide(cands, qset) &&
 	                          std::max(cands->max_count, qset->max_count) < 65536 && n_q * m <= 0x7fffffffull &&
 	                          n_q * m * sizeof(MscPartial) <= (4096ull << 20) && !getenv("MSC_SPARSE_NO_MP") && !getenv("MSC_SPARSE_LDS");
 	if (sparse_multi) {
@@ -471,27 +531,11 @@ static int score_multi_impl(msc_ctx* ctx, const msc_model* model, const msc_hist
 	const bool compact = 64ull * L.R * mc_ * mc_ < (1ull << 32) && 64ull * L.R * ms_ < (1ull << 32);
 	// every prefix of excess counts (count - 1) is at most the histogram's k-mer total = sum - 4^k: 16-bit prefix form when that fits
 	const bool excess16 = ms_ >= L.nbins && ms_ - L.nbins < 65536;
-	static const bool no_digest = getenv("MSC_MULTI_NO_DIGEST") != nullptr;
 	static const bool no_ranks = getenv("MSC_MULTI_NO_RANKS") != nullptr;
-	const bool tuned_by_hand = getenv("MSC_MULTI_TQ") || getenv("MSC_DIGEST_SLOTS");          // A/B switches of the older kernels: keep to them
 	// The earth mover's distance from sorted k-mer ranks (msc_emd_ranks.hip) -- O(k-mers) per pair instead of O(bins): while the
 	// longest list is a quarter of the bins or less, for up to 256 queries and 2^20 bins (32-bit wave sums)
 	const bool ranks_fit = !no_ranks && !tuned_by_hand && n_q <= 256 && L.nbins <= (1ull << 20) && ms_ >= L.nbins && (ms_ - L.nbins) * 4 <= L.nbins && msc_digest_supported(L);
-	// EVERYTHING on the matrix cores (msc_pair_gemm.hip): one int8 product per tile of bins over the presence-bit mirrors + corrections from the
-	// lists of large bins -- exact for any counts of the narrow range; one read of a candidate byte per 256 queries, no partial records.
-	// The queries' large bins become this block's hot list: its size is known here (the lists' lengths are mirrored on the host), and
-	// a block whose list would average more than 64 entries per 128-bin step (long sequences in few bins: the walk over the list would
-	// then take several times the step's product) is left to the older routes.
-	bool manh_gemm = false, emd_ranks = false;
-	uint64_t n_hot = 0;
-	if (kb_fit && simple && !tuned_by_hand && !no_digest) {
-		for (uint64_t q = 0; q < n_q; q++) n_hot += std::min(qset->mb_n_host[q_slots[q]], qset->mb_pitch);
-		manh_gemm = n_hot <= 64 * (L.nbins / 128);
-		if (manh_gemm && need_emd) {
-			if ((r = ensure_ranks(ctx, cands)) || (r = ensure_ranks(ctx, qset))) return r;
-			manh_gemm = emd_ranks = cands->ranks && qset->ranks;
-		}
-	}
+	if (kb_fit && simple && !cands->sparse && !tuned_by_hand && !no_digest && (r = pick_matrix())) return r;          // (dense sets: the block is decided here)
 	// (blocks of the matrix-core pass queued without a host wait between them: any other route first waits for them and reads their error word)
 	if (!manh_gemm && ctx->defer == 2 && (r = flush_deferred(ctx))) return r;
 	if (!manh_gemm && n_q > 64) {          // (a block of up to 256 was cut for the matrix cores: the older routes take it in blocks of 64)
@@ -628,7 +672,8 @@ static int score_multi_impl(msc_ctx* ctx, const msc_model* model, const msc_hist
 	if (emd_ranks && (r = ensure(ctx, ctx->emd_out, chunk * (manh_gemm ? kb_qn : 64) * sizeof(uint64_t)))) return r;
 	const bool count_only = digest && tps == 2 && !digest_emd;
 	if (manh_gemm) {
-		snprintf(ctx->last_kernel_buf, sizeof ctx->last_kernel_buf, "%s<%u query rows, one matrix product per tile of presence bits%s>", msc_pair_gemm_kernel_name(), kb_qn, emd_ranks ? ", emd by ranks" : ", no emd");
+		snprintf(ctx->last_kernel_buf, sizeof ctx->last_kernel_buf, "%s<%u query rows, one matrix product per tile of presence bits%s%s>", msc_pair_gemm_kernel_name(), kb_qn, emd_ranks ? ", emd by ranks" : ", no emd",
+		         cands->sparse ? ", mirrors from lists" : "");
 		ctx->last_kernel = ctx->last_kernel_buf;
 	} else if (digest) {
 		snprintf(ctx->last_kernel_buf, sizeof ctx->last_kernel_buf, "k_pair_digest_multi<%s counts%s%s>", mc_ < 256 ? "u8" : "u16",
@@ -643,7 +688,7 @@ static int score_multi_impl(msc_ctx* ctx, const msc_model* model, const msc_hist
 	for (uint64_t off = 0; off < m; off += chunk) {
 		const uint32_t mc = (uint32_t)std::min(chunk, m - off);
 		const uint32_t* d_slots = cand_slots ? (const uint32_t*)ctx->slots.p + off : nullptr;
-		const uint8_t* c_bins = cands->bins + (cand_slots ? 0 : off * L.slot_bytes);
+		const uint8_t* c_bins = cands->bins ? cands->bins + (cand_slots ? 0 : off * L.slot_bytes) : nullptr;          // (a sparse set on the matrix-core pass has none, and nothing of that pass reads a bin)
 		const uint8_t* c_scal = cands->scalars + (cand_slots ? 0 : off * cands->scalar_stride);
 		hipEvent_t ev_t0 = ctx->ev_tiles0, ev_t1 = ctx->ev_tiles1;
 		if (deferred && ctx->timing && ((r = pool_event(ctx, &ev_t0)) || (r = pool_event(ctx, &ev_t1)))) return r;      // (read when the call's last block is through)

@@ -240,8 +240,8 @@ int run_matrix(PairsCall& c) {
 	c.fp64 += open + (c.reg ? total : 0);
 	ctx->pl_n = total;
 	if (last_qn) {          // msc_last_kernel_info names the product kernel, as msc_score_multi does
-		snprintf(ctx->last_kernel_buf, sizeof ctx->last_kernel_buf, "%s<%u query rows, one matrix product per tile of presence bits%s%s>", msc_pair_gemm_kernel_name(), last_qn,
-		         c.need_emd ? ", emd by ranks" : ", no emd", c.cls_div || c.reg_div ? ", divergence sums from cells" : "");
+		snprintf(ctx->last_kernel_buf, sizeof ctx->last_kernel_buf, "%s<%u query rows, one matrix product per tile of presence bits%s%s%s>", msc_pair_gemm_kernel_name(), last_qn,
+		         c.need_emd ? ", emd by ranks" : ", no emd", c.cls_div || c.reg_div ? ", divergence sums from cells" : "", cands->sparse ? ", mirrors from lists" : "");
 		ctx->last_kernel = ctx->last_kernel_buf;
 		ctx->last_query_tile = (int)c.blocks.back().nq;
 		ctx->have_timing = false;

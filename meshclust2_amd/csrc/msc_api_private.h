@@ -44,7 +44,7 @@ hipError_t launch_sparse_pass(msc_ctx* ctx, SparseKernel k, const msc_hist_set* 
                               uint32_t div_stride = 1);
 
 // ---- msc_api_multi.hip (shared with msc_api_pairs.hip)
-int ensure_kb(msc_ctx* ctx, const msc_hist_set* set);          // the presence-bit mirror and lists of large bins of a dense set (set->kb null: unavailable)
-int ensure_ranks(msc_ctx* ctx, const msc_hist_set* set);       // the ranks mirror (set->ranks null: unavailable)
+int ensure_kb(msc_ctx* ctx, const msc_hist_set* set);          // the presence-bit mirror and lists of large bins of a set, from its bins or its lists (set->kb null: unavailable)
+int ensure_ranks(msc_ctx* ctx, const msc_hist_set* set);       // the ranks mirror, likewise (set->ranks null: unavailable)
 bool kb_route_fits(const msc_hist_set* cands, const msc_hist_set* qset, bool need_emd);          // host-side bounds of the matrix-core pass
 int read_error_word(msc_ctx* ctx);                             // the epilogue's error word as a status (the stream is idle)

@@ -68,6 +68,31 @@ __global__ void __launch_bounds__(256) k_ranks_build(const uint8_t* __restrict__
 	}
 }
 
+// The same mirror from the lists of a sparse set (sparse.hip), one wave per slot: entry j = (logical bin, count) puts count - 1 copies of
+// its bin at [cum[j] - (count - 1), cum[j]) -- cum is the inclusive prefix of the excess counts, the walk k_rkl_fill of msc_ranks_pass.hip
+// takes -- then nbins up to the pitch. Word for word what k_ranks_build writes for a dense slot of the same sequence; a slot without a
+// list (never written, cleared) is all padding with n = 0.
+__global__ void __launch_bounds__(256) k_ranks_build_sparse(const uint2* __restrict__ ent, const uint32_t* __restrict__ cum, const MscSparseHdr* __restrict__ hdr,
+                                                            uint32_t* __restrict__ ranks, uint32_t* __restrict__ n_of, uint64_t pitch, uint32_t nbins, uint64_t first_slot,
+                                                            uint64_t n_slots, int32_t* __restrict__ bad) {
+	const uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+	const uint32_t lane = threadIdx.x & 63;
+	if (i >= n_slots) return;
+	const uint64_t slot = first_slot + i;
+	const MscSparseHdr* h = hdr + slot;
+	const uint32_t nnz = h->nnz;
+	const uint64_t off = h->off;
+	uint32_t* out = ranks + slot * pitch;
+	const uint32_t n = nnz ? cum[off + nnz - 1] : 0u;
+	for (uint32_t j = lane; j < nnz; j += 64) {
+		const uint2 en = ent[off + j];
+		const uint32_t e = en.y ? en.y - 1u : 0u, end = cum[off + j];
+		for (uint32_t t = end - e; t < end; t++) if (t < pitch) out[t] = en.x;
+	}
+	if (lane == 0) { n_of[slot] = n; if (n > pitch) atomicOr(bad, 2); }          // (the host sized the pitch from the set's largest sum)
+	for (uint64_t t = (uint64_t)n + lane; t < pitch; t += 64) out[t] = nbins;
+}
+
 typedef int v4i_ __attribute__((ext_vector_type(4)));
 
 // 16 per-lane sums (one per query of a group) -> one register: lane (row r, bank b) holds the wave total of query {0, 2, 1, 3}[b] + 4 r
@@ -393,6 +418,15 @@ hipError_t msc_launch_ranks_build(hipStream_t st, const MscLayout& L, int dtype,
 	else if (dtype == 16) k_ranks_build<uint16_t><<<grid, dim3(256), 0, st>>>(bins, L.slot_bytes, scalars, ss, ranks, n_of, pitch, L.nbins, first_slot, n_slots, L.S, bad);
 	else if (dtype == 32) k_ranks_build<uint32_t><<<grid, dim3(256), 0, st>>>(bins, L.slot_bytes, scalars, ss, ranks, n_of, pitch, L.nbins, first_slot, n_slots, L.S, bad);
 	else return hipErrorInvalidValue;
+	return hipGetLastError();
+}
+
+// the same for slots of a sparse set, from their lists; *bad |= 2 when a list is longer than the pitch (a list holds no zero count)
+hipError_t msc_launch_ranks_build_sparse(hipStream_t st, const MscLayout& L, const void* ent, const uint32_t* cum, const MscSparseHdr* hdr, uint32_t* ranks, uint32_t* n_of,
+                                         uint64_t pitch, uint64_t first_slot, uint64_t n_slots, int32_t* bad) {
+	if (n_slots == 0) return hipSuccess;
+	if (L.nbins > (1ull << 20)) return hipErrorInvalidValue;
+	k_ranks_build_sparse<<<dim3((unsigned)((n_slots + 3) / 4)), dim3(256), 0, st>>>((const uint2*)ent, cum, hdr, ranks, n_of, pitch, (uint32_t)L.nbins, first_slot, n_slots, bad);
 	return hipGetLastError();
 }
 

@@ -211,6 +211,8 @@ hipError_t msc_launch_pair_digest_multi(hipStream_t st, const MscLayout& L, cons
 uint64_t msc_ranks_pitch(uint64_t max_excess);
 hipError_t msc_launch_ranks_build(hipStream_t st, const MscLayout& L, int dtype, const uint8_t* bins, const uint8_t* scalars, uint32_t* ranks, uint32_t* n_of, uint64_t pitch,
                                   uint64_t first_slot, uint64_t n_slots, int32_t* bad);
+hipError_t msc_launch_ranks_build_sparse(hipStream_t st, const MscLayout& L, const void* ent, const uint32_t* cum, const MscSparseHdr* hdr, uint32_t* ranks, uint32_t* n_of,
+                                         uint64_t pitch, uint64_t first_slot, uint64_t n_slots, int32_t* bad);
 hipError_t msc_launch_emd_ranks(hipStream_t st, uint64_t nbins, const uint32_t* c_ranks, uint64_t c_pitch, const uint32_t* c_n, const uint32_t* cand_slots, uint64_t first,
                                 uint32_t m, const uint32_t* q_ranks, uint64_t q_pitch, const uint32_t* q_n, const uint32_t* q_slots_dev, uint32_t n_q, uint64_t* out,
                                 uint32_t out_stride = 64);
@@ -221,6 +223,9 @@ hipError_t msc_launch_emd_ranks16(hipStream_t st, uint64_t nbins, const uint16_t
 uint64_t msc_kb_bytes(const MscLayout& L, uint64_t capacity);
 hipError_t msc_launch_kb_build(hipStream_t st, const MscLayout& L, int dtype, const uint8_t* bins, uint8_t* kb, uint64_t first_slot, uint64_t n_slots, void* mb,
                                uint32_t* mb_n, uint32_t pitch, int32_t* flags);
+bool msc_kb_build_sparse_fits(const MscLayout& L);
+hipError_t msc_launch_kb_build_sparse(hipStream_t st, const MscLayout& L, const void* ent, const MscSparseHdr* hdr, uint8_t* kb, uint64_t first_slot, uint64_t n_slots,
+                                      void* mb, uint32_t* mb_n, uint32_t pitch, int32_t* flags);
 uint32_t msc_pair_gemm_rows(uint32_t n_q);
 // msc_ranks_pass.hip: the 1 x M pass over rank lists
 size_t msc_ranks_pass_lds(uint64_t nbins, uint64_t q_kmers);

@@ -64,6 +64,7 @@ struct msc_ctx {
 	bool copy_pending = false;
 	bool block_pipe = true;                // msc_set_block_pipe: the blocks of msc_score_multi on three streams
 	bool pairs_div_cells = false;          // msc_set_pairs_div_cells: msc_search_pairs keeps divergence-statistic models on the matrix-core route
+	bool sparse_matrix_pass = false;       // msc_set_sparse_matrix_pass: two sparse sets may take the matrix-core Q x M route (mirrors built from their lists)
 	bool mirror_pass = true;               // msc_set_mirror_pass: a dense set's 1 x M passes merge the lists of its sparse mirror
 	bool packed_on_device = false;         // msc_hist_build_packed_dev: the 2-bit stream of the build in progress is device memory
 	bool no_kb_now = false;                // msc_score_multi: this block is taken by the older routes (its hot list would be too long)
@@ -132,7 +133,8 @@ struct msc_hist_set {
 	// presence-bit mirror (msc_pair_gemm.hip, msc_kbits.h): one BIT per bin = [count >= 2], slots blocked by 32 -- the B operand of the
 	// int8 product of the Q x M pass -- and beside it the lists of large bins (count - 1 >= 2) that make the pass exact for any counts:
 	// mb[slot][mb_pitch] = (bin, count - 1), sorted by bin; mb_n = entries per slot (also on the host: the size of a query block's hot list is
-	// known without a read-back). slots [kb_lo, kb_hi) are stale (mark_stale)
+	// known without a read-back). slots [kb_lo, kb_hi) are stale (mark_stale). A sparse set carries the same mirror, built from its lists
+	// (msc_set_sparse_matrix_pass; lists_written keeps the stale range)
 	mutable uint8_t* kb = nullptr;
 	mutable uint64_t kb_lo = 0, kb_hi = 0;
 	mutable bool kb_unavailable = false;
@@ -214,6 +216,9 @@ int ensure(msc_ctx* ctx, DevBuf& b, size_t bytes);             // growable devic
 int ensure_pinned(msc_ctx* ctx, DevBuf& b, size_t bytes);      // growable page-locked host staging
 void release(DevBuf& b);
 void mark_written(msc_hist_set* s, uint64_t first, uint64_t n);
+// every writer of the lists of slots [first, first + n) of a sparse set ends here: the rank-list caches are keyed on list_epoch, the
+// mirrors of the matrix-core pass (kb / mb / ranks, where the set has them) rebuild the stale range
+void lists_written(msc_hist_set* s, uint64_t first, uint64_t n);
 int refresh_bounds(msc_ctx* ctx, msc_hist_set* s, uint64_t first, uint64_t n);
 void learn_length(const msc_hist_set* s, uint64_t slot, uint64_t len);
 int slot_length(msc_ctx* ctx, const msc_hist_set* set, uint64_t slot, uint64_t* len);

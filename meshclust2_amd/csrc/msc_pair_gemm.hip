@@ -98,6 +98,75 @@ __global__ void __launch_bounds__(256) k_kb_sort(uint2* __restrict__ mb, const u
 	}
 }
 
+// ------------------------------------------------------------------------------------------------ the same mirror from the lists of a sparse set
+// A sparse slot (sparse.hip) keeps the (logical bin, count) entries with count >= 2, sorted by bin: exactly the bins whose presence bit is
+// set. One workgroup = one block of 32 slots x one window of kKbWin bins. The window is a whole number of tiles (<= 4 096 bins), and the
+// tile permutation stays inside a tile, so the window's logical bins are its physical ones; its piece of the mirror -- [super-step][slot %
+// 32][32 bytes], msc_kbits.h -- is kKbWin / 256 contiguous KiB, built in LDS (zeros, then one LDS atomic per entry) and stored with 16-byte
+// stores: every byte of the slots of the run is written on every rebuild, the all-zero super-steps included, no global atomics and no
+// zero-fill pass. hdr.split[] brackets the entries of the window (the 16 equal sub-ranges of the bins); the test against the window does the rest.
+constexpr uint32_t kKbWin = 8192;          // bins per window: 32 slots x 1 KiB of bits = 32 KiB of LDS
+__global__ void __launch_bounds__(256) k_kb_build_sparse(const uint2* __restrict__ ent, const MscSparseHdr* __restrict__ hdr, uint64_t nbins, uint32_t E, uint32_t R,
+                                                         uint8_t* __restrict__ kb, uint64_t first_slot, uint64_t n_slots) {
+	__shared__ uint4 img4[kKbWin / 4];          // [super-step of the window][slot % 32][8 words]
+	uint32_t* img = reinterpret_cast<uint32_t*>(img4);
+	const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	const uint64_t blk = (first_slot >> 5) + blockIdx.x;
+	const uint32_t lo = blockIdx.y * kKbWin, hi = lo + kKbWin, sub = (uint32_t)(nbins / MSC_SPARSE_SUB);
+	for (uint32_t i = tid; i < kKbWin / 4; i += 256) img4[i] = make_uint4(0, 0, 0, 0);
+	__syncthreads();
+	const uint32_t s0 = lo / sub, s1 = (hi + sub - 1) / sub < MSC_SPARSE_SUB ? (hi + sub - 1) / sub : MSC_SPARSE_SUB;
+	for (uint32_t sl = wave; sl < 32; sl += 4) {
+		const uint64_t slot = blk * 32 + sl;
+		if (slot < first_slot || slot >= first_slot + n_slots) continue;
+		const MscSparseHdr* h = hdr + slot;
+		if (h->nnz == 0) continue;
+		const uint64_t off = h->off;
+		for (uint32_t j = h->split[s0] + lane, jend = h->split[s1]; j < jend; j += 64) {
+			const uint2 en = ent[off + j];
+			if (en.x < lo || en.x >= hi || en.y < 2) continue;
+			const uint32_t p = (uint32_t)msc_phys_index(en.x, E, R) - lo;          // (inside the window: the permutation is local to a tile)
+			const uint32_t hw = 8 * ((p >> 4) & 1) + ((p >> 5) & 7);
+			atomicOr(&img[(p >> 8) * 256 + sl * 8 + (hw >> 1)], 1u << (16 * (hw & 1) + (p & 15)));
+		}
+	}
+	__syncthreads();
+	uint8_t* dst = kb + blk * msc_kb_block_bytes(nbins) + (uint64_t)(lo / 256) * 1024;
+	for (uint32_t i = tid; i < kKbWin / 4; i += 256) {          // 16-byte piece i: super-step i / 64, slot (i % 64) / 2
+		const uint64_t slot = blk * 32 + ((i & 63) >> 1);
+		if (slot >= first_slot && slot < first_slot + n_slots) *reinterpret_cast<uint4*>(dst + (uint64_t)i * 16) = img4[i];
+	}
+}
+
+// The lists of large bins of sparse slots: one wave per slot compacts the entries with count - 1 >= 2 as (physical bin, count - 1) in
+// list order (k_kb_sort then orders them by physical position); mb_n = the true count, flags[1] = the longest list. A slot without a
+// list (never written, cleared) gets mb_n = 0.
+__global__ void __launch_bounds__(256) k_mb_build_sparse(const uint2* __restrict__ ent, const MscSparseHdr* __restrict__ hdr, uint32_t E, uint32_t R, uint64_t first_slot,
+                                                         uint64_t n_slots, uint2* __restrict__ mb, uint32_t* __restrict__ mb_n, uint32_t pitch, int32_t* __restrict__ flags) {
+	const uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+	const uint32_t lane = threadIdx.x & 63;
+	if (i >= n_slots) return;
+	const uint64_t slot = first_slot + i;
+	const MscSparseHdr* h = hdr + slot;
+	const uint32_t nnz = h->nnz;
+	const uint64_t off = h->off;
+	uint32_t n = 0;
+	for (uint32_t j0 = 0; j0 < nnz; j0 += 64) {
+		const uint32_t j = j0 + lane;
+		uint2 en = make_uint2(0, 0);
+		if (j < nnz) en = ent[off + j];
+		const bool big = en.y >= 3;
+		const unsigned long long mask = __builtin_amdgcn_ballot_w64(big);
+		const uint32_t pos = n + (uint32_t)__popcll(mask & ((1ull << lane) - 1));
+		if (big && pos < pitch) mb[slot * pitch + pos] = make_uint2((uint32_t)msc_phys_index(en.x, E, R), en.y - 1);
+		n += (uint32_t)__popcll(mask);
+	}
+	if (lane == 0) {
+		mb_n[slot] = n;
+		if (n) atomicMax(&flags[1], (int32_t)n);
+	}
+}
+
 // ------------------------------------------------------------------------------------------------ the queries' side of a block
 // One workgroup per 128-bin step, one thread per query row (rows past n_q are zero). anib = the queries' tile of each 256-bin super-step
 // as k_pair_gemm_fp4_dma copies it into LDS: [super-step][row][16-byte segment (2 t + h) ^ ((row >> 1) & 7)] = the nibbles lane half h
@@ -384,6 +453,25 @@ hipError_t msc_launch_kb_build(hipStream_t st, const MscLayout& L, int dtype, co
 	else if (dtype == 16) k_kb_build<uint16_t><<<grid, dim3(256), 0, st>>>((const uint16_t*)bins, L.padded_bins, kb, first_slot, n_slots, (uint2*)mb, mb_n, pitch, flags);
 	else if (dtype == 32) k_kb_build<uint32_t><<<grid, dim3(256), 0, st>>>((const uint32_t*)bins, L.padded_bins, kb, first_slot, n_slots, (uint2*)mb, mb_n, pitch, flags);
 	else return hipErrorInvalidValue;
+	k_kb_sort<<<dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, st>>>((uint2*)mb, mb_n, pitch, first_slot, n_slots);
+	return hipGetLastError();
+}
+
+// the same mirror and lists for slots [first_slot, first_slot + n_slots) of a sparse set, from its entry lists: byte for byte what
+// msc_launch_kb_build writes for dense slots of the same sequences (flags[0] stays clear: a list holds no zero count)
+// whether the builder below takes histograms of this layout: whole windows of whole tiles, up to 2^20 bins (kb_route_fits asks first)
+bool msc_kb_build_sparse_fits(const MscLayout& L) {
+	return L.nbins == L.padded_bins && L.nbins % kKbWin == 0 && kKbWin % L.tile_bins == 0 && L.nbins <= (1ull << 20);
+}
+
+hipError_t msc_launch_kb_build_sparse(hipStream_t st, const MscLayout& L, const void* ent, const MscSparseHdr* hdr, uint8_t* kb, uint64_t first_slot, uint64_t n_slots,
+                                      void* mb, uint32_t* mb_n, uint32_t pitch, int32_t* flags) {
+	if (n_slots == 0) return hipSuccess;
+	if (!msc_kb_build_sparse_fits(L)) return hipErrorInvalidValue;
+	const uint64_t blocks = ((first_slot + n_slots - 1) >> 5) - (first_slot >> 5) + 1;
+	if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+	k_kb_build_sparse<<<dim3((unsigned)blocks, (unsigned)(L.nbins / kKbWin)), dim3(256), 0, st>>>((const uint2*)ent, hdr, L.nbins, L.E, L.R, kb, first_slot, n_slots);
+	k_mb_build_sparse<<<dim3((unsigned)((n_slots + 3) / 4)), dim3(256), 0, st>>>((const uint2*)ent, hdr, L.E, L.R, first_slot, n_slots, (uint2*)mb, mb_n, pitch, flags);
 	k_kb_sort<<<dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, st>>>((uint2*)mb, mb_n, pitch, first_slot, n_slots);
 	return hipGetLastError();
 }

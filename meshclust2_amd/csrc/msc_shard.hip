@@ -220,8 +220,12 @@ extern "C" int msc_hist_set_reset(msc_ctx* ctx, msc_hist_set* set) {
 	if (!set->sparse) return MSC_OK;
 	// (whatever is queued on the ctx stream still reads the old lists; what overwrites them is queued behind it on the same stream)
 	set->ent_used = 0;
-	set->list_epoch++;
+	lists_written(set, 0, set->capacity);
 	for (MscSparseHdr& h : set->hdr_host) { h.nnz = 0; h.off = 0; }
+	// the device headers too, queued behind those readers: a slot that is not written again holds no list, for the merge passes and for
+	// the mirror builders of the matrix-core pass alike (a stale (off, nnz) would point at other slots' entries once the arena refills)
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipMemsetAsync(set->hdr, 0, set->capacity * sizeof(MscSparseHdr), ctx->stream));
 	return MSC_OK;
 }
 
@@ -263,7 +267,7 @@ extern "C" int msc_hist_unpack(msc_ctx* ctx, msc_hist_set* set, const uint32_t* 
 				HIP_TRY(ctx, hipMemcpyAsync(set->cum + h.off, p + up16((uint64_t)ph.nnz * 8), (uint64_t)ph.nnz * 4, hipMemcpyDeviceToDevice, ctx->stream));
 			}
 			set->ent_used += ph.nnz;
-			set->list_epoch++;
+			lists_written(set, slot, 1);
 			set->hdr_host[slot] = h;          // (the mirror outlives the copy below: it is the source)
 			HIP_TRY(ctx, hipMemcpyAsync(set->hdr + slot, &set->hdr_host[slot], sizeof(MscSparseHdr), hipMemcpyHostToDevice, ctx->stream));
 			set->max_nnz = std::max(set->max_nnz, h.nnz);
@@ -329,8 +333,7 @@ extern "C" int msc_hist_unpack(msc_ctx* ctx, msc_hist_set* set, const uint32_t* 
 	if ((r = run_copies(ctx, segs))) return r;
 	if (set->sparse) {
 		set->ent_used = used;
-		set->list_epoch++;
-		for (uint64_t i = 0; i < n; i++) set->hdr_host[slots[i]] = new_hdr[i];
+		for (uint64_t i = 0; i < n; i++) { set->hdr_host[slots[i]] = new_hdr[i]; lists_written(set, slots[i], 1); }
 	}
 	// 3. the host-side bounds and lengths follow the records that arrived (consecutive slots in one strided copy)
 	uint64_t i = 0;

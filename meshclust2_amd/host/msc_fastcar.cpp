@@ -91,7 +91,7 @@ int main(int argc, char** argv) {
 	std::vector<std::string> files, qfiles;
 	std::string weights, output = "output";
 	size_t chunk = 10000, qblock = 16;
-	bool format = true, sparse = false, report_kernels = false, div_cells = false;
+	bool format = true, sparse = false, report_kernels = false, div_cells = false, sparse_matrix = false;
 	int device = 0;
 	for (int i = 1; i < argc; i++) {
 		std::string a = argv[i];
@@ -106,11 +106,12 @@ int main(int argc, char** argv) {
 		else if (a == "--kernels") report_kernels = true;   // after the run: the streaming kernels the library picked for the scoring passes, on stderr
 		else if (a == "--sparse") sparse = true;        // sparse histogram layout (required for k >= 13; also the faster one for --feat slow models)
 		else if (a == "--div-cells") div_cells = true;  // msc_set_pairs_div_cells: a --feat slow model's query blocks on the matrix-core route
+		else if (a == "--sparse-matrix") sparse_matrix = true;  // msc_set_sparse_matrix_pass: with --sparse, the query blocks on the matrix-core route
 		else if (a == "--device") device = std::atoi(need("--device").c_str());
 		else files.push_back(a);
 	}
 	if (files.empty() || qfiles.empty() || weights.empty()) {
-		std::fprintf(stderr, "usage: %s <db.fa> --query <q.fa> --recover weights.txt [--output prefix] [--chunk 10000] [--no-format] [--sparse] [--div-cells]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s <db.fa> --query <q.fa> --recover weights.txt [--output prefix] [--chunk 10000] [--no-format] [--sparse] [--sparse-matrix] [--div-cells]\n", argv[0]);
 		return 1;
 	}
 	try {
@@ -128,6 +129,7 @@ int main(int argc, char** argv) {
 		}
 		msc::Context ctx(device);
 		ctx.set_pairs_div_cells(div_cells);
+		ctx.set_sparse_matrix_pass(sparse_matrix);
 		msc::Predictor pred(ctx, weights);
 		std::vector<Rec> db, queries;
 		for (const auto& f : files) { auto r = read_fasta(f); db.insert(db.end(), r.begin(), r.end()); }
