@@ -377,6 +377,23 @@ int msc_search_pairs(msc_ctx* ctx, const msc_model* cls, const msc_model* reg,
                      const uint64_t* win_lo, const uint64_t* win_hi, uint64_t* offsets, msc_pairs_info* info);
 int msc_search_pairs_fetch(msc_ctx* ctx, uint64_t first, uint64_t n, uint32_t* cand_idx, double* sim);
 
+/* msc_search_pairs with each query's list cut to its top_n best pairs on the device: the loop whose output is cut is fastcar's work()
+ * (fastcar/FC_Runner.cpp:426-471). Let S_q be the pairs msc_search_pairs lists for query q (same windows, models and similarities).
+ * With top_n > 0 the call lists all of S_q when |S_q| <= top_n, and otherwise the top_n pairs of S_q with the largest similarity:
+ * similarities are compared as doubles (-0.0 == 0.0), ties go to the lower candidate index i, the kept pairs stay in ascending i (the
+ * result is a subsequence of the full list) and their similarities are the bits the full list holds. Pairs of similarity 0 take part
+ * like any other: they are the smallest, so they are kept only where fewer than top_n pairs are positive. top_n == 0 means no cut: the
+ * result is msc_search_pairs's. There is no upper limit on top_n.
+ * Argument checks, error statuses, the route, info->route and info->fp64_pairs are msc_search_pairs's; offsets and info->n_pairs describe
+ * the kept list, which msc_search_pairs_fetch reads; close_counts (nullable, [n_q]) receives |S_q|, the pairs before the cut. The
+ * selection runs on the device block by block of queries: the list never holds more than the kept pairs, and one block's uncut pairs
+ * lie beside it in a staging list. */
+int msc_search_pairs_top(msc_ctx* ctx, const msc_model* cls, const msc_model* reg,
+                         const msc_hist_set* db, const uint32_t* db_slots, uint64_t m,
+                         const msc_hist_set* qset, const uint32_t* q_slots, uint64_t n_q,
+                         const uint64_t* win_lo, const uint64_t* win_hi, uint32_t top_n,
+                         uint64_t* offsets, uint64_t* close_counts, msc_pairs_info* info);
+
 /* ------------------------------------------------------------------ a8 over a device-resident window
  * The accumulate loop (cluster/ClusterFactory.cpp:553-610) hands Trainer::get_close an iterator range of the length-sorted store
  * (bvec::get_range, cluster/bvec.cpp:261-330; the loop `for (i = istart; i < iend; ++i)` of cluster/Trainer.cpp:41-48). A

@@ -41,6 +41,7 @@ class PairsInfo(C.Structure):
 
 
 _vp, _u64, _i64, _int, _dbl = C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_double
+_u32 = C.c_uint32
 _pu8, _pu32, _pu64, _pi64, _pdbl = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_double)
 PROTOTYPES = {
     "msc_abi_version": (_int, []),
@@ -100,6 +101,7 @@ PROTOTYPES = {
     "msc_merge": (_int, [_vp, _vp, _dbl, _vp, _vp, _u64, _i64, _i64, _i64, _pi64]),
     "msc_search": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp]),
     "msc_search_pairs": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "msc_search_pairs_top": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u32, _vp, _vp, _vp]),
     "msc_search_pairs_fetch": (_int, [_vp, _u64, _u64, _vp, _vp]),
     "msc_mean_nearest": (_int, [_vp, _vp, _vp, _u64, _pi64, _vp, _vp]),
     "msc_update_centres": (_int, [_vp, _vp, C.c_double, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),

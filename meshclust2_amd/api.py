@@ -654,3 +654,32 @@ class Predictor:
         sim = np.zeros(max(n, 1))
         self.ctx.check(lib.msc_search_pairs_fetch(h, 0, n, _ptr(idx), _ptr(sim)))
         return offsets, idx[:n], sim[:n], dict(n_pairs=n, route=int(info.route), fp64_pairs=int(info.fp64_pairs))
+
+    def search_pairs_top(self, db, db_slots, qset, q_slots, top, win_lo=None, win_hi=None, m=None):
+        """search_pairs with each query's list cut to its `top` best pairs on the device (msc_search_pairs_top): all of a query's pairs where
+        it has at most `top`, else the `top` of largest similarity (compared as doubles, ties to the lower candidate index), still in
+        ascending candidate index and with the bits search_pairs returns; top = 0 is no cut. -> (offsets, cand_idx, sim, info) as
+        search_pairs, info["close_counts"] (uint64 [n_q]) = each query's pairs before the cut."""
+        sl, m = _slots(db_slots, m)
+        qs = np.ascontiguousarray(q_slots, dtype=np.uint32)
+        nq = qs.size
+        top = int(top)
+        if not 0 <= top <= 0xFFFFFFFF:
+            raise ValueError("top is a 32-bit count")
+        if (win_lo is None) != (win_hi is None):
+            raise ValueError("win_lo and win_hi are given together or not at all")
+        lo = None if win_lo is None else np.ascontiguousarray(win_lo, dtype=np.uint64)
+        hi = None if win_hi is None else np.ascontiguousarray(win_hi, dtype=np.uint64)
+        if lo is not None and (lo.size != nq or hi.size != nq):
+            raise ValueError("one window per query")
+        offsets = np.zeros(nq + 1, dtype=np.uint64)
+        counts = np.zeros(max(nq, 1), dtype=np.uint64)
+        info = _capi.PairsInfo()
+        lib, h = self.ctx.lib, self.ctx.h
+        self.ctx.check(lib.msc_search_pairs_top(h, self.cls.h if self.cls else None, self.reg.h if self.reg else None, db.h, _ptr(sl), m, qset.h, _ptr(qs), nq,
+                                                _ptr(lo), _ptr(hi), top, _ptr(offsets), _ptr(counts), C.byref(info)))
+        n = int(info.n_pairs)
+        idx = np.zeros(max(n, 1), dtype=np.uint32)
+        sim = np.zeros(max(n, 1))
+        self.ctx.check(lib.msc_search_pairs_fetch(h, 0, n, _ptr(idx), _ptr(sim)))
+        return offsets, idx[:n], sim[:n], dict(n_pairs=n, route=int(info.route), fp64_pairs=int(info.fp64_pairs), close_counts=counts[:nq])

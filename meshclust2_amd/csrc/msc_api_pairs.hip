@@ -7,6 +7,8 @@
 //               cells (k_pair_epilogue_bits_div) and agree with the fallback's to rounding, not bit for bit.
 //   fallback -- every other case: msc_score_multi one block of queries at a time (dense flags and sums of that block on the host), compacted
 //               there and copied up, so that msc_search_pairs_fetch reads one list whichever route ran.
+// msc_search_pairs_top is the same body with a cut behind each block's list: the block's pairs go to the staging list on either route, and
+// k_pair_top_plan / k_pair_top_select (pair_features.hip) write each query's top_n best from there to the call's list.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -71,7 +73,23 @@ struct PairsCall {
 	uint64_t fp64 = 0;
 	bool need_emd = false;
 	bool cls_div = false, reg_div = false;          // msc_set_pairs_div_cells: the model holds a divergence statistic, its sums come from cells
+	uint32_t top_n = 0;                 // msc_search_pairs_top: pairs kept per query (0 = all; qcount stays the count before the cut)
 };
+
+// the cut of a block whose pairs lie in the staging list as pl_seg says ([n_chunks][nb] of {first, n}): the list grows from `total` by
+// the kept pairs, known once the plan kernel has run, and the selection writes them to their final places
+int cut_block(msc_ctx* ctx, uint32_t n_chunks, uint32_t nb, uint32_t top_n, uint64_t& total) {
+	int r;
+	uint64_t* words = (uint64_t*)ctx->pl_words.p;
+	HIP_TRY(ctx, msc_launch_pair_top_plan(ctx->stream, (const uint64_t*)ctx->pl_seg.p, n_chunks, nb, top_n, words, (uint64_t*)ctx->pl_dst.p));
+	uint64_t now = 0;
+	if ((r = read_word(ctx, words, &now))) return r;
+	if ((r = grow_list(ctx, ctx->pl_idx, ctx->pl_sim, total, now))) return r;
+	HIP_TRY(ctx, msc_launch_pair_top_select(ctx->stream, (const uint64_t*)ctx->pl_seg.p, n_chunks, nb, top_n, (const uint64_t*)ctx->pl_dst.p, (const uint32_t*)ctx->pl_stage_idx.p,
+	                                        (const double*)ctx->pl_stage_sim.p, (uint32_t*)ctx->pl_idx.p, (double*)ctx->pl_sim.p));
+	total = now;
+	return MSC_OK;
+}
 
 // blocks of up to blk queries (none of one query when there are more: the product pass takes two and up), each with its union window;
 // a block whose members' windows are all empty is left out
@@ -116,6 +134,8 @@ int run_matrix(PairsCall& c) {
 	}
 	uint64_t* words = (uint64_t*)ctx->pl_words.p;
 	uint64_t total = 0;          // pairs in the list so far
+	uint64_t uncut = 0;          // msc_search_pairs_top: pairs listed before the cut
+	const bool cut = c.top_n != 0;
 	const bool screen = c.cls && c.cls->h.screen_ok;
 	const bool emd16 = c.need_emd && cands->ranks16 && qset->ranks16 && cands->rk_pitch == qset->rk_pitch;
 	uint32_t last_qn = 0;
@@ -131,6 +151,7 @@ int run_matrix(PairsCall& c) {
 		chunk = std::min(std::max<uint64_t>(chunk, 256), mall);
 		chunk = (mall + (mall + chunk - 1) / chunk - 1) / ((mall + chunk - 1) / chunk);
 		const uint32_t n_chunks = (uint32_t)((mall + chunk - 1) / chunk);
+		const bool stage = n_chunks > 1 || cut;          // the block's pairs go to the staging list first
 		const uint32_t slices = msc_pair_gemm_slices(L.nbins, (uint32_t)chunk, kb_qn, ctx->num_cus);
 		const uint32_t tiles = msc_pair_list_tiles((uint32_t)chunk);
 		const uint64_t nsteps = L.nbins / 128;
@@ -149,7 +170,7 @@ int run_matrix(PairsCall& c) {
 		}
 		if (c.need_emd && (r = ensure(ctx, ctx->emd_out, chunk * kb_qn * sizeof(uint64_t)))) return r;
 		if (c.cls && (r = ensure(ctx, ctx->pl_flags, (size_t)nb * chunk))) return r;
-		if (n_chunks > 1) {
+		if (stage) {
 			if ((r = ensure(ctx, ctx->pl_seg, (size_t)n_chunks * nb * 2 * sizeof(uint64_t))) || (r = ensure(ctx, ctx->pl_dst, (size_t)n_chunks * nb * sizeof(uint64_t)))) return r;
 			HIP_TRY(ctx, hipMemsetAsync(words + 1, 0, sizeof(uint64_t), st));
 		}
@@ -210,22 +231,25 @@ int run_matrix(PairsCall& c) {
 				if (!ea.screen) c.fp64 += (uint64_t)nb * mc;
 			}
 			HIP_TRY(ctx, msc_launch_pair_list_count(st, flags, nb, mc, off, dwl, dwh, (uint32_t*)ctx->pl_counts.p));
-			uint64_t* base = n_chunks == 1 ? words : words + 1;
+			uint64_t* base = stage ? words + 1 : words;
 			HIP_TRY(ctx, msc_launch_pair_list_scan(st, (const uint32_t*)ctx->pl_counts.p, nb, msc_pair_list_tiles(mc), base, (uint64_t*)ctx->pl_offsets.p,
-			                                       (uint64_t*)ctx->pl_qcount.p + b.q0, n_chunks > 1 ? (uint64_t*)ctx->pl_seg.p + (uint64_t)ci * nb * 2 : nullptr));
+			                                       (uint64_t*)ctx->pl_qcount.p + b.q0, stage ? (uint64_t*)ctx->pl_seg.p + (uint64_t)ci * nb * 2 : nullptr));
 			uint64_t now = 0;
 			if ((r = read_word(ctx, base, &now))) return r;          // the list grows before the write: no block runs past its end
-			DevBuf& out_idx = n_chunks == 1 ? ctx->pl_idx : ctx->pl_stage_idx;
-			DevBuf& out_sim = n_chunks == 1 ? ctx->pl_sim : ctx->pl_stage_sim;
-			if ((r = grow_list(ctx, out_idx, out_sim, n_chunks == 1 ? total : staged, now))) return r;
-			if (n_chunks == 1) total = now; else staged = now;
+			DevBuf& out_idx = stage ? ctx->pl_stage_idx : ctx->pl_idx;
+			DevBuf& out_sim = stage ? ctx->pl_stage_sim : ctx->pl_sim;
+			if ((r = grow_list(ctx, out_idx, out_sim, stage ? staged : total, now))) return r;
+			if (stage) staged = now; else total = now;
 			ea.model = c.reg ? c.reg->d : nullptr;
 			ea.close_soa = nullptr;
 			ea.screen = 0;
 			ea.div_cells = c.reg_div;
 			HIP_TRY(ctx, msc_launch_pair_list_write(st, ea, flags, off, dwl, dwh, (const uint64_t*)ctx->pl_offsets.p, (uint32_t*)out_idx.p, (double*)out_sim.p));
 		}
-		if (n_chunks > 1) {          // the block's chunks were staged chunk by chunk: into the list query by query
+		if (cut) {          // each query's best pairs out of the staged ones, into the list
+			uncut += staged;
+			if ((r = cut_block(ctx, n_chunks, nb, c.top_n, total))) return r;
+		} else if (stage) {          // the block's chunks were staged chunk by chunk: into the list query by query
 			if ((r = grow_list(ctx, ctx->pl_idx, ctx->pl_sim, total, total + staged))) return r;
 			HIP_TRY(ctx, msc_launch_pair_list_gather(st, (const uint64_t*)ctx->pl_seg.p, n_chunks, nb, words, (uint64_t*)ctx->pl_dst.p, (const uint32_t*)ctx->pl_stage_idx.p,
 			                                         (const double*)ctx->pl_stage_sim.p, (uint32_t*)ctx->pl_idx.p, (double*)ctx->pl_sim.p));
@@ -237,7 +261,7 @@ int run_matrix(PairsCall& c) {
 	HIP_TRY(ctx, hipMemcpy(c.qcount.data(), ctx->pl_qcount.p, n_q * sizeof(uint64_t), hipMemcpyDeviceToHost));
 	uint64_t open = 0;
 	if ((r = read_word(ctx, words + 2, &open))) return r;
-	c.fp64 += open + (c.reg ? total : 0);
+	c.fp64 += open + (c.reg ? (cut ? uncut : total) : 0);
 	ctx->pl_n = total;
 	if (last_qn) {          // msc_last_kernel_info names the product kernel, as msc_score_multi does
 		snprintf(ctx->last_kernel_buf, sizeof ctx->last_kernel_buf, "%s<%u query rows, one matrix product per tile of presence bits%s%s%s>", msc_pair_gemm_kernel_name(), last_qn,
@@ -257,6 +281,13 @@ int run_fallback(PairsCall& c) {
 	std::vector<uint8_t> bclose;
 	std::vector<double> bsim;
 	std::vector<uint32_t> ids;
+	const bool cut = c.top_n != 0;
+	uint64_t total = 0;          // msc_search_pairs_top: pairs in the list so far
+	std::vector<uint64_t> seg;
+	if (cut) {
+		if ((r = ensure(ctx, ctx->pl_words, 4 * sizeof(uint64_t)))) return r;
+		HIP_TRY(ctx, hipMemsetAsync(ctx->pl_words.p, 0, 4 * sizeof(uint64_t), ctx->stream));
+	}
 	for (const PairsBlock& b : c.blocks) {
 		const uint64_t mw = b.hi - b.lo;
 		const uint32_t* sl = c.cand_slots ? c.cand_slots + b.lo : nullptr;
@@ -276,9 +307,11 @@ int run_fallback(PairsCall& c) {
 			c.fp64 += b.nq * mw;
 			for (double& v : bsim) v = v < 0 ? 0 : (v > 1 ? 1 : v);      // p_predict clamps to [0,1], predict/Predictor.cpp:293-298
 		}
+		if (cut) seg.assign(2 * b.nq, 0);
 		for (uint64_t j = 0; j < b.nq; j++) {
 			const uint64_t q = b.q0 + j;
 			const uint64_t lo = c.windows ? c.win[q] : 0, hi = c.windows ? c.win[c.n_q + q] : c.m;
+			if (cut) seg[2 * j] = idx.size();
 			for (uint64_t i = lo; i < hi; i++) {
 				const uint64_t at = j * mw + (i - b.lo);
 				if (!bclose[at]) continue;
@@ -286,7 +319,24 @@ int run_fallback(PairsCall& c) {
 				sim.push_back(bsim[at]);
 				c.qcount[q]++;
 			}
+			if (cut) seg[2 * j + 1] = idx.size() - seg[2 * j];
 		}
+		if (cut && !idx.empty()) {          // the block's pairs up to the staging list, and the kernels of the matrix route cut them
+			if ((r = ensure(ctx, ctx->pl_seg, seg.size() * sizeof(uint64_t))) || (r = ensure(ctx, ctx->pl_dst, b.nq * sizeof(uint64_t))) ||
+			    (r = grow_list(ctx, ctx->pl_stage_idx, ctx->pl_stage_sim, 0, idx.size())))
+				return r;
+			HIP_TRY(ctx, hipMemcpyAsync(ctx->pl_seg.p, seg.data(), seg.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+			HIP_TRY(ctx, hipMemcpyAsync(ctx->pl_stage_idx.p, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+			HIP_TRY(ctx, hipMemcpyAsync(ctx->pl_stage_sim.p, sim.data(), sim.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+			if ((r = cut_block(ctx, 1, (uint32_t)b.nq, c.top_n, total))) return r;
+			HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // (the vectors are reused by the next block)
+			idx.clear();
+			sim.clear();
+		}
+	}
+	if (cut) {
+		ctx->pl_n = total;
+		return MSC_OK;
 	}
 	if ((r = grow_list(ctx, ctx->pl_idx, ctx->pl_sim, 0, idx.size()))) return r;
 	if (!idx.empty()) {
@@ -298,11 +348,10 @@ int run_fallback(PairsCall& c) {
 	return MSC_OK;
 }
 
-}  // namespace
-
-extern "C" int msc_search_pairs(msc_ctx* ctx, const msc_model* cls, const msc_model* reg, const msc_hist_set* db, const uint32_t* db_slots, uint64_t m,
-                                const msc_hist_set* qset, const uint32_t* q_slots, uint64_t n_q, const uint64_t* win_lo, const uint64_t* win_hi, uint64_t* offsets,
-                                msc_pairs_info* info) {
+// msc_search_pairs (top_n = 0, close_counts = NULL) and msc_search_pairs_top
+int search_pairs(msc_ctx* ctx, const msc_model* cls, const msc_model* reg, const msc_hist_set* db, const uint32_t* db_slots, uint64_t m, const msc_hist_set* qset,
+                 const uint32_t* q_slots, uint64_t n_q, const uint64_t* win_lo, const uint64_t* win_hi, uint32_t top_n, uint64_t* offsets, uint64_t* close_counts,
+                 msc_pairs_info* info) {
 	if (!ctx || !db || !qset || !offsets || (n_q && !q_slots)) return MSC_ERR_INVALID_ARG;
 	if ((cls && cls->ctx != ctx) || (reg && reg->ctx != ctx)) return MSC_ERR_INVALID_ARG;
 	if (info) memset(info, 0, sizeof *info);
@@ -311,6 +360,7 @@ extern "C" int msc_search_pairs(msc_ctx* ctx, const msc_model* cls, const msc_mo
 	if (!win_lo != !win_hi) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_search_pairs: win_lo and win_hi are given together or not at all");
 	if (m > 0xffffffffull) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_search_pairs: candidate indices are 32-bit");
 	memset(offsets, 0, (n_q + 1) * sizeof(uint64_t));
+	if (close_counts) memset(close_counts, 0, n_q * sizeof(uint64_t));
 	if (n_q == 0 || m == 0) return MSC_OK;
 	for (uint64_t i = 0; i < n_q; i++) if (q_slots[i] >= qset->capacity) return fail(ctx, MSC_ERR_INVALID_ARG, "query slot out of range");
 	int r = validate_pair(ctx, db, qset, q_slots[0], db_slots, m);
@@ -318,6 +368,7 @@ extern "C" int msc_search_pairs(msc_ctx* ctx, const msc_model* cls, const msc_mo
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	PairsCall c;
 	c.ctx = ctx; c.cls = cls; c.reg = reg; c.cands = db; c.cand_slots = db_slots; c.m = m; c.qset = qset; c.q_slots = q_slots; c.n_q = n_q;
+	c.top_n = top_n;
 	c.windows = win_lo != nullptr;
 	if (c.windows) {
 		c.win.resize(2 * n_q);
@@ -361,7 +412,8 @@ extern "C" int msc_search_pairs(msc_ctx* ctx, const msc_model* cls, const msc_mo
 	if (!matrix) plan_blocks(c, 128);
 	r = matrix ? run_matrix(c) : run_fallback(c);
 	if (r) { ctx->pl_n = 0; return r; }
-	for (uint64_t q = 0; q < n_q; q++) offsets[q + 1] = offsets[q] + c.qcount[q];
+	for (uint64_t q = 0; q < n_q; q++) offsets[q + 1] = offsets[q] + (top_n ? std::min<uint64_t>(c.qcount[q], top_n) : c.qcount[q]);
+	if (close_counts) memcpy(close_counts, c.qcount.data(), n_q * sizeof(uint64_t));
 	if (offsets[n_q] != ctx->pl_n) { ctx->pl_n = 0; return fail(ctx, MSC_ERR_HIP, "msc_search_pairs: %llu pairs listed, %llu counted", (unsigned long long)ctx->pl_n, (unsigned long long)offsets[n_q]); }
 	if (info) {
 		info->n_pairs = ctx->pl_n;
@@ -369,6 +421,20 @@ extern "C" int msc_search_pairs(msc_ctx* ctx, const msc_model* cls, const msc_mo
 		info->fp64_pairs = c.fp64;
 	}
 	return MSC_OK;
+}
+
+}  // namespace
+
+extern "C" int msc_search_pairs(msc_ctx* ctx, const msc_model* cls, const msc_model* reg, const msc_hist_set* db, const uint32_t* db_slots, uint64_t m,
+                                const msc_hist_set* qset, const uint32_t* q_slots, uint64_t n_q, const uint64_t* win_lo, const uint64_t* win_hi, uint64_t* offsets,
+                                msc_pairs_info* info) {
+	return search_pairs(ctx, cls, reg, db, db_slots, m, qset, q_slots, n_q, win_lo, win_hi, 0, offsets, nullptr, info);
+}
+
+extern "C" int msc_search_pairs_top(msc_ctx* ctx, const msc_model* cls, const msc_model* reg, const msc_hist_set* db, const uint32_t* db_slots, uint64_t m,
+                                    const msc_hist_set* qset, const uint32_t* q_slots, uint64_t n_q, const uint64_t* win_lo, const uint64_t* win_hi, uint32_t top_n,
+                                    uint64_t* offsets, uint64_t* close_counts, msc_pairs_info* info) {
+	return search_pairs(ctx, cls, reg, db, db_slots, m, qset, q_slots, n_q, win_lo, win_hi, top_n, offsets, close_counts, info);
 }
 
 extern "C" int msc_search_pairs_fetch(msc_ctx* ctx, uint64_t first, uint64_t n, uint32_t* cand_idx, double* sim) {

@@ -277,6 +277,11 @@ hipError_t msc_launch_pair_list_write(hipStream_t st, const MscEpilogueArgs& a, 
                                       const uint64_t* offsets, uint32_t* out_idx, double* out_sim);
 hipError_t msc_launch_pair_list_gather(hipStream_t st, const uint64_t* seg, uint32_t n_chunks, uint32_t n_q, uint64_t* base, uint64_t* dst, const uint32_t* s_idx,
                                        const double* s_sim, uint32_t* out_idx, double* out_sim);
+// the cut of msc_search_pairs_top: each query's place in the list (it keeps min(pairs, top_n); *base grows by their sum), then -- once the
+// list has that room -- the selection out of the block's staged pairs (seg[chunk][query] = {first, n}) straight to those places
+hipError_t msc_launch_pair_top_plan(hipStream_t st, const uint64_t* seg, uint32_t n_chunks, uint32_t n_q, uint32_t top_n, uint64_t* base, uint64_t* dst);
+hipError_t msc_launch_pair_top_select(hipStream_t st, const uint64_t* seg, uint32_t n_chunks, uint32_t n_q, uint32_t top_n, const uint64_t* dst, const uint32_t* s_idx,
+                                      const double* s_sim, uint32_t* out_idx, double* out_sim);
 // the window bookkeeping the fused epilogue + reduce kernels do for msc_get_close_window (msc_window.hip): pos[i] = position of candidate i,
 // alive[] = the window's flags, counter / out = the host-visible list of closed positions (out[0] = best position + 1, out[2 ..] = the list)
 struct MscCloseList {

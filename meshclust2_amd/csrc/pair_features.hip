@@ -2757,7 +2757,184 @@ __global__ void __launch_bounds__(kBlock) k_pair_list_gather(const unsigned long
 		out_sim[to + i] = s_sim[from + i];
 	}
 }
+
+// ---------------------------------------------------------------------------------------- the cut (msc_search_pairs_top)
+// Each query's top_n pairs by similarity out of a block's staged pairs: chunk c's pairs of query q lie in the staging list at
+// seg[c][q] = {first, n}, chunks in ascending candidate order. k_pair_top_plan gives every query its place in the call's list (it keeps
+// min(pairs, top_n)) before anything is selected; k_pair_top_select finds the top_n-th largest similarity v by a radix select over the
+// bit patterns (similarities are >= 0, so the pattern orders them once -0.0 is folded to +0.0 -- in the key only) and writes, in the order
+// they are staged, every pair above v and the first top_n - #{> v} pairs equal to v straight to their final positions. Positions come
+// from ballots and running counts alone: no atomic decides the order, and the written similarity keeps its bits.
+constexpr uint32_t kTopLdsKeys = 4096;          // a query with this many pairs or fewer is selected from LDS after one read (32 KiB of keys)
+
+__device__ __forceinline__ unsigned long long top_key(double s) {
+	const unsigned long long k = (unsigned long long)__double_as_longlong(s);
+	return k == 0x8000000000000000ull ? 0ull : k;
+}
+
+// one workgroup, thread q for query q (a block has at most 128): dst[q] = the first position of q's kept pairs, from *base; *base += kept
+__global__ void __launch_bounds__(kBlock) k_pair_top_plan(const unsigned long long* __restrict__ seg, uint32_t n_chunks, uint32_t n_q, uint32_t top_n,
+                                                          unsigned long long* __restrict__ base, unsigned long long* __restrict__ dst) {
+	__shared__ unsigned long long part[kBlock];
+	const uint32_t q = threadIdx.x;
+	unsigned long long n = 0;
+	if (q < n_q)
+		for (uint32_t c = 0; c < n_chunks; c++) n += seg[2 * ((uint64_t)c * n_q + q) + 1];
+	const unsigned long long keep = n < top_n ? n : top_n;
+	part[q] = keep;
+	__syncthreads();
+	for (uint32_t d = 1; d < (uint32_t)kBlock; d <<= 1) {
+		const unsigned long long v = q >= d ? part[q - d] : 0ull;
+		__syncthreads();
+		part[q] += v;
+		__syncthreads();
+	}
+	const unsigned long long b = *base;
+	if (q < n_q) dst[q] = b + part[q] - keep;
+	__syncthreads();          // (every thread has read *base)
+	if (q == 0) *base = b + part[kBlock - 1];
+}
+
+// a wave adds its lanes' digits to the histogram: one add for the wave where every lane holds the same digit (the high bytes of
+// similarities in [0, 1] take a handful of values, and tied similarities share all eight), an LDS atomic per lane otherwise
+__device__ __forceinline__ void top_hist_add(uint32_t* hist, bool in, uint32_t bin) {
+	const uint64_t act = __ballot(in);
+	if (!act) return;
+	const int src = __ffsll((unsigned long long)act) - 1;
+	const uint32_t first = (uint32_t)__shfl((int)bin, src, 64);
+	if (__ballot(in && bin == first) == act) {
+		if ((int)(threadIdx.x & 63) == src) atomicAdd(&hist[first], (uint32_t)__popcll(act));
+	} else if (in) atomicAdd(&hist[bin], 1u);
+}
+
+// One workgroup per query. A query that keeps everything is a plain copy. Otherwise eight passes of an 8-bit digit, most significant
+// first, over the keys that match the digits found so far: a 256-bin histogram in LDS, its sums from the top bin down, and the bin in
+// which the k-th largest lies. The keys come from LDS where the query's pairs fit kTopLdsKeys, from the staging list (L2) otherwise; the
+// pieces are read in chunk order either way.
+__global__ void __launch_bounds__(kBlock) k_pair_top_select(const unsigned long long* __restrict__ seg, uint32_t n_chunks, uint32_t n_q, uint32_t top_n,
+                                                            const unsigned long long* __restrict__ dst, const uint32_t* __restrict__ s_idx,
+                                                            const double* __restrict__ s_sim, uint32_t* __restrict__ out_idx, double* __restrict__ out_sim) {
+	__shared__ unsigned long long keys[kTopLdsKeys];
+	__shared__ uint32_t hist[256], sums[256], pick[2], wtot[kWavesPerBlock][2];
+	static_assert(kBlock == 256, "one thread per bin");
+	const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	unsigned long long count = 0;
+	for (uint32_t c = 0; c < n_chunks; c++) count += seg[2 * ((uint64_t)c * n_q + q) + 1];
+	const unsigned long long to = dst[q];
+	if (count <= top_n) {
+		unsigned long long at = to;
+		for (uint32_t c = 0; c < n_chunks; c++) {
+			const unsigned long long from = seg[2 * ((uint64_t)c * n_q + q)], n = seg[2 * ((uint64_t)c * n_q + q) + 1];
+			for (unsigned long long i = tid; i < n; i += kBlock) {
+				out_idx[at + i] = s_idx[from + i];
+				out_sim[at + i] = s_sim[from + i];
+			}
+			at += n;
+		}
+		return;
+	}
+	const bool in_lds = count <= kTopLdsKeys;
+	if (in_lds) {
+		uint32_t p0 = 0;
+		for (uint32_t c = 0; c < n_chunks; c++) {
+			const unsigned long long from = seg[2 * ((uint64_t)c * n_q + q)];
+			const uint32_t n = (uint32_t)seg[2 * ((uint64_t)c * n_q + q) + 1];
+			for (uint32_t i = tid; i < n; i += kBlock) keys[p0 + i] = top_key(s_sim[from + i]);
+			p0 += n;
+		}
+	}
+	unsigned long long prefix = 0, mask = 0;
+	uint32_t k = top_n;          // the k-th largest of the keys that match prefix under mask
+	for (int d = 7; d >= 0; d--) {
+		const int sh = 8 * d;
+		hist[tid] = 0;
+		__syncthreads();          // (and the keys are in LDS)
+		if (in_lds) {
+			for (uint32_t b0 = 0; b0 < (uint32_t)count; b0 += kBlock) {
+				const bool in = b0 + tid < (uint32_t)count;
+				const unsigned long long key = in ? keys[b0 + tid] : 0ull;
+				top_hist_add(hist, in && (key & mask) == prefix, (uint32_t)(key >> sh) & 255u);
+			}
+		} else {
+			for (uint32_t c = 0; c < n_chunks; c++) {
+				const unsigned long long from = seg[2 * ((uint64_t)c * n_q + q)], n = seg[2 * ((uint64_t)c * n_q + q) + 1];
+				for (unsigned long long b0 = 0; b0 < n; b0 += kBlock) {
+					const bool in = b0 + tid < n;
+					const unsigned long long key = in ? top_key(s_sim[from + b0 + tid]) : 0ull;
+					top_hist_add(hist, in && (key & mask) == prefix, (uint32_t)(key >> sh) & 255u);
+				}
+			}
+		}
+		__syncthreads();
+		const uint32_t own = hist[255 - tid];          // thread t holds bin 255 - t: the sums run from the largest digit down
+		sums[tid] = own;
+		__syncthreads();
+		for (uint32_t o = 1; o < 256; o <<= 1) {
+			const uint32_t v = tid >= o ? sums[tid - o] : 0u;
+			__syncthreads();
+			sums[tid] += v;
+			__syncthreads();
+		}
+		const uint32_t incl = sums[tid];
+		if (incl >= k && incl - own < k) { pick[0] = 255 - tid; pick[1] = k - (incl - own); }          // (one thread: the sums do not decrease)
+		__syncthreads();
+		prefix |= (unsigned long long)pick[0] << sh;
+		mask |= 0xffull << sh;
+		k = pick[1];
+		__syncthreads();
+	}
+	// prefix = v, the top_n-th largest key; k = how many of the pairs equal to v are kept, the first ones in staged order
+	const uint64_t below = (1ull << lane) - 1ull;
+	unsigned long long above = 0, equal = 0;          // pairs > v and == v in the tiles before this one
+	uint32_t p0 = 0;
+	for (uint32_t c = 0; c < n_chunks; c++) {
+		const unsigned long long from = seg[2 * ((uint64_t)c * n_q + q)], n = seg[2 * ((uint64_t)c * n_q + q) + 1];
+		for (unsigned long long b0 = 0; b0 < n; b0 += kBlock) {
+			const unsigned long long i = b0 + tid;
+			const bool in = i < n;
+			const unsigned long long key = !in ? 0ull : (in_lds ? keys[p0 + (uint32_t)i] : top_key(s_sim[from + i]));
+			const bool g = in && key > prefix, e = in && key == prefix;
+			const uint64_t mg = __ballot(g), me = __ballot(e);
+			uint32_t gb = (uint32_t)__popcll(mg & below), eb = (uint32_t)__popcll(me & below);
+			if (lane == 0) { wtot[wave][0] = (uint32_t)__popcll(mg); wtot[wave][1] = (uint32_t)__popcll(me); }
+			__syncthreads();
+			uint32_t tg = 0, te = 0;
+			for (uint32_t w = 0; w < (uint32_t)kWavesPerBlock; w++) {
+				const uint32_t a = wtot[w][0], b = wtot[w][1];
+				if (w < wave) { gb += a; eb += b; }
+				tg += a;
+				te += b;
+			}
+			const unsigned long long rank_e = equal + eb;          // pairs equal to v before this one
+			if (g || (e && rank_e < k)) {
+				const unsigned long long pos = to + above + gb + (rank_e < k ? rank_e : (unsigned long long)k);
+				out_idx[pos] = s_idx[from + i];
+				out_sim[pos] = s_sim[from + i];
+			}
+			above += tg;
+			equal += te;
+			__syncthreads();
+		}
+		p0 += (uint32_t)n;
+	}
+}
 }  // namespace
+
+hipError_t msc_launch_pair_top_plan(hipStream_t st, const uint64_t* seg, uint32_t n_chunks, uint32_t n_q, uint32_t top_n, uint64_t* base, uint64_t* dst) {
+	if ((uint64_t)n_chunks * n_q == 0) return hipSuccess;
+	if (n_q > (uint32_t)kBlock || top_n == 0) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(k_pair_top_plan, dim3(1), dim3(kBlock), 0, st, (const unsigned long long*)seg, n_chunks, n_q, top_n, (unsigned long long*)base, (unsigned long long*)dst);
+	return hipGetLastError();
+}
+
+// queued behind msc_launch_pair_top_plan once the list holds *base pairs
+hipError_t msc_launch_pair_top_select(hipStream_t st, const uint64_t* seg, uint32_t n_chunks, uint32_t n_q, uint32_t top_n, const uint64_t* dst, const uint32_t* s_idx,
+                                      const double* s_sim, uint32_t* out_idx, double* out_sim) {
+	if ((uint64_t)n_chunks * n_q == 0) return hipSuccess;
+	hipLaunchKernelGGL(k_pair_top_select, dim3(n_q), dim3(kBlock), 0, st, (const unsigned long long*)seg, n_chunks, n_q, top_n, (const unsigned long long*)dst, s_idx, s_sim,
+	                   out_idx, out_sim);
+	return hipGetLastError();
+}
 
 uint32_t msc_pair_list_tiles(uint32_t mc) { return (mc + kListTile - 1) / kListTile; }
 

@@ -235,6 +235,26 @@ public:
 		if (info) *info = inf;
 		return offsets;
 	}
+	// search_pairs with each query's list cut on the device to its top_n pairs of largest similarity (msc_search_pairs_top: ties to the lower
+	// index, the kept pairs in ascending index with the bits search_pairs gives; top_n = 0 is no cut). close_counts (nullable) = pairs per
+	// query before the cut. Empty windows mean every candidate.
+	std::vector<uint64_t> search_pairs_top(const PointSet& db, const std::vector<uint32_t>& slots, const PointSet& q, const std::vector<uint32_t>& q_slots,
+	                                       const std::vector<uint64_t>& win_lo, const std::vector<uint64_t>& win_hi, uint32_t top_n, std::vector<uint32_t>& cand_idx,
+	                                       std::vector<double>& similarity, std::vector<uint64_t>* close_counts = nullptr, msc_pairs_info* info = nullptr) const {
+		const bool windows = !win_lo.empty() || !win_hi.empty();
+		if (windows && (win_lo.size() != q_slots.size() || win_hi.size() != q_slots.size())) throw Error(MSC_ERR_INVALID_ARG, "search_pairs_top: one window per query");
+		std::vector<uint64_t> offsets(q_slots.size() + 1, 0);
+		if (close_counts) close_counts->assign(q_slots.size(), 0);
+		msc_pairs_info inf;
+		ctx_.check(msc_search_pairs_top(ctx_.get(), cls_ ? cls_->get() : nullptr, reg_ ? reg_->get() : nullptr, db.get(), slots.data(), slots.size(), q.get(), q_slots.data(),
+		                                q_slots.size(), windows ? win_lo.data() : nullptr, windows ? win_hi.data() : nullptr, top_n, offsets.data(),
+		                                close_counts ? close_counts->data() : nullptr, &inf));
+		cand_idx.resize(inf.n_pairs);
+		similarity.resize(inf.n_pairs);
+		ctx_.check(msc_search_pairs_fetch(ctx_.get(), 0, inf.n_pairs, cand_idx.data(), similarity.data()));
+		if (info) *info = inf;
+		return offsets;
+	}
 private:
 	Context& ctx_;
 	std::unique_ptr<Feature> cls_, reg_;

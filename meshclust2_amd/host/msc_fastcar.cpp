@@ -6,7 +6,12 @@
 // std::sort by length, bin_search, format_header and the output formatting follow fastcar/FC_Runner.cpp:389-471,
 // 560-611 at one thread (one output file "<prefix>0"); training is out of scope, a two-block weights file is required.
 //
-//   msc_fastcar <db.fa> --query <q.fa> --recover weights.txt [--output output] [--chunk 10000] [--no-format] [--device 0] [--div-cells]
+//   msc_fastcar <db.fa> --query <q.fa> --recover weights.txt [--output output] [--chunk 10000] [--no-format] [--device 0] [--div-cells] [--top N]
+//
+// --top N: each query's N best hits over the whole database (the rule of msc_search_pairs_top: largest similarity, ties to the earlier
+// database chunk and then to the lower position in the chunk's window order). Per database chunk the cut runs on the device; across
+// chunks at most N survivors per chunk and query are merged here by the same rule, and a query's lines are written once every database
+// chunk of its query chunk is done, in the order they would have had without the flag.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -85,12 +90,29 @@ void load_chunk(msc::PointSet& set, const std::vector<Rec>& recs, size_t off, si
 	for (size_t i = 0; i < n; i++) pts[i] = Pt{recs[off + i].header, set.get_length(i), (uint32_t)i};
 }
 
+// a hit that survived its database chunk's cut; `chunk` and `cand` give its place in the output without --top
+struct Surv { size_t chunk, cand; double sim; std::string header; };
+
+// the rule of msc_search_pairs_top on the host: the n of largest similarity (compared as doubles), ties to the earlier entry, order kept
+template <class T>
+void cut_top(std::vector<T>& v, size_t n) {
+	if (n == 0 || v.size() <= n) return;
+	std::vector<size_t> order(v.size());
+	for (size_t i = 0; i < order.size(); i++) order[i] = i;
+	std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return v[a].sim > v[b].sim; });
+	order.resize(n);
+	std::sort(order.begin(), order.end());
+	std::vector<T> kept;
+	for (size_t i : order) kept.push_back(std::move(v[i]));
+	v.swap(kept);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
 	std::vector<std::string> files, qfiles;
 	std::string weights, output = "output";
-	size_t chunk = 10000, qblock = 16;
+	size_t chunk = 10000, qblock = 16, top = 0;
 	bool format = true, sparse = false, report_kernels = false, div_cells = false, sparse_matrix = false;
 	int device = 0;
 	for (int i = 1; i < argc; i++) {
@@ -107,11 +129,12 @@ int main(int argc, char** argv) {
 		else if (a == "--sparse") sparse = true;        // sparse histogram layout (required for k >= 13; also the faster one for --feat slow models)
 		else if (a == "--div-cells") div_cells = true;  // msc_set_pairs_div_cells: a --feat slow model's query blocks on the matrix-core route
 		else if (a == "--sparse-matrix") sparse_matrix = true;  // msc_set_sparse_matrix_pass: with --sparse, the query blocks on the matrix-core route
+		else if (a == "--top") top = (size_t)std::max(0l, std::atol(need("--top").c_str()));          // each query's N best hits (0: all)
 		else if (a == "--device") device = std::atoi(need("--device").c_str());
 		else files.push_back(a);
 	}
 	if (files.empty() || qfiles.empty() || weights.empty()) {
-		std::fprintf(stderr, "usage: %s <db.fa> --query <q.fa> --recover weights.txt [--output prefix] [--chunk 10000] [--no-format] [--sparse] [--sparse-matrix] [--div-cells]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s <db.fa> --query <q.fa> --recover weights.txt [--output prefix] [--chunk 10000] [--no-format] [--sparse] [--sparse-matrix] [--div-cells] [--top N]\n", argv[0]);
 		return 1;
 	}
 	try {
@@ -156,6 +179,8 @@ int main(int argc, char** argv) {
 			if (sparse && qo) qset_p = make_set(queries, qo, std::min(chunk, queries.size() - qo));
 			msc::PointSet& qset = *qset_p;
 			load_chunk(qset, queries, qo, std::min(chunk, queries.size() - qo), qp);
+			std::vector<std::vector<Surv> > best(top ? qp.size() : 0);          // --top: each query's survivors over the database chunks so far
+			size_t n_dchunks = 0;
 			for (size_t d0 = 0; d0 < db.size(); d0 += chunk) {
 				std::vector<Pt> dp;
 				if (sparse && (d0 || qo)) dset_p = make_set(db, d0, std::min(chunk, db.size() - d0));
@@ -165,6 +190,7 @@ int main(int argc, char** argv) {
 				for (auto& p : dp) pts.push_back(&p);
 				std::sort(pts.begin(), pts.end(), [](Pt* a, Pt* b) { return a->length < b->length; });      // FC_Runner.cpp:590-592
 				if (pts.empty()) continue;
+				const size_t dchunk = n_dchunks++;
 				// work() (:426-471) for every query of the chunk. Queries are taken in blocks of `qblock` neighbours in LENGTH order, so
 				// their length windows nearly coincide and one Q x M pass over the union window serves the block; each query then
 				// keeps only its own window, and the lines are written in the reference's order (query order, then window order).
@@ -204,8 +230,11 @@ int main(int argc, char** argv) {
 						std::vector<double> sim;
 						pred.search(dset, window, qset, q_slots[0], close, sim);
 						note_kernel();
+						const size_t before = hits[members[0]].size();
 						for (size_t i = win_start[members[0]]; i < win_end[members[0]]; i++)
 							if (close[i - lo]) hits[members[0]].push_back(Hit{i, sim[i - lo]});
+						num_pred_pos += hits[members[0]].size() - before;
+						cut_top(hits[members[0]], top);
 						continue;
 					}
 					// the block in one pass over the union window, each member's own window given: only its close pairs come back
@@ -213,21 +242,41 @@ int main(int argc, char** argv) {
 					for (size_t j = 0; j < members.size(); j++) { wl[j] = win_start[members[j]] - lo; wh[j] = win_end[members[j]] - lo; }
 					std::vector<uint32_t> idx;
 					std::vector<double> sim;
-					const std::vector<uint64_t> offsets = pred.search_pairs(dset, window, qset, q_slots, wl, wh, idx, sim);
+					std::vector<uint64_t> counts;
+					const std::vector<uint64_t> offsets = top ? pred.search_pairs_top(dset, window, qset, q_slots, wl, wh, (uint32_t)std::min<size_t>(top, 0xffffffffu), idx, sim, &counts)
+					                                          : pred.search_pairs(dset, window, qset, q_slots, wl, wh, idx, sim);
 					note_kernel();
+					for (size_t j = 0; j < members.size(); j++) num_pred_pos += top ? counts[j] : offsets[j + 1] - offsets[j];
 					for (size_t j = 0; j < members.size(); j++)
 						for (uint64_t p = offsets[j]; p < offsets[j + 1]; p++) hits[members[j]].push_back(Hit{lo + idx[p], sim[p]});
+				}
+				if (top) {          // the chunk's survivors behind those of the chunks before, cut again: ties stay with the earlier chunk
+					for (size_t qi = 0; qi < qp.size(); qi++) {
+						for (const Hit& h : hits[qi]) best[qi].push_back(Surv{dchunk, h.cand, h.sim, pts[h.cand]->header});
+						cut_top(best[qi], top);
+					}
+					continue;
 				}
 				for (size_t qi = 0; qi < qp.size(); qi++) {
 					const Pt& query = qp[qi];
 					for (const Hit& h : hits[qi]) {
-						num_pred_pos++;
 						if (h.sim > 0) {
 							if (format) out << format_header(query.header) << delim << format_header(pts[h.cand]->header) << delim << 100 * h.sim << std::endl;
 							else out << query.header << delim << pts[h.cand]->header << delim << 100 * h.sim << std::endl;
 						}
 					}
 				}
+			}
+			if (top) {          // the lines of the query chunk, in the order they have without the flag: database chunk, query, window position
+				std::vector<size_t> at(qp.size(), 0);
+				for (size_t dc = 0; dc < n_dchunks; dc++)
+					for (size_t qi = 0; qi < qp.size(); qi++)
+						for (; at[qi] < best[qi].size() && best[qi][at[qi]].chunk == dc; at[qi]++) {
+							const Surv& h = best[qi][at[qi]];
+							if (!(h.sim > 0)) continue;
+							if (format) out << format_header(qp[qi].header) << delim << format_header(h.header) << delim << 100 * h.sim << std::endl;
+							else out << qp[qi].header << delim << h.header << delim << 100 * h.sim << std::endl;
+						}
 			}
 		}
 		std::cout << "# of predicted positive: " << num_pred_pos << std::endl;
