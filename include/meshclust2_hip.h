@@ -317,6 +317,38 @@ int msc_score_multi(msc_ctx* ctx, const msc_model* model, const msc_hist_set* ca
  * over n_q x m flags). MSC_ERR_UNSUPPORTED when that call took a route that keeps no counts (one pass per query). */
 int msc_last_close_counts(msc_ctx* ctx, uint64_t* counts, uint64_t n_q);
 
+/* An explicit list of n pairs (a_i, b_i) scored in one pass: the shape of the reference's feature table, which walks a
+ * vector<pair<Point*, Point*>> (predict/FeatureSelector.cpp:23-33; the table both trainers start from, predict/Predictor.cpp:876-985), and of
+ * any caller that wants the statistics or the score of chosen pairs (every member to its centre, a model checked on labelled pairs,
+ * candidate pairs of another tool) without one 1 x 1 pass per pair.
+ *   Row i of every output is what msc_pair_features_raw / msc_score give for the single-candidate call (m = 1, same order, same feat_mask /
+ *   model) with candidate = slot a_slots[i] of a_set and query = slot b_slots[i] of b_set; close_out[i] = round(classify_sum) > 0 as in
+ *   msc_score_multi. Rows come back in the caller's order. Repeated pairs, a_set == b_set and a_slots[i] == b_slots[i] are legal.
+ *   a_slots == NULL or b_slots == NULL means slots 0 .. n-1. raw_out is n x popcount(feat_mask), columns in ascending bit order (feat_mask
+ *   is read only with raw_out); singles_out n x n_singles, combos_out n x n_combos, sum_out / csum_out / close_out n. Any output pointer
+ *   may be NULL, model may be NULL when only raw_out is wanted; all outputs NULL is MSC_ERR_INVALID_ARG; n == 0 is MSC_OK.
+ *   Argument checks are those of msc_score: the ctx owns both sets and the model, the sets agree in k, dtype and layout (one dense and one
+ *   sparse set are refused, as by every 1 x M call), slots in range; and the model's k is the sets'. A row for which the reference would
+ *   throw holds NaN and the call returns MSC_ERR_ZERO_LENGTH / MSC_ERR_NAN as msc_score does; the other rows are still filled. There is
+ *   no length window.
+ * Which values share bits with the per-pair calls: every statistic other than jefferey_divergence / jensen_shannon is a closed form of exact
+ * integer reductions and the slots' scalars, evaluated by the one epilogue, so those columns -- and singles / combos / sum / csum / close of
+ * a model that holds no divergence statistic -- are bit-equal to msc_pair_features_raw / msc_score per pair on every route. The two
+ * divergence sums come from the pair-list form of the chunked merge kernel only, so they are bit-equal to the routes DESIGN.md 4.6 lists as
+ * sharing bits (msc_score_multi's raw_out is one of them), whatever the order of the list or the way it is cut into calls; where that
+ * kernel does not apply the call goes query by query through the 1 x M calls, so nothing new is introduced there.
+ * The pairs are grouped by b slot; msc_last_kernel_info names the pass kernel (queries_per_candidate_read = 1): "k_pair_sparse_wl_pairs"
+ * (two sparse sets, or dense sets of histograms >= 64 KiB through their mirrors; 32-bit range; the two sets' longest lists fit a wave's
+ * LDS region together; integer statistics), "k_pair_sparse_mp" (the same with longer lists, or with a divergence statistic),
+ * "k_pair_tiles_batch" (dense sets without a list form, narrow range, no divergence statistic), or -- the wide range, sparse counts >=
+ * 2^16, MSC_FEAT_GROUPS, a divergence statistic the chunked merge kernel would not serve -- one 1 x M call per distinct b slot, reported as
+ * that call's kernel name followed by " per query". */
+int msc_score_pair_list(msc_ctx* ctx, const msc_model* model,
+                        const msc_hist_set* a_set, const uint32_t* a_slots,
+                        const msc_hist_set* b_set, const uint32_t* b_slots, uint64_t n, int order,
+                        uint64_t feat_mask, double* raw_out,
+                        double* singles_out, double* combos_out, double* sum_out, double* csum_out, uint8_t* close_out);
+
 /* ------------------------------------------------------------------ a8/a9: Trainer operators */
 /* Trainer<T>::get_close (cluster/Trainer.cpp:23-71; caller cluster/ClusterFactory.cpp:566).
  * The window [istart, iend) is cand_slots[0..m). Candidates outside floor(len_q*cutoff) <= len <= floor(len_q/cutoff)

@@ -362,6 +362,16 @@ class Feature:
                                               _ptr(singles), _ptr(combos), _ptr(s), _ptr(cs)))
         return dict(singles=singles, combos=combos, sum=s, csum=cs)
 
+    def compute_pairs(self, a_set, a_slots, b_set, b_slots, order=ORDER_CAND_FIRST, n=None):
+        """Feature::compute + operator() for an explicit list of pairs (a_slots[i] of a_set, b_slots[i] of b_set) in one call
+        (msc_score_pair_list) -> (singles [n,n_singles], combos [n,n_combos]), rows in the caller's order"""
+        a, b, n = _pair_slots(a_slots, b_slots, n)
+        singles = np.zeros((n, self.n_singles))
+        combos = np.zeros((n, self.n_combos))
+        self.ctx.check(self.ctx.lib.msc_score_pair_list(self.ctx.h, self.h, a_set.h, _ptr(a), b_set.h, _ptr(b), n, order, 0, None,
+                                                        _ptr(singles), _ptr(combos), None, None, None))
+        return singles, combos
+
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):
             self.ctx.lib.msc_model_destroy(self.h)
@@ -422,6 +432,36 @@ def score_multi(ctx, feat, cands, cand_slots, qset, q_slots, order=ORDER_CAND_FI
         if ctx.lib.msc_last_close_counts(ctx.h, _ptr(counts), nq) != 0:
             counts = np.einsum("ij->i", close, dtype=np.uint64)
     return dict(sum=s, csum=cs, close=close, raw=raw, counts=counts)
+
+
+def _pair_slots(a_slots, b_slots, n=None):
+    """the two slot lists of a pair list (None = slots 0 .. n-1) -> (a, b, n)"""
+    a = None if a_slots is None else np.ascontiguousarray(a_slots, dtype=np.uint32)
+    b = None if b_slots is None else np.ascontiguousarray(b_slots, dtype=np.uint32)
+    if a is not None and b is not None and a.size != b.size:
+        raise ValueError("a_slots and b_slots are one pair list: equal lengths")
+    if a is None and b is None and n is None:
+        raise ValueError("n is needed when both slot lists are None")
+    n = int(n) if a is None and b is None else (a if a is not None else b).size
+    return a, b, n
+
+
+def score_pair_list(ctx, feat, a_set, a_slots, b_set, b_slots, order=ORDER_CAND_FIRST, feat_mask=0, want=("sum", "csum", "close"), n=None):
+    """An explicit list of pairs (a_slots[i] of a_set as the candidate, b_slots[i] of b_set as the query) in one call (msc_score_pair_list):
+    row i = what pair_features_raw / Feature.compute give for that one pair, in the caller's order.
+    -> dict(sum [n], csum [n], close [n], singles [n,n_singles], combos [n,n_combos], raw [n,nf]); what `want` / feat_mask leave out is None"""
+    a, b, n = _pair_slots(a_slots, b_slots, n)
+    nf = bin(feat_mask).count("1")
+    has = feat is not None
+    s = np.zeros(n) if has and "sum" in want else None
+    cs = np.zeros(n) if has and "csum" in want else None
+    close = np.zeros(n, dtype=np.uint8) if has and "close" in want else None
+    singles = np.zeros((n, feat.n_singles)) if has and "singles" in want else None
+    combos = np.zeros((n, feat.n_combos)) if has and "combos" in want else None
+    raw = np.zeros((n, nf)) if nf else None
+    ctx.check(ctx.lib.msc_score_pair_list(ctx.h, feat.h if has else None, a_set.h, _ptr(a), b_set.h, _ptr(b), n, order, feat_mask, _ptr(raw),
+                                          _ptr(singles), _ptr(combos), _ptr(s), _ptr(cs), _ptr(close)))
+    return dict(sum=s, csum=cs, close=close, singles=singles, combos=combos, raw=raw)
 
 
 class Trainer:
@@ -629,6 +669,21 @@ class Predictor:
         self.ctx.check(self.ctx.lib.msc_search(self.ctx.h, self.cls.h if self.cls else None, self.reg.h if self.reg else None, db.h, _ptr(sl), m,
                                                qset.h, q_slot, _ptr(close), _ptr(sim)))
         return close[:m], sim[:m]
+
+    def score_pairs(self, db, a_slots, qset, b_slots, n=None):
+        """search() for an explicit list of pairs (a_slots[i] of db against query b_slots[i] of qset) -> (close [n], sim [n]) with msc_search's
+        rules per pair: no classification block -> close, no regression block -> similarity 1, else clamp(p_predict, 0, 1). One
+        msc_score_pair_list call per model block."""
+        a, b, n = _pair_slots(a_slots, b_slots, n)
+        lib, h = self.ctx.lib, self.ctx.h
+        close = np.ones(n, dtype=np.uint8)
+        sim = np.ones(n)
+        if self.cls is not None:
+            self.ctx.check(lib.msc_score_pair_list(h, self.cls.h, db.h, _ptr(a), qset.h, _ptr(b), n, ORDER_CAND_FIRST, 0, None, None, None, None, None, _ptr(close)))
+        if self.reg is not None:
+            self.ctx.check(lib.msc_score_pair_list(h, self.reg.h, db.h, _ptr(a), qset.h, _ptr(b), n, ORDER_CAND_FIRST, 0, None, None, None, _ptr(sim), None, None))
+            np.clip(sim, 0.0, 1.0, out=sim)          # p_predict clamps to [0,1], predict/Predictor.cpp:293-298
+        return close, sim
 
     def search_pairs(self, db, db_slots, qset, q_slots, win_lo=None, win_hi=None, m=None):
         """work() for every query of q_slots against the candidate list, the CLOSE pairs only (msc_search_pairs). Pair (q, i) is listed when

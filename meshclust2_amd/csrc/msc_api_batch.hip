@@ -213,7 +213,7 @@ static int sparse_means_and_distances(msc_ctx* ctx, const msc_hist_set* pts, con
 // The two divergence sums of a pair list inside the batched entry points: which lists to merge (the sets themselves, or the sparse
 // mirrors of dense sets) -- or nothing (*ok = false: the caller goes centre by centre) when a 1 x M call on these sets would NOT take
 // the chunked merge kernel, because a pair must get the same kernel, hence the same evaluation order, in every route.
-static int batch_div_lists(msc_ctx* ctx, const msc_hist_set* cands, const msc_hist_set* queries, uint64_t any_q_slot, const msc_hist_set** c_sp,
+int batch_div_lists(msc_ctx* ctx, const msc_hist_set* cands, const msc_hist_set* queries, uint64_t any_q_slot, const msc_hist_set** c_sp,
                            const msc_hist_set** q_sp, bool* ok) {
 	*ok = false;
 	int r;
@@ -224,7 +224,7 @@ static int batch_div_lists(msc_ctx* ctx, const msc_hist_set* cands, const msc_hi
 }
 // ... and the pass itself, for P pairs already described by ctx->slots / ctx->segs / ctx->pair_seg: sums -> ctx->div_partials[2 * pair].
 // A sparse pair of sets gets its integer records from the same launch (partials); dense sets have theirs from k_pair_tiles_batch.
-static int batch_div_pass(msc_ctx* ctx, const msc_hist_set* cands, const msc_hist_set* queries, const msc_hist_set* c_sp, const msc_hist_set* q_sp, uint64_t P,
+int batch_div_pass(msc_ctx* ctx, const msc_hist_set* cands, const msc_hist_set* queries, const msc_hist_set* c_sp, const msc_hist_set* q_sp, uint64_t P,
                           int order, MscPartial* partials, uint32_t* div_n) {
 	int r;
 	const uint32_t dvn = msc_sparse_mp_div_records((uint64_t)c_sp->max_nnz + q_sp->max_nnz);      // records per pair (the 1 x M form's granules)

@@ -1,5 +1,5 @@
 // msc_api_private.h -- what the translation units of the C ABI's host side (msc_api.hip: context, sets, builds, models; msc_api_score.hip: the
-// scoring driver and the 1 x M calls; msc_api_multi.hip: msc_score_multi; msc_api_batch.hip: the batched update stage) share beyond
+// scoring driver and the 1 x M calls; msc_api_multi.hip: msc_score_multi; msc_api_batch.hip: the batched update stage; msc_api_pairlist.hip: msc_score_pair_list) share beyond
 // msc_objects.h / msc_internal.h.
 #pragma once
 #include <algorithm>
@@ -42,6 +42,14 @@ hipError_t launch_sparse_pass(msc_ctx* ctx, SparseKernel k, const msc_hist_set* 
                               uint64_t off, uint32_t mc, const msc_hist_set* q_sp, uint64_t q_slot, const uint8_t* q_scal, uint64_t nbins, int use_window,
                               uint64_t min_len, uint64_t max_len, MscPartial* partials, void* div_tables, void* div_partials, int order, uint32_t parts = 1,
                               uint32_t div_stride = 1);
+
+// ---- msc_api_batch.hip (shared with msc_api_pairlist.hip): the two divergence sums of a pair list
+// which lists to merge (the sets themselves, or the sparse mirrors of dense sets); *ok = false when a 1 x M call on these sets would not take the
+// chunked merge kernel -- the caller then goes query by query
+int batch_div_lists(msc_ctx* ctx, const msc_hist_set* cands, const msc_hist_set* queries, uint64_t any_q_slot, const msc_hist_set** c_sp, const msc_hist_set** q_sp, bool* ok);
+// the pass, for P pairs described by ctx->slots / ctx->segs / ctx->pair_seg: sums -> ctx->div_partials[pair][*div_n][2], integer records -> partials
+int batch_div_pass(msc_ctx* ctx, const msc_hist_set* cands, const msc_hist_set* queries, const msc_hist_set* c_sp, const msc_hist_set* q_sp, uint64_t P, int order,
+                   MscPartial* partials, uint32_t* div_n);
 
 // ---- msc_api_multi.hip (shared with msc_api_pairs.hip)
 int ensure_kb(msc_ctx* ctx, const msc_hist_set* set);          // the presence-bit mirror and lists of large bins of a set, from its bins or its lists (set->kb null: unavailable)

@@ -332,6 +332,13 @@ hipError_t msc_launch_pair_sparse_mp_pairs(hipStream_t st, const void* c_ent, co
                                            const MscSparseHdr* q_hdr, uint64_t nbins, int use_window, const MscBatchSeg* segs, const uint32_t* pair_seg,
                                            MscPartial* partials, int order, int num_cus, const uint8_t* q_scalars = nullptr, uint64_t q_scalar_stride = 0,
                                            void* div_tables = nullptr, void* div_partials = nullptr, uint32_t div_stride = 1);
+// the whole-list kernel for a pair list (k_pair_sparse_wl_pairs): the fit rule over the two sets' longest lists, the largest sum of the
+// two it admits, and the launch (integer records only, no window; c_max_nnz / q_max_nnz size a wave's LDS region)
+bool msc_sparse_wl_pairs_fits(uint32_t a_max_nnz, uint32_t b_max_nnz);
+uint32_t msc_sparse_wl_pairs_limit();
+hipError_t msc_launch_pair_sparse_wl_pairs(hipStream_t st, const void* c_ent, const uint32_t* c_cum, const MscSparseHdr* c_hdr, const uint32_t* cand_slots, uint32_t m,
+                                           const void* q_ent, const uint32_t* q_cum, const MscSparseHdr* q_hdr, const MscBatchSeg* segs, const uint32_t* pair_seg,
+                                           uint32_t c_max_nnz, uint32_t q_max_nnz, uint64_t nbins, MscPartial* partials, int num_cus);
 hipError_t msc_launch_sparse_scatter_batch(hipStream_t st, const void* ent, const MscSparseHdr* hdr, const uint32_t* slots, const uint32_t* seg, uint32_t n_members,
                                            uint64_t nbins, uint32_t* acc, uint32_t* touched = nullptr);
 // (m_of == nullptr: one centre of m_one members; touched == nullptr: the sweeps over all bins)

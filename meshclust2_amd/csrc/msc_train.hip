@@ -152,9 +152,17 @@ int build_table(msc_ctx* ctx, const msc_hist_set* pts, const uint32_t* first_slo
 	t.n_test = (size_t)n_test;
 	for (uint64_t f = 1; f <= feat_flags; f <<= 1) if (feat_flags & f) { t.singles.push_back(f); t.is_sim.push_back(msc_feat_is_sim(f)); }
 	const size_t ns = t.singles.size();
-	// ---- raw statistics of every pair: func(*pair.first, *pair.second), one streaming pass per distinct second point
+	// ---- raw statistics of every pair: func(*pair.first, *pair.second). Without a divergence or group statistic on offer (`--feat fast`): the
+	// whole list in ONE msc_score_pair_list call -- bit-equal to the per-pair calls, so the weights files do not move; otherwise one streaming
+	// pass per distinct second point
 	std::vector<std::vector<double> > raw(n, std::vector<double>(ns));
-	{
+	if (n && !(feat_flags & (MSC_FEAT_DIV | MSC_FEAT_GROUPS))) {
+		std::vector<double> out(n * ns, 0.0);
+		const int r = msc_score_pair_list(ctx, nullptr, pts, first_slots, pts, second_slots, n, MSC_ORDER_CAND_FIRST, feat_flags, out.data(), nullptr, nullptr, nullptr, nullptr,
+		                                  nullptr);
+		if (r) return r;
+		for (size_t i = 0; i < n; i++) for (size_t s = 0; s < ns; s++) raw[i][s] = out[i * ns + s];
+	} else {
 		std::map<uint32_t, std::vector<size_t> > by_second;
 		for (size_t i = 0; i < n; i++) by_second[second_slots[i]].push_back(i);
 		std::vector<uint32_t> cands;

@@ -1179,6 +1179,103 @@ __global__ void __launch_bounds__(256) k_pair_sparse_wl(
 	}
 }
 
+// The same walk for an explicit PAIR LIST (msc_score_pair_list): pair c = candidate slot cand_slots[c] against query slot
+// segs[pair_seg[c]].q_slot (the addressing of k_pair_sparse_mp's PAIRS form), so no list is shared by a workgroup -- a wave stages
+// BOTH lists of its pair into its own region [candidate: c_cap + 2][query: q_cap + 2] (entry 0 the neutral predecessor, entry n + 1 the
+// end marker) and then walks exactly as above. c_cap / q_cap = the longest list of either set (msc_sparse_wl_pairs_fits). No window, no
+// divergence form, no shared state: after set-up a wave meets no other wave, and one without a pair leaves the loop. `order` does not
+// enter: the three reductions are symmetric (it belongs to the epilogue, as in k_pair_sparse_mp<false, ..., PAIRS>).
+__global__ void __launch_bounds__(256) k_pair_sparse_wl_pairs(
+    const uint2* __restrict__ c_ent, const uint32_t* __restrict__ c_cum, const MscSparseHdr* __restrict__ c_hdr, const uint32_t* __restrict__ cand_slots, uint32_t m,
+    const uint2* __restrict__ q_ent, const uint32_t* __restrict__ q_cum, const MscSparseHdr* __restrict__ q_hdr, const MscBatchSeg* __restrict__ segs,
+    const uint32_t* __restrict__ pair_seg, uint32_t c_cap, uint32_t q_cap, uint64_t nbins, MscPartial* __restrict__ partials) {
+	extern __shared__ __attribute__((aligned(16))) uint2 s_wlp[];
+	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const uint32_t kInf = 0xffffffffu;
+	uint2* cl = s_wlp + (size_t)wave * (c_cap + q_cap + 4);      // cl[0] predecessor, cl[1 + i] = P[i], cl[nc + 1] marker
+	uint2* ql = cl + (c_cap + 2);                                // ql likewise
+	auto heads = [](uint32_t pa, uint32_t pb, uint2& a, uint2& b) {       // one ds_read_b64 per head (see k_pair_sparse_mp)
+		uint64_t wa, wb;
+		asm volatile("ds_read_b64 %0, %2\n\tds_read_b64 %1, %3\n\ts_waitcnt lgkmcnt(0)" : "=&v"(wa), "=&v"(wb) : "v"(pa), "v"(pb) : "memory");
+		a = make_uint2((uint32_t)wa, (uint32_t)(wa >> 32));
+		b = make_uint2((uint32_t)wb, (uint32_t)(wb >> 32));
+	};
+	auto stage = [&](const uint2* __restrict__ src, uint32_t n, uint2* dst) {      // four loads in flight per lane
+		for (uint32_t k0 = lane; k0 < n; k0 += 256) {
+			uint2 v[4];
+#pragma unroll
+			for (uint32_t u = 0; u < 4; u++) v[u] = k0 + 64 * u < n ? src[k0 + 64 * u] : make_uint2(kInf, 1u);
+#pragma unroll
+			for (uint32_t u = 0; u < 4; u++) if (k0 + 64 * u < n) dst[1 + k0 + 64 * u] = v[u];
+		}
+		if (lane == 0) { dst[0] = make_uint2(0u, 1u); dst[n + 1] = make_uint2(kInf, 1u); }
+	};
+	const uint32_t total_waves = gridDim.x * 4;
+	for (uint32_t c = blockIdx.x * 4 + wave; c < m; c += total_waves) {
+		const MscSparseHdr ch = c_hdr[cand_slots ? cand_slots[c] : c];
+		const MscSparseHdr qh = q_hdr[segs[pair_seg[c]].q_slot];
+		const uint2* P = c_ent + ch.off;
+		const uint32_t* CP = c_cum + ch.off;
+		const uint2* Q = q_ent + qh.off;
+		const uint32_t* CQ = q_cum + qh.off;
+		const uint32_t nc = ch.nnz, nq = qh.nnz;
+		__builtin_amdgcn_wave_barrier();                       // every lane is done with the previous pair's entries
+		stage(P, nc, cl);
+		stage(Q, nq, ql);
+		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+		__builtin_amdgcn_wave_barrier();
+		const uint32_t n = nc + nq, seg = ((n + 63) >> 6) | 1u;             // odd share length: the lanes' heads spread over the LDS banks
+		uint32_t i, j;
+		{
+			const uint32_t d = lane * seg < n ? lane * seg : n;
+			mp_split(d, nc, nq, [&](uint32_t a) { return cl[a + 1].x; }, [&](uint32_t b) { return ql[b + 1].x; }, i, j);
+		}
+		// prefix difference entering the share: the stored inclusive sums of the excess counts before it
+		const uint32_t d_in = (i ? CP[i - 1] : 0u) - (j ? CQ[j - 1] : 0u);
+		uint32_t pa = (uint32_t)(uintptr_t)(cl + i + 1), pb = (uint32_t)(uintptr_t)(ql + j + 1);
+		uint2 a, b;
+		heads(pa, pb, a, b);
+		uint32_t e = a.x < b.x ? a.x : b.x;
+		uint32_t e_end = __shfl_down(e, 1, 64);
+		if (lane == 63) e_end = kInf;
+		uint32_t manh = 0;
+		uint64_t dotx = 0, emd = 0;
+		{
+			const uint32_t pc = cl[i].x, pq = ql[j].x;                         // predecessors (the neutral entries have bin 0)
+			uint32_t pos = pc > pq ? pc : pq;
+			int32_t D = (int32_t)d_in;
+			uint32_t events = 0;
+			while (e < e_end) {
+				const bool ta = a.x == e, tb = b.x == e;
+				const uint32_t absD = (uint32_t)(D < 0 ? -D : D);
+				emd += (uint64_t)absD * (e - pos);
+				const uint32_t pv = ta ? a.y : 1u, qv = tb ? b.y : 1u;
+				manh += pv > qv ? pv - qv : qv - pv;
+				dotx += (uint64_t)pv * qv;
+				events++;
+				D += (int32_t)pv - (int32_t)qv;
+				pos = e;
+				pa += ta ? 8u : 0u;
+				pb += tb ? 8u : 0u;
+				heads(pa, pb, a, b);
+				e = a.x < b.x ? a.x : b.x;
+			}
+			dotx -= events;
+		}
+		if (lane == 0) {      // the stretch behind the last event of either list
+			const uint32_t lc = cl[nc].x, lq = ql[nq].x;                       // (bin 0 of the neutral entry when a list is empty)
+			const int64_t D = (int64_t)(nc ? CP[nc - 1] : 0u) - (int64_t)(nq ? CQ[nq - 1] : 0u);
+			emd += (uint64_t)(D < 0 ? -D : D) * (nbins - (uint64_t)(lc > lq ? lc : lq));
+		}
+		const uint64_t manh_t = wave_sum_u64(manh), dot_t = wave_sum_u64(dotx), emd_t = wave_sum_u64(emd);
+		if (lane == 0) {
+			MscPartial out;
+			out.manh = manh_t; out.dot = dot_t; out.emd = emd_t;
+			partials[c] = out;
+		}
+	}
+}
+
 // ================================================================================================ launchers
 hipError_t msc_launch_sparse_count(hipStream_t st, const void* scratch_bins, const MscLayout& L, int dtype, uint32_t n, uint64_t* counts) {
 	if (n == 0) return hipSuccess;
@@ -1371,6 +1468,32 @@ hipError_t msc_launch_pair_sparse_mp(hipStream_t st, const void* c_ent, const ui
 bool msc_sparse_wl_fits(uint32_t q_nnz, uint32_t c_max_nnz) {
 	static const bool no_wl = getenv("MSC_SPARSE_NO_WL") != nullptr;
 	return !no_wl && c_max_nnz && (uint64_t)q_nnz + 4ull * c_max_nnz + 10 <= 8192;
+}
+// ... and the pair-list form: four waves per workgroup, each with both lists of its pair (and their two predecessor and two marker
+// entries) in LDS. 1 024 entries per wave = 32 KiB per workgroup, four to five workgroups per CU. With 2 048 entries (the 64 KiB a
+// launch may ask for without raising the limit: two 1 kb sequences at k = 9) two workgroups fit a CU, and 10^6 pairs of 1 kb lists took
+// 4.95 ms here against 4.15 ms in the chunked kernel, which keeps 8 waves per SIMD; at 450 bases the order is 1.57 ms against 2.46 ms
+// (profiles/pair_list.md, case b): 1 kb lists stay with the chunked kernel. A function of the two sets' longest lists only, never of
+// the pairs of a call; the records are exact integers, so the rule decides speed, never values. tests/pair_list_check.py reads this
+// constant (LIMIT), and test_fit_boundary in tests/test_gpu_pair_list.py holds the routing to it on both sides: keep the line's form.
+constexpr uint32_t kWlPairsEntries = 1024;
+uint32_t msc_sparse_wl_pairs_limit() { return kWlPairsEntries - 4; }
+bool msc_sparse_wl_pairs_fits(uint32_t a_max_nnz, uint32_t b_max_nnz) {
+	static const bool no_wl = getenv("MSC_SPARSE_NO_WL") != nullptr;
+	return !no_wl && (uint64_t)a_max_nnz + b_max_nnz + 4 <= kWlPairsEntries;
+}
+hipError_t msc_launch_pair_sparse_wl_pairs(hipStream_t st, const void* c_ent, const uint32_t* c_cum, const MscSparseHdr* c_hdr, const uint32_t* cand_slots, uint32_t m,
+                                           const void* q_ent, const uint32_t* q_cum, const MscSparseHdr* q_hdr, const MscBatchSeg* segs, const uint32_t* pair_seg,
+                                           uint32_t c_max_nnz, uint32_t q_max_nnz, uint64_t nbins, MscPartial* partials, int num_cus) {
+	if (m == 0) return hipSuccess;
+	if (!segs || !pair_seg || (uint64_t)c_max_nnz + q_max_nnz + 4 > kWlPairsEntries) return hipErrorInvalidValue;
+	const size_t lds = 4 * ((size_t)c_max_nnz + q_max_nnz + 4) * sizeof(uint2);
+	const uint32_t blocks_per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / (lds + 256)));
+	uint32_t blocks = (uint32_t)num_cus * blocks_per_cu;
+	if (blocks > (m + 3) / 4) blocks = (m + 3) / 4;
+	k_pair_sparse_wl_pairs<<<dim3(blocks), dim3(256), lds, st>>>((const uint2*)c_ent, c_cum, c_hdr, cand_slots, m, (const uint2*)q_ent, q_cum, q_hdr, segs, pair_seg, c_max_nnz,
+	                                                           q_max_nnz, nbins, partials);
+	return hipGetLastError();
 }
 uint32_t msc_sparse_mp_parts(uint32_t m, uint64_t entries, int num_cus, bool div) {
 	static const bool off = getenv("MSC_SPARSE_MP_NO_PARTS") != nullptr;

@@ -128,6 +128,18 @@ public:
 		                     combos ? combos->data() : nullptr, sums ? sums->data() : nullptr, nullptr));
 		return singles;
 	}
+	// the same for an explicit list of pairs (a_slots[i] of a, b_slots[i] of b) in one call (msc_score_pair_list; the reference's table walks
+	// a vector<pair<Point*, Point*>>, predict/FeatureSelector.cpp:23-33): rows of normalised singles in the caller's order
+	std::vector<double> compute_pairs(const PointSet& a, const std::vector<uint32_t>& a_slots, const PointSet& b, const std::vector<uint32_t>& b_slots,
+	                                  int order = MSC_ORDER_CAND_FIRST, std::vector<double>* combos = nullptr, std::vector<double>* sums = nullptr) const {
+		if (a_slots.size() != b_slots.size()) throw Error(MSC_ERR_INVALID_ARG, "compute_pairs: the two slot lists are one pair list");
+		std::vector<double> singles(a_slots.size() * (size_t)n_singles());
+		if (combos) combos->resize(a_slots.size() * size());
+		if (sums) sums->resize(a_slots.size());
+		ctx_.check(msc_score_pair_list(ctx_.get(), h_, a.get(), a_slots.data(), b.get(), b_slots.data(), a_slots.size(), order, 0, nullptr, singles.data(),
+		                               combos ? combos->data() : nullptr, sums ? sums->data() : nullptr, nullptr, nullptr));
+		return singles;
+	}
 private:
 	Context& ctx_;
 	msc_model* h_ = nullptr;
@@ -201,6 +213,24 @@ public:
 		similarity.resize(slots.size());
 		ctx_.check(msc_search(ctx_.get(), cls_ ? cls_->get() : nullptr, reg_ ? reg_->get() : nullptr, db.get(), slots.data(), slots.size(), q.get(), q_slot,
 		                      close.data(), similarity.data()));
+	}
+	// search() for an explicit list of pairs (a_slots[i] of db against query b_slots[i] of q): msc_search's rules per pair, one
+	// msc_score_pair_list call per block of the weights file
+	void score_pairs(const PointSet& db, const std::vector<uint32_t>& a_slots, const PointSet& q, const std::vector<uint32_t>& b_slots, std::vector<uint8_t>& close,
+	                 std::vector<double>& similarity) const {
+		if (a_slots.size() != b_slots.size()) throw Error(MSC_ERR_INVALID_ARG, "score_pairs: the two slot lists are one pair list");
+		const size_t n = a_slots.size();
+		close.assign(n, 1);
+		similarity.assign(n, 1.0);
+		if (n == 0) return;
+		if (cls_)
+			ctx_.check(msc_score_pair_list(ctx_.get(), cls_->get(), db.get(), a_slots.data(), q.get(), b_slots.data(), n, MSC_ORDER_CAND_FIRST, 0, nullptr, nullptr, nullptr,
+			                               nullptr, nullptr, close.data()));
+		if (reg_) {
+			ctx_.check(msc_score_pair_list(ctx_.get(), reg_->get(), db.get(), a_slots.data(), q.get(), b_slots.data(), n, MSC_ORDER_CAND_FIRST, 0, nullptr, nullptr, nullptr,
+			                               similarity.data(), nullptr, nullptr));
+			for (double& v : similarity) v = v < 0 ? 0 : (v > 1 ? 1 : v);      // p_predict clamps to [0,1], predict/Predictor.cpp:293-298
+		}
 	}
 	// the same for a block of queries in ONE pass over the database window (msc_score_multi: each candidate tile fetched from HBM
 	// serves 16 queries): close[q * slots.size() + i], similarity likewise. Values are bit-identical to search() per query.
