@@ -101,16 +101,14 @@ extern "C" int msc_create(int device, msc_ctx** out) {
 	ctx->device = device;
 	ctx->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
 	snprintf(ctx->dev_name, sizeof ctx->dev_name, "%s (%s, %d CUs)", prop.name, prop.gcnArchName, ctx->num_cus);
-	if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&ctx->ev_tiles0) != hipSuccess ||
-	    hipEventCreate(&ctx->ev_tiles1) != hipSuccess || hipEventCreate(&ctx->ev_all0) != hipSuccess || hipEventCreate(&ctx->ev_all1) != hipSuccess ||
-	    hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&ctx->tail_stream, hipStreamNonBlocking) != hipSuccess ||
-	    hipEventCreateWithFlags(&ctx->ev_head[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_head[1], hipEventDisableTiming) != hipSuccess ||
-	    hipEventCreateWithFlags(&ctx->ev_product[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_product[1], hipEventDisableTiming) != hipSuccess ||
-	    hipEventCreateWithFlags(&ctx->ev_tail[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_tail[1], hipEventDisableTiming) != hipSuccess ||
-	    hipEventCreateWithFlags(&ctx->ev_scored[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_scored[1], hipEventDisableTiming) != hipSuccess ||
-	    hipEventCreateWithFlags(&ctx->ev_copied[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_copied[1], hipEventDisableTiming) != hipSuccess ||
-	    hipStreamCreateWithFlags(&ctx->prep_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_call, hipEventDisableTiming) != hipSuccess ||
-	    hipEventCreateWithFlags(&ctx->ev_prep[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_prep[1], hipEventDisableTiming) != hipSuccess) {
+	BlockPipe& pipe = ctx->pipe;
+	bool ok = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) == hipSuccess;
+	for (hipEvent_t* e : {&ctx->ev_tiles0, &ctx->ev_tiles1, &ctx->ev_all0, &ctx->ev_all1}) ok = ok && hipEventCreate(e) == hipSuccess;
+	for (hipStream_t* s : {&pipe.copy_stream, &pipe.tail_stream, &pipe.prep_stream}) ok = ok && hipStreamCreateWithFlags(s, hipStreamNonBlocking) == hipSuccess;
+	for (int i = 0; i < 2; i++)
+		for (hipEvent_t* e : {&pipe.side[i].ev_head, &pipe.side[i].ev_product, &pipe.side[i].ev_tail, &pipe.side[i].ev_prep, &pipe.ev_scored[i], &pipe.ev_copied[i]})
+			ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+	if (!ok || hipEventCreateWithFlags(&pipe.ev_call, hipEventDisableTiming) != hipSuccess) {
 		delete ctx;
 		return fail(nullptr, MSC_ERR_HIP, "msc_create: stream/event creation failed");
 	}
@@ -124,9 +122,8 @@ extern "C" void msc_destroy(msc_ctx* ctx) {
 	if (!ctx) return;
 	(void)hipSetDevice(ctx->device);
 	(void)hipStreamSynchronize(ctx->stream);
-	(void)hipStreamSynchronize(ctx->copy_stream);
-	(void)hipStreamSynchronize(ctx->tail_stream);          // (nothing may still be running on any of the context's streams when its buffers go)
-	(void)hipStreamSynchronize(ctx->prep_stream);
+	BlockPipe& pipe = ctx->pipe;
+	for (hipStream_t s : {pipe.copy_stream, pipe.tail_stream, pipe.prep_stream}) (void)hipStreamSynchronize(s);          // (nothing may still be running on any of the context's streams when its buffers go)
 	if (g_profile_calls && ctx->prof_calls && ctx->prof_wait > 0) {
 		fprintf(stderr, "[msc] 1 x M scoring calls: %llu (%llu candidates) | slot list %.3f s, launches %.3f s, stream wait %.3f s\n", (unsigned long long)ctx->prof_calls,
 		        (unsigned long long)ctx->prof_cands, ctx->prof_prep, ctx->prof_issue, ctx->prof_wait);
@@ -144,87 +141,28 @@ extern "C" void msc_destroy(msc_ctx* ctx) {
 			}
 		}
 	}
-	if (ctx->scratch_set) msc_hist_set_destroy(ctx->scratch_set);
-	if (ctx->sparse_scratch) msc_hist_set_destroy(ctx->sparse_scratch);
-	if (ctx->sparse_mean_set) msc_hist_set_destroy(ctx->sparse_mean_set);
-	if (ctx->sparse_mean_batch) msc_hist_set_destroy(ctx->sparse_mean_batch);
-	if (ctx->batch_scratch) msc_hist_set_destroy(ctx->batch_scratch);
-	if (ctx->shard_gather) msc_hist_set_destroy(ctx->shard_gather);
-	release(ctx->shard_payload);
-	release(ctx->shard_hdrs);
-	release(ctx->kb_anib);
-	release(ctx->rk_q);
-	release(ctx->rk_acc);
-	release(ctx->rk_counters);
-	release(ctx->rk_tables);
-	release(ctx->rk_items);
-	release(ctx->rk_big);
-	release(ctx->kb_qT);
-	release(ctx->pl_idx);
-	release(ctx->pl_sim);
-	release(ctx->pl_stage_idx);
-	release(ctx->pl_stage_sim);
-	release(ctx->pl_flags);
-	release(ctx->pl_counts);
-	release(ctx->pl_offsets);
-	release(ctx->pl_seg);
-	release(ctx->pl_dst);
-	release(ctx->pl_qslots);
-	release(ctx->pl_win);
-	release(ctx->pl_qcount);
-	release(ctx->pl_words);
-	if (ctx->pl_pin.p) (void)hipHostFree(ctx->pl_pin.p);
-	release(ctx->kb_hot);
-	release(ctx->kb_hot_idx);
-	release(ctx->kb_min);
-	release(ctx->kb_diff);
-	release(ctx->emd_out);
-	release(ctx->close_counts);
-	release(ctx->rk_bad);
-	release(ctx->prof_nnz);
-	if (ctx->rk_guard) (void)hipHostFree(ctx->rk_guard);
-	if (ctx->pin_up.p) (void)hipHostFree(ctx->pin_up.p);
-	if (ctx->pin_down.p) (void)hipHostFree(ctx->pin_down.p);
-	if (ctx->pin_parts.p) (void)hipHostFree(ctx->pin_parts.p);
-	if (ctx->pin_mean.p) (void)hipHostFree(ctx->pin_mean.p);
-	release(ctx->segs);
-	release(ctx->pair_seg);
-	release(ctx->dist);
-	release(ctx->sp_counts);
-	release(ctx->sp_cumbase);
-	release(ctx->sp_acc);
-	release(ctx->sp_chunk_off);
-	release(ctx->sp_chunk_cum);
-	release(ctx->sp_partials);
-	release(ctx->grp_pairs);
-	release(ctx->grp_self);
-	release(ctx->tile_scratch);
-	release(ctx->reduce_parts);
-	release(ctx->sp_touched);
-	release(ctx->sp_acc_batch);
-	DevBuf* bufs[] = {&ctx->partials, &ctx->pair_out, &ctx->flags, &ctx->reduce_out, &ctx->slots, &ctx->raw, &ctx->singles, &ctx->combos,
-	                  &ctx->packed, &ctx->seg_seq, &ctx->seg_start, &ctx->kmer_off, &ctx->nat, &ctx->model_tmp, &ctx->floor_sum, &ctx->mean,
-	                  &ctx->div_tables, &ctx->div_partials, &ctx->qslots, &ctx->soa_sum, &ctx->soa_csum, &ctx->soa_close,
-	                  &ctx->err_word, &ctx->seq_seg, &ctx->seq_ids, &ctx->seq_meta, &ctx->qslots_all};
+	for (msc_hist_set* s : {ctx->scratch_set, ctx->sparse_scratch, ctx->sparse_mean_set, ctx->sparse_mean_batch, ctx->batch_scratch, ctx->shard_gather})
+		if (s) msc_hist_set_destroy(s);
+	for (void* pinned : {ctx->pl_pin.p, (void*)ctx->rk_guard, ctx->pin_up.p, ctx->pin_down.p, ctx->pin_parts.p, ctx->pin_mean.p})
+		if (pinned) (void)hipHostFree(pinned);
+	DevBuf* bufs[] = {&ctx->partials, &ctx->pair_out, &ctx->flags, &ctx->reduce_out, &ctx->slots, &ctx->raw, &ctx->singles, &ctx->combos, &ctx->packed,
+	                  &ctx->seg_seq, &ctx->seg_start, &ctx->kmer_off, &ctx->nat, &ctx->model_tmp, &ctx->floor_sum, &ctx->mean, &ctx->div_tables,
+	                  &ctx->div_partials, &ctx->qslots, &ctx->soa_sum, &ctx->soa_csum, &ctx->soa_close, &ctx->err_word, &ctx->seq_seg, &ctx->seq_ids,
+	                  &ctx->seq_meta, &ctx->qslots_all, &ctx->shard_payload, &ctx->shard_hdrs, &ctx->rk_q, &ctx->rk_acc, &ctx->rk_counters,
+	                  &ctx->rk_tables, &ctx->rk_items, &ctx->rk_big, &ctx->pl_idx, &ctx->pl_sim, &ctx->pl_stage_idx, &ctx->pl_stage_sim, &ctx->pl_flags,
+	                  &ctx->pl_counts, &ctx->pl_offsets, &ctx->pl_seg, &ctx->pl_dst, &ctx->pl_qslots, &ctx->pl_win, &ctx->pl_qcount, &ctx->pl_words,
+	                  &ctx->emd_out, &ctx->close_counts, &ctx->rk_bad, &ctx->prof_nnz, &ctx->segs, &ctx->pair_seg, &ctx->dist, &ctx->sp_counts,
+	                  &ctx->sp_cumbase, &ctx->sp_acc, &ctx->sp_chunk_off, &ctx->sp_chunk_cum, &ctx->sp_partials, &ctx->grp_pairs, &ctx->grp_self,
+	                  &ctx->tile_scratch, &ctx->reduce_parts, &ctx->sp_touched, &ctx->sp_acc_batch};
 	for (DevBuf* b : bufs) release(*b);
-	for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
-	(void)hipEventDestroy(ctx->ev_tiles0);
-	(void)hipEventDestroy(ctx->ev_tiles1);
-	(void)hipEventDestroy(ctx->ev_all0);
-	(void)hipEventDestroy(ctx->ev_all1);
-	for (int i = 0; i < 2; i++) { release(ctx->close_pp[i]); (void)hipEventDestroy(ctx->ev_scored[i]); (void)hipEventDestroy(ctx->ev_copied[i]); }
-	(void)hipStreamDestroy(ctx->copy_stream);
-	release(ctx->kb_qT2);
-	release(ctx->kb_min2);
-	release(ctx->kb_diff2);
-	release(ctx->kb_anib2);
-	release(ctx->kb_hot2);
-	release(ctx->kb_hot_idx2);
-	(void)hipEventDestroy(ctx->ev_call);
-	for (int i = 0; i < 2; i++) (void)hipEventDestroy(ctx->ev_prep[i]);
-	(void)hipStreamDestroy(ctx->prep_stream);
-	for (int i = 0; i < 2; i++) { (void)hipEventDestroy(ctx->ev_head[i]); (void)hipEventDestroy(ctx->ev_product[i]); (void)hipEventDestroy(ctx->ev_tail[i]); }
-	(void)hipStreamDestroy(ctx->tail_stream);
+	for (hipEvent_t e : pipe.ev_pool) (void)hipEventDestroy(e);
+	for (hipEvent_t e : {ctx->ev_tiles0, ctx->ev_tiles1, ctx->ev_all0, ctx->ev_all1, pipe.ev_call}) (void)hipEventDestroy(e);
+	for (int i = 0; i < 2; i++) {
+		BlockPipe::Side& sd = pipe.side[i];
+		for (DevBuf* b : {&sd.qT, &sd.min, &sd.diff, &sd.anib, &sd.hot, &sd.hot_idx, &pipe.close_pp[i]}) release(*b);
+		for (hipEvent_t e : {sd.ev_head, sd.ev_product, sd.ev_tail, sd.ev_prep, pipe.ev_scored[i], pipe.ev_copied[i]}) (void)hipEventDestroy(e);
+	}
+	for (hipStream_t s : {pipe.copy_stream, pipe.tail_stream, pipe.prep_stream}) (void)hipStreamDestroy(s);
 	(void)hipStreamDestroy(ctx->stream);
 	delete ctx;
 }
@@ -549,23 +487,10 @@ extern "C" int msc_hist_set_build_info(const msc_hist_set* s, char* builder, siz
 // every writer of slots ends here: the mirrors the set has (dense: digest, sparse lists, presence bits, ranks; sparse: presence bits,
 // ranks) are stale for [first, first + n)
 static void mark_stale(msc_hist_set* s, uint64_t first, uint64_t n) {
-	if (n == 0) return;
-	if (s->digest) {
-		if (s->dg_lo >= s->dg_hi) { s->dg_lo = first; s->dg_hi = first + n; }
-		else { s->dg_lo = std::min(s->dg_lo, first); s->dg_hi = std::max(s->dg_hi, first + n); }
-	}
-	if (s->sp_mirror) {
-		if (s->sm_lo >= s->sm_hi) { s->sm_lo = first; s->sm_hi = first + n; }
-		else { s->sm_lo = std::min(s->sm_lo, first); s->sm_hi = std::max(s->sm_hi, first + n); }
-	}
-	if (s->kb) {
-		if (s->kb_lo >= s->kb_hi) { s->kb_lo = first; s->kb_hi = first + n; }
-		else { s->kb_lo = std::min(s->kb_lo, first); s->kb_hi = std::max(s->kb_hi, first + n); }
-	}
-	if (s->ranks) {
-		if (s->rk_lo >= s->rk_hi) { s->rk_lo = first; s->rk_hi = first + n; }
-		else { s->rk_lo = std::min(s->rk_lo, first); s->rk_hi = std::max(s->rk_hi, first + n); }
-	}
+	if (s->digest) s->dg_stale.add(first, n);
+	if (s->sp_mirror) s->sm_stale.add(first, n);
+	if (s->kb) s->kb_stale.add(first, n);
+	if (s->ranks) s->rk_stale.add(first, n);
 }
 
 static void forget_lengths(const msc_hist_set* s, uint64_t first, uint64_t n) {
@@ -666,30 +591,20 @@ int ensure_sparse_mirror(msc_ctx* ctx, const msc_hist_set* set, const msc_hist_s
 	static const bool disabled = getenv("MSC_NO_SPARSE_MIRROR") != nullptr;
 	if (set->sparse) { *out = set; return MSC_OK; }
 	if (disabled || set->sp_mirror_unavailable || set->L.S % MSC_SPARSE_SUB != 0 || set->k > 15 || set->written.empty()) return MSC_OK;
-	// runs of written slots inside [lo, hi)
-	auto runs_of = [&](uint64_t lo, uint64_t hi) {
-		std::vector<std::pair<uint64_t, uint64_t> > runs;
-		for (uint64_t i = lo; i < hi;) {
-			if (!set->written[i]) { i++; continue; }
-			uint64_t j = i;
-			while (j < hi && set->written[j]) j++;
-			runs.emplace_back(i, j - i);
-			i = j;
-		}
-		return runs;
-	};
+	auto written = [&](uint64_t i) { return set->written[i] != 0; };
 	int r;
 	for (int attempt = 0; attempt < 2; attempt++) {
-		uint64_t lo = set->sm_lo, hi = set->sm_hi;
+		uint64_t lo = set->sm_stale.lo, hi = set->sm_stale.hi;
 		if (!set->sp_mirror) { lo = 0; hi = set->capacity; }
 		if (lo >= hi) break;
-		const auto runs = runs_of(lo, hi);
 		uint64_t need = 0;
-		for (const auto& run : runs) {
-			uint64_t nr = 0;
-			if ((r = sparsify_slots(ctx, set, run.first, nullptr, 0, run.second, &nr))) return r;
-			need += nr;
-		}
+		if ((r = for_each_run(lo, hi, written, [&](uint64_t first, uint64_t n) {
+			     uint64_t nr = 0;
+			     const int e = sparsify_slots(ctx, set, first, nullptr, 0, n, &nr);
+			     need += nr;
+			     return e;
+		     })))
+			return r;
 		if (set->sp_mirror && set->sp_mirror->ent_used + need > set->sp_mirror->ent_capacity) {
 			// arena full (slots rewritten many times leave their old entries behind): start over, compactly
 			msc_hist_set_destroy(set->sp_mirror);
@@ -702,9 +617,8 @@ int ensure_sparse_mirror(msc_ctx* ctx, const msc_hist_set* set, const msc_hist_s
 			if (msc_hist_set_create_sparse(ctx, set->k, set->dtype, set->capacity, arena, &m) != MSC_OK) { set->sp_mirror_unavailable = true; return MSC_OK; }
 			set->sp_mirror = m;
 		}
-		for (const auto& run : runs)
-			if ((r = sparsify_slots(ctx, set, run.first, set->sp_mirror, run.first, run.second, nullptr))) return r;
-		set->sm_lo = set->sm_hi = 0;
+		if ((r = for_each_run(lo, hi, written, [&](uint64_t first, uint64_t n) { return sparsify_slots(ctx, set, first, set->sp_mirror, first, n, nullptr); }))) return r;
+		set->sm_stale.clear();
 		break;
 	}
 	set->sp_mirror->max_count = set->max_count;

@@ -1,19 +1,9 @@
 // msc_api_multi.hip -- msc_score_multi, the Q x M all-pairs call (fastcar's loop, fastcar/FC_Runner.cpp:426-471): the mirrors of a dense set it
 // reads (digest, presence bits, ranks), the routes, the block pipe over three streams. Split from msc_api.hip in r05.
 #include <algorithm>
-#include <cctype>
-#include <cfloat>
-#include <chrono>
-#include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <fstream>
-#include <functional>
-#include <sstream>
-#include <string>
-#include <thread>
 #include <vector>
 
 #include "msc_internal.h"
@@ -33,12 +23,11 @@ static int ensure_digest(msc_ctx* ctx, const msc_hist_set* set) {
 			return MSC_OK;
 		}
 		set->digest = (uint8_t*)p;
-		set->dg_lo = 0;
-		set->dg_hi = set->capacity;
+		set->dg_stale.all(set->capacity);
 	}
-	if (set->dg_lo < set->dg_hi) {
-		HIP_TRY(ctx, msc_launch_digest_build(ctx->stream, set->L, set->bins, set->scalars, set->digest, set->dg_lo, set->dg_hi - set->dg_lo));
-		set->dg_lo = set->dg_hi = 0;
+	if (set->dg_stale.any()) {
+		HIP_TRY(ctx, msc_launch_digest_build(ctx->stream, set->L, set->bins, set->scalars, set->digest, set->dg_stale.lo, set->dg_stale.hi - set->dg_stale.lo));
+		set->dg_stale.clear();
 	}
 	return MSC_OK;
 }
@@ -69,33 +58,29 @@ int ensure_kb(msc_ctx* ctx, const msc_hist_set* set) {
 		set->mb_n = (uint32_t*)pn;
 		HIP_TRY(ctx, hipMemsetAsync(set->mb_n, 0, (size_t)set->capacity * 4, ctx->stream));
 		set->mb_n_host.assign(set->capacity, 0);
-		set->kb_lo = 0;
-		set->kb_hi = set->capacity;
+		set->kb_stale.all(set->capacity);
 	}
-	while (set->kb_lo < set->kb_hi) {
+	auto written = [&](uint64_t i) { return set->written[i] != 0; };
+	while (set->kb_stale.any()) {
 		// runs of slots that hold a histogram; the build reports a zero count (sticky: the pass's identities take count - 1 of every
 		// bin) and the longest list of large bins it met: past the pitch, the lists are laid out again and every written slot rebuilt
 		int r;
 		if ((r = ensure(ctx, ctx->rk_bad, 2 * sizeof(int32_t)))) return r;
 		HIP_TRY(ctx, hipMemsetAsync(ctx->rk_bad.p, 0, 2 * sizeof(int32_t), ctx->stream));
-		const uint64_t lo = set->kb_lo, hi = std::min<uint64_t>(set->kb_hi, set->sparse ? set->capacity : set->written.size());
+		const uint64_t lo = set->kb_stale.lo, hi = std::min<uint64_t>(set->kb_stale.hi, set->sparse ? set->capacity : set->written.size());
 		if (set->sparse) {          // every slot of the range: one without a list gets an all-zero image and an empty list
 			if (hi > lo) HIP_TRY(ctx, msc_launch_kb_build_sparse(ctx->stream, set->L, set->ent, set->hdr, set->kb, lo, hi - lo, set->mb, set->mb_n, set->mb_pitch, (int32_t*)ctx->rk_bad.p));
-		} else {
-			for (uint64_t i = lo; i < hi;) {
-				if (!set->written[i]) { i++; continue; }
-				uint64_t j = i;
-				while (j < hi && set->written[j]) j++;
-				HIP_TRY(ctx, msc_launch_kb_build(ctx->stream, set->L, set->dtype, set->bins, set->kb, i, j - i, set->mb, set->mb_n, set->mb_pitch, (int32_t*)ctx->rk_bad.p));
-				i = j;
-			}
-		}
+		} else if ((r = for_each_run(lo, hi, written, [&](uint64_t first, uint64_t n) {
+			            HIP_TRY(ctx, msc_launch_kb_build(ctx->stream, set->L, set->dtype, set->bins, set->kb, first, n, set->mb, set->mb_n, set->mb_pitch, (int32_t*)ctx->rk_bad.p));
+			            return (int)MSC_OK;
+		            })))
+			return r;
 		int32_t flags[2] = {0, 0};
 		HIP_TRY(ctx, hipMemcpyAsync(flags, ctx->rk_bad.p, sizeof flags, hipMemcpyDeviceToHost, ctx->stream));
 		if (hi > lo) HIP_TRY(ctx, hipMemcpyAsync(set->mb_n_host.data() + lo, set->mb_n + lo, (hi - lo) * 4, hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 		if (flags[0]) set->kb_has_zero = true;
-		set->kb_lo = set->kb_hi = 0;
+		set->kb_stale.clear();
 		if ((uint32_t)flags[1] > set->mb_pitch) {
 			const uint32_t pitch = ((uint32_t)flags[1] + 15) / 16 * 16;
 			void* pm = nullptr;
@@ -104,8 +89,7 @@ int ensure_kb(msc_ctx* ctx, const msc_hist_set* set) {
 			if (hipMalloc(&pm, (size_t)set->capacity * pitch * 8) != hipSuccess) return give_up();
 			set->mb = pm;
 			set->mb_pitch = pitch;
-			set->kb_lo = 0;
-			set->kb_hi = set->capacity;
+			set->kb_stale.all(set->capacity);
 		}
 	}
 	return MSC_OK;
@@ -134,48 +118,40 @@ int ensure_ranks(msc_ctx* ctx, const msc_hist_set* set) {
 		set->ranks = (uint32_t*)p;
 		set->rk_n = (uint32_t*)pn;
 		set->rk_pitch = pitch;
-		set->rk_lo = 0;
-		set->rk_hi = set->capacity;
+		set->rk_stale.all(set->capacity);
 	}
 	static const bool no_rk16 = getenv("MSC_NO_RANKS16") != nullptr;
 	if (!set->ranks16 && !set->rk16_off && !no_rk16 && set->rk_pitch % 1024 == 0) {          // the 16-bit form beside it (k_emd_ranks16)
 		void* p16 = nullptr;
 		if (hipMalloc(&p16, set->rk_pitch * 2 * set->capacity) != hipSuccess) { (void)hipGetLastError(); set->rk16_off = true; }
-		else { set->ranks16 = (uint16_t*)p16; set->rk_lo = 0; set->rk_hi = set->capacity; }
+		else { set->ranks16 = (uint16_t*)p16; set->rk_stale.all(set->capacity); }
 	}
-	if (set->rk_lo < set->rk_hi) {
+	if (set->rk_stale.any()) {
 		int r;
 		if ((r = ensure(ctx, ctx->rk_bad, 2 * sizeof(int32_t)))) return r;
 		HIP_TRY(ctx, hipMemsetAsync(ctx->rk_bad.p, 0, 2 * sizeof(int32_t), ctx->stream));
 		// runs of slots that hold a histogram (an unwritten slot's digest is whatever the allocation held)
-		const uint64_t hi = std::min<uint64_t>(set->rk_hi, set->sparse ? set->capacity : set->written.size());
+		const uint64_t lo = set->rk_stale.lo, hi = std::min<uint64_t>(set->rk_stale.hi, set->sparse ? set->capacity : set->written.size());
+		int32_t* bad_word = (int32_t*)ctx->rk_bad.p;
+		auto build16 = [&](uint64_t first, uint64_t n) {
+			if (set->ranks16) HIP_TRY(ctx, msc_launch_ranks16_build(ctx->stream, set->L.nbins, set->ranks, set->ranks16, set->rk_pitch, first, n, bad_word + 1));
+			return (int)MSC_OK;
+		};
 		if (set->sparse) {
 			// the 32-bit ranks of every slot of the range from its list (one without a list: all padding, n = 0); the 16-bit form only of the
 			// runs that hold a list, as a dense set's unwritten slots are skipped: the ranks16 row of an empty slot is NOT maintained (all
 			// padding does not fit 16 bits and would switch the form off for the set; nothing reads a row past its rk_n = 0)
-			if (hi > set->rk_lo)
-				HIP_TRY(ctx, msc_launch_ranks_build_sparse(ctx->stream, set->L, set->ent, set->cum, set->hdr, set->ranks, set->rk_n, set->rk_pitch, set->rk_lo, hi - set->rk_lo, (int32_t*)ctx->rk_bad.p));
-			for (uint64_t i = set->rk_lo; i < hi && set->ranks16;) {
-				if (!set->hdr_host[i].nnz) { i++; continue; }
-				uint64_t j = i;
-				while (j < hi && set->hdr_host[j].nnz) j++;
-				HIP_TRY(ctx, msc_launch_ranks16_build(ctx->stream, set->L.nbins, set->ranks, set->ranks16, set->rk_pitch, i, j - i, (int32_t*)ctx->rk_bad.p + 1));
-				i = j;
-			}
-		} else {
-			for (uint64_t i = set->rk_lo; i < hi;) {
-				if (!set->written[i]) { i++; continue; }
-				uint64_t j = i;
-				while (j < hi && set->written[j]) j++;
-				HIP_TRY(ctx, msc_launch_ranks_build(ctx->stream, set->L, set->dtype, set->bins, set->scalars, set->ranks, set->rk_n, set->rk_pitch, i, j - i, (int32_t*)ctx->rk_bad.p));
-				if (set->ranks16) HIP_TRY(ctx, msc_launch_ranks16_build(ctx->stream, set->L.nbins, set->ranks, set->ranks16, set->rk_pitch, i, j - i, (int32_t*)ctx->rk_bad.p + 1));
-				i = j;
-			}
-		}
+			if (hi > lo) HIP_TRY(ctx, msc_launch_ranks_build_sparse(ctx->stream, set->L, set->ent, set->cum, set->hdr, set->ranks, set->rk_n, set->rk_pitch, lo, hi - lo, bad_word));
+			if ((r = for_each_run(lo, hi, [&](uint64_t i) { return set->hdr_host[i].nnz != 0; }, build16))) return r;
+		} else if ((r = for_each_run(lo, hi, [&](uint64_t i) { return set->written[i] != 0; }, [&](uint64_t first, uint64_t n) {
+			            HIP_TRY(ctx, msc_launch_ranks_build(ctx->stream, set->L, set->dtype, set->bins, set->scalars, set->ranks, set->rk_n, set->rk_pitch, first, n, bad_word));
+			            return build16(first, n);
+		            })))
+			return r;
 		int32_t bad[2] = {0, 0};
 		HIP_TRY(ctx, hipMemcpyAsync(bad, ctx->rk_bad.p, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-		set->rk_lo = set->rk_hi = 0;
+		set->rk_stale.clear();
 		if (bad[0]) {
 			(void)hipFree(set->ranks);
 			set->ranks = nullptr;
@@ -208,627 +184,727 @@ bool kb_route_fits(const msc_hist_set* cands, const msc_hist_set* qset, bool nee
 	return true;
 }
 
-static int score_multi_impl(msc_ctx* ctx, const msc_model* model, const msc_hist_set* cands, const uint32_t* cand_slots, uint64_t m,
-                            const msc_hist_set* qset, const uint32_t* q_slots, uint64_t n_q, int order, double* sum_out, double* csum_out,
-                            uint8_t* close_out, uint64_t feat_mask, double* raw_out);
 
-// the epilogue's error word (the stream is idle): the first failing pair's status
-int read_error_word(msc_ctx* ctx) {
-	int32_t first_err = 0;
-	HIP_TRY(ctx, hipMemcpy(&first_err, ctx->err_word.p, sizeof first_err, hipMemcpyDeviceToHost));
+// the first failing pair's status, as the epilogue left it in the error word
+static int error_word_status(msc_ctx* ctx, int32_t first_err) {
 	if (first_err == MSC_ERR_ZERO_LENGTH) return fail(ctx, first_err, "length_difference: a point has length 0 (the reference throws 123, predict/Feature.cpp:878-886)");
 	if (first_err == MSC_ERR_NAN) return fail(ctx, first_err, "normalisation produced NaN (the reference throws, predict/Feature.cpp:143-146)");
 	if (first_err < 0) return fail(ctx, first_err, "feature evaluation failed with status %d", first_err);
 	return MSC_OK;
 }
 
-// timing events of queued blocks (two per launch of the streaming kernel), kept for the life of the context
-static int pool_event(msc_ctx* ctx, hipEvent_t* e) {
-	if (ctx->ev_used == ctx->ev_pool.size()) {
-		hipEvent_t n = nullptr;
-		HIP_TRY(ctx, hipEventCreate(&n));
-		ctx->ev_pool.push_back(n);
-	}
-	*e = ctx->ev_pool[ctx->ev_used++];
+// the epilogue's error word (the stream is idle)
+int read_error_word(msc_ctx* ctx) {
+	int32_t first_err = 0;
+	HIP_TRY(ctx, hipMemcpy(&first_err, ctx->err_word.p, sizeof first_err, hipMemcpyDeviceToHost));
+	return error_word_status(ctx, first_err);
+}
+
+// ---- what the matrix-core drivers of msc_score_multi and msc_search_pairs (msc_api_pairs.hip) both compute
+uint64_t block_hot_size(const msc_hist_set* qset, const uint32_t* q_slots, uint64_t nq) {
+	uint64_t n_hot = 0;
+	for (uint64_t q = 0; q < nq; q++) n_hot += std::min(qset->mb_n_host[q_slots[q]], qset->mb_pitch);
+	return n_hot;
+}
+
+// the product array of a chunk, [slices][chunk][rows] int32, is kept to 2 GiB (and the chunk to `limit` candidates)
+MscCandChunks matrix_chunks(const msc_ctx* ctx, uint64_t nbins, uint64_t m, uint32_t rows, uint64_t limit) {
+	const uint64_t cap = (2048ull << 20) / ((uint64_t)msc_pair_gemm_slices(nbins, (uint32_t)std::min<uint64_t>(m, 1u << 30), rows, ctx->num_cus) * rows * sizeof(int32_t));
+	return msc_cand_chunks(m, std::min(cap, limit));
+}
+
+int ensure_side(msc_ctx* ctx, BlockPipe::Side& s, uint64_t nbins, uint32_t rows, uint32_t slices, uint64_t chunk, uint64_t n_hot, HotList* hot) {
+	const uint64_t nsteps = nbins / 128;
+	int r;
+	if ((r = ensure(ctx, s.anib, msc_pair_gemm_anib_bytes(nbins, rows))) || (r = ensure(ctx, s.qT, msc_pair_gemm_qt_bytes(nbins, rows))) ||
+	    (r = ensure(ctx, s.min, (size_t)slices * chunk * rows * sizeof(int32_t))))
+		return r;
+	*hot = HotList();
+	if (!n_hot) return MSC_OK;
+	if ((r = ensure(ctx, s.hot, n_hot * 8)) || (r = ensure(ctx, s.hot_idx, 3 * (nsteps + 1) * sizeof(uint32_t))) || (r = ensure(ctx, s.diff, chunk * rows * sizeof(int32_t)))) return r;
+	hot->ptr = (uint32_t*)s.hot_idx.p;
+	hot->cursor = hot->ptr + (nsteps + 1);
+	hot->cnt = hot->cursor + (nsteps + 1);
 	return MSC_OK;
 }
 
-// the queued blocks of msc_score_multi: wait for them, add up their kernel times, read the error word they share
-static int flush_deferred(msc_ctx* ctx) {
-	if (ctx->defer != 2) return MSC_OK;
-	ctx->defer = 1;
+void fill_matrix_args(MscEpilogueArgs& ea, const BlockPipe::Side& s, const msc_hist_set* cands, const msc_hist_set* qset, uint32_t slices, uint32_t rows, uint64_t first, uint64_t n_hot, const void* emd_out) {
+	ea.kb_min = (const int32_t*)s.min.p;
+	ea.kb_diff = n_hot ? (const int32_t*)s.diff.p : nullptr;
+	ea.kb_slices = slices; ea.kb_qn = rows; ea.kb_first = first;
+	ea.kb_c_mb = cands->mb; ea.kb_c_mb_n = cands->mb_n; ea.kb_c_pitch = cands->mb_pitch;
+	ea.kb_q_mb = qset->mb; ea.kb_q_mb_n = qset->mb_n; ea.kb_q_pitch = qset->mb_pitch;
+	ea.kb_qT = (const uint8_t*)s.qT.p;
+	ea.emd_stride = rows; ea.emd_ranks = (const uint64_t*)emd_out;
+}
+
+hipError_t launch_emd_ranks(hipStream_t st, const msc_hist_set* cands, const msc_hist_set* qset, const uint32_t* d_slots, uint64_t off, uint32_t mc, const uint32_t* dq, uint32_t nq, uint64_t* out, uint32_t stride) {
+	const uint64_t nbins = cands->L.nbins;
+	if (cands->ranks16 && qset->ranks16 && cands->rk_pitch == qset->rk_pitch)          // every reduced rank of both sets fits 16 bits: two per v_sad_u16
+		return msc_launch_emd_ranks16(st, nbins, cands->ranks16, cands->rk_pitch, cands->rk_n, d_slots, off, mc, qset->ranks16, qset->rk_n, dq, nq, out, stride);
+	return msc_launch_emd_ranks(st, nbins, cands->ranks, cands->rk_pitch, cands->rk_n, d_slots, off, mc, qset->ranks, qset->rk_pitch, qset->rk_n, dq, nq, out, stride);
+}
+
+void fill_pair_args(MscEpilogueArgs& ea, msc_ctx* ctx, const msc_hist_set* cands, const msc_hist_set* qset, const uint32_t* d_slots, uint64_t first, uint32_t mc, const uint32_t* dq, uint32_t q_slot0, uint32_t nq, uint32_t n_rec, int order) {
+	memset(&ea, 0, sizeof ea);
+	ea.S = n_rec; ea.m = nq * mc; ea.n_queries = nq; ea.m_per_query = mc;
+	ea.cand_scalars = cands->scalars + first * cands->scalar_stride; ea.cand_scalar_stride = cands->scalar_stride; ea.cand_slots = d_slots;
+	ea.q_slots = dq; ea.qset_scalars = qset->scalars; ea.q_scalar_stride = qset->scalar_stride;
+	ea.q_scalars = qset->scalars + (uint64_t)q_slot0 * qset->scalar_stride;
+	ea.nbins = cands->L.nbins; ea.dtype = cands->dtype; ea.order = order;
+	ea.error_word = (int32_t*)ctx->err_word.p;
+}
+
+void name_matrix_kernel(msc_ctx* ctx, uint32_t rows, bool emd, bool cells, bool from_lists) {
+	snprintf(ctx->last_kernel_buf, sizeof ctx->last_kernel_buf, "%s<%u query rows, one matrix product per tile of presence bits%s%s%s>", msc_pair_gemm_kernel_name(), rows,
+	         emd ? ", emd by ranks" : ", no emd", cells ? ", divergence sums from cells" : "", from_lists ? ", mirrors from lists" : "");
+	ctx->last_kernel = ctx->last_kernel_buf;
+}
+
+namespace {
+
+// ---- msc_score_multi: the call, its blocks, a route per block
+enum Route { R_MATRIX, R_DIGEST, R_RING, R_TILES, R_SPARSE_QUEUED, R_PER_QUERY };
+
+// what pick_route decides for one block
+struct BlockRoute {
+	Route kind = R_PER_QUERY;
+	bool queued = false;          // matrix: the block is queued behind the one before it, and nothing waits for the stream
+	uint64_t n_hot = 0;           // matrix: entries of the queries' hot list
+	bool emd_ranks = false;       // matrix, digest: the earth mover's distance comes from the ranks mirrors
+	int tq = 0, tps = 1;          // ring, tiles: queries per group; digest: tiles per step
+	bool prefix16 = false;        // ring: 16-bit prefix form
+};
+
+struct MultiCall {
+	msc_ctx* ctx;          // the arguments of msc_score_multi
+	const msc_model* model;
+	const msc_hist_set* cands; const uint32_t* cand_slots; uint64_t m;
+	const msc_hist_set* qset; const uint32_t* q_slots; uint64_t n_q;
+	int order;
+	double *sum_out, *csum_out; uint8_t* close_out; uint64_t feat_mask; double* raw_out;
+	uint64_t want = 0;            // the statistics of the model's singles and of feat_mask; nf: those of feat_mask, per pair of raw_out
+	bool need_emd = false, want_div = false, want_grp = false;
+	int nf = 0;
+	const msc_hist_set *c_sp = nullptr, *q_sp = nullptr;          // sparse mirrors of dense sets, for the divergence / group passes
+	bool grp_dense = false;       // the group passes read the dense slots
+	bool kb_fit = false;          // the matrix cores can take the call's blocks
+	bool simple = false;          // dense sets: a block of two or more runs on one of the Q x M kernels
+	uint64_t mc_ = 0, ms_ = 0;    // largest count / sum of either set
+	bool compact = false, excess16 = false;
+	bool queue_up = false;        // the call's query slots are in qslots_all
+	bool in_flight = false;       // queued blocks have not been waited for; they share the error word, cleared by the first of them
+	bool cands_up = false;        // the candidate slot list is in ctx->slots
+	float ms = 0.f;               // msc_last_kernel_ms / _launches cover the whole call
+	int launches = 0;
+	std::vector<MscMultiBlock> blocks;
+	std::vector<BlockRoute> taken;          // the routes of the blocks the matrix cores take, in the order of `blocks`
+};
+
+// one block of the call: its queries, its rows of the caller's arrays, and what its route's steps hand one another while it runs
+struct Block {
+	uint64_t q0, nq;
+	const uint32_t* q_slots;
+	double *sum, *csum, *raw;
+	uint8_t* close;
+	const uint32_t* dq_slots = nullptr;          // the query slots on the device
+	uint64_t chunk = 0;                          // candidates per launch
+	hipStream_t tail = nullptr;                  // where the epilogue and the copies home run
+	SparseKernel spk = SPK_MP;                   // divergence statistics: one merge kernel for the whole block ...
+	uint32_t dvn = 1;                            // ... and its {jd, js} records per pair
+};
+// candidates [off, off + mc) of a block: their device slot list (or null), bins and scalars
+struct Chunk { uint64_t off; uint32_t mc; const uint32_t* d_slots; const uint8_t *c_bins, *c_scal; };
+
+// timing events of queued blocks (two per launch of the streaming kernel), kept for the life of the context
+int pool_event(msc_ctx* ctx, hipEvent_t* e) {
+	BlockPipe& pipe = ctx->pipe;
+	if (pipe.ev_used == pipe.ev_pool.size()) {
+		hipEvent_t n = nullptr;
+		HIP_TRY(ctx, hipEventCreate(&n));
+		pipe.ev_pool.push_back(n);
+	}
+	*e = pipe.ev_pool[pipe.ev_used++];
+	return MSC_OK;
+}
+
+// the queued blocks: wait for them, add up their kernel times, read the error word they share
+int flush_deferred(MultiCall& c) {
+	if (!c.in_flight) return MSC_OK;
+	c.in_flight = false;
+	msc_ctx* ctx = c.ctx;
+	BlockPipe& pipe = ctx->pipe;
 	hipError_t e = hipStreamSynchronize(ctx->stream);
-	if (ctx->tail_used) {          // (the epilogues of the queued blocks run on the second stream)
-		const hipError_t e2 = hipStreamSynchronize(ctx->tail_stream);
+	if (pipe.tail_used) {          // (the epilogues of the queued blocks run on the second stream)
+		const hipError_t e2 = hipStreamSynchronize(pipe.tail_stream);
 		if (e == hipSuccess) e = e2;
-		ctx->tail_used = false;
-		ctx->tail_busy[0] = ctx->tail_busy[1] = false;
-		ctx->product_busy[0] = ctx->product_busy[1] = false;          // (every product waited for its queries' side: the prep stream is idle too)
+		pipe.tail_used = false;
+		for (BlockPipe::Side& s : pipe.side) s.tail_busy = s.product_busy = false;          // (every product waited for its queries' side: the prep stream is idle too)
 	}
-	for (size_t i = 0; i + 1 < ctx->ev_used; i += 2) {
+	for (size_t i = 0; i + 1 < pipe.ev_used; i += 2) {
 		float t = 0;
-		if (e == hipSuccess && hipEventElapsedTime(&t, ctx->ev_pool[i], ctx->ev_pool[i + 1]) == hipSuccess) { ctx->defer_ms += t; ctx->have_timing = true; }
+		if (e == hipSuccess && hipEventElapsedTime(&t, pipe.ev_pool[i], pipe.ev_pool[i + 1]) == hipSuccess) { c.ms += t; ctx->have_timing = true; }
 	}
-	ctx->ev_used = 0;
+	pipe.ev_used = 0;
 	if (e != hipSuccess) return fail(ctx, MSC_ERR_HIP, "queued blocks failed: %s", hipGetErrorString(e));
 	return read_error_word(ctx);
 }
 
-extern "C" int msc_score_multi(msc_ctx* ctx, const msc_model* model, const msc_hist_set* cands, const uint32_t* cand_slots, uint64_t m,
-                               const msc_hist_set* qset, const uint32_t* q_slots, uint64_t n_q, int order, double* sum_out, double* csum_out,
-                               uint8_t* close_out, uint64_t feat_mask, double* raw_out) {
-	const int r = score_multi_impl(ctx, model, cands, cand_slots, m, qset, q_slots, n_q, order, sum_out, csum_out, close_out, feat_mask, raw_out);
-	if (ctx && ctx->copy_pending) {          // the flag copies of the last blocks (issued beside the kernels that followed them)
-		const hipError_t e = hipStreamSynchronize(ctx->copy_stream);
-		ctx->copy_pending = false;
-		ctx->close_pp_busy[0] = ctx->close_pp_busy[1] = false;
-		if (e != hipSuccess && r == MSC_OK) return fail(ctx, MSC_ERR_HIP, "copy of the close flags failed: %s", hipGetErrorString(e));
-	}
-	return r;
-}
-
-static int score_multi_impl(msc_ctx* ctx, const msc_model* model, const msc_hist_set* cands, const uint32_t* cand_slots, uint64_t m,
-                            const msc_hist_set* qset, const uint32_t* q_slots, uint64_t n_q, int order, double* sum_out, double* csum_out,
-                            uint8_t* close_out, uint64_t feat_mask, double* raw_out) {
-	if (!ctx || !cands || !qset || !q_slots) return MSC_ERR_INVALID_ARG;
-	if (model && model->ctx != ctx) return MSC_ERR_INVALID_ARG;
-	if (raw_out && (feat_mask == 0 || (feat_mask & ~kSupportedFeats))) return fail(ctx, MSC_ERR_UNSUPPORTED, "feat_mask holds statistics outside the GPU path");
-	if (!raw_out) feat_mask = 0;
-	if (n_q == 0 || m == 0) return MSC_OK;
-	for (uint64_t i = 0; i < n_q; i++) if (q_slots[i] >= qset->capacity) return fail(ctx, MSC_ERR_INVALID_ARG, "query slot out of range");
-	int r = validate_pair(ctx, cands, qset, q_slots[0], cand_slots, m);
-	if (r) return r;
-	const MscLayout& L = cands->L;
-	const int nf = __builtin_popcountll(feat_mask);
-	uint64_t want = feat_mask;
-	if (model) for (int i = 0; i < model->h.n_singles; i++) want |= model->h.single_flag[i];
-	const bool need_emd = (want & MSC_FEAT_EMD) != 0;           // Feature::compute evaluates only the model's singles too
-	// The pass on the matrix cores (msc_pair_gemm.hip) serves blocks of up to 128 queries per pass over the candidates' bits; the older routes 64
-	bool kb_fit = !ctx->no_kb_now && n_q >= 2 && kb_route_fits(cands, qset, need_emd);
-	// (two sparse sets, msc_set_sparse_matrix_pass: a divergence or group statistic keeps the call on the merge kernels, blocks of 64 and all)
-	if (kb_fit && cands->sparse && (want & (MSC_FEAT_DIV | MSC_FEAT_GROUPS))) kb_fit = false;
-	if (kb_fit) {
-		if ((r = ensure_kb(ctx, cands)) || (r = ensure_kb(ctx, qset))) return r;
-		kb_fit = cands->kb && qset->kb && !cands->kb_has_zero && !qset->kb_has_zero;
-	}
-	// close candidates per query, kept on the device for msc_last_close_counts (a caller that only needs the counts of a block of the
-	// pairwise matrix does not have to add up n_q x m flags on the host)
-	const bool top_level = !ctx->in_score_multi;
-	if (top_level && close_out) {
-		if ((r = ensure(ctx, ctx->close_counts, n_q * sizeof(uint64_t)))) return r;
-		HIP_TRY(ctx, hipMemsetAsync(ctx->close_counts.p, 0, n_q * sizeof(uint64_t), ctx->stream));
-		ctx->close_counts_n = n_q;
-		ctx->close_counts_base = 0;
-	} else if (top_level) { ctx->close_counts_n = 0; ctx->close_counts_base = 0; }
-	const uint64_t blk = kb_fit ? 128 : 64;
-	if (n_q > blk) {
-		// blocks of queries: the unit of the pass on the matrix cores (a 128-row operand) and of the digest kernel (four groups of 16);
-		// msc_last_kernel_ms / _launches then cover the whole call
-		float ms = 0.f;
-		int launches = 0;
-		const bool was_in = ctx->in_score_multi;
-		const uint64_t base0 = ctx->close_counts_base;
-		ctx->in_score_multi = true;
-		// the blocks of the matrix-core pass are queued back to back (score_multi_impl below, `deferred`): the whole call's query slots
-		// go up once, here
-		static const bool no_defer = getenv("MSC_GEMM_NO_QUEUE") != nullptr;
-		const bool defer = kb_fit && top_level && !no_defer;
-		if (defer) {
-			if ((r = ensure(ctx, ctx->qslots_all, n_q * sizeof(uint32_t)))) { ctx->in_score_multi = was_in; return r; }
-			HIP_TRY(ctx, hipMemcpyAsync(ctx->qslots_all.p, q_slots, n_q * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-			HIP_TRY(ctx, hipEventRecord(ctx->ev_call, ctx->stream));
-			ctx->defer = 1;
-			ctx->defer_cands_up = false;
-			ctx->defer_ms = 0.f;
-			ctx->ev_used = 0;
-		}
-		for (uint64_t b = 0; b < n_q; b += blk) {
-			const uint64_t nb = std::min<uint64_t>(blk, n_q - b);
-			ctx->close_counts_base = base0 + b;
-			ctx->defer_q_off = b;
-			if ((r = score_multi_impl(ctx, model, cands, cand_slots, m, qset, q_slots + b, nb, order, sum_out ? sum_out + b * m : nullptr, csum_out ? csum_out + b * m : nullptr,
-			                         close_out ? close_out + b * m : nullptr, feat_mask, raw_out ? raw_out + b * m * nf : nullptr))) {
-				if (defer) { (void)flush_deferred(ctx); ctx->defer = 0; }          // (nothing of this call may still be running when it returns)
-				ctx->in_score_multi = was_in;
-				ctx->close_counts_base = base0;
-				return r;
-			}
-			ms += ctx->tiles_ms_accum;
-			launches += ctx->tiles_launches;
-		}
-		if (defer) {
-			r = flush_deferred(ctx);
-			ctx->defer = 0;
-			ms += ctx->defer_ms;
-		}
-		ctx->in_score_multi = was_in;
-		ctx->close_counts_base = base0;
-		if (r) return r;
-		ctx->tiles_ms_accum = ms;
-		ctx->tiles_launches = launches;
-		return MSC_OK;
-	}
-	// divergence statistics in the Q x M pass: the integer reductions come from the streaming kernel below, the two FP64 sums from
-	// one merge pass per query over the sparse mirrors, queued behind it -- the same kernel, hence the same values,
-	// as a 1 x M pass per query
-	const bool want_div = (want & MSC_FEAT_DIV) != 0;
-	const msc_hist_set *c_sp = nullptr, *q_sp = nullptr;
-	// sim_mm / rre_k_r likewise: one group pass per query behind the streaming kernel, over the mirrors' lists or (histograms under
-	// 64 KiB) the dense slots -- the kernels and records of the 1 x M pass
-	const bool want_grp = (want & MSC_FEAT_GROUPS) != 0;
-	if ((want_div || want_grp) && !cands->sparse && n_q > 1 && L.nbins == L.padded_bins && !needs_wide(cands, qset)) {
-		if ((r = ensure_sparse_mirror(ctx, cands, &c_sp)) || (r = ensure_sparse_mirror(ctx, qset, &q_sp))) return r;
-		if (!c_sp || !q_sp) c_sp = q_sp = nullptr;
-	}
-	const bool grp_dense = want_grp && !c_sp;
+// The route of block [q_slots, q_slots + nq) -- the only reader of the MSC_MULTI_*, MSC_GEMM_NO_QUEUE, MSC_SPARSE_NO_* and MSC_DIGEST_* switches.
+// may_matrix: the plan offers the block to the matrix cores and only asks whether they take it; otherwise the choice is among the other routes.
+//   matrix  EVERYTHING on the matrix cores (msc_pair_gemm.hip): one int8 product per tile of bins over the presence-bit mirrors + corrections from
+//           the lists of large bins -- exact for any counts of the narrow range. The queries' large bins become the block's hot list (its size is
+//           known here: the lists' lengths are mirrored on the host); a block whose list would average more than 64 entries per 128-bin step is
+//           left to the older routes, as is one without ranks mirrors when the earth mover's distance is wanted.
+//   digest  (pair_digest.hip) counts and excess prefixes within 16 bits, from four queries up: the mirror streams 4 bytes per bin, which against 8/16-bit
+//           raw bins pays once enough queries share each candidate read (measured crossovers at k = 9: 7 queries for uint8_t, 5-6 for uint16_t, 4 for uint32_t)
+//   ring    LDS-DMA ring over the raw bins: 32/64-bit bins, compact totals, query groups of four or eight; tiles: the raw register kernel, for everything else
+//   sparse-queued  two sparse sets: a merge-path or rank-list pass per query, queued into one record array with one epilogue
+//   per-query      one 1 x M pass per query (run_score): padded tiny histograms, wide sets, a single query, an unavailable sparse mirror
+BlockRoute pick_route(const MultiCall& c, const uint32_t* q_slots, uint64_t nq, bool may_matrix, int* err) {
 	static const bool no_digest = getenv("MSC_MULTI_NO_DIGEST") != nullptr;
-	const bool tuned_by_hand = getenv("MSC_MULTI_TQ") || getenv("MSC_DIGEST_SLOTS");          // A/B switches of the older kernels: keep to them
-	// EVERYTHING on the matrix cores (msc_pair_gemm.hip): one int8 product per tile of bins over the presence-bit mirrors + corrections from the
-	// lists of large bins -- exact for any counts of the narrow range; one read of a candidate byte per 256 queries, no partial records.
-	// The queries' large bins become this block's hot list: its size is known here (the lists' lengths are mirrored on the host), and
-	// a block whose list would average more than 64 entries per 128-bin step (long sequences in few bins: the walk over the list would
-	// then take several times the step's product) is left to the older routes.
-	bool manh_gemm = false, emd_ranks = false;
-	uint64_t n_hot = 0;
-	auto pick_matrix = [&]() -> int {
-		for (uint64_t q = 0; q < n_q; q++) n_hot += std::min(qset->mb_n_host[q_slots[q]], qset->mb_pitch);
-		manh_gemm = n_hot <= 64 * (L.nbins / 128);
-		if (manh_gemm && need_emd) {
-			int e;
-			if ((e = ensure_ranks(ctx, cands)) || (e = ensure_ranks(ctx, qset))) return e;
-			manh_gemm = emd_ranks = cands->ranks && qset->ranks;
-		}
-		return MSC_OK;
-	};
-	// Two sparse sets whose mirrors stand (kb_fit): the block is decided here, ahead of the sparse branch below. One that declines -- hot
-	// list too long, no ranks mirror -- goes on exactly as without the switch: the merge / rank-list passes, in blocks of 64.
-	if (kb_fit && cands->sparse) {
-		if (!tuned_by_hand && !no_digest && (r = pick_matrix())) return r;
-		if (!manh_gemm) {
-			if (ctx->defer == 2 && (r = flush_deferred(ctx))) return r;
-			if (n_q > 64) {
-				ctx->no_kb_now = true;
-				r = score_multi_impl(ctx, model, cands, cand_slots, m, qset, q_slots, n_q, order, sum_out, csum_out, close_out, feat_mask, raw_out);
-				ctx->no_kb_now = false;
-				return r;
-			}
-		}
-	}
-	const bool simple = (!grp_dense || std::max(cands->max_count, qset->max_count) <= 0xffffffffull) && (!want_div || c_sp) && L.nbins == L.padded_bins && n_q > 1 &&
-	                    !needs_wide(cands, qset) && (!cands->sparse || manh_gemm);
-	// Sparse sets: one merge-path pass per query, but queued back to back into one [n_q][m] record array with ONE epilogue and one
-	// copy back -- no host round trip between the passes.
+	static const bool no_queue = getenv("MSC_GEMM_NO_QUEUE") != nullptr;
 	static const bool no_sp_multi = getenv("MSC_SPARSE_NO_MULTI") != nullptr;
-	const bool sparse_multi = cands->sparse && qset->sparse && !manh_gemm && !no_sp_multi && !(want & (MSC_FEAT_DIV | MSC_FEAT_GROUPS)) && n_q > 1 && !needs_wide(cands, qset) &&
-	                          std::max(cands->max_count, qset->max_count) < 65536 && n_q * m <= 0x7fffffffull &&
-	                          n_q * m * sizeof(MscPartial) <= (4096ull << 20) && !getenv("MSC_SPARSE_NO_MP") && !getenv("MSC_SPARSE_LDS");
-	if (sparse_multi) {
-		HIP_TRY(ctx, hipSetDevice(ctx->device));
-		ctx->tiles_ms_accum = 0.f;
-		ctx->tiles_launches = 0;
-		ctx->have_timing = false;
-		// (msc_launch_pair_sparse_mp hands a pass whose lists fit LDS whole to k_pair_sparse_wl: the name says which of the two the
-		// queries' passes ran, "k_pair_sparse_mp+wl" when some queries fit and some do not)
-		uint64_t n_wl = 0;
-		for (uint64_t q = 0; q < n_q; q++) n_wl += msc_sparse_wl_fits(qset->hdr_host[q_slots[q]].nnz, cands->max_nnz) ? 1 : 0;
-		ctx->last_kernel = n_wl == n_q ? "k_pair_sparse_wl" : n_wl ? "k_pair_sparse_mp+wl" : "k_pair_sparse_mp";
-		ctx->last_query_tile = 1;
-		ctx->last_partial_stride = 1;
-		if ((r = ensure(ctx, ctx->err_word, sizeof(int32_t)))) return r;
-		if ((r = ensure(ctx, ctx->qslots, n_q * sizeof(uint32_t)))) return r;
-		if ((r = ensure(ctx, ctx->partials, n_q * m * sizeof(MscPartial)))) return r;
-		if (sum_out && (r = ensure(ctx, ctx->soa_sum, n_q * m * sizeof(double)))) return r;
-		if (csum_out && (r = ensure(ctx, ctx->soa_csum, n_q * m * sizeof(double)))) return r;
-		if (close_out && (r = ensure(ctx, ctx->soa_close, n_q * m))) return r;
-		if (raw_out && (r = ensure(ctx, ctx->raw, n_q * m * nf * sizeof(double)))) return r;
-		HIP_TRY(ctx, hipMemcpyAsync(ctx->qslots.p, q_slots, n_q * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-		HIP_TRY(ctx, hipMemsetAsync(ctx->err_word.p, 0, sizeof(int32_t), ctx->stream));
-		if (cand_slots) {
-			if ((r = ensure(ctx, ctx->slots, m * sizeof(uint32_t)))) return r;
-			HIP_TRY(ctx, hipMemcpyAsync(ctx->slots.p, cand_slots, m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-		}
-		const uint32_t* d_slots = cand_slots ? (const uint32_t*)ctx->slots.p : nullptr;
-		// up to k = 9: the passes over the candidates' rank lists (msc_ranks_pass.hip), as in run_score
-		const uint64_t q_kmers = qset->max_sum >= L.nbins ? qset->max_sum - L.nbins : ~0ull;
-		bool rank_pass = false;
-		if (getenv("MSC_NO_RANKS_1XM") == nullptr && q_kmers <= msc_ranks_pass_query_cap() && msc_ranks_pass_lds(L.nbins, q_kmers) != 0) {
-			int e = MSC_OK;
-			rank_pass = rank_lists_ready(ctx, cands, &e);
-			if (e) return e;
-			if (rank_pass && !ctx->rk_guard) {
-				HIP_TRY(ctx, hipHostMalloc((void**)&ctx->rk_guard, 64, hipHostMallocDefault));
-				*ctx->rk_guard = 0;
-			}
-			if (rank_pass && msc_ranks_pass_query_scratch(q_kmers) && (r = ensure(ctx, ctx->rk_q, msc_ranks_pass_query_scratch(q_kmers) * sizeof(uint32_t)))) return r;
-			if (rank_pass) ctx->last_kernel = "k_pair_ranks_1xm";
-		}
-		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_all0, ctx->stream));
-		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_tiles0, ctx->stream));
-		for (uint64_t q = 0; q < n_q && rank_pass; q++)
-			HIP_TRY(ctx, msc_launch_pair_ranks_1xm(ctx->stream, cands->rkl, cands->rkl_off, cands->rkl_n, cands->scalars, cands->scalar_stride, d_slots, 0, (uint32_t)m, qset->ent, qset->cum,
-			                                       qset->hdr + q_slots[q], L.nbins, 0, 0, ~0ull, (MscPartial*)ctx->partials.p + q * m, ctx->num_cus, q_kmers, ctx->rk_guard, (uint32_t*)ctx->rk_q.p));
-		for (uint64_t q = 0; q < n_q && !rank_pass; q++)
-			HIP_TRY(ctx, msc_launch_pair_sparse_mp(ctx->stream, cands->ent, cands->cum, cands->hdr, cands->scalars, cands->scalar_stride, d_slots, (uint32_t)m, qset->ent,
-			                                       qset->cum, qset->hdr + q_slots[q], qset->scalars + (uint64_t)q_slots[q] * qset->scalar_stride, L.nbins, 0, 0, ~0ull,
-			                                       (MscPartial*)ctx->partials.p + q * m, nullptr, nullptr, order, ctx->num_cus,
-			                                       (uint32_t)std::min<uint64_t>(0x7fffffffull, (uint64_t)qset->hdr_host[q_slots[q]].nnz + cands->max_nnz), 1,
-			                                       qset->hdr_host[q_slots[q]].nnz, cands->max_nnz));
-		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_tiles1, ctx->stream));
-		MscEpilogueArgs ea;
-		memset(&ea, 0, sizeof ea);
-		ea.partials = (const MscPartial*)ctx->partials.p;
-		ea.S = 1;
-		ea.m = (uint32_t)(n_q * m);
-		ea.cand_scalars = cands->scalars;
-		ea.cand_scalar_stride = cands->scalar_stride;
-		ea.cand_slots = d_slots;
-		ea.n_queries = (uint32_t)n_q;
-		ea.m_per_query = (uint32_t)m;
-		ea.q_slots = (const uint32_t*)ctx->qslots.p;
-		ea.qset_scalars = qset->scalars;
-		ea.q_scalar_stride = qset->scalar_stride;
-		ea.q_scalars = qset->scalars + (uint64_t)q_slots[0] * qset->scalar_stride;
-		ea.nbins = L.nbins;
-		ea.dtype = cands->dtype;
-		ea.order = order;
-		ea.feat_mask = feat_mask;
-		ea.sparse_base = L.nbins;
-		ea.raw_out = raw_out ? (double*)ctx->raw.p : nullptr;
-		ea.model = model ? model->d : nullptr;
-		ea.sum_soa = sum_out ? (double*)ctx->soa_sum.p : nullptr;
-		ea.csum_soa = csum_out ? (double*)ctx->soa_csum.p : nullptr;
-		ea.close_soa = close_out ? (uint8_t*)ctx->soa_close.p : nullptr;
-		ea.error_word = (int32_t*)ctx->err_word.p;
-		HIP_TRY(ctx, msc_launch_epilogue(ctx->stream, ea));
-		if (close_out && ctx->close_counts_n) HIP_TRY(ctx, msc_launch_close_counts(ctx->stream, (const uint8_t*)ctx->soa_close.p, (uint32_t)n_q, (uint32_t)m, (uint64_t*)ctx->close_counts.p + ctx->close_counts_base));
-		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_all1, ctx->stream));
-		if (sum_out) HIP_TRY(ctx, hipMemcpyAsync(sum_out, ctx->soa_sum.p, n_q * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-		if (csum_out) HIP_TRY(ctx, hipMemcpyAsync(csum_out, ctx->soa_csum.p, n_q * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-		if (close_out) HIP_TRY(ctx, hipMemcpyAsync(close_out, ctx->soa_close.p, n_q * m, hipMemcpyDeviceToHost, ctx->stream));
-		if (raw_out) HIP_TRY(ctx, hipMemcpyAsync(raw_out, ctx->raw.p, n_q * m * nf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-		int32_t first_err = 0;
-		HIP_TRY(ctx, hipMemcpyAsync(&first_err, ctx->err_word.p, sizeof first_err, hipMemcpyDeviceToHost, ctx->stream));
-		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-		float t = 0;
-		if (ctx->timing && hipEventElapsedTime(&t, ctx->ev_tiles0, ctx->ev_tiles1) == hipSuccess) { ctx->tiles_ms_accum = t; ctx->tiles_launches = (int)n_q; ctx->have_timing = true; }
-		if (rank_pass && *ctx->rk_guard) {
-			*ctx->rk_guard = 0;
-			return fail(ctx, MSC_ERR_HIP, "rank pass: a query's list is longer than its set's bound (max_sum not maintained by a writer of that set)");
-		}
-		if (first_err == MSC_ERR_ZERO_LENGTH) return fail(ctx, first_err, "length_difference: a point has length 0 (the reference throws 123, predict/Feature.cpp:878-886)");
-		if (first_err == MSC_ERR_NAN) return fail(ctx, first_err, "normalisation produced NaN (the reference throws, predict/Feature.cpp:143-146)");
-		if (first_err < 0) return fail(ctx, first_err, "feature evaluation failed with status %d", first_err);
-		return MSC_OK;
-	}
-	if (!simple) {
-		ctx->close_counts_n = 0;          // (no counts from this route: msc_last_close_counts says so)
-		// divergence statistics / padded tiny histograms: one streaming pass per query through the single-query kernel
-		float ms = 0.f;
-		int launches = 0;
-		for (uint64_t q = 0; q < n_q; q++) {
-			ScoreRequest rq;
-			rq.model = model; rq.cands = cands; rq.cand_slots = cand_slots; rq.m = m; rq.qset = qset; rq.q_slot = q_slots[q]; rq.order = order;
-			rq.feat_mask = feat_mask; rq.raw_out = raw_out ? raw_out + q * m * nf : nullptr;
-			rq.sum_out = sum_out ? sum_out + q * m : nullptr; rq.csum_out = csum_out ? csum_out + q * m : nullptr;
-			rq.flags_out = close_out ? close_out + q * m : nullptr;
-			if ((r = run_score(ctx, rq))) return r;
-			ms += ctx->tiles_ms_accum;
-			launches += ctx->tiles_launches;
-		}
-		ctx->tiles_ms_accum = ms;          // msc_last_kernel_ms / _launches cover the whole call
-		ctx->tiles_launches = launches;
-		return MSC_OK;
-	}
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	ctx->tiles_ms_accum = 0.f;
-	ctx->tiles_launches = 0;
-	ctx->have_timing = false;
-	int tq = n_q >= 4 ? 4 : 2;                     // TQ = 4 keeps the 32-bit register kernel HBM-bound
-	if (const char* e = getenv("MSC_MULTI_TQ")) { const int v = atoi(e); if (v == 2 || v == 4 || v == 8) tq = v; }
-	if (tq > (int)n_q && n_q >= 2) tq = n_q >= 4 ? 4 : 2;
-	// wave totals of the per-lane 32-bit partial sums fit 32 bits when 64*R*max^2 and 64*R*max|prefix difference| do
-	const uint64_t mc_ = std::max(cands->max_count, qset->max_count), ms_ = std::max(cands->max_sum, qset->max_sum);
-	const bool compact = 64ull * L.R * mc_ * mc_ < (1ull << 32) && 64ull * L.R * ms_ < (1ull << 32);
-	// every prefix of excess counts (count - 1) is at most the histogram's k-mer total = sum - 4^k: 16-bit prefix form when that fits
-	const bool excess16 = ms_ >= L.nbins && ms_ - L.nbins < 65536;
 	static const bool no_ranks = getenv("MSC_MULTI_NO_RANKS") != nullptr;
-	// The earth mover's distance from sorted k-mer ranks (msc_emd_ranks.hip) -- O(k-mers) per pair instead of O(bins): while the
-	// longest list is a quarter of the bins or less, for up to 256 queries and 2^20 bins (32-bit wave sums)
-	const bool ranks_fit = !no_ranks && !tuned_by_hand && n_q <= 256 && L.nbins <= (1ull << 20) && ms_ >= L.nbins && (ms_ - L.nbins) * 4 <= L.nbins && msc_digest_supported(L);
-	if (kb_fit && simple && !cands->sparse && !tuned_by_hand && !no_digest && (r = pick_matrix())) return r;          // (dense sets: the block is decided here)
-	// (blocks of the matrix-core pass queued without a host wait between them: any other route first waits for them and reads their error word)
-	if (!manh_gemm && ctx->defer == 2 && (r = flush_deferred(ctx))) return r;
-	if (!manh_gemm && n_q > 64) {          // (a block of up to 256 was cut for the matrix cores: the older routes take it in blocks of 64)
-		ctx->no_kb_now = true;
-		r = score_multi_impl(ctx, model, cands, cand_slots, m, qset, q_slots, n_q, order, sum_out, csum_out, close_out, feat_mask, raw_out);
-		ctx->no_kb_now = false;
-		return r;
+	static const bool no_ring = getenv("MSC_MULTI_NO_RING") != nullptr;
+	static const bool no_p16 = getenv("MSC_RING_NO_P16") != nullptr;
+	const char* env_tq = getenv("MSC_MULTI_TQ");
+	const bool tuned_by_hand = env_tq || getenv("MSC_DIGEST_SLOTS");          // A/B switches of the older kernels: keep to them
+	msc_ctx* ctx = c.ctx;
+	const msc_hist_set *cands = c.cands, *qset = c.qset;
+	const MscLayout& L = cands->L;
+	BlockRoute rt;
+	*err = MSC_OK;
+	if (may_matrix) {          // R_MATRIX, or any other answer: the plan then cuts the block for the older routes and asks again, block by block
+		if (tuned_by_hand || no_digest || !(cands->sparse || c.simple)) return rt;
+		rt.n_hot = block_hot_size(qset, q_slots, nq);
+		if (rt.n_hot > 64 * (L.nbins / 128)) return rt;
+		if (c.need_emd) {
+			if ((*err = ensure_ranks(ctx, cands)) || (*err = ensure_ranks(ctx, qset)) || !cands->ranks || !qset->ranks) return rt;
+			rt.emd_ranks = true;
+		}
+		rt.kind = R_MATRIX;
+		rt.queued = c.n_q > 128 && !no_queue;          // (a call of one block has nothing to queue behind)
+		return rt;
 	}
-	// A block of a larger call on the matrix cores is QUEUED: its query slots are part of the list the call sent up once, the error word is
-	// cleared by the first block and read after the last, and nothing here waits for the stream -- the scratch buffers the next block
-	// overwrites are ordered behind this block's kernels by the stream itself (a buffer that has to grow goes through hipFree, which waits).
-	const bool deferred = manh_gemm && ctx->defer != 0;
-	const uint32_t* dq_slots = nullptr;
-	if ((r = ensure(ctx, ctx->err_word, sizeof(int32_t)))) return r;
-	if (deferred) dq_slots = (const uint32_t*)ctx->qslots_all.p + ctx->defer_q_off;
-	else {
-		if ((r = ensure(ctx, ctx->qslots, n_q * sizeof(uint32_t)))) return r;
-		HIP_TRY(ctx, hipMemcpyAsync(ctx->qslots.p, q_slots, n_q * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-		dq_slots = (const uint32_t*)ctx->qslots.p;
+	if (cands->sparse) {
+		const bool queued = !no_sp_multi && !(c.want & (MSC_FEAT_DIV | MSC_FEAT_GROUPS)) && nq > 1 && !needs_wide(cands, qset) && c.mc_ < 65536 && nq * c.m <= 0x7fffffffull &&
+		                    nq * c.m * sizeof(MscPartial) <= (4096ull << 20) && !getenv("MSC_SPARSE_NO_MP") && !getenv("MSC_SPARSE_LDS");
+		rt.kind = queued ? R_SPARSE_QUEUED : R_PER_QUERY;
+		return rt;
 	}
-	if (!deferred || ctx->defer == 1) HIP_TRY(ctx, hipMemsetAsync(ctx->err_word.p, 0, sizeof(int32_t), ctx->stream));
-	if (cand_slots && !(deferred && ctx->defer_cands_up)) {
-		if ((r = ensure(ctx, ctx->slots, m * sizeof(uint32_t)))) return r;
-		HIP_TRY(ctx, hipMemcpyAsync(ctx->slots.p, cand_slots, m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-		if (deferred) ctx->defer_cands_up = true;
-	}
-	if (deferred) ctx->defer = 2;
-	// Digest form (pair_digest.hip): sets whose counts and excess prefixes fit 16 bits, from four queries up. Sixteen (or 32)
-	// queries share one HBM read of each candidate tile; the raw kernels below remain for everything else.
-	// (one digest tile per lane-run of 16 bins: wave totals of 1024 * max^2 must fit 32 bits)
-	// The mirror streams 4 bytes per bin: against 8/16-bit raw bins it pays once enough queries share each candidate read
-	// (measured crossovers at k = 9: 7 queries for uint8_t, 5-6 for uint16_t, 4 for uint32_t)
+	if (!c.simple || nq < 2) return rt;
+	rt.tq = nq >= 4 ? 4 : 2;                     // TQ = 4 keeps the 32-bit register kernel HBM-bound
+	if (env_tq) { const int v = atoi(env_tq); if (v == 2 || v == 4 || v == 8) rt.tq = v; }
+	if (rt.tq > (int)nq) rt.tq = nq >= 4 ? 4 : 2;
 	const uint64_t dg_min_q = cands->dtype == 8 ? 8 : cands->dtype == 16 ? 6 : 4;
-	bool digest = !manh_gemm && !no_digest && excess16 && msc_digest_supported(L) && mc_ < 2048 && n_q >= dg_min_q && !getenv("MSC_MULTI_TQ");
+	// (one digest tile per lane-run of 16 bins: wave totals of 1024 * max^2 must fit 32 bits)
+	bool digest = !no_digest && c.excess16 && msc_digest_supported(L) && c.mc_ < 2048 && nq >= dg_min_q && !env_tq;
 	if (digest) {
-		if ((r = ensure_digest(ctx, cands)) || (r = ensure_digest(ctx, qset))) return r;
+		if ((*err = ensure_digest(ctx, cands)) || (*err = ensure_digest(ctx, qset))) return rt;
 		digest = cands->digest && qset->digest;
 	}
-	const bool gemm_dot = false;          // (r03's digest forms without their products took them from an int8 GEMM over a count mirror: the presence-bit route replaced both)
-	// LDS-DMA ring form over the raw bins: 32/64-bit bins, compact totals, query groups of four or eight
-	static const bool no_ring = getenv("MSC_MULTI_NO_RING") != nullptr;
-	if (!digest && !manh_gemm && n_q >= 16 && !getenv("MSC_MULTI_TQ") && (cands->dtype == 32 || cands->dtype == 64)) tq = 8;      // measured best from 16 queries up
-	const bool ring = !digest && !manh_gemm && !no_ring && compact && L.LPT == 4 && (cands->dtype == 32 || cands->dtype == 64) && (tq == 4 || tq == 8) && n_q >= 4;
-	static const bool no_p16 = getenv("MSC_RING_NO_P16") != nullptr;
-	const bool prefix16 = ring && !no_p16 && excess16;
-	// partial records of one launch are capped at 4 GiB: equal candidate chunks
-	const int tps = digest ? msc_digest_tiles_per_step(L, mc_) : 1;          // the digest kernel writes one record per step of tps tiles
-	if (digest && need_emd && ranks_fit && tps == 2) {          // the digest kernel then runs its count-only form (two tiles per step)
-		if ((r = ensure_ranks(ctx, cands)) || (r = ensure_ranks(ctx, qset))) return r;
-		emd_ranks = cands->ranks && qset->ranks;
+	if (digest) {
+		rt.kind = R_DIGEST;
+		rt.tps = msc_digest_tiles_per_step(L, c.mc_);
+		// The earth mover's distance from sorted k-mer ranks (msc_emd_ranks.hip) -- O(k-mers) per pair instead of O(bins): while the longest
+		// list is a quarter of the bins or less, for up to 256 queries and 2^20 bins (32-bit wave sums). The digest kernel then runs its
+		// count-only form (two tiles per step)
+		const bool ranks_fit = !no_ranks && !tuned_by_hand && nq <= 256 && L.nbins <= (1ull << 20) && c.ms_ >= L.nbins && (c.ms_ - L.nbins) * 4 <= L.nbins;
+		if (c.need_emd && ranks_fit && rt.tps == 2) {
+			if ((*err = ensure_ranks(ctx, cands)) || (*err = ensure_ranks(ctx, qset))) return rt;
+			rt.emd_ranks = cands->ranks && qset->ranks;
+		}
+		return rt;
 	}
-	const bool digest_emd = need_emd && !emd_ranks;                          // the digest kernel streams and scores the prefix half
-	const uint32_t n_rec = digest ? (uint32_t)(L.nbins / 1024) / tps : L.S;
-	// manh is all that is left to the digest kernel: eight queries per wave (32 per candidate tile fetched), 4-byte records
-	static const bool no_tq8 = getenv("MSC_DIGEST_NO_TQ8") != nullptr;
-	const int dg_tq = digest && gemm_dot && !digest_emd && n_q > 16 && !no_tq8 ? 8 : 4;
-	const uint64_t rec_bytes = digest && dg_tq == 8 ? 4 : digest && gemm_dot ? 8 : digest || ring ? 16 : sizeof(MscPartial);
-	const uint64_t q_rows = digest ? (n_q + 4 * dg_tq - 1) / (4 * dg_tq) * (4 * dg_tq) : ring ? (n_q + tq - 1) / tq * tq : n_q;       // records cover the padded query count
-	uint64_t chunk = (4096ull << 20) / ((uint64_t)n_rec * rec_bytes * q_rows);
-	// (no records without the digest kernel: the product array of the GEMM, [slices][chunk][rows] int32, kept to 2 GiB)
-	const uint32_t kb_qn = manh_gemm ? msc_pair_gemm_rows((uint32_t)n_q) : 0;
-	if (manh_gemm) chunk = (2048ull << 20) / ((uint64_t)msc_pair_gemm_slices(L.nbins, (uint32_t)std::min<uint64_t>(m, 1u << 30), kb_qn, ctx->num_cus) * kb_qn * sizeof(int32_t));
-	if (want_grp) chunk = std::min<uint64_t>(chunk, (1024ull << 20) / (n_q * 32 * sizeof(double)));      // [n_q][chunk][16][2] group records: 1 GiB
-	chunk = std::min(std::max<uint64_t>(chunk, 256), m);
-	chunk = (m + (m + chunk - 1) / chunk - 1) / ((m + chunk - 1) / chunk);
-	if (!manh_gemm && (r = ensure(ctx, ctx->partials, q_rows * chunk * n_rec * rec_bytes))) return r;
-	if (want_grp) {
-		if ((r = ensure(ctx, ctx->grp_pairs, n_q * chunk * 32 * sizeof(double)))) return r;
-		if ((r = ensure(ctx, ctx->grp_self, (chunk + n_q) * 16 * sizeof(double)))) return r;      // [candidates][16] then [queries][16]
+	const bool wide_bins = cands->dtype == 32 || cands->dtype == 64;
+	if (nq >= 16 && !env_tq && wide_bins) rt.tq = 8;      // measured best from 16 queries up
+	const bool ring = !no_ring && c.compact && L.LPT == 4 && wide_bins && (rt.tq == 4 || rt.tq == 8) && nq >= 4;
+	rt.kind = ring ? R_RING : R_TILES;
+	rt.prefix16 = ring && !no_p16 && c.excess16;
+	return rt;
+}
+
+int begin_block(msc_ctx* ctx) {
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	ctx->tiles_ms_accum = 0.f; ctx->tiles_launches = 0; ctx->have_timing = false;
+	return MSC_OK;
+}
+
+// one streaming pass per query through the single-query kernel; msc_last_close_counts keeps no counts for the call
+int run_per_query(MultiCall& c, Block& b) {
+	msc_ctx* ctx = c.ctx;
+	ctx->close_counts_n = 0;
+	float ms = 0.f;
+	int launches = 0, r;
+	for (uint64_t q = 0; q < b.nq; q++) {
+		ScoreRequest rq;
+		rq.model = c.model; rq.cands = c.cands; rq.cand_slots = c.cand_slots; rq.m = c.m; rq.qset = c.qset; rq.q_slot = b.q_slots[q]; rq.order = c.order;
+		rq.feat_mask = c.feat_mask; rq.raw_out = b.raw ? b.raw + q * c.m * c.nf : nullptr; rq.sum_out = b.sum ? b.sum + q * c.m : nullptr;
+		rq.csum_out = b.csum ? b.csum + q * c.m : nullptr; rq.flags_out = b.close ? b.close + q * c.m : nullptr;
+		if ((r = run_score(ctx, rq))) return r;
+		ms += ctx->tiles_ms_accum; launches += ctx->tiles_launches;
 	}
-	SparseKernel spk = SPK_MP;
-	uint32_t dvn = 1;        // {jd, js} records per pair (one stride for the whole block)
-	if (want_div) {          // one kernel for the whole block: merge-path unless some query's lists are out of its range
-		for (uint64_t q = 0; q < n_q; q++) if (pick_sparse_kernel(c_sp, q_sp, q_slots[q], mc_, false) != SPK_MP) spk = SPK_GENERIC;
-		const uint32_t spn = sparse_records(spk);
+	ctx->tiles_ms_accum = ms; ctx->tiles_launches = launches;
+	return MSC_OK;
+}
+
+// the fields of the epilogue's arguments every Q x M route fills alike
+void fill_block_args(const MultiCall& c, Block& b, const uint32_t* dq_slots, const Chunk& k, uint32_t n_rec, MscEpilogueArgs& ea) {
+	msc_ctx* ctx = c.ctx;
+	fill_pair_args(ea, ctx, c.cands, c.qset, k.d_slots, c.cand_slots ? 0 : k.off, k.mc, dq_slots, b.q_slots[0], (uint32_t)b.nq, n_rec, c.order);
+	ea.partials = (const MscPartial*)ctx->partials.p;
+	ea.feat_mask = c.feat_mask;
+	ea.model = c.model ? c.model->d : nullptr;
+	ea.raw_out = b.raw ? (double*)ctx->raw.p : nullptr;
+	ea.sum_soa = b.sum ? (double*)ctx->soa_sum.p : nullptr;
+	ea.csum_soa = b.csum ? (double*)ctx->soa_csum.p : nullptr;
+}
+
+// ---- the Q x M kernels over two dense sets (and the matrix cores over two sparse ones): the steps their routes share
+// The block's query slots, the cleared error word and the candidate slot list, on the context's stream. A QUEUED block's query slots are part of the list the
+// call sent up once, the error word is cleared by the first queued block and read after the last, the candidate list goes up once -- and nothing waits for the
+// stream: the scratch buffers the next block overwrites are ordered behind this block's kernels by the stream (a buffer that has to grow goes through hipFree, which waits).
+int block_uploads(MultiCall& c, Block& b, bool queued) {
+	msc_ctx* ctx = c.ctx;
+	int r;
+	if ((r = ensure(ctx, ctx->err_word, sizeof(int32_t)))) return r;
+	if (queued) b.dq_slots = (const uint32_t*)ctx->qslots_all.p + b.q0;
+	else {
+		if ((r = ensure(ctx, ctx->qslots, b.nq * sizeof(uint32_t)))) return r;
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->qslots.p, b.q_slots, b.nq * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+		b.dq_slots = (const uint32_t*)ctx->qslots.p;
+	}
+	if (!queued || !c.in_flight) HIP_TRY(ctx, hipMemsetAsync(ctx->err_word.p, 0, sizeof(int32_t), ctx->stream));
+	if (c.cand_slots && !(queued && c.cands_up)) {
+		if ((r = ensure(ctx, ctx->slots, c.m * sizeof(uint32_t)))) return r;
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->slots.p, c.cand_slots, c.m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+		if (queued) c.cands_up = true;
+	}
+	if (queued) c.in_flight = true;
+	return MSC_OK;
+}
+
+// [n_q][chunk][16][2] group records are kept to 1 GiB
+uint64_t group_chunk_limit(const MultiCall& c, uint64_t nq) { return c.want_grp ? (1024ull << 20) / (nq * 32 * sizeof(double)) : ~0ull; }
+
+// Scratch of a block's chunks: the results, and what the divergence / group passes behind the streaming kernel write. Divergence statistics: the integer
+// reductions come from the streaming kernel, the two FP64 sums from one merge pass per query over the sparse mirrors, queued behind it -- the
+// same kernel, hence the same values, as a 1 x M pass per query. sim_mm / rre_k_r likewise: one group pass per query, over the mirrors' lists or (histograms
+// under 64 KiB) the dense slots -- the kernels and records of the 1 x M pass.
+int ensure_block_scratch(MultiCall& c, Block& b, bool flags_by_copy_stream) {
+	msc_ctx* ctx = c.ctx;
+	const uint64_t n_q = b.nq, chunk = b.chunk;
+	int r;
+	if (c.want_grp) {
+		if ((r = ensure(ctx, ctx->grp_pairs, n_q * chunk * 32 * sizeof(double))) || (r = ensure(ctx, ctx->grp_self, (chunk + n_q) * 16 * sizeof(double)))) return r;      // [candidates][16] then [queries][16]
+	}
+	if (c.want_div) {          // one kernel for the whole block: merge-path unless some query's lists are out of its range
 		uint64_t q_nnz_max = 0;
-		for (uint64_t q = 0; q < n_q; q++) q_nnz_max = std::max<uint64_t>(q_nnz_max, q_sp->hdr_host[q_slots[q]].nnz);
-		dvn = div_records(spk, q_nnz_max + c_sp->max_nnz);
-		if ((r = ensure(ctx, ctx->div_tables, chunk * 256 * 16))) return r;
-		if ((r = ensure(ctx, ctx->div_partials, n_q * chunk * dvn * 16))) return r;
-		if ((r = ensure(ctx, ctx->sp_partials, chunk * spn * sizeof(MscPartial)))) return r;
+		for (uint64_t q = 0; q < n_q; q++) {
+			if (pick_sparse_kernel(c.c_sp, c.q_sp, b.q_slots[q], c.mc_, false) != SPK_MP) b.spk = SPK_GENERIC;
+			q_nnz_max = std::max<uint64_t>(q_nnz_max, c.q_sp->hdr_host[b.q_slots[q]].nnz);
+		}
+		b.dvn = div_records(b.spk, q_nnz_max + c.c_sp->max_nnz);
+		if ((r = ensure(ctx, ctx->div_tables, chunk * 256 * 16)) || (r = ensure(ctx, ctx->div_partials, n_q * chunk * b.dvn * 16)) ||
+		    (r = ensure(ctx, ctx->sp_partials, chunk * sparse_records(b.spk) * sizeof(MscPartial))))
+			return r;
 	}
-	if (sum_out && (r = ensure(ctx, ctx->soa_sum, n_q * chunk * sizeof(double)))) return r;
-	if (csum_out && (r = ensure(ctx, ctx->soa_csum, n_q * chunk * sizeof(double)))) return r;
-	if (close_out && !manh_gemm && (r = ensure(ctx, ctx->soa_close, n_q * chunk))) return r;
-	if (close_out && manh_gemm && ((r = ensure(ctx, ctx->close_pp[0], n_q * chunk)) || (r = ensure(ctx, ctx->close_pp[1], n_q * chunk)))) return r;
-	if (raw_out && (r = ensure(ctx, ctx->raw, n_q * chunk * nf * sizeof(double)))) return r;
-	const uint32_t gemm_slices = manh_gemm ? msc_pair_gemm_slices(L.nbins, (uint32_t)chunk, kb_qn, ctx->num_cus) : 0;
-	uint32_t *hot_ptr = nullptr, *hot_cursor = nullptr, *hot_cnt = nullptr;
-	// Queued blocks run in two stages on two streams (msc_objects.h): the product of block i on ctx->stream beside the rank walk of block i
-	// and the epilogue of block i - 1 on tail_stream -- the product is bound by the matrix pipe, the other two by vector arithmetic and
-	// latency. Blocks take turns on two copies of what both stages touch. (Single chunk, no divergence / group passes between the stages.)
-	const bool piped = deferred && chunk == m && !want_div && !want_grp && ctx->block_pipe;
-	const int pb = piped ? (int)(ctx->pipe_next++ & 1) : 0;
-	hipStream_t tail = piped ? ctx->tail_stream : ctx->stream;
-	DevBuf& b_qT = pb ? ctx->kb_qT2 : ctx->kb_qT;
-	DevBuf& b_min = pb ? ctx->kb_min2 : ctx->kb_min;
-	DevBuf& b_diff = pb ? ctx->kb_diff2 : ctx->kb_diff;
-	DevBuf& b_anib = pb ? ctx->kb_anib2 : ctx->kb_anib;
-	DevBuf& b_hot = pb ? ctx->kb_hot2 : ctx->kb_hot;
-	DevBuf& b_hot_idx = pb ? ctx->kb_hot_idx2 : ctx->kb_hot_idx;
-	// the queries' side of a piped block goes on the prep stream, under the product of the block before it (MSC_GEMM_NO_PREP: on the product's stream, as in r04)
-	static const bool no_prep = getenv("MSC_GEMM_NO_PREP") != nullptr;
-	hipStream_t prep = piped && !no_prep ? ctx->prep_stream : ctx->stream;
-	if (ctx->tail_used)          // a block on ONE stream after piped ones waits for every epilogue in flight; a piped one for the epilogue that read its copy
-		for (int i = 0; i < 2; i++)
-			if (ctx->tail_busy[i] && (!piped || i == pb)) {
-				HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_tail[i], 0));
-				if (prep != ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(prep, ctx->ev_tail[i], 0));          // (it rewrites the transposed image that epilogue read)
-				if (!piped) ctx->tail_busy[i] = false;
-			}
-	if (manh_gemm) {
-		const uint64_t nsteps = L.nbins / 128;
-		if ((r = ensure(ctx, b_anib, msc_pair_gemm_anib_bytes(L.nbins, kb_qn))) || (r = ensure(ctx, b_qT, msc_pair_gemm_qt_bytes(L.nbins, kb_qn))) || (r = ensure(ctx, b_min, (size_t)gemm_slices * chunk * kb_qn * sizeof(int32_t)))) return r;
-		if (n_hot) {
-			if ((r = ensure(ctx, b_hot, n_hot * 8)) || (r = ensure(ctx, b_hot_idx, 3 * (nsteps + 1) * sizeof(uint32_t))) ||
-			    (r = ensure(ctx, b_diff, chunk * kb_qn * sizeof(int32_t)))) return r;
-			hot_ptr = (uint32_t*)b_hot_idx.p;
-			hot_cursor = hot_ptr + (nsteps + 1);
-			hot_cnt = hot_cursor + (nsteps + 1);
-		}
-		if (prep != ctx->stream) {
-			HIP_TRY(ctx, hipStreamWaitEvent(prep, ctx->ev_call, 0));          // the call's query slots are up
-			if (ctx->product_busy[pb]) HIP_TRY(ctx, hipStreamWaitEvent(prep, ctx->ev_product[pb], 0));      // the product that read this copy is through
-		}
-		// the queries' side of the block, once for all chunks of candidates
-		HIP_TRY(ctx, msc_launch_pair_gemm_queries(prep, L.nbins, qset->kb, qset->mb, qset->mb_n, qset->mb_pitch, dq_slots, (uint32_t)n_q, kb_qn,
-		                                          (uint8_t*)b_qT.p, n_hot, b_hot.p, hot_ptr, hot_cursor, hot_cnt, (uint8_t*)b_anib.p));
-		if (prep != ctx->stream) {
-			HIP_TRY(ctx, hipEventRecord(ctx->ev_prep[pb], prep));
-			HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_prep[pb], 0));
-		}
+	if (b.sum && (r = ensure(ctx, ctx->soa_sum, n_q * chunk * sizeof(double)))) return r;
+	if (b.csum && (r = ensure(ctx, ctx->soa_csum, n_q * chunk * sizeof(double)))) return r;
+	if (b.close && !flags_by_copy_stream && (r = ensure(ctx, ctx->soa_close, n_q * chunk))) return r;
+	if (b.close && flags_by_copy_stream && ((r = ensure(ctx, ctx->pipe.close_pp[0], n_q * chunk)) || (r = ensure(ctx, ctx->pipe.close_pp[1], n_q * chunk)))) return r;
+	if (b.raw && (r = ensure(ctx, ctx->raw, n_q * chunk * c.nf * sizeof(double)))) return r;
+	return MSC_OK;
+}
+
+Chunk chunk_at(const MultiCall& c, const Block& b, uint64_t off) {
+	const msc_hist_set* cands = c.cands;
+	const uint64_t first = c.cand_slots ? 0 : off;          // (a sparse set on the matrix-core pass has no bins, and nothing of that pass reads one)
+	return Chunk{off, (uint32_t)std::min(b.chunk, c.m - off), c.cand_slots ? (const uint32_t*)c.ctx->slots.p + off : nullptr,
+	             cands->bins ? cands->bins + first * cands->L.slot_bytes : nullptr, cands->scalars + first * cands->scalar_stride};
+}
+
+// the divergence and group passes of a chunk, on the context's stream behind the streaming kernel, and their part of the epilogue's arguments
+int side_passes(MultiCall& c, Block& b, const Chunk& k, MscEpilogueArgs& ea) {
+	msc_ctx* ctx = c.ctx;
+	const msc_hist_set *cands = c.cands, *qset = c.qset, *c_sp = c.c_sp, *q_sp = c.q_sp;
+	const MscLayout& L = cands->L;
+	const uint64_t n_q = b.nq, mc = k.mc;
+	if (c.want_div) {
+		for (uint64_t q = 0; q < n_q; q++)
+			HIP_TRY(ctx, launch_sparse_pass(ctx, b.spk, c_sp, cands->scalars, cands->scalar_stride, k.d_slots, k.off, mc, q_sp, b.q_slots[q],
+			                                qset->scalars + (uint64_t)b.q_slots[q] * qset->scalar_stride, L.nbins, 0, 0, ~0ull, (MscPartial*)ctx->sp_partials.p,
+			                                ctx->div_tables.p, (double*)ctx->div_partials.p + q * mc * b.dvn * 2, c.order, 1, b.dvn));
+		ea.div_direct = (const double*)ctx->div_partials.p; ea.div_direct_n = b.dvn; ea.div_base = L.nbins;
 	}
-	if (emd_ranks && (r = ensure(ctx, ctx->emd_out, chunk * (manh_gemm ? kb_qn : 64) * sizeof(uint64_t)))) return r;
-	const bool count_only = digest && tps == 2 && !digest_emd;
-	if (manh_gemm) {
-		snprintf(ctx->last_kernel_buf, sizeof ctx->last_kernel_buf, "%s<%u query rows, one matrix product per tile of presence bits%s%s>", msc_pair_gemm_kernel_name(), kb_qn, emd_ranks ? ", emd by ranks" : ", no emd",
-		         cands->sparse ? ", mirrors from lists" : "");
-		ctx->last_kernel = ctx->last_kernel_buf;
-	} else if (digest) {
-		snprintf(ctx->last_kernel_buf, sizeof ctx->last_kernel_buf, "k_pair_digest_multi<%s counts%s%s>", mc_ < 256 ? "u8" : "u16",
-		         emd_ranks ? ", emd by ranks" : count_only ? ", no emd" : "", gemm_dot ? ", dot by mfma" : "");
+	if (c.want_grp) {
+		double *gp = (double*)ctx->grp_pairs.p, *gs_c = (double*)ctx->grp_self.p, *gs_q = gs_c + b.chunk * 16;
+		if (c.grp_dense) {
+			HIP_TRY(ctx, msc_launch_self_markov_dense(ctx->stream, L, cands->dtype, cands->bins, k.d_slots, k.off, mc, gs_c));
+			HIP_TRY(ctx, msc_launch_self_markov_dense(ctx->stream, qset->L, qset->dtype, qset->bins, b.dq_slots, 0, (uint32_t)n_q, gs_q));
+			for (uint64_t q = 0; q < n_q; q++)
+				HIP_TRY(ctx, msc_launch_pair_groups_dense(ctx->stream, L, cands->dtype, k.c_bins, k.c_scal, cands->scalar_stride, k.d_slots, mc,
+				                                          qset->bins + (uint64_t)b.q_slots[q] * qset->L.slot_bytes, 0, 0, ~0ull, gp + q * mc * 32));
+		} else {
+			HIP_TRY(ctx, msc_launch_sparse_self_markov(ctx->stream, c_sp->ent, c_sp->hdr, k.d_slots, k.off, mc, gs_c));
+			HIP_TRY(ctx, msc_launch_sparse_self_markov(ctx->stream, q_sp->ent, q_sp->hdr, b.dq_slots, 0, (uint32_t)n_q, gs_q));
+			for (uint64_t q = 0; q < n_q; q++)
+				HIP_TRY(ctx, msc_launch_pair_sparse_groups(ctx->stream, c_sp->ent, c_sp->hdr + (k.d_slots ? 0 : k.off), k.c_scal, cands->scalar_stride, k.d_slots, mc, q_sp->ent,
+				                                           q_sp->hdr + b.q_slots[q], 0, 0, ~0ull, gp + q * mc * 32));
+		}
+		ea.grp_pairs = gp; ea.grp_self_c = gs_c; ea.grp_self_q = gs_q;
+	}
+	return MSC_OK;
+}
+
+// query-major [n_q][mc] on the device -> [n_q][m] at a column of the host's rows. (One chunk: the rows are contiguous on both sides -- a plain copy. A 2-D
+// copy whose width is not a multiple of four bytes goes row by row inside the runtime: 1 024 rows of 6 250 flags took 9 ms of a 1.7 ms step)
+hipError_t rows_home(void* dst, size_t dpitch, const void* src, size_t width, size_t rows, hipStream_t st) {
+	if (dpitch == width) return hipMemcpyAsync(dst, src, width * rows, hipMemcpyDeviceToHost, st);
+	return hipMemcpy2DAsync(dst, dpitch, src, width, width, rows, hipMemcpyDeviceToHost, st);
+}
+
+// sums and raw statistics of a chunk to the caller's arrays (the close flags go their route's own way)
+int results_home(MultiCall& c, Block& b, const Chunk& k) {
+	msc_ctx* ctx = c.ctx;
+	const uint64_t m = c.m;
+	if (b.sum) HIP_TRY(ctx, rows_home(b.sum + k.off, m * sizeof(double), ctx->soa_sum.p, (size_t)k.mc * sizeof(double), b.nq, b.tail));
+	if (b.csum) HIP_TRY(ctx, rows_home(b.csum + k.off, m * sizeof(double), ctx->soa_csum.p, (size_t)k.mc * sizeof(double), b.nq, b.tail));
+	if (b.raw) HIP_TRY(ctx, rows_home(b.raw + k.off * c.nf, m * c.nf * sizeof(double), ctx->raw.p, (size_t)k.mc * c.nf * sizeof(double), b.nq, b.tail));
+	return MSC_OK;
+}
+
+// a chunk that is not queued is waited for, and its streaming kernel's time read
+int chunk_done(msc_ctx* ctx, hipEvent_t ev_t0, hipEvent_t ev_t1) {
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	float t = 0;
+	if (ctx->timing && hipEventElapsedTime(&t, ev_t0, ev_t1) == hipSuccess) { ctx->tiles_ms_accum += t; ctx->tiles_launches++; ctx->have_timing = true; }
+	return MSC_OK;
+}
+
+// Sparse sets: one merge-path pass per query (up to k = 9 over the candidates' rank lists, msc_ranks_pass.hip, as in run_score), queued back
+// to back into one [n_q][m] record array with ONE epilogue and one copy back -- no host round trip between the passes.
+int run_sparse_queued(MultiCall& c, Block& b) {
+	msc_ctx* ctx = c.ctx;
+	const msc_hist_set *cands = c.cands, *qset = c.qset;
+	const MscLayout& L = cands->L;
+	const uint64_t n_q = b.nq, m = c.m;
+	const uint32_t* q_slots = b.q_slots;
+	int r;
+	if ((r = begin_block(ctx))) return r;
+	// (msc_launch_pair_sparse_mp hands a pass whose lists fit LDS whole to k_pair_sparse_wl: the name says which of the two the
+	// queries' passes ran, "k_pair_sparse_mp+wl" when some queries fit and some do not)
+	uint64_t n_wl = 0;
+	for (uint64_t q = 0; q < n_q; q++) n_wl += msc_sparse_wl_fits(qset->hdr_host[q_slots[q]].nnz, cands->max_nnz) ? 1 : 0;
+	ctx->last_kernel = n_wl == n_q ? "k_pair_sparse_wl" : n_wl ? "k_pair_sparse_mp+wl" : "k_pair_sparse_mp";
+	ctx->last_query_tile = 1; ctx->last_partial_stride = 1;
+	b.chunk = m;          // (every candidate in one launch per query: pick_route keeps n_q x m records within 4 GiB)
+	b.tail = ctx->stream;
+	if ((r = ensure(ctx, ctx->partials, n_q * m * sizeof(MscPartial))) || (r = ensure_block_scratch(c, b, false)) || (r = block_uploads(c, b, false))) return r;
+	const Chunk k = chunk_at(c, b, 0);
+	const uint64_t q_kmers = qset->max_sum >= L.nbins ? qset->max_sum - L.nbins : ~0ull;
+	bool rank_pass = false;
+	if (getenv("MSC_NO_RANKS_1XM") == nullptr && q_kmers <= msc_ranks_pass_query_cap() && msc_ranks_pass_lds(L.nbins, q_kmers) != 0) {
+		int e = MSC_OK;
+		rank_pass = rank_lists_ready(ctx, cands, &e);
+		if (e) return e;
+		if (rank_pass && !ctx->rk_guard) {
+			HIP_TRY(ctx, hipHostMalloc((void**)&ctx->rk_guard, 64, hipHostMallocDefault));
+			*ctx->rk_guard = 0;
+		}
+		if (rank_pass && msc_ranks_pass_query_scratch(q_kmers) && (r = ensure(ctx, ctx->rk_q, msc_ranks_pass_query_scratch(q_kmers) * sizeof(uint32_t)))) return r;
+		if (rank_pass) ctx->last_kernel = "k_pair_ranks_1xm";
+	}
+	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_all0, ctx->stream));
+	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_tiles0, ctx->stream));
+	for (uint64_t q = 0; q < n_q && rank_pass; q++)
+		HIP_TRY(ctx, msc_launch_pair_ranks_1xm(ctx->stream, cands->rkl, cands->rkl_off, cands->rkl_n, cands->scalars, cands->scalar_stride, k.d_slots, 0, (uint32_t)m, qset->ent, qset->cum,
+		                                       qset->hdr + q_slots[q], L.nbins, 0, 0, ~0ull, (MscPartial*)ctx->partials.p + q * m, ctx->num_cus, q_kmers, ctx->rk_guard, (uint32_t*)ctx->rk_q.p));
+	for (uint64_t q = 0; q < n_q && !rank_pass; q++)
+		HIP_TRY(ctx, msc_launch_pair_sparse_mp(ctx->stream, cands->ent, cands->cum, cands->hdr, cands->scalars, cands->scalar_stride, k.d_slots, (uint32_t)m, qset->ent,
+		                                       qset->cum, qset->hdr + q_slots[q], qset->scalars + (uint64_t)q_slots[q] * qset->scalar_stride, L.nbins, 0, 0, ~0ull,
+		                                       (MscPartial*)ctx->partials.p + q * m, nullptr, nullptr, c.order, ctx->num_cus,
+		                                       (uint32_t)std::min<uint64_t>(0x7fffffffull, (uint64_t)qset->hdr_host[q_slots[q]].nnz + cands->max_nnz), 1,
+		                                       qset->hdr_host[q_slots[q]].nnz, cands->max_nnz));
+	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_tiles1, ctx->stream));
+	MscEpilogueArgs ea;
+	fill_block_args(c, b, b.dq_slots, k, 1, ea);
+	ea.sparse_base = L.nbins;
+	ea.close_soa = b.close ? (uint8_t*)ctx->soa_close.p : nullptr;
+	HIP_TRY(ctx, msc_launch_epilogue(ctx->stream, ea));
+	if (b.close && ctx->close_counts_n) HIP_TRY(ctx, msc_launch_close_counts(ctx->stream, (const uint8_t*)ctx->soa_close.p, (uint32_t)n_q, (uint32_t)m, (uint64_t*)ctx->close_counts.p + b.q0));
+	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_all1, ctx->stream));
+	if ((r = results_home(c, b, k))) return r;
+	if (b.close) HIP_TRY(ctx, hipMemcpyAsync(b.close, ctx->soa_close.p, n_q * m, hipMemcpyDeviceToHost, ctx->stream));
+	int32_t first_err = 0;
+	HIP_TRY(ctx, hipMemcpyAsync(&first_err, ctx->err_word.p, sizeof first_err, hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	float t = 0;
+	if (ctx->timing && hipEventElapsedTime(&t, ctx->ev_tiles0, ctx->ev_tiles1) == hipSuccess) { ctx->tiles_ms_accum = t; ctx->tiles_launches = (int)n_q; ctx->have_timing = true; }
+	if (rank_pass && *ctx->rk_guard) {
+		*ctx->rk_guard = 0;
+		return fail(ctx, MSC_ERR_HIP, "rank pass: a query's list is longer than its set's bound (max_sum not maintained by a writer of that set)");
+	}
+	return error_word_status(ctx, first_err);
+}
+
+// The digest, ring and raw-tile kernels: partial records per (query, candidate), folded by the epilogue; one chunk at a time, waited for.
+int run_streamed(MultiCall& c, Block& b, const BlockRoute& rt) {
+	msc_ctx* ctx = c.ctx;
+	const msc_hist_set *cands = c.cands, *qset = c.qset;
+	const MscLayout& L = cands->L;
+	const uint64_t n_q = b.nq, m = c.m;
+	const bool digest = rt.kind == R_DIGEST, ring = rt.kind == R_RING;
+	int r;
+	if ((r = begin_block(ctx))) return r;
+	b.tail = ctx->stream;
+	if ((r = block_uploads(c, b, false))) return r;
+	const bool digest_emd = c.need_emd && !rt.emd_ranks;          // the digest kernel streams and scores the prefix half
+	const bool count_only = digest && rt.tps == 2 && !digest_emd;
+	// the digest kernel writes one record per step of tps tiles, four groups of four queries per workgroup; partial records of one launch
+	// are capped at 4 GiB: equal candidate chunks
+	const uint32_t n_rec = digest ? (uint32_t)(L.nbins / 1024) / rt.tps : L.S;
+	const uint64_t rec_bytes = digest || ring ? 16 : sizeof(MscPartial);
+	const uint64_t q_rows = digest ? (n_q + 15) / 16 * 16 : ring ? (n_q + rt.tq - 1) / rt.tq * rt.tq : n_q;       // records cover the padded query count
+	b.chunk = msc_cand_chunks(m, std::min<uint64_t>((4096ull << 20) / ((uint64_t)n_rec * rec_bytes * q_rows), group_chunk_limit(c, n_q))).chunk;
+	if ((r = ensure(ctx, ctx->partials, q_rows * b.chunk * n_rec * rec_bytes)) || (r = ensure_block_scratch(c, b, false))) return r;
+	if (rt.emd_ranks && (r = ensure(ctx, ctx->emd_out, b.chunk * 64 * sizeof(uint64_t)))) return r;
+	if (digest) {
+		snprintf(ctx->last_kernel_buf, sizeof ctx->last_kernel_buf, "k_pair_digest_multi<%s counts%s>", c.mc_ < 256 ? "u8" : "u16", rt.emd_ranks ? ", emd by ranks" : count_only ? ", no emd" : "");
 		ctx->last_kernel = ctx->last_kernel_buf;
 	} else ctx->last_kernel = ring ? "k_pair_tiles_multi32_ring" : "k_pair_tiles_multi";
 	// the digest kernel's workgroup scores up to 16 queries per candidate tile it fetches; the ring kernel's co-located query
 	// blocks fetch the tile once per group of tq queries (the followers usually hit in L2, which is not counted on)
-	ctx->last_query_tile = manh_gemm ? (int)n_q : digest ? (int)std::min<uint64_t>(n_q, 4 * dg_tq) : (int)std::min<uint64_t>(n_q, (uint64_t)tq);
-	const bool whole = chunk == m;                 // one chunk: results land in the caller's arrays with plain copies
+	ctx->last_query_tile = (int)std::min<uint64_t>(n_q, digest ? 16 : (uint64_t)rt.tq);
 	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_all0, ctx->stream));
-	for (uint64_t off = 0; off < m; off += chunk) {
-		const uint32_t mc = (uint32_t)std::min(chunk, m - off);
-		const uint32_t* d_slots = cand_slots ? (const uint32_t*)ctx->slots.p + off : nullptr;
-		const uint8_t* c_bins = cands->bins ? cands->bins + (cand_slots ? 0 : off * L.slot_bytes) : nullptr;          // (a sparse set on the matrix-core pass has none, and nothing of that pass reads a bin)
-		const uint8_t* c_scal = cands->scalars + (cand_slots ? 0 : off * cands->scalar_stride);
-		hipEvent_t ev_t0 = ctx->ev_tiles0, ev_t1 = ctx->ev_tiles1;
-		if (deferred && ctx->timing && ((r = pool_event(ctx, &ev_t0)) || (r = pool_event(ctx, &ev_t1)))) return r;      // (read when the call's last block is through)
-		if (piped) {          // everything the tail needs from this stream so far (slot lists, the cleared error word) is behind this mark
-			HIP_TRY(ctx, hipEventRecord(ctx->ev_head[pb], ctx->stream));
-			HIP_TRY(ctx, hipStreamWaitEvent(tail, ctx->ev_head[pb], 0));
-		}
-		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ev_t0, ctx->stream));
-		if (manh_gemm)         // the whole pass over the candidates' bins: products and level products on the matrix cores (timed as the streaming kernel)
-			HIP_TRY(ctx, msc_launch_pair_gemm(ctx->stream, L.nbins, cands->kb, d_slots, off, mc, kb_qn, gemm_slices, hot_ptr, b_hot.p,
-			                                  (int32_t*)b_min.p, (int32_t*)b_diff.p, (const uint8_t*)b_anib.p));
-		else if (digest)
-			HIP_TRY(ctx, msc_launch_pair_digest_multi(ctx->stream, L, cands->digest + (cand_slots ? 0 : off * msc_digest_slot_bytes(L)), d_slots, mc, qset->digest,
-			                                          dq_slots, (uint32_t)n_q, mc_ < 256, tps, digest_emd, ctx->partials.p, ctx->num_cus, !gemm_dot, dg_tq));
+	for (uint64_t off = 0; off < m; off += b.chunk) {
+		const Chunk k = chunk_at(c, b, off);
+		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_tiles0, ctx->stream));
+		if (digest)
+			HIP_TRY(ctx, msc_launch_pair_digest_multi(ctx->stream, L, cands->digest + (c.cand_slots ? 0 : off * msc_digest_slot_bytes(L)), k.d_slots, k.mc, qset->digest,
+			                                          b.dq_slots, (uint32_t)n_q, c.mc_ < 256, rt.tps, digest_emd, ctx->partials.p, ctx->num_cus, true, 4));
 		else if (ring)
-			HIP_TRY(ctx, msc_launch_pair_tiles_multi_ring(ctx->stream, L, cands->dtype, c_bins, c_scal, d_slots, mc, qset->bins, qset->L.slot_bytes, qset->scalars,
-			                                              qset->scalar_stride, dq_slots, (uint32_t)n_q, tq, prefix16, ctx->partials.p, ctx->num_cus));
+			HIP_TRY(ctx, msc_launch_pair_tiles_multi_ring(ctx->stream, L, cands->dtype, k.c_bins, k.c_scal, k.d_slots, k.mc, qset->bins, qset->L.slot_bytes, qset->scalars,
+			                                              qset->scalar_stride, b.dq_slots, (uint32_t)n_q, rt.tq, rt.prefix16, ctx->partials.p, ctx->num_cus));
 		else
-			HIP_TRY(ctx, msc_launch_pair_tiles_multi(ctx->stream, L, cands->dtype, c_bins, c_scal, d_slots, mc, qset->bins, qset->L.slot_bytes, qset->scalars,
-			                                         qset->scalar_stride, dq_slots, (uint32_t)n_q, tq, compact, (MscPartial*)ctx->partials.p, ctx->num_cus));
-		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ev_t1, ctx->stream));
-		if (piped) { HIP_TRY(ctx, hipEventRecord(ctx->ev_product[pb], ctx->stream)); ctx->product_busy[pb] = true; }
-		if (emd_ranks && cands->ranks16 && qset->ranks16 && cands->rk_pitch == qset->rk_pitch)          // every reduced rank of both sets fits 16 bits: two per v_sad_u16
-			HIP_TRY(ctx, msc_launch_emd_ranks16(tail, L.nbins, cands->ranks16, cands->rk_pitch, cands->rk_n, d_slots, off, mc, qset->ranks16, qset->rk_n,
-			                                    dq_slots, (uint32_t)n_q, (uint64_t*)ctx->emd_out.p, manh_gemm ? kb_qn : 64));
-		else if (emd_ranks)
-			HIP_TRY(ctx, msc_launch_emd_ranks(tail, L.nbins, cands->ranks, cands->rk_pitch, cands->rk_n, d_slots, off, mc, qset->ranks, qset->rk_pitch, qset->rk_n,
-			                                  dq_slots, (uint32_t)n_q, (uint64_t*)ctx->emd_out.p, manh_gemm ? kb_qn : 64));
-		if (want_div) {
-			for (uint64_t q = 0; q < n_q; q++)
-				HIP_TRY(ctx, launch_sparse_pass(ctx, spk, c_sp, cands->scalars, cands->scalar_stride, d_slots, off, mc, q_sp, q_slots[q],
-				                                qset->scalars + (uint64_t)q_slots[q] * qset->scalar_stride, L.nbins, 0, 0, ~0ull, (MscPartial*)ctx->sp_partials.p,
-				                                ctx->div_tables.p, (double*)ctx->div_partials.p + q * mc * dvn * 2, order, 1, dvn));
-		}
-		if (want_grp) {
-			double* gp = (double*)ctx->grp_pairs.p;
-			double* gs_c = (double*)ctx->grp_self.p;
-			double* gs_q = gs_c + chunk * 16;
-			const uint32_t* d_q = dq_slots;
-			if (grp_dense) {
-				HIP_TRY(ctx, msc_launch_self_markov_dense(ctx->stream, L, cands->dtype, cands->bins, d_slots, off, mc, gs_c));
-				HIP_TRY(ctx, msc_launch_self_markov_dense(ctx->stream, qset->L, qset->dtype, qset->bins, d_q, 0, (uint32_t)n_q, gs_q));
-				for (uint64_t q = 0; q < n_q; q++)
-					HIP_TRY(ctx, msc_launch_pair_groups_dense(ctx->stream, L, cands->dtype, c_bins, c_scal, cands->scalar_stride, d_slots, mc,
-					                                          qset->bins + (uint64_t)q_slots[q] * qset->L.slot_bytes, 0, 0, ~0ull, gp + q * mc * 32));
-			} else {
-				HIP_TRY(ctx, msc_launch_sparse_self_markov(ctx->stream, c_sp->ent, c_sp->hdr, d_slots, off, mc, gs_c));
-				HIP_TRY(ctx, msc_launch_sparse_self_markov(ctx->stream, q_sp->ent, q_sp->hdr, d_q, 0, (uint32_t)n_q, gs_q));
-				for (uint64_t q = 0; q < n_q; q++)
-					HIP_TRY(ctx, msc_launch_pair_sparse_groups(ctx->stream, c_sp->ent, c_sp->hdr + (d_slots ? 0 : off), c_scal, cands->scalar_stride, d_slots, mc, q_sp->ent,
-					                                           q_sp->hdr + q_slots[q], 0, 0, ~0ull, gp + q * mc * 32));
-			}
-		}
+			HIP_TRY(ctx, msc_launch_pair_tiles_multi(ctx->stream, L, cands->dtype, k.c_bins, k.c_scal, k.d_slots, k.mc, qset->bins, qset->L.slot_bytes, qset->scalars,
+			                                         qset->scalar_stride, b.dq_slots, (uint32_t)n_q, rt.tq, c.compact, (MscPartial*)ctx->partials.p, ctx->num_cus));
+		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_tiles1, ctx->stream));
+		if (rt.emd_ranks) HIP_TRY(ctx, launch_emd_ranks(ctx->stream, cands, qset, k.d_slots, off, k.mc, b.dq_slots, (uint32_t)n_q, (uint64_t*)ctx->emd_out.p, 64));
 		MscEpilogueArgs ea;
-		memset(&ea, 0, sizeof ea);
-		ea.partials = (const MscPartial*)ctx->partials.p;
-		if (want_div) { ea.div_direct = (const double*)ctx->div_partials.p; ea.div_direct_n = dvn; ea.div_base = L.nbins; }
-		if (want_grp) { ea.grp_pairs = (const double*)ctx->grp_pairs.p; ea.grp_self_c = (const double*)ctx->grp_self.p; ea.grp_self_q = (const double*)ctx->grp_self.p + chunk * 16; }
+		fill_block_args(c, b, b.dq_slots, k, n_rec, ea);
+		if ((r = side_passes(c, b, k, ea))) return r;
 		ea.partials16 = ring ? ctx->partials.p : nullptr;
 		ea.partials_cq = digest ? ctx->partials.p : nullptr;
-		if (manh_gemm) {
-			ea.kb_min = (const int32_t*)b_min.p;
-			ea.kb_diff = n_hot ? (const int32_t*)b_diff.p : nullptr;
-			ea.kb_slices = gemm_slices;
-			ea.kb_qn = kb_qn;
-			ea.kb_first = cand_slots ? 0 : off;
-			ea.kb_c_mb = cands->mb; ea.kb_c_mb_n = cands->mb_n; ea.kb_c_pitch = cands->mb_pitch;
-			ea.kb_q_mb = qset->mb; ea.kb_q_mb_n = qset->mb_n; ea.kb_q_pitch = qset->mb_pitch;
-			ea.kb_qT = (const uint8_t*)b_qT.p;
-			ea.emd_stride = kb_qn;
+		ea.cq_group = 16;
+		if (rt.emd_ranks) ea.emd_ranks = (const uint64_t*)ctx->emd_out.p;
+		ea.close_soa = b.close ? (uint8_t*)ctx->soa_close.p : nullptr;
+		HIP_TRY(ctx, msc_launch_epilogue(ctx->stream, ea));
+		if (b.close && ctx->close_counts_n) HIP_TRY(ctx, msc_launch_close_counts(ctx->stream, ea.close_soa, (uint32_t)n_q, k.mc, (uint64_t*)ctx->close_counts.p + b.q0));
+		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_all1, ctx->stream));
+		if ((r = results_home(c, b, k))) return r;
+		if (b.close) HIP_TRY(ctx, rows_home(b.close + off, m, ea.close_soa, (size_t)k.mc, n_q, ctx->stream));
+		if ((r = chunk_done(ctx, ctx->ev_tiles0, ctx->ev_tiles1))) return r;
+	}
+	return read_error_word(ctx);
+}
+
+// The matrix cores. Queued blocks run in stages on three streams (BlockPipe, msc_objects.h): the product of block i on the context's stream beside the rank
+// walk of block i and the epilogue of block i - 1 on tail_stream, the queries' side of block i + 1 on prep_stream -- the product is bound by the matrix pipe,
+// the others by vector arithmetic and latency. Blocks take turns on the two sides of the pipe. (Single chunk, no divergence / group passes between the stages;
+// MSC_GEMM_NO_PREP: the queries' side on the product's stream, as in r04.) The close flags go into one of two buffers and home on the copy stream, under the next block's kernels.
+int run_matrix(MultiCall& c, Block& b, const BlockRoute& rt) {
+	msc_ctx* ctx = c.ctx;
+	BlockPipe& pipe = ctx->pipe;
+	const msc_hist_set *cands = c.cands, *qset = c.qset;
+	const MscLayout& L = cands->L;
+	const uint64_t n_q = b.nq, m = c.m;
+	const bool queued = rt.queued;
+	int r;
+	if ((r = begin_block(ctx))) return r;
+	if ((r = block_uploads(c, b, queued))) return r;
+	const uint32_t rows = msc_pair_gemm_rows((uint32_t)n_q);
+	b.chunk = matrix_chunks(ctx, L.nbins, m, rows, group_chunk_limit(c, n_q)).chunk;
+	if ((r = ensure_block_scratch(c, b, true))) return r;
+	const uint32_t slices = msc_pair_gemm_slices(L.nbins, (uint32_t)b.chunk, rows, ctx->num_cus);
+	const bool piped = queued && b.chunk == m && !c.want_div && !c.want_grp && ctx->block_pipe;
+	const int pb = piped ? (int)(pipe.next++ & 1) : 0;
+	BlockPipe::Side& s = pipe.side[pb];
+	b.tail = piped ? pipe.tail_stream : ctx->stream;
+	static const bool no_prep = getenv("MSC_GEMM_NO_PREP") != nullptr;
+	hipStream_t prep = piped && !no_prep ? pipe.prep_stream : ctx->stream;
+	if (pipe.tail_used)          // a block on ONE stream after piped ones waits for every epilogue in flight; a piped one for the epilogue that read its side
+		for (int i = 0; i < 2; i++)
+			if (pipe.side[i].tail_busy && (!piped || i == pb)) {
+				HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, pipe.side[i].ev_tail, 0));
+				if (prep != ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(prep, pipe.side[i].ev_tail, 0));          // (it rewrites the transposed image that epilogue read)
+				if (!piped) pipe.side[i].tail_busy = false;
+			}
+	HotList hot;
+	if ((r = ensure_side(ctx, s, L.nbins, rows, slices, b.chunk, rt.n_hot, &hot))) return r;
+	if (prep != ctx->stream) {
+		HIP_TRY(ctx, hipStreamWaitEvent(prep, pipe.ev_call, 0));          // the call's query slots are up
+		if (s.product_busy) HIP_TRY(ctx, hipStreamWaitEvent(prep, s.ev_product, 0));      // the product that read this side is through
+	}
+	// the queries' side of the block, once for all chunks of candidates
+	HIP_TRY(ctx, msc_launch_pair_gemm_queries(prep, L.nbins, qset->kb, qset->mb, qset->mb_n, qset->mb_pitch, b.dq_slots, (uint32_t)n_q, rows, (uint8_t*)s.qT.p, rt.n_hot, s.hot.p,
+	                                          hot.ptr, hot.cursor, hot.cnt, (uint8_t*)s.anib.p));
+	if (prep != ctx->stream) {
+		HIP_TRY(ctx, hipEventRecord(s.ev_prep, prep));
+		HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.ev_prep, 0));
+	}
+	if (rt.emd_ranks && (r = ensure(ctx, ctx->emd_out, b.chunk * rows * sizeof(uint64_t)))) return r;
+	name_matrix_kernel(ctx, rows, rt.emd_ranks, false, cands->sparse);
+	ctx->last_query_tile = (int)n_q;
+	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_all0, ctx->stream));
+	for (uint64_t off = 0; off < m; off += b.chunk) {
+		const Chunk k = chunk_at(c, b, off);
+		hipEvent_t ev_t0 = ctx->ev_tiles0, ev_t1 = ctx->ev_tiles1;
+		if (queued && ctx->timing && ((r = pool_event(ctx, &ev_t0)) || (r = pool_event(ctx, &ev_t1)))) return r;      // (read when the call's last block is through)
+		if (piped) {          // everything the tail needs from this stream so far (slot lists, the cleared error word) is behind this mark
+			HIP_TRY(ctx, hipEventRecord(s.ev_head, ctx->stream));
+			HIP_TRY(ctx, hipStreamWaitEvent(b.tail, s.ev_head, 0));
 		}
-		ea.cq_group = 4 * dg_tq;
-		if (emd_ranks) ea.emd_ranks = (const uint64_t*)ctx->emd_out.p;
-		ea.S = n_rec;
-		ea.m = (uint32_t)(n_q * mc);
-		ea.cand_scalars = c_scal;
-		ea.cand_scalar_stride = cands->scalar_stride;
-		ea.cand_slots = d_slots;
-		ea.n_queries = (uint32_t)n_q;
-		ea.m_per_query = mc;
-		ea.q_slots = dq_slots;
-		ea.qset_scalars = qset->scalars;
-		ea.q_scalar_stride = qset->scalar_stride;
-		ea.q_scalars = qset->scalars + (uint64_t)q_slots[0] * qset->scalar_stride;
-		ea.nbins = L.nbins;
-		ea.dtype = cands->dtype;
-		ea.order = order;
-		ea.feat_mask = feat_mask;
-		ea.raw_out = raw_out ? (double*)ctx->raw.p : nullptr;
-		ea.model = model ? model->d : nullptr;
-		ea.sum_soa = sum_out ? (double*)ctx->soa_sum.p : nullptr;
-		ea.csum_soa = csum_out ? (double*)ctx->soa_csum.p : nullptr;
-		// (matrix-core pass: the flags go into one of two buffers and back to the host on the copy stream, under the next block's kernels)
-		const int pp = ctx->close_pp_next;
-		uint8_t* d_close = !close_out ? nullptr : manh_gemm ? (uint8_t*)ctx->close_pp[pp].p : (uint8_t*)ctx->soa_close.p;
-		if (close_out && manh_gemm) {
-			ctx->close_pp_next ^= 1;
-			if (ctx->close_pp_busy[pp]) HIP_TRY(ctx, hipStreamWaitEvent(tail, ctx->ev_copied[pp], 0));
+		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ev_t0, ctx->stream));
+		// the whole pass over the candidates' bins: products and level products on the matrix cores (timed as the streaming kernel)
+		HIP_TRY(ctx, msc_launch_pair_gemm(ctx->stream, L.nbins, cands->kb, k.d_slots, off, k.mc, rows, slices, hot.ptr, s.hot.p, (int32_t*)s.min.p, (int32_t*)s.diff.p, (const uint8_t*)s.anib.p));
+		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ev_t1, ctx->stream));
+		if (piped) { HIP_TRY(ctx, hipEventRecord(s.ev_product, ctx->stream)); s.product_busy = true; }
+		if (rt.emd_ranks) HIP_TRY(ctx, launch_emd_ranks(b.tail, cands, qset, k.d_slots, off, k.mc, b.dq_slots, (uint32_t)n_q, (uint64_t*)ctx->emd_out.p, rows));
+		MscEpilogueArgs ea;
+		fill_block_args(c, b, b.dq_slots, k, L.S, ea);
+		if ((r = side_passes(c, b, k, ea))) return r;
+		fill_matrix_args(ea, s, cands, qset, slices, rows, c.cand_slots ? 0 : off, rt.n_hot, rt.emd_ranks ? ctx->emd_out.p : nullptr);
+		ea.cq_group = 16;
+		const int pp = pipe.close_pp_next;
+		uint8_t* d_close = b.close ? (uint8_t*)pipe.close_pp[pp].p : nullptr;
+		if (b.close) {
+			pipe.close_pp_next ^= 1;
+			if (pipe.close_pp_busy[pp]) HIP_TRY(ctx, hipStreamWaitEvent(b.tail, pipe.ev_copied[pp], 0));
 		}
 		ea.close_soa = d_close;
 		// only the close flags are wanted: k_pair_epilogue_bits decides them in f32 with an error bound and evaluates in FP64 only the
 		// pairs the bound leaves open -- the same flags (MSC_NO_SCREEN: FP64 for every pair)
 		static const bool no_screen = getenv("MSC_NO_SCREEN") != nullptr;
-		ea.screen = manh_gemm && model && model->h.screen_ok && d_close && !sum_out && !csum_out && !raw_out && !want_div && !want_grp && !no_screen;
-		ea.error_word = (int32_t*)ctx->err_word.p;
-		if (piped) HIP_TRY(ctx, hipStreamWaitEvent(tail, ctx->ev_product[pb], 0));
-		HIP_TRY(ctx, msc_launch_epilogue(tail, ea));
-		if (close_out && ctx->close_counts_n) HIP_TRY(ctx, msc_launch_close_counts(tail, d_close, (uint32_t)n_q, mc, (uint64_t*)ctx->close_counts.p + ctx->close_counts_base));
+		ea.screen = c.model && c.model->h.screen_ok && d_close && !b.sum && !b.csum && !b.raw && !c.want_div && !c.want_grp && !no_screen;
+		if (piped) HIP_TRY(ctx, hipStreamWaitEvent(b.tail, s.ev_product, 0));
+		HIP_TRY(ctx, msc_launch_epilogue(b.tail, ea));
+		if (b.close && ctx->close_counts_n) HIP_TRY(ctx, msc_launch_close_counts(b.tail, d_close, (uint32_t)n_q, k.mc, (uint64_t*)ctx->close_counts.p + b.q0));
 		if (piped) {
-			HIP_TRY(ctx, hipEventRecord(ctx->ev_tail[pb], tail));
-			ctx->tail_busy[pb] = true;
-			ctx->tail_used = true;
+			HIP_TRY(ctx, hipEventRecord(s.ev_tail, b.tail));
+			s.tail_busy = true;
+			pipe.tail_used = true;
 		}
 		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_all1, ctx->stream));
-		// query-major [n_q][mc] on the device -> [n_q][m] at column `off` on the host
-		const size_t rows = (size_t)n_q;
-		// (one chunk: the rows are contiguous on both sides -- a plain copy. A 2-D copy whose width is not a multiple of four bytes goes row
-		// by row inside the runtime: 1 024 rows of 6 250 flags took 9 ms of a 1.7 ms step)
-		auto rows_home = [&](void* dst, size_t dpitch, const void* src, size_t width, hipStream_t st) -> hipError_t {
-			if (dpitch == width) return hipMemcpyAsync(dst, src, width * rows, hipMemcpyDeviceToHost, st);
-			return hipMemcpy2DAsync(dst, dpitch, src, width, width, rows, hipMemcpyDeviceToHost, st);
-		};
-		if (sum_out) HIP_TRY(ctx, rows_home(sum_out + off, m * sizeof(double), ctx->soa_sum.p, (size_t)mc * sizeof(double), tail));
-		if (csum_out) HIP_TRY(ctx, rows_home(csum_out + off, m * sizeof(double), ctx->soa_csum.p, (size_t)mc * sizeof(double), tail));
-		if (close_out && manh_gemm) {
-			HIP_TRY(ctx, hipEventRecord(ctx->ev_scored[pp], tail));
-			HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_scored[pp], 0));
-			HIP_TRY(ctx, rows_home(close_out + off, m, d_close, (size_t)mc, ctx->copy_stream));
-			HIP_TRY(ctx, hipEventRecord(ctx->ev_copied[pp], ctx->copy_stream));
-			ctx->close_pp_busy[pp] = true;
-			ctx->copy_pending = true;
-		} else if (close_out) HIP_TRY(ctx, rows_home(close_out + off, m, d_close, (size_t)mc, tail));
-		if (raw_out) HIP_TRY(ctx, rows_home(raw_out + off * nf, m * nf * sizeof(double), ctx->raw.p, (size_t)mc * nf * sizeof(double), tail));
-		if (deferred) { ctx->tiles_launches++; continue; }
-		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-		float t = 0;
-		if (ctx->timing && hipEventElapsedTime(&t, ev_t0, ev_t1) == hipSuccess) { ctx->tiles_ms_accum += t; ctx->tiles_launches++; ctx->have_timing = true; }
-		(void)whole;
+		if ((r = results_home(c, b, k))) return r;
+		if (b.close) {
+			HIP_TRY(ctx, hipEventRecord(pipe.ev_scored[pp], b.tail));
+			HIP_TRY(ctx, hipStreamWaitEvent(pipe.copy_stream, pipe.ev_scored[pp], 0));
+			HIP_TRY(ctx, rows_home(b.close + off, m, d_close, (size_t)k.mc, n_q, pipe.copy_stream));
+			HIP_TRY(ctx, hipEventRecord(pipe.ev_copied[pp], pipe.copy_stream));
+			pipe.close_pp_busy[pp] = true;
+			pipe.copy_pending = true;
+		}
+		if (queued) ctx->tiles_launches++;
+		else if ((r = chunk_done(ctx, ev_t0, ev_t1))) return r;
 	}
-	if (deferred) return MSC_OK;
-	return read_error_word(ctx);
+	return queued ? MSC_OK : read_error_word(ctx);
 }
 
+// validate, decide kb_fit once, plan the blocks, run each on its route, wait for what was queued
+int score_multi(MultiCall& c) {
+	msc_ctx* ctx = c.ctx;
+	const msc_hist_set *cands = c.cands, *qset = c.qset;
+	const uint64_t n_q = c.n_q, m = c.m;
+	if (!ctx || !cands || !qset || !c.q_slots || (c.model && c.model->ctx != ctx)) return MSC_ERR_INVALID_ARG;
+	if (c.raw_out && (c.feat_mask == 0 || (c.feat_mask & ~kSupportedFeats))) return fail(ctx, MSC_ERR_UNSUPPORTED, "feat_mask holds statistics outside the GPU path");
+	if (!c.raw_out) c.feat_mask = 0;
+	if (n_q == 0 || m == 0) return MSC_OK;
+	for (uint64_t i = 0; i < n_q; i++) if (c.q_slots[i] >= qset->capacity) return fail(ctx, MSC_ERR_INVALID_ARG, "query slot out of range");
+	int r = validate_pair(ctx, cands, qset, c.q_slots[0], c.cand_slots, m);
+	if (r) return r;
+	const MscLayout& L = cands->L;
+	c.nf = __builtin_popcountll(c.feat_mask);
+	c.want = c.feat_mask;
+	if (c.model) for (int i = 0; i < c.model->h.n_singles; i++) c.want |= c.model->h.single_flag[i];
+	c.need_emd = (c.want & MSC_FEAT_EMD) != 0;           // Feature::compute evaluates only the model's singles too
+	c.want_div = (c.want & MSC_FEAT_DIV) != 0; c.want_grp = (c.want & MSC_FEAT_GROUPS) != 0;
+	// The pass on the matrix cores (msc_pair_gemm.hip) serves blocks of up to 128 queries per pass over the candidates' bits; the older routes 64
+	// (two sparse sets, msc_set_sparse_matrix_pass: a divergence or group statistic keeps the call on the merge kernels, blocks of 64 and all)
+	c.kb_fit = n_q >= 2 && kb_route_fits(cands, qset, c.need_emd) && !(cands->sparse && (c.want_div || c.want_grp));
+	if (c.kb_fit) {
+		if ((r = ensure_kb(ctx, cands)) || (r = ensure_kb(ctx, qset))) return r;
+		c.kb_fit = cands->kb && qset->kb && !cands->kb_has_zero && !qset->kb_has_zero;
+	}
+	// close candidates per query, kept on the device for msc_last_close_counts (a caller that only needs the counts of a block of the
+	// pairwise matrix does not have to add up n_q x m flags on the host)
+	ctx->close_counts_n = 0;
+	if (c.close_out) {
+		if ((r = ensure(ctx, ctx->close_counts, n_q * sizeof(uint64_t)))) return r;
+		HIP_TRY(ctx, hipMemsetAsync(ctx->close_counts.p, 0, n_q * sizeof(uint64_t), ctx->stream));
+		ctx->close_counts_n = n_q;
+	}
+	const bool whole_tiles = L.nbins == L.padded_bins && !needs_wide(cands, qset);
+	if ((c.want_div || c.want_grp) && !cands->sparse && n_q > 1 && whole_tiles) {          // the sparse mirrors of two dense sets, both or neither
+		if ((r = ensure_sparse_mirror(ctx, cands, &c.c_sp)) || (r = ensure_sparse_mirror(ctx, qset, &c.q_sp))) return r;
+		if (!c.c_sp || !c.q_sp) c.c_sp = c.q_sp = nullptr;
+	}
+	c.grp_dense = c.want_grp && !c.c_sp;
+	c.mc_ = std::max(cands->max_count, qset->max_count); c.ms_ = std::max(cands->max_sum, qset->max_sum);
+	c.simple = !cands->sparse && (!c.grp_dense || c.mc_ <= 0xffffffffull) && (!c.want_div || c.c_sp) && whole_tiles;
+	// wave totals of the per-lane 32-bit partial sums fit 32 bits when 64*R*max^2 and 64*R*max|prefix difference| do
+	c.compact = 64ull * L.R * c.mc_ * c.mc_ < (1ull << 32) && 64ull * L.R * c.ms_ < (1ull << 32);
+	// every prefix of excess counts (count - 1) is at most the histogram's k-mer total = sum - 4^k: 16-bit prefix form when that fits
+	c.excess16 = c.ms_ >= L.nbins && c.ms_ - L.nbins < 65536;
+	int err = MSC_OK;
+	msc_multi_plan(n_q, c.kb_fit, [&](uint64_t q0, uint64_t nq) {
+		const BlockRoute rt = err ? BlockRoute() : pick_route(c, c.q_slots + q0, nq, true, &err);
+		if (rt.kind == R_MATRIX) c.taken.push_back(rt);
+		return rt.kind != R_MATRIX;
+	}, c.blocks);
+	if (err) return err;
+	size_t next_taken = 0;
+	for (const MscMultiBlock& pb : c.blocks) {
+		Block b{pb.q0, pb.nq, c.q_slots + pb.q0, c.sum_out ? c.sum_out + pb.q0 * m : nullptr, c.csum_out ? c.csum_out + pb.q0 * m : nullptr,
+		              c.raw_out ? c.raw_out + pb.q0 * m * c.nf : nullptr, c.close_out ? c.close_out + pb.q0 * m : nullptr};
+		// (blocks of the matrix-core pass are queued without a host wait between them: any other route first waits for them and reads their error word)
+		r = pb.matrix ? MSC_OK : flush_deferred(c);
+		BlockRoute rt;
+		if (pb.matrix) rt = c.taken[next_taken++];
+		else if (!r) rt = pick_route(c, b.q_slots, b.nq, false, &r);
+		if (!r && rt.queued && !c.queue_up) {          // the first queued block: the whole call's query slots go up once
+			if (!(r = ensure(ctx, ctx->qslots_all, n_q * sizeof(uint32_t)))) {
+				HIP_TRY(ctx, hipMemcpyAsync(ctx->qslots_all.p, c.q_slots, n_q * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+				HIP_TRY(ctx, hipEventRecord(ctx->pipe.ev_call, ctx->stream));
+				ctx->pipe.ev_used = 0; c.queue_up = true;
+			}
+		}
+		if (!r) switch (rt.kind) {
+			case R_MATRIX: r = run_matrix(c, b, rt); break;
+			case R_DIGEST: case R_RING: case R_TILES: r = run_streamed(c, b, rt); break;
+			case R_SPARSE_QUEUED: r = run_sparse_queued(c, b); break;
+			case R_PER_QUERY: r = run_per_query(c, b); break;
+		}
+		if (r) { (void)flush_deferred(c); return r; }          // (nothing of this call may still be running when it returns)
+		c.ms += ctx->tiles_ms_accum; c.launches += ctx->tiles_launches;
+	}
+	if ((r = flush_deferred(c))) return r;
+	ctx->tiles_ms_accum = c.ms; ctx->tiles_launches = c.launches;
+	return MSC_OK;
+}
+
+}  // namespace
+
+extern "C" int msc_score_multi(msc_ctx* ctx, const msc_model* model, const msc_hist_set* cands, const uint32_t* cand_slots, uint64_t m,
+                               const msc_hist_set* qset, const uint32_t* q_slots, uint64_t n_q, int order, double* sum_out, double* csum_out,
+                               uint8_t* close_out, uint64_t feat_mask, double* raw_out) {
+	MultiCall c{ctx, model, cands, cand_slots, m, qset, q_slots, n_q, order, sum_out, csum_out, close_out, feat_mask, raw_out};
+	const int r = score_multi(c);
+	if (ctx && ctx->pipe.copy_pending) {          // the flag copies of the last blocks (issued beside the kernels that followed them)
+		const hipError_t e = hipStreamSynchronize(ctx->pipe.copy_stream);
+		ctx->pipe.copy_pending = ctx->pipe.close_pp_busy[0] = ctx->pipe.close_pp_busy[1] = false;
+		if (e != hipSuccess && r == MSC_OK) return fail(ctx, MSC_ERR_HIP, "copy of the close flags failed: %s", hipGetErrorString(e));
+	}
+	return r;
+}

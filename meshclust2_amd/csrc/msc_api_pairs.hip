@@ -137,37 +137,24 @@ int run_matrix(PairsCall& c) {
 	uint64_t uncut = 0;          // msc_search_pairs_top: pairs listed before the cut
 	const bool cut = c.top_n != 0;
 	const bool screen = c.cls && c.cls->h.screen_ok;
-	const bool emd16 = c.need_emd && cands->ranks16 && qset->ranks16 && cands->rk_pitch == qset->rk_pitch;
 	uint32_t last_qn = 0;
+	BlockPipe::Side& side = ctx->pipe.side[0];
 	for (const PairsBlock& b : c.blocks) {
 		const uint32_t nb = (uint32_t)b.nq;
 		const uint64_t mall = b.hi - b.lo;
 		const uint32_t kb_qn = msc_pair_gemm_rows(nb);
 		last_qn = kb_qn;
-		uint64_t n_hot = 0;
-		for (uint64_t q = b.q0; q < b.q0 + nb; q++) n_hot += std::min(qset->mb_n_host[c.q_slots[q]], qset->mb_pitch);
-		// candidate chunks as msc_score_multi cuts them: the product array [slices][chunk][rows] int32 within 2 GiB
-		uint64_t chunk = (2048ull << 20) / ((uint64_t)msc_pair_gemm_slices(L.nbins, (uint32_t)std::min<uint64_t>(mall, 1u << 30), kb_qn, ctx->num_cus) * kb_qn * sizeof(int32_t));
-		chunk = std::min(std::max<uint64_t>(chunk, 256), mall);
-		chunk = (mall + (mall + chunk - 1) / chunk - 1) / ((mall + chunk - 1) / chunk);
-		const uint32_t n_chunks = (uint32_t)((mall + chunk - 1) / chunk);
+		const uint64_t n_hot = block_hot_size(qset, c.q_slots + b.q0, nb);
+		const MscCandChunks cc = matrix_chunks(ctx, L.nbins, mall, kb_qn);          // candidate chunks as msc_score_multi cuts them
+		const uint64_t chunk = cc.chunk;
+		const uint32_t n_chunks = (uint32_t)cc.n;
 		const bool stage = n_chunks > 1 || cut;          // the block's pairs go to the staging list first
 		const uint32_t slices = msc_pair_gemm_slices(L.nbins, (uint32_t)chunk, kb_qn, ctx->num_cus);
 		const uint32_t tiles = msc_pair_list_tiles((uint32_t)chunk);
-		const uint64_t nsteps = L.nbins / 128;
-		if ((r = ensure(ctx, ctx->kb_anib, msc_pair_gemm_anib_bytes(L.nbins, kb_qn))) || (r = ensure(ctx, ctx->kb_qT, msc_pair_gemm_qt_bytes(L.nbins, kb_qn))) ||
-		    (r = ensure(ctx, ctx->kb_min, (size_t)slices * chunk * kb_qn * sizeof(int32_t))) ||
-		    (r = ensure(ctx, ctx->pl_counts, (size_t)nb * tiles * sizeof(uint32_t))) || (r = ensure(ctx, ctx->pl_offsets, ((size_t)nb * tiles + 1) * sizeof(uint64_t))))
+		HotList hot;
+		if ((r = ensure_side(ctx, side, L.nbins, kb_qn, slices, chunk, n_hot, &hot)) || (r = ensure(ctx, ctx->pl_counts, (size_t)nb * tiles * sizeof(uint32_t))) ||
+		    (r = ensure(ctx, ctx->pl_offsets, ((size_t)nb * tiles + 1) * sizeof(uint64_t))))
 			return r;
-		uint32_t *hot_ptr = nullptr, *hot_cursor = nullptr, *hot_cnt = nullptr;
-		if (n_hot) {
-			if ((r = ensure(ctx, ctx->kb_hot, n_hot * 8)) || (r = ensure(ctx, ctx->kb_hot_idx, 3 * (nsteps + 1) * sizeof(uint32_t))) ||
-			    (r = ensure(ctx, ctx->kb_diff, chunk * kb_qn * sizeof(int32_t))))
-				return r;
-			hot_ptr = (uint32_t*)ctx->kb_hot_idx.p;
-			hot_cursor = hot_ptr + (nsteps + 1);
-			hot_cnt = hot_cursor + (nsteps + 1);
-		}
 		if (c.need_emd && (r = ensure(ctx, ctx->emd_out, chunk * kb_qn * sizeof(uint64_t)))) return r;
 		if (c.cls && (r = ensure(ctx, ctx->pl_flags, (size_t)nb * chunk))) return r;
 		if (stage) {
@@ -179,48 +166,19 @@ int run_matrix(PairsCall& c) {
 		const uint64_t* dwh = c.windows ? (const uint64_t*)ctx->pl_win.p + n_q + b.q0 : nullptr;
 		uint8_t* flags = c.cls ? (uint8_t*)ctx->pl_flags.p : nullptr;
 		// the queries' side of the block, once for all chunks of candidates
-		HIP_TRY(ctx, msc_launch_pair_gemm_queries(st, L.nbins, qset->kb, qset->mb, qset->mb_n, qset->mb_pitch, dq, nb, kb_qn, (uint8_t*)ctx->kb_qT.p, n_hot, ctx->kb_hot.p,
-		                                          hot_ptr, hot_cursor, hot_cnt, (uint8_t*)ctx->kb_anib.p));
+		HIP_TRY(ctx, msc_launch_pair_gemm_queries(st, L.nbins, qset->kb, qset->mb, qset->mb_n, qset->mb_pitch, dq, nb, kb_qn, (uint8_t*)side.qT.p, n_hot, side.hot.p,
+		                                          hot.ptr, hot.cursor, hot.cnt, (uint8_t*)side.anib.p));
 		uint64_t staged = 0;
 		uint32_t ci = 0;
 		for (uint64_t off = b.lo; off < b.hi; off += chunk, ci++) {
 			const uint32_t mc = (uint32_t)std::min(chunk, b.hi - off);
 			const uint32_t* d_slots = c.cand_slots ? (const uint32_t*)ctx->slots.p + off : nullptr;
-			HIP_TRY(ctx, msc_launch_pair_gemm(st, L.nbins, cands->kb, d_slots, off, mc, kb_qn, slices, hot_ptr, ctx->kb_hot.p, (int32_t*)ctx->kb_min.p,
-			                                  (int32_t*)ctx->kb_diff.p, (const uint8_t*)ctx->kb_anib.p));
-			if (emd16)
-				HIP_TRY(ctx, msc_launch_emd_ranks16(st, L.nbins, cands->ranks16, cands->rk_pitch, cands->rk_n, d_slots, off, mc, qset->ranks16, qset->rk_n, dq, nb,
-				                                    (uint64_t*)ctx->emd_out.p, kb_qn));
-			else if (c.need_emd)
-				HIP_TRY(ctx, msc_launch_emd_ranks(st, L.nbins, cands->ranks, cands->rk_pitch, cands->rk_n, d_slots, off, mc, qset->ranks, qset->rk_pitch, qset->rk_n, dq, nb,
-				                                  (uint64_t*)ctx->emd_out.p, kb_qn));
+			HIP_TRY(ctx, msc_launch_pair_gemm(st, L.nbins, cands->kb, d_slots, off, mc, kb_qn, slices, hot.ptr, side.hot.p, (int32_t*)side.min.p, (int32_t*)side.diff.p,
+			                                  (const uint8_t*)side.anib.p));
+			if (c.need_emd) HIP_TRY(ctx, launch_emd_ranks(st, cands, qset, d_slots, off, mc, dq, nb, (uint64_t*)ctx->emd_out.p, kb_qn));
 			MscEpilogueArgs ea;
-			memset(&ea, 0, sizeof ea);
-			ea.kb_min = (const int32_t*)ctx->kb_min.p;
-			ea.kb_diff = n_hot ? (const int32_t*)ctx->kb_diff.p : nullptr;
-			ea.kb_slices = slices;
-			ea.kb_qn = kb_qn;
-			ea.kb_first = c.cand_slots ? 0 : off;
-			ea.kb_c_mb = cands->mb; ea.kb_c_mb_n = cands->mb_n; ea.kb_c_pitch = cands->mb_pitch;
-			ea.kb_q_mb = qset->mb; ea.kb_q_mb_n = qset->mb_n; ea.kb_q_pitch = qset->mb_pitch;
-			ea.kb_qT = (const uint8_t*)ctx->kb_qT.p;
-			ea.emd_stride = kb_qn;
-			if (c.need_emd) ea.emd_ranks = (const uint64_t*)ctx->emd_out.p;
-			ea.S = slices;
-			ea.m = nb * mc;
-			ea.cand_scalars = cands->scalars + (c.cand_slots ? 0 : off * cands->scalar_stride);
-			ea.cand_scalar_stride = cands->scalar_stride;
-			ea.cand_slots = d_slots;
-			ea.n_queries = nb;
-			ea.m_per_query = mc;
-			ea.q_slots = dq;
-			ea.qset_scalars = qset->scalars;
-			ea.q_scalar_stride = qset->scalar_stride;
-			ea.q_scalars = qset->scalars + (uint64_t)c.q_slots[b.q0] * qset->scalar_stride;
-			ea.nbins = L.nbins;
-			ea.dtype = cands->dtype;
-			ea.order = MSC_ORDER_CAND_FIRST;
-			ea.error_word = (int32_t*)ctx->err_word.p;
+			fill_pair_args(ea, ctx, cands, qset, d_slots, c.cand_slots ? 0 : off, mc, dq, c.q_slots[b.q0], nb, slices, MSC_ORDER_CAND_FIRST);
+			fill_matrix_args(ea, side, cands, qset, slices, kb_qn, c.cand_slots ? 0 : off, n_hot, c.need_emd ? ctx->emd_out.p : nullptr);
 			ea.kb_c_bits = cands->kb;
 			if (c.cls) {          // the flags, as msc_score_multi decides them, kept here
 				ea.model = c.cls->d;
@@ -264,9 +222,7 @@ int run_matrix(PairsCall& c) {
 	c.fp64 += open + (c.reg ? (cut ? uncut : total) : 0);
 	ctx->pl_n = total;
 	if (last_qn) {          // msc_last_kernel_info names the product kernel, as msc_score_multi does
-		snprintf(ctx->last_kernel_buf, sizeof ctx->last_kernel_buf, "%s<%u query rows, one matrix product per tile of presence bits%s%s%s>", msc_pair_gemm_kernel_name(), last_qn,
-		         c.need_emd ? ", emd by ranks" : ", no emd", c.cls_div || c.reg_div ? ", divergence sums from cells" : "", cands->sparse ? ", mirrors from lists" : "");
-		ctx->last_kernel = ctx->last_kernel_buf;
+		name_matrix_kernel(ctx, last_qn, c.need_emd, c.cls_div || c.reg_div, cands->sparse);
 		ctx->last_query_tile = (int)c.blocks.back().nq;
 		ctx->have_timing = false;
 	}
@@ -378,9 +334,10 @@ int search_pairs(msc_ctx* ctx, const msc_model* cls, const msc_model* reg, const
 		}
 	}
 	c.qcount.assign(n_q, 0);
-	uint64_t want = 0;
-	for (const msc_model* md : {cls, reg})
-		if (md) for (int i = 0; i < md->h.n_singles; i++) want |= md->h.single_flag[i];
+	uint64_t wants[2] = {0, 0};          // the statistics of the classification and of the regression model
+	for (int i = 0; i < 2; i++)
+		if (const msc_model* md = i ? reg : cls) for (int j = 0; j < md->h.n_singles; j++) wants[i] |= md->h.single_flag[j];
+	const uint64_t want = wants[0] | wants[1];
 	c.need_emd = (want & MSC_FEAT_EMD) != 0;
 	// the matrix-core route: where msc_score_multi would put every block of this call on the product kernel, for both models at once
 	// (a divergence statistic leaves it unless msc_set_pairs_div_cells asks for the sums from cells; the 4-bin group statistics always do)
@@ -390,26 +347,18 @@ int search_pairs(msc_ctx* ctx, const msc_model* cls, const msc_model* reg, const
 		if ((r = ensure_kb(ctx, db)) || (r = ensure_kb(ctx, qset))) return r;
 		matrix = db->kb && qset->kb && !db->kb_has_zero && !qset->kb_has_zero;
 	}
+	plan_blocks(c, 128);
 	if (matrix) {
-		plan_blocks(c, 128);
 		for (const PairsBlock& b : c.blocks) {          // (a block whose queries' hot list would be too long goes to the older routes there)
-			uint64_t n_hot = 0;
-			for (uint64_t q = b.q0; q < b.q0 + b.nq; q++) n_hot += std::min(qset->mb_n_host[q_slots[q]], qset->mb_pitch);
-			if (n_hot > 64 * (db->L.nbins / 128)) matrix = false;
+			if (block_hot_size(qset, q_slots + b.q0, b.nq) > 64 * (db->L.nbins / 128)) matrix = false;
 		}
 	}
 	if (matrix && c.need_emd) {
 		if ((r = ensure_ranks(ctx, db)) || (r = ensure_ranks(ctx, qset))) return r;
 		matrix = db->ranks && qset->ranks;
 	}
-	if (matrix)
-		for (int i = 0; i < 2; i++) {
-			const msc_model* md = i ? reg : cls;
-			uint64_t w = 0;
-			if (md) for (int j = 0; j < md->h.n_singles; j++) w |= md->h.single_flag[j];
-			(i ? c.reg_div : c.cls_div) = (w & MSC_FEAT_DIV) != 0;
-		}
-	if (!matrix) plan_blocks(c, 128);
+	c.cls_div = matrix && (wants[0] & MSC_FEAT_DIV) != 0;
+	c.reg_div = matrix && (wants[1] & MSC_FEAT_DIV) != 0;
 	r = matrix ? run_matrix(c) : run_fallback(c);
 	if (r) { ctx->pl_n = 0; return r; }
 	for (uint64_t q = 0; q < n_q; q++) offsets[q + 1] = offsets[q] + (top_n ? std::min<uint64_t>(c.qcount[q], top_n) : c.qcount[q]);

@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "msc_objects.h"
+#include "msc_multi_plan.h"
 
 // largest bin for which 32-bit per-lane partial sums of p*q cannot overflow: R * max^2 < 2^32 with R <= 64
 static const uint64_t kNarrowMaxCount = 8191;
@@ -56,3 +57,18 @@ int ensure_kb(msc_ctx* ctx, const msc_hist_set* set);          // the presence-b
 int ensure_ranks(msc_ctx* ctx, const msc_hist_set* set);       // the ranks mirror, likewise (set->ranks null: unavailable)
 bool kb_route_fits(const msc_hist_set* cands, const msc_hist_set* qset, bool need_emd);          // host-side bounds of the matrix-core pass
 int read_error_word(msc_ctx* ctx);                             // the epilogue's error word as a status (the stream is idle)
+// ... and what a block on the matrix cores needs in either driver (the drivers themselves stay apart: msc_score_multi pipes its blocks over three
+// streams and scores every pair, msc_search_pairs lists the close ones on one stream)
+uint64_t block_hot_size(const msc_hist_set* qset, const uint32_t* q_slots, uint64_t nq);          // entries of the hot list of a block of query slots
+// the candidate chunks of a block of `rows` query rows: the product array [slices][chunk][rows] int32 within 2 GiB, at most `limit` candidates a chunk
+MscCandChunks matrix_chunks(const msc_ctx* ctx, uint64_t nbins, uint64_t m, uint32_t rows, uint64_t limit = ~0ull);
+struct HotList { uint32_t *ptr = nullptr, *cursor = nullptr, *cnt = nullptr; };          // the three step arrays of a hot list (null: the list is empty)
+int ensure_side(msc_ctx* ctx, BlockPipe::Side& s, uint64_t nbins, uint32_t rows, uint32_t slices, uint64_t chunk, uint64_t n_hot, HotList* hot);
+// the epilogue's arguments cleared, then the fields that say which pairs a chunk holds: nq queries (device slots dq, the first one's host slot q_slot0)
+// x mc candidates (device slot list d_slots, or slots from `first` on), n_rec records per pair
+void fill_pair_args(MscEpilogueArgs& ea, msc_ctx* ctx, const msc_hist_set* cands, const msc_hist_set* qset, const uint32_t* d_slots, uint64_t first, uint32_t mc, const uint32_t* dq, uint32_t q_slot0, uint32_t nq, uint32_t n_rec, int order);
+// the kb_* and emd_* fields of the epilogue's arguments (first: the chunk's first candidate, 0 with a slot list; emd_out null: no emd)
+void fill_matrix_args(MscEpilogueArgs& ea, const BlockPipe::Side& s, const msc_hist_set* cands, const msc_hist_set* qset, uint32_t slices, uint32_t rows, uint64_t first, uint64_t n_hot, const void* emd_out);
+// the earth mover's distances of a chunk from the ranks mirrors: the 16-bit walk where both sets keep that form at one pitch
+hipError_t launch_emd_ranks(hipStream_t st, const msc_hist_set* cands, const msc_hist_set* qset, const uint32_t* d_slots, uint64_t off, uint32_t mc, const uint32_t* dq, uint32_t nq, uint64_t* out, uint32_t stride);
+void name_matrix_kernel(msc_ctx* ctx, uint32_t rows, bool emd, bool cells, bool from_lists);      // msc_last_kernel_info's name of the product kernel

@@ -1,6 +1,7 @@
 // msc_objects.h -- the objects behind the opaque handles of include/meshclust2_hip.h and the host helpers the C-ABI translation
 // units share (msc_api*.hip define them; msc_window.hip and msc_shard.hip use them). Private to the library.
 #pragma once
+#include <algorithm>
 #include <functional>
 #include <string>
 #include <vector>
@@ -10,6 +11,30 @@
 struct DevBuf {
 	void* p = nullptr;
 	size_t cap = 0;
+};
+
+// The matrix-core block pipe (msc_pair_gemm.hip, msc_api_multi.hip). msc_score_multi queues the blocks of its matrix-core pass in stages on three
+// streams: the queries' side of block i + 1 (prep_stream) under the product of block i (the context's stream), beside the rank walk of block i and the
+// epilogue of block i - 1 (tail_stream). What two stages touch exists twice and blocks take turns; msc_search_pairs, on one stream, uses side[0] alone.
+struct BlockPipe {
+	struct Side {
+		// bit image transposed, P1 per slice, P2, the queries' tiles as nibbles (what the product copies into LDS), hot list + its three step arrays
+		DevBuf qT, min, diff, anib, hot, hot_idx;
+		// the product of a block on this side is about to start / is through, the epilogue that read this side is through, the queries' side is ready
+		hipEvent_t ev_head = nullptr, ev_product = nullptr, ev_tail = nullptr, ev_prep = nullptr;
+		bool product_busy = false, tail_busy = false;          // a product that reads this side / an epilogue that read it has been queued
+	} side[2];
+	hipStream_t tail_stream = nullptr, prep_stream = nullptr, copy_stream = nullptr;
+	hipEvent_t ev_call = nullptr;          // the call's query slots are on the device
+	// the close flags of a block go back to the host on copy_stream, under the next block's kernels: two device buffers take turns, and
+	// msc_score_multi waits for the copies before it returns
+	DevBuf close_pp[2];
+	hipEvent_t ev_scored[2] = {nullptr, nullptr}, ev_copied[2] = {nullptr, nullptr};
+	bool close_pp_busy[2] = {false, false}, copy_pending = false, tail_used = false;
+	int close_pp_next = 0;
+	uint32_t next = 0;                     // the side the next piped block takes (its low bit)
+	std::vector<hipEvent_t> ev_pool;       // timing events of the queued blocks, kept for the life of the context
+	size_t ev_used = 0;
 };
 
 struct msc_ctx {
@@ -52,22 +77,12 @@ struct msc_ctx {
 	uint64_t sp_acc_bins = 0;
 	// msc_shard.hip: the payload of msc_colsum_partial, the gathered column-sum lists of the other ranks, header staging
 	DevBuf shard_payload, shard_hdrs;
-	// msc_pair_gemm.hip: the queries' side of a block (bit image, transposed counts, hot list + its three step arrays), P1 per slice, P2
-	DevBuf kb_qT, kb_hot, kb_hot_idx, kb_min, kb_diff, kb_anib;          // (kb_anib: the queries' tiles as nibbles, what the product copies into LDS)
-	// the close flags of a block of the matrix-core pass go back to the host on a stream of their own, under the next block's kernels:
-	// two device buffers take turns; msc_score_multi waits for the copies before it returns
-	hipStream_t copy_stream = nullptr;
-	hipEvent_t ev_scored[2] = {nullptr, nullptr}, ev_copied[2] = {nullptr, nullptr};
-	DevBuf close_pp[2];
-	bool close_pp_busy[2] = {false, false};
-	int close_pp_next = 0;
-	bool copy_pending = false;
+	BlockPipe pipe;                        // msc_pair_gemm.hip: the queries' side of a block and the streams its stages run on
 	bool block_pipe = true;                // msc_set_block_pipe: the blocks of msc_score_multi on three streams
 	bool pairs_div_cells = false;          // msc_set_pairs_div_cells: msc_search_pairs keeps divergence-statistic models on the matrix-core route
 	bool sparse_matrix_pass = false;       // msc_set_sparse_matrix_pass: two sparse sets may take the matrix-core Q x M route (mirrors built from their lists)
 	bool mirror_pass = true;               // msc_set_mirror_pass: a dense set's 1 x M passes merge the lists of its sparse mirror
 	bool packed_on_device = false;         // msc_hist_build_packed_dev: the 2-bit stream of the build in progress is device memory
-	bool no_kb_now = false;                // msc_score_multi: this block is taken by the older routes (its hot list would be too long)
 	DevBuf close_counts;                   // msc_score_multi: close candidates per query of the call in progress / the last call (msc_last_close_counts)
 	// msc_search_pairs (msc_api_pairs.hip): the list of the last call (candidate index, similarity), kept until the next call, and its scratch
 	DevBuf pl_idx, pl_sim;
@@ -75,35 +90,8 @@ struct msc_ctx {
 	DevBuf pl_stage_idx, pl_stage_sim;     // a block's pairs chunk by chunk, when its candidates take several chunks
 	DevBuf pl_flags, pl_counts, pl_offsets, pl_seg, pl_dst, pl_qslots, pl_win, pl_qcount, pl_words;
 	DevBuf pl_pin;                         // page-locked: the running totals read back before a list grows
-	uint64_t close_counts_n = 0, close_counts_base = 0;
-	bool in_score_multi = false;
-	// msc_score_multi queues the blocks of its matrix-core pass without waiting between them: 0 = off, 1 = the next queued block clears
-	// the error word, 2 = blocks are in flight (flush_deferred)
-	int defer = 0;
-	bool defer_cands_up = false;           // the call's candidate slot list is on the device
-	uint64_t defer_q_off = 0;              // first query of the block being queued, in qslots_all
-	float defer_ms = 0.f;
-	DevBuf qslots_all;                     // the query slots of the whole call
-	// ... and in two stages on two streams: a block's product (stream) runs beside the rank walk of the same block and the epilogue of
-	// the block before it (tail_stream). What both stages touch exists twice (second copies below; the first are kb_qT, kb_min, kb_diff):
-	// ev_head[i] = the product of a block using copy i is about to start, ev_product[i] = it is through, ev_tail[i] = the epilogue that
-	// read copy i is through
-	hipStream_t tail_stream = nullptr;
-	hipEvent_t ev_head[2] = {nullptr, nullptr}, ev_product[2] = {nullptr, nullptr}, ev_tail[2] = {nullptr, nullptr};
-	DevBuf kb_qT2, kb_min2, kb_diff2;
-	// r05: the queries' side of a block (k_kb_gather, k_hot_*) is prepared on a third stream while the product of the block before it
-	// runs, so the product stream goes from product to product. Everything that side writes exists twice (the first copies are
-	// kb_anib, kb_hot, kb_hot_idx, kb_qT). ev_call = this call's query slots are on the device; ev_prep[i] = the queries' side in copy i
-	// is ready; product_busy[i] = a product that reads copy i has been queued and ev_product[i] says when it is through
-	hipStream_t prep_stream = nullptr;
-	hipEvent_t ev_call = nullptr, ev_prep[2] = {nullptr, nullptr};
-	DevBuf kb_anib2, kb_hot2, kb_hot_idx2;
-	bool product_busy[2] = {false, false};
-	bool tail_busy[2] = {false, false};
-	bool tail_used = false;
-	uint32_t pipe_next = 0;
-	std::vector<hipEvent_t> ev_pool;       // timing events of the queued blocks
-	size_t ev_used = 0;
+	uint64_t close_counts_n = 0;           // queries the counts on file cover (0: the last call kept none)
+	DevBuf qslots_all;                     // msc_score_multi: the query slots of a whole call whose blocks are queued
 	DevBuf emd_out, rk_bad;                // msc_emd_ranks.hip: the distances of a chunk, the build's error word
 	msc_hist_set* shard_gather = nullptr;
 	// MSC_PROFILE_CALLS: host wall clock of the 1 x M scoring calls, split into preparing + queueing the slot list, issuing the
@@ -114,6 +102,28 @@ struct msc_ctx {
 	uint64_t prof_q_nnz = 0;               // sum over the passes of the query's stored bins
 	uint64_t prof_calls = 0, prof_cands = 0;
 };
+
+// the slots of a set one of its mirrors has not seen written yet: their hull [lo, hi)
+struct StaleRange {
+	uint64_t lo = 0, hi = 0;
+	bool any() const { return lo < hi; }
+	void add(uint64_t first, uint64_t n) {
+		if (n) *this = any() ? StaleRange{std::min(lo, first), std::max(hi, first + n)} : StaleRange{first, first + n};
+	}
+	void all(uint64_t capacity) { lo = 0; hi = capacity; }
+	void clear() { lo = hi = 0; }
+};
+
+// fn(first, n) for every run of consecutive slots i of [lo, hi) with holds(i); the first status other than 0 ends the walk and is returned
+template <class Holds, class Fn>
+inline int for_each_run(uint64_t lo, uint64_t hi, Holds holds, Fn fn) {
+	for (uint64_t i = lo, j; i < hi; i = j) {
+		for (j = i; j < hi && holds(j);) j++;
+		if (j == i) j++;
+		else if (const int r = fn(i, j - i)) return r;
+	}
+	return 0;
+}
 
 struct msc_hist_set {
 	msc_ctx* ctx = nullptr;
@@ -126,17 +136,17 @@ struct msc_hist_set {
 	// host-side bounds over every slot ever written (monotone; used to pick the kernels' integer range)
 	uint64_t max_count = 0, max_sum = 0;
 	const char* last_builder = "";        // what the last msc_hist_build* call on this set ran (msc_hist_set_build_info)
-	// digest mirror (pair_digest.hip), allocated on the first Q x M pass that can use it; slots [dg_lo, dg_hi) are stale
+	// digest mirror (pair_digest.hip), allocated on the first Q x M pass that can use it; dg_stale: the slots written since
 	mutable uint8_t* digest = nullptr;    // a cache: maintained through const handles
-	mutable uint64_t dg_lo = 0, dg_hi = 0;
+	mutable StaleRange dg_stale;
 	mutable bool digest_unavailable = false;      // allocation failed once: do not retry every pass
 	// presence-bit mirror (msc_pair_gemm.hip, msc_kbits.h): one BIT per bin = [count >= 2], slots blocked by 32 -- the B operand of the
 	// int8 product of the Q x M pass -- and beside it the lists of large bins (count - 1 >= 2) that make the pass exact for any counts:
 	// mb[slot][mb_pitch] = (bin, count - 1), sorted by bin; mb_n = entries per slot (also on the host: the size of a query block's hot list is
-	// known without a read-back). slots [kb_lo, kb_hi) are stale (mark_stale). A sparse set carries the same mirror, built from its lists
+	// known without a read-back). kb_stale: the slots written since (mark_stale). A sparse set carries the same mirror, built from its lists
 	// (msc_set_sparse_matrix_pass; lists_written keeps the stale range)
 	mutable uint8_t* kb = nullptr;
-	mutable uint64_t kb_lo = 0, kb_hi = 0;
+	mutable StaleRange kb_stale;
 	mutable bool kb_unavailable = false;
 	mutable bool kb_has_zero = false;         // a slot with a zero count went into the mirror (never the case for built histograms and their means)
 	mutable void* mb = nullptr;
@@ -145,19 +155,20 @@ struct msc_hist_set {
 	mutable std::vector<uint32_t> mb_n_host;
 	// ranks mirror (msc_emd_ranks.hip): per slot the bins of its counted k-mers in bin order (rk_pitch entries, padded with 4^k) and
 	// their number: the earth mover's distance of the Q x M pass in O(k-mers) instead of O(bins). Built from the digest mirror;
-	// slots [rk_lo, rk_hi) are stale
+	// rk_stale: the slots written since
 	mutable uint32_t* ranks = nullptr;
 	mutable uint32_t* rk_n = nullptr;
-	mutable uint64_t rk_pitch = 0, rk_lo = 0, rk_hi = 0;
+	mutable uint64_t rk_pitch = 0;
+	mutable StaleRange rk_stale;
 	mutable bool ranks_unavailable = false;
 	// ... and their 16-bit form (rank - floor(t * 4^k / pitch) + 32768; msc_emd_ranks.hip, k_emd_ranks16), kept while every slot's reduced
 	// ranks fit and the pitch is a multiple of 1 024; rk16_off: a slot did not fit (or the allocation failed): the 32-bit walk stays
 	mutable uint16_t* ranks16 = nullptr;
 	mutable bool rk16_off = false;
 	// sparse mirror of a DENSE set: the sorted (bin, value) lists of its slots, kept so that the divergence
-	// statistics of every route come from the one merge kernel; slots [sm_lo, sm_hi) are stale. Built on first use.
+	// statistics of every route come from the one merge kernel; sm_stale: the slots written since. Built on first use.
 	mutable msc_hist_set* sp_mirror = nullptr;
-	mutable uint64_t sm_lo = 0, sm_hi = 0;
+	mutable StaleRange sm_stale;
 	mutable bool sp_mirror_unavailable = false;
 	std::vector<uint8_t> written;         // dense sets: slot holds a histogram (unwritten slots are never sparsified)
 	// effective lengths as the host last learnt them (len_known[i] != 0): Trainer::get_close / filter / merge derive their length

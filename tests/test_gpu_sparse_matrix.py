@@ -201,21 +201,24 @@ def _hot_bins(seq, k):
     return int((np.unique(kmers, return_counts=True)[1] >= 2).sum())
 
 
-def test_a_block_declines_inside_a_queued_call(ctx):
+@pytest.fixture(scope="module")
+def declining_case(ctx):
+    """140 plain sequences (slots 0 .. 139), then 100 tandem repeats of ~147 large bins each: a block made of the latter has too long a hot list"""
+    k, n_plain, n_rep = 7, 140, 100
+    rng = np.random.default_rng(57)
+    plain, _ = synth.families(5307, n_plain, 600, family=5, length_jitter=40)
+    reps = [bytes(rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=150)) * 4 for _ in range(n_rep)]
+    seqs = [bytes(s) for s in plain] + reps
+    sp, de = _sets(ctx, seqs, k, 32)
+    return dict(sp=sp, de=de, feat=api.Feature.from_text(ctx, _text(k, 32), 0), cands=np.arange(len(seqs), dtype=np.uint32), hot=np.array([_hot_bins(s, k) for s in seqs]),
+                limit=64 * (4 ** k // 128), rep0=n_plain)
+
+
+def test_a_block_declines_inside_a_queued_call(ctx, declining_case):
     """blocks of one call that take different routes: plain queries on the matrix cores, tandem-repeat queries whose hot list is too long
     on the list passes (the queued blocks are waited for first), in the middle of the call (a block of 128, cut into two of 64) and at its
     end (a block of 60)"""
-    k, n_plain, n_rep = 7, 140, 100
-    limit = 64 * (4 ** k // 128)
-    rng = np.random.default_rng(57)
-    plain, _ = synth.families(5307, n_plain, 600, family=5, length_jitter=40)
-    reps = [bytes(rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=150)) * 4 for _ in range(n_rep)]          # ~147 large bins each
-    seqs = [bytes(s) for s in plain] + reps
-    sp, de = _sets(ctx, seqs, k, 32)
-    feat = api.Feature.from_text(ctx, _text(k, 32), 0)
-    cands = np.arange(len(seqs), dtype=np.uint32)
-    hot = np.array([_hot_bins(s, k) for s in seqs])
-    rep0 = n_plain
+    sp, de, feat, cands, hot, limit, rep0 = (declining_case[x] for x in ("sp", "de", "feat", "cands", "hot", "limit", "rep0"))
     middle = np.concatenate([np.arange(128), rep0 + np.arange(100), 100 + np.arange(28), np.arange(12)]).astype(np.uint32)      # 128 | 100 + 28 | 12
     at_end = np.concatenate([np.arange(128), rep0 + 40 + np.arange(60)]).astype(np.uint32)                                      # 128 | 60
     assert hot[middle[:128]].sum() <= limit and hot[middle[128:256]].sum() > limit and hot[middle[256:]].sum() <= limit
@@ -229,6 +232,23 @@ def test_a_block_declines_inside_a_queued_call(ctx):
         _same(on, off, ("switch off", last_on_matrix))
         dense, _ = _multi(ctx, True, feat, de, cands, q_slots, **kw)
         _same(on, dense, ("dense", last_on_matrix))
+
+
+def test_the_second_block_of_192_declines_while_the_first_is_queued(ctx, declining_case):
+    """128 plain queries, queued on the matrix cores, then a block of 64 tandem-repeat queries whose hot list is too long: it waits for the
+    queued block and runs on the list passes as one block of 64"""
+    sp, feat, cands, hot, limit, rep0 = (declining_case[x] for x in ("sp", "feat", "cands", "hot", "limit", "rep0"))
+    q_slots = np.concatenate([np.arange(128), rep0 + np.arange(64)]).astype(np.uint32)
+    assert q_slots.size == 192 and hot[q_slots[:128]].sum() <= limit and hot[q_slots[128:]].sum() > limit
+    kw = dict(feat_mask=FAST_MASK, want=WANT)
+    on, kernel = _multi(ctx, True, feat, sp, cands, q_slots, **kw)
+    assert kernel in SPARSE_KERNELS, kernel          # (the name is the last block's)
+    first, k_first = _multi(ctx, True, feat, sp, cands, q_slots[:130], **kw)          # (the same first block did take the matrix cores: two blocks, 128 | 2)
+    assert k_first.startswith(GEMM), k_first
+    off, k_off = _multi(ctx, False, feat, sp, cands, q_slots, **kw)
+    assert k_off in SPARSE_KERNELS, k_off
+    _same(on, off, "192 queries, the second block declined")
+    assert np.array_equal(on["counts"], on["close"].sum(axis=1, dtype=np.uint64))
 
 
 # ------------------------------------------------------------------------------------------------ E. staleness
