@@ -137,8 +137,28 @@ int         msc_set_block_pipe(msc_ctx* ctx, int on);
  * list or the windows. That order is not the merge kernels': the similarities agree with the fallback's to rounding (1e-9 relative), NOT bit
  * for bit, and a pair whose weighted sum sits within rounding of the threshold may be listed by one route only. msc_pairs_info.route reports
  * MSC_PAIRS_ROUTE_MATRIX, and msc_last_kernel_info's name says that the sums came from cells. msc_score_multi and every other call are
- * unaffected. Default: off. */
+ * unaffected (msc_score_multi has a switch of its own, msc_set_multi_div_cells; the two are independent). Default: off. */
 int         msc_set_pairs_div_cells(msc_ctx* ctx, int on);
+/* msc_score_multi queues one merge pass per query behind the matrix product when the model's singles or feat_mask hold
+ * jefferey_divergence or jensen_shannon (every --feat slow model): the two sums come from the sparse merge kernels over the sets' sparse
+ * mirrors. on = 1 keeps a block of such a call on the matrix-core route with NO pass between the product and the epilogue: the epilogue
+ * evaluates the two sums per pair from exact (count, count) cell counts and the lists of large bins, as msc_search_pairs does under
+ * msc_set_pairs_div_cells, and fills every output -- sums, classify sums, flags, close counts (msc_last_close_counts answers), raw
+ * statistics with the two divergence columns beside the others. The route's other conditions are unchanged (8/16/32-bit sets of the
+ * narrow range in whole 4 KiB tiles, n_q >= 2, a hot list within its bound, ranks mirrors when emd is wanted); it then also serves
+ * histograms under 64 KiB, which have no list form (k = 7 with 16-bit bins), two sparse sets under msc_set_sparse_matrix_pass, and the
+ * three-stream block pipe; a dense set whose blocks all take it builds no sparse mirror. What goes on exactly as with the switch off --
+ * same kernels, names and bits: a model or feat_mask with sim_mm or rre_k_r, a block whose hot list is too long, a set off the matrix
+ * route (k = 5, wide counts, k = 13, padded tiles), a single query, mirrors that cannot be allocated.
+ * Values: every statistic other than the two divergence sums is bit-equal to the switch-off call's (the same exact integers). The two
+ * sums, and what a model derives from them, agree with the switch-off call and with the reference to 1e-9 relative (1e-13 absolute), NOT
+ * bit for bit: the order of the FP64 additions is not the merge kernels'. A pair whose weighted sum lies within that rounding of zero may
+ * get the other flag. A pair's value depends on the pair alone -- not on its block, the chunk of candidates, the slot list, the block pipe
+ * or dense versus sparse sets -- and has the bits msc_search_pairs with msc_set_pairs_div_cells gives that pair. Error statuses and NaN
+ * rows (zero length, NaN) are the switch-off call's. msc_last_kernel_info names the product kernel and adds "divergence sums from
+ * cells". msc_search_pairs's own matrix route follows msc_set_pairs_div_cells alone; its fallback IS a sequence of msc_score_multi calls
+ * and follows this switch as they do. No other call is affected. Default: off. */
+int         msc_set_multi_div_cells(msc_ctx* ctx, int on);
 /* A Q x M call over two SPARSE sets (msc_score_multi, msc_search_pairs) runs one 1 x M pass per query over the lists: the matrix-core
  * route reads a presence bit per bin, the lists of large bins and the sorted ranks of a set -- mirrors only dense sets used to carry.
  * on = 1 lets two sparse sets of equal k and dtype take that route as well, under its usual conditions (8/16/32-bit bins of the narrow

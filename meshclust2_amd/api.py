@@ -72,6 +72,12 @@ class Context:
         fallback through score_multi (default); similarities agree to rounding (1e-9 relative), not bit for bit"""
         self.check(self.lib.msc_set_pairs_div_cells(self.h, 1 if on else 0))
 
+    def set_multi_div_cells(self, on):
+        """score_multi with a divergence statistic in the model or the mask: the matrix-core route with the two sums from cells and no merge
+        pass per query (on) or the merge passes behind the product (default); every other statistic is bit-equal, the two sums and what
+        a model derives from them agree to rounding (1e-9 relative), not bit for bit"""
+        self.check(self.lib.msc_set_multi_div_cells(self.h, 1 if on else 0))
+
     def set_sparse_matrix_pass(self, on):
         """score_multi / search_pairs over two sparse sets: the matrix-core route over mirrors built from the lists (on) or one 1 x M pass
         per query (default); identical results"""

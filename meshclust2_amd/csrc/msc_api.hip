@@ -193,6 +193,12 @@ extern "C" int msc_set_pairs_div_cells(msc_ctx* ctx, int on) {
 	return MSC_OK;
 }
 
+extern "C" int msc_set_multi_div_cells(msc_ctx* ctx, int on) {
+	if (!ctx) return MSC_ERR_INVALID_ARG;
+	ctx->multi_div_cells = on != 0;
+	return MSC_OK;
+}
+
 extern "C" int msc_set_sparse_matrix_pass(msc_ctx* ctx, int on) {
 	if (!ctx) return MSC_ERR_INVALID_ARG;
 	ctx->sparse_matrix_pass = on != 0;

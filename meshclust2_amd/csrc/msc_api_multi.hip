@@ -287,6 +287,8 @@ struct MultiCall {
 	bool need_emd = false, want_div = false, want_grp = false;
 	int nf = 0;
 	const msc_hist_set *c_sp = nullptr, *q_sp = nullptr;          // sparse mirrors of dense sets, for the divergence / group passes
+	bool cells = false;           // msc_set_multi_div_cells: the matrix-core blocks take the divergence sums from cells, no merge pass
+	bool mirrors_settled = false; // c_sp / q_sp, grp_dense and simple are what the older routes need (with cells: not before a block falls back)
 	bool grp_dense = false;       // the group passes read the dense slots
 	bool kb_fit = false;          // the matrix cores can take the call's blocks
 	bool simple = false;          // dense sets: a block of two or more runs on one of the Q x M kernels
@@ -310,7 +312,8 @@ struct Block {
 	const uint32_t* dq_slots = nullptr;          // the query slots on the device
 	uint64_t chunk = 0;                          // candidates per launch
 	hipStream_t tail = nullptr;                  // where the epilogue and the copies home run
-	SparseKernel spk = SPK_MP;                   // divergence statistics: one merge kernel for the whole block ...
+	bool div_pass = false;                       // divergence statistics from a merge pass per query (not from cells)
+	SparseKernel spk = SPK_MP;                   // ... one merge kernel for the whole block ...
 	uint32_t dvn = 1;                            // ... and its {jd, js} records per pair
 };
 // candidates [off, off + mc) of a block: their device slot list (or null), bins and scalars
@@ -499,7 +502,7 @@ int ensure_block_scratch(MultiCall& c, Block& b, bool flags_by_copy_stream) {
 	if (c.want_grp) {
 		if ((r = ensure(ctx, ctx->grp_pairs, n_q * chunk * 32 * sizeof(double))) || (r = ensure(ctx, ctx->grp_self, (chunk + n_q) * 16 * sizeof(double)))) return r;      // [candidates][16] then [queries][16]
 	}
-	if (c.want_div) {          // one kernel for the whole block: merge-path unless some query's lists are out of its range
+	if (b.div_pass) {          // one kernel for the whole block: merge-path unless some query's lists are out of its range
 		uint64_t q_nnz_max = 0;
 		for (uint64_t q = 0; q < n_q; q++) {
 			if (pick_sparse_kernel(c.c_sp, c.q_sp, b.q_slots[q], c.mc_, false) != SPK_MP) b.spk = SPK_GENERIC;
@@ -531,7 +534,7 @@ int side_passes(MultiCall& c, Block& b, const Chunk& k, MscEpilogueArgs& ea) {
 	const msc_hist_set *cands = c.cands, *qset = c.qset, *c_sp = c.c_sp, *q_sp = c.q_sp;
 	const MscLayout& L = cands->L;
 	const uint64_t n_q = b.nq, mc = k.mc;
-	if (c.want_div) {
+	if (b.div_pass) {
 		for (uint64_t q = 0; q < n_q; q++)
 			HIP_TRY(ctx, launch_sparse_pass(ctx, b.spk, c_sp, cands->scalars, cands->scalar_stride, k.d_slots, k.off, mc, q_sp, b.q_slots[q],
 			                                qset->scalars + (uint64_t)b.q_slots[q] * qset->scalar_stride, L.nbins, 0, 0, ~0ull, (MscPartial*)ctx->sp_partials.p,
@@ -601,6 +604,7 @@ int run_sparse_queued(MultiCall& c, Block& b) {
 	ctx->last_query_tile = 1; ctx->last_partial_stride = 1;
 	b.chunk = m;          // (every candidate in one launch per query: pick_route keeps n_q x m records within 4 GiB)
 	b.tail = ctx->stream;
+	b.div_pass = c.want_div;
 	if ((r = ensure(ctx, ctx->partials, n_q * m * sizeof(MscPartial))) || (r = ensure_block_scratch(c, b, false)) || (r = block_uploads(c, b, false))) return r;
 	const Chunk k = chunk_at(c, b, 0);
 	const uint64_t q_kmers = qset->max_sum >= L.nbins ? qset->max_sum - L.nbins : ~0ull;
@@ -659,6 +663,7 @@ int run_streamed(MultiCall& c, Block& b, const BlockRoute& rt) {
 	int r;
 	if ((r = begin_block(ctx))) return r;
 	b.tail = ctx->stream;
+	b.div_pass = c.want_div;
 	if ((r = block_uploads(c, b, false))) return r;
 	const bool digest_emd = c.need_emd && !rt.emd_ranks;          // the digest kernel streams and scores the prefix half
 	const bool count_only = digest && rt.tps == 2 && !digest_emd;
@@ -712,7 +717,7 @@ int run_streamed(MultiCall& c, Block& b, const BlockRoute& rt) {
 
 // The matrix cores. Queued blocks run in stages on three streams (BlockPipe, msc_objects.h): the product of block i on the context's stream beside the rank
 // walk of block i and the epilogue of block i - 1 on tail_stream, the queries' side of block i + 1 on prep_stream -- the product is bound by the matrix pipe,
-// the others by vector arithmetic and latency. Blocks take turns on the two sides of the pipe. (Single chunk, no divergence / group passes between the stages;
+// the others by vector arithmetic and latency. Blocks take turns on the two sides of the pipe. (Single chunk, no divergence / group passes between the stages -- divergence sums from cells run none;
 // MSC_GEMM_NO_PREP: the queries' side on the product's stream, as in r04.) The close flags go into one of two buffers and home on the copy stream, under the next block's kernels.
 int run_matrix(MultiCall& c, Block& b, const BlockRoute& rt) {
 	msc_ctx* ctx = c.ctx;
@@ -726,9 +731,10 @@ int run_matrix(MultiCall& c, Block& b, const BlockRoute& rt) {
 	if ((r = block_uploads(c, b, queued))) return r;
 	const uint32_t rows = msc_pair_gemm_rows((uint32_t)n_q);
 	b.chunk = matrix_chunks(ctx, L.nbins, m, rows, group_chunk_limit(c, n_q)).chunk;
+	b.div_pass = c.want_div && !c.cells;
 	if ((r = ensure_block_scratch(c, b, true))) return r;
 	const uint32_t slices = msc_pair_gemm_slices(L.nbins, (uint32_t)b.chunk, rows, ctx->num_cus);
-	const bool piped = queued && b.chunk == m && !c.want_div && !c.want_grp && ctx->block_pipe;
+	const bool piped = queued && b.chunk == m && !b.div_pass && !c.want_grp && ctx->block_pipe;
 	const int pb = piped ? (int)(pipe.next++ & 1) : 0;
 	BlockPipe::Side& s = pipe.side[pb];
 	b.tail = piped ? pipe.tail_stream : ctx->stream;
@@ -755,7 +761,7 @@ int run_matrix(MultiCall& c, Block& b, const BlockRoute& rt) {
 		HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.ev_prep, 0));
 	}
 	if (rt.emd_ranks && (r = ensure(ctx, ctx->emd_out, b.chunk * rows * sizeof(uint64_t)))) return r;
-	name_matrix_kernel(ctx, rows, rt.emd_ranks, false, cands->sparse);
+	name_matrix_kernel(ctx, rows, rt.emd_ranks, c.cells, cands->sparse);
 	ctx->last_query_tile = (int)n_q;
 	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_all0, ctx->stream));
 	for (uint64_t off = 0; off < m; off += b.chunk) {
@@ -777,6 +783,7 @@ int run_matrix(MultiCall& c, Block& b, const BlockRoute& rt) {
 		if ((r = side_passes(c, b, k, ea))) return r;
 		fill_matrix_args(ea, s, cands, qset, slices, rows, c.cand_slots ? 0 : off, rt.n_hot, rt.emd_ranks ? ctx->emd_out.p : nullptr);
 		ea.cq_group = 16;
+		if (c.cells) { ea.div_cells = 1; ea.kb_c_bits = cands->kb; }          // the two sums in the epilogue, as msc_search_pairs sets them (msc_api_pairs.hip)
 		const int pp = pipe.close_pp_next;
 		uint8_t* d_close = b.close ? (uint8_t*)pipe.close_pp[pp].p : nullptr;
 		if (b.close) {
@@ -812,6 +819,24 @@ int run_matrix(MultiCall& c, Block& b, const BlockRoute& rt) {
 	return queued ? MSC_OK : read_error_word(ctx);
 }
 
+// What the older routes need of two dense sets when a divergence or group statistic is wanted: the sparse mirrors, both or neither, and with them
+// whether a block of two or more can run on one of the Q x M kernels (c.simple).
+int settle_mirrors(MultiCall& c) {
+	msc_ctx* ctx = c.ctx;
+	const msc_hist_set *cands = c.cands, *qset = c.qset;
+	const MscLayout& L = cands->L;
+	int r;
+	c.mirrors_settled = true;
+	const bool whole_tiles = L.nbins == L.padded_bins && !needs_wide(cands, qset);
+	if ((c.want_div || c.want_grp) && !cands->sparse && c.n_q > 1 && whole_tiles) {
+		if ((r = ensure_sparse_mirror(ctx, cands, &c.c_sp)) || (r = ensure_sparse_mirror(ctx, qset, &c.q_sp))) return r;
+		if (!c.c_sp || !c.q_sp) c.c_sp = c.q_sp = nullptr;
+	}
+	c.grp_dense = c.want_grp && !c.c_sp;
+	c.simple = !cands->sparse && (!c.grp_dense || c.mc_ <= 0xffffffffull) && (!c.want_div || c.c_sp) && whole_tiles;
+	return MSC_OK;
+}
+
 // validate, decide kb_fit once, plan the blocks, run each on its route, wait for what was queued
 int score_multi(MultiCall& c) {
 	msc_ctx* ctx = c.ctx;
@@ -831,12 +856,16 @@ int score_multi(MultiCall& c) {
 	c.need_emd = (c.want & MSC_FEAT_EMD) != 0;           // Feature::compute evaluates only the model's singles too
 	c.want_div = (c.want & MSC_FEAT_DIV) != 0; c.want_grp = (c.want & MSC_FEAT_GROUPS) != 0;
 	// The pass on the matrix cores (msc_pair_gemm.hip) serves blocks of up to 128 queries per pass over the candidates' bits; the older routes 64
-	// (two sparse sets, msc_set_sparse_matrix_pass: a divergence or group statistic keeps the call on the merge kernels, blocks of 64 and all)
-	c.kb_fit = n_q >= 2 && kb_route_fits(cands, qset, c.need_emd) && !(cands->sparse && (c.want_div || c.want_grp));
+	// A divergence statistic without a group statistic, under msc_set_multi_div_cells (div_cells): the epilogue forms the two sums from cells (bits_pair_div,
+	// pair_features.hip) and no pass runs between the product and it -- dense sets, and two sparse sets under msc_set_sparse_matrix_pass. Any other divergence
+	// or group statistic: dense sets queue their passes behind the product, two sparse sets keep the call on the merge kernels, blocks of 64 and all
+	const bool div_cells = ctx->multi_div_cells && c.want_div && !c.want_grp;
+	c.kb_fit = n_q >= 2 && kb_route_fits(cands, qset, c.need_emd) && !(cands->sparse && (c.want_grp || (c.want_div && !div_cells)));
 	if (c.kb_fit) {
 		if ((r = ensure_kb(ctx, cands)) || (r = ensure_kb(ctx, qset))) return r;
 		c.kb_fit = cands->kb && qset->kb && !cands->kb_has_zero && !qset->kb_has_zero;
 	}
+	c.cells = div_cells && c.kb_fit;
 	// close candidates per query, kept on the device for msc_last_close_counts (a caller that only needs the counts of a block of the
 	// pairwise matrix does not have to add up n_q x m flags on the host)
 	ctx->close_counts_n = 0;
@@ -845,14 +874,10 @@ int score_multi(MultiCall& c) {
 		HIP_TRY(ctx, hipMemsetAsync(ctx->close_counts.p, 0, n_q * sizeof(uint64_t), ctx->stream));
 		ctx->close_counts_n = n_q;
 	}
-	const bool whole_tiles = L.nbins == L.padded_bins && !needs_wide(cands, qset);
-	if ((c.want_div || c.want_grp) && !cands->sparse && n_q > 1 && whole_tiles) {          // the sparse mirrors of two dense sets, both or neither
-		if ((r = ensure_sparse_mirror(ctx, cands, &c.c_sp)) || (r = ensure_sparse_mirror(ctx, qset, &c.q_sp))) return r;
-		if (!c.c_sp || !c.q_sp) c.c_sp = c.q_sp = nullptr;
-	}
-	c.grp_dense = c.want_grp && !c.c_sp;
 	c.mc_ = std::max(cands->max_count, qset->max_count); c.ms_ = std::max(cands->max_sum, qset->max_sum);
-	c.simple = !cands->sparse && (!c.grp_dense || c.mc_ <= 0xffffffffull) && (!c.want_div || c.c_sp) && whole_tiles;
+	// (sums from cells read no sparse mirror: a call whose blocks all stay with the matrix cores builds none; the first block that falls back settles them)
+	if (c.cells) c.simple = !cands->sparse;
+	else if ((r = settle_mirrors(c))) return r;
 	// wave totals of the per-lane 32-bit partial sums fit 32 bits when 64*R*max^2 and 64*R*max|prefix difference| do
 	c.compact = 64ull * L.R * c.mc_ * c.mc_ < (1ull << 32) && 64ull * L.R * c.ms_ < (1ull << 32);
 	// every prefix of excess counts (count - 1) is at most the histogram's k-mer total = sum - 4^k: 16-bit prefix form when that fits
@@ -872,7 +897,10 @@ int score_multi(MultiCall& c) {
 		r = pb.matrix ? MSC_OK : flush_deferred(c);
 		BlockRoute rt;
 		if (pb.matrix) rt = c.taken[next_taken++];
-		else if (!r) rt = pick_route(c, b.q_slots, b.nq, false, &r);
+		else {
+			if (!r && !c.mirrors_settled) r = settle_mirrors(c);          // (sums from cells, and this block falls back)
+			if (!r) rt = pick_route(c, b.q_slots, b.nq, false, &r);
+		}
 		if (!r && rt.queued && !c.queue_up) {          // the first queued block: the whole call's query slots go up once
 			if (!(r = ensure(ctx, ctx->qslots_all, n_q * sizeof(uint32_t)))) {
 				HIP_TRY(ctx, hipMemcpyAsync(ctx->qslots_all.p, c.q_slots, n_q * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));

@@ -142,8 +142,9 @@ struct MscEpilogueArgs {
 	const double* grp_pairs;          // [pairs][16][2] = {markov, rre}
 	const double* grp_self_c;         // [m_per_query or m][16]: markov(c, c) of every candidate of the launch (index = candidate position)
 	const double* grp_self_q;         // [n_queries or 1][16]: markov(q, q)
-	// msc_search_pairs with msc_set_pairs_div_cells: the divergence statistics on the matrix-core route, from (count, count) cells and the
-	// two lists of large bins (k_pair_epilogue_bits_div, k_pair_list_write<true, true>); kb_c_bits = the candidates' presence mirror
+	// msc_search_pairs with msc_set_pairs_div_cells, msc_score_multi with msc_set_multi_div_cells: the divergence statistics on the matrix-core
+	// route, from (count, count) cells and the two lists of large bins (k_pair_epilogue_bits_div -- through msc_launch_epilogue for
+	// msc_score_multi --, k_pair_list_write<true, true>); kb_c_bits = the candidates' presence mirror
 	const uint8_t* kb_c_bits;
 	int32_t  div_cells;
 };

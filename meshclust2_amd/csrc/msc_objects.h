@@ -80,6 +80,7 @@ struct msc_ctx {
 	BlockPipe pipe;                        // msc_pair_gemm.hip: the queries' side of a block and the streams its stages run on
 	bool block_pipe = true;                // msc_set_block_pipe: the blocks of msc_score_multi on three streams
 	bool pairs_div_cells = false;          // msc_set_pairs_div_cells: msc_search_pairs keeps divergence-statistic models on the matrix-core route
+	bool multi_div_cells = false;          // msc_set_multi_div_cells: msc_score_multi keeps blocks that want a divergence statistic on the matrix-core route, no merge pass
 	bool sparse_matrix_pass = false;       // msc_set_sparse_matrix_pass: two sparse sets may take the matrix-core Q x M route (mirrors built from their lists)
 	bool mirror_pass = true;               // msc_set_mirror_pass: a dense set's 1 x M passes merge the lists of its sparse mirror
 	bool packed_on_device = false;         // msc_hist_build_packed_dev: the 2-bit stream of the build in progress is device memory

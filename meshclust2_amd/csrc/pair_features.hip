@@ -1314,7 +1314,9 @@ __device__ __forceinline__ void bits_div_query(const MscEpilogueArgs& a, uint32_
 // image, so every pair is an FP64 evaluation. The layout of k_pair_epilogue_bits_screen: a wave takes kDivChunk consecutive candidates x 64
 // queries, lane = query, the candidate's record and list wave-uniform (scalar cache), the queries' side -- slot, scalar record, list,
 // D_q - |L_q| -- fetched once per chunk.
-// -Rpass-analysis=kernel-resource-usage (gfx950, two waves per SIMD asked of the compiler): 165 VGPRs, no AGPRs, 104 SGPRs with 75 more
+// msc_score_multi with msc_set_multi_div_cells launches this same kernel through msc_launch_epilogue (the block's epilogue, no merge pass
+// before it): epilogue_eval then fills the sums, the classify sums and the raw statistics too, with or without a model.
+// -Rpass-analysis=kernel-resource-usage (gfx950, two waves per SIMD asked of the compiler; read again with both callers in place): 165 VGPRs, no AGPRs, 104 SGPRs with 75 more
 // spilled into VGPR lanes, no VGPR spill, no LDS: 3 waves per SIMD. (k_pair_epilogue_bits with the FP64 evaluation alone: 116 VGPRs, 4 waves;
 // the difference is the list walks and the logarithms of bits_pair_div kept live beside epilogue_eval's statistics.)
 template <uint32_t kDivChunk>
@@ -2267,7 +2269,12 @@ hipError_t msc_launch_epilogue(hipStream_t st, const MscEpilogueArgs& a) {
 		const uint64_t waves = (uint64_t)a.m_per_query * ((a.n_queries + 63) / 64);
 		const bool screen = a.screen && a.model && a.close_soa && !a.sum_soa && !a.csum_soa && !a.raw_out && !a.singles_out && !a.combos_out && !a.pair_out && !a.use_window &&
 		                    !a.div_direct && !a.grp_pairs && !a.sparse_base;
-		if (screen) {
+		if (a.div_cells) {          // msc_set_multi_div_cells: the two divergence sums from cells, every output of epilogue_eval, every pair in FP64
+			if (!a.kb_c_bits || a.div_direct || a.grp_pairs || a.sparse_base) return hipErrorInvalidValue;
+			constexpr uint32_t chunk = 4;          // (as msc_launch_pair_list_flags takes it: one form of the kernel)
+			const uint64_t cw = (uint64_t)((a.m_per_query + chunk - 1) / chunk) * ((a.n_queries + 63) / 64);
+			hipLaunchKernelGGL(k_pair_epilogue_bits_div<chunk>, dim3((unsigned)((cw + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, st, a);
+		} else if (screen) {
 			constexpr uint32_t chunk = 4;          // candidates per wave: 1 / 4 / 8 / 16 took 265 / 274 / 609 / 678 us per block before the screen was slimmed; 4 keeps the queries' side per wave
 			const uint64_t cw = (uint64_t)((a.m_per_query + chunk - 1) / chunk) * ((a.n_queries + 63) / 64);
 			hipLaunchKernelGGL(k_pair_epilogue_bits_screen<chunk>, dim3((unsigned)((cw + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, st, a);
