@@ -185,19 +185,11 @@ bool kb_route_fits(const msc_hist_set* cands, const msc_hist_set* qset, bool nee
 }
 
 
-// the first failing pair's status, as the epilogue left it in the error word
-static int error_word_status(msc_ctx* ctx, int32_t first_err) {
-	if (first_err == MSC_ERR_ZERO_LENGTH) return fail(ctx, first_err, "length_difference: a point has length 0 (the reference throws 123, predict/Feature.cpp:878-886)");
-	if (first_err == MSC_ERR_NAN) return fail(ctx, first_err, "normalisation produced NaN (the reference throws, predict/Feature.cpp:143-146)");
-	if (first_err < 0) return fail(ctx, first_err, "feature evaluation failed with status %d", first_err);
-	return MSC_OK;
-}
-
 // the epilogue's error word (the stream is idle)
 int read_error_word(msc_ctx* ctx) {
 	int32_t first_err = 0;
 	HIP_TRY(ctx, hipMemcpy(&first_err, ctx->err_word.p, sizeof first_err, hipMemcpyDeviceToHost));
-	return error_word_status(ctx, first_err);
+	return pair_status(ctx, first_err);
 }
 
 // ---- what the matrix-core drivers of msc_score_multi and msc_search_pairs (msc_api_pairs.hip) both compute
@@ -650,7 +642,7 @@ int run_sparse_queued(MultiCall& c, Block& b) {
 		*ctx->rk_guard = 0;
 		return fail(ctx, MSC_ERR_HIP, "rank pass: a query's list is longer than its set's bound (max_sum not maintained by a writer of that set)");
 	}
-	return error_word_status(ctx, first_err);
+	return pair_status(ctx, first_err);
 }
 
 // The digest, ring and raw-tile kernels: partial records per (query, candidate), folded by the epilogue; one chunk at a time, waited for.

@@ -120,8 +120,7 @@ extern "C" int msc_score_pair_list(msc_ctx* ctx, const msc_model* model, const m
 	if (!per_query) {
 		if (sp) { c_sp = a_set; q_sp = b_set; }
 		else {
-			static const bool no_mirror_env = getenv("MSC_NO_SPARSE_MIRROR") != nullptr;
-			if (!no_mirror_env && ctx->mirror_pass && L.nbins == L.padded_bins) {          // (the rule of the 1 x M calls, run_score)
+			if (mirror_pass_allowed(ctx, L)) {
 				if ((r = ensure_sparse_mirror(ctx, a_set, &c_sp)) || (r = ensure_sparse_mirror(ctx, b_set, &q_sp))) return r;
 				if (!c_sp || !q_sp) c_sp = q_sp = nullptr;
 			}

@@ -31,6 +31,11 @@ const uint64_t kSupportedFeats = MSC_FEAT_SLOW | MSC_FEAT_GROUPS;          // th
 static inline double trainer_get_id(double cutoff) { return cutoff > 1 ? cutoff / 100.0 : cutoff; }      // cluster/Trainer.h:35
 // both sets and the slots named exist and belong to ctx; same k and dtype
 int validate_pair(msc_ctx* ctx, const msc_hist_set* cands, const msc_hist_set* qset, uint64_t q_slot, const uint32_t* slots, uint64_t m);
+// the rule of the mirror pass: a DENSE set's passes may merge the lists of its sparse mirror -- not switched off (MSC_NO_SPARSE_MIRROR,
+// msc_set_mirror_pass) and the histograms are not padded (the 1 x M calls and msc_score_pair_list)
+bool mirror_pass_allowed(const msc_ctx* ctx, const MscLayout& L);
+// the first failing pair's status as the call's: 0, or the status with the message of what the reference would have thrown
+int pair_status(msc_ctx* ctx, int first_err);
 // which of the merge kernels of sparse.hip takes a pass over the lists of c_sp against slot q_slot of q_sp
 enum SparseKernel { SPK_LDS = 0, SPK_MP = 1, SPK_GENERIC = 2 };
 SparseKernel pick_sparse_kernel(const msc_hist_set* c_sp, const msc_hist_set* q_sp, uint64_t q_slot, uint64_t max_count, bool wide);

@@ -2,19 +2,14 @@
 // scratch, the epilogue and the reduction -- and msc_pair_features_raw / msc_score / msc_get_close / msc_filter / msc_merge / msc_search /
 // msc_mean_nearest (Trainer::get_close / filter / merge / closest, cluster/Trainer.cpp:23-157). Split from msc_api.hip in r05.
 #include <algorithm>
-#include <cctype>
 #include <cfloat>
 #include <chrono>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <fstream>
 #include <functional>
-#include <sstream>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "msc_internal.h"
@@ -26,7 +21,7 @@
 
 
 // integer range of the fast streaming kernels (pair_features.hip header); outside it the 64-bit kernel runs
-static bool needs_wide_impl(const msc_hist_set* a, const msc_hist_set* b) {
+bool needs_wide(const msc_hist_set* a, const msc_hist_set* b) {
 	const uint64_t mc = std::max(a->max_count, b->max_count), ms = std::max(a->max_sum, b->max_sum);
 	// a lane adds the |prefix difference| of its R bins of a tile in 32 bits; a prefix difference is at most the larger excess
 	// (k-mer) total, so R * excess must stay below 2^32 (only sequences of >= 2^26 k-mers can break it)
@@ -83,6 +78,27 @@ hipError_t launch_sparse_pass(msc_ctx* ctx, SparseKernel k, const msc_hist_set* 
 	                              use_window, min_len, max_len, partials, div_tables, div_partials, order);
 }
 
+// The two list caches of a set -- its rank lists and its repeated-bin lists -- are built alike: the slots' sizes and offsets, the total read
+// back, the entry array grown with 1/8 slack, the fill. *no_memory: an allocation failed (nothing reported: what follows is the caller's policy)
+template <class E, class Sizes, class Fill>
+static int build_slot_lists(msc_ctx* ctx, uint64_t capacity, uint64_t*& off, uint32_t*& n, E*& ent, uint64_t& entries, bool* no_memory, Sizes sizes, Fill fill) {
+	*no_memory = true;
+	if (!off && (hipMalloc((void**)&off, (capacity + 1) * sizeof(uint64_t)) != hipSuccess || hipMalloc((void**)&n, capacity * sizeof(uint32_t)) != hipSuccess)) return MSC_ERR_OOM;
+	*no_memory = false;
+	HIP_TRY(ctx, sizes());
+	uint64_t total = 0;
+	HIP_TRY(ctx, hipMemcpyAsync(&total, off + capacity, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	if (total + 4 > entries) {
+		if (ent) (void)hipFree(ent);
+		ent = nullptr;
+		entries = total + total / 8 + 1024;
+		if (hipMalloc((void**)&ent, entries * sizeof(E)) != hipSuccess) { entries = 0; *no_memory = true; return MSC_ERR_OOM; }
+	}
+	HIP_TRY(ctx, fill());
+	return MSC_OK;
+}
+
 // The rank lists of the sparse set (or sparse mirror) `s`, for the 1 x M pass of msc_ranks_pass.hip: true when they are current. Built only
 // once the same state of the set has been asked for three times (msc_objects.h).
 bool rank_lists_ready(msc_ctx* ctx, const msc_hist_set* s, int* err, bool eager) {
@@ -97,32 +113,20 @@ bool rank_lists_ready(msc_ctx* ctx, const msc_hist_set* s, int* err, bool eager)
 	// candidate must not depend on how many passes its rank has seen (a rank whose window was empty for a step would otherwise switch a
 	// step later than the others, and two identical sequences on two ranks would differ in the last bit of a divergence sum)
 	if (!eager && ++s->rkl_seen < after) return false;
-	// (no memory for the lists: the merge kernels stay -- except in the step-serial loop's own call, where it is an error: which kernel scores
-	// a pass there must not depend on what one rank's allocator had left)
-	auto give_up = [&]() {
+	bool no_memory = false;
+	*err = build_slot_lists(
+	    ctx, s->capacity, s->rkl_off, s->rkl_n, s->rkl, s->rkl_entries, &no_memory,
+	    [&] { return msc_launch_rank_lists_sizes(ctx->stream, s->hdr, s->cum, s->capacity, s->rkl_n, s->rkl_off); },
+	    [&] { return msc_launch_rank_lists_fill(ctx->stream, s->ent, s->cum, s->hdr, s->capacity, s->rkl_n, s->rkl_off, s->L.nbins, s->rkl); });
+	if (no_memory) {
+		// (no memory for the lists: the merge kernels stay -- except in the step-serial loop's own call, where it is an error: which kernel scores
+		// a pass there must not depend on what one rank's allocator had left)
 		(void)hipGetLastError();
-		if (eager) { *err = fail(ctx, MSC_ERR_OOM, "rank lists: out of device memory"); return false; }
-		s->rkl_unavailable = true;
-		return false;
-	};
-	if (!s->rkl_off && (hipMalloc((void**)&s->rkl_off, (s->capacity + 1) * sizeof(uint64_t)) != hipSuccess || hipMalloc((void**)&s->rkl_n, s->capacity * sizeof(uint32_t)) != hipSuccess))
-		return give_up();
-	if (msc_launch_rank_lists_sizes(ctx->stream, s->hdr, s->cum, s->capacity, s->rkl_n, s->rkl_off) != hipSuccess) { *err = fail(ctx, MSC_ERR_HIP, "rank lists: size pass failed"); return false; }
-	uint64_t total = 0;
-	if (hipMemcpyAsync(&total, s->rkl_off + s->capacity, sizeof total, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
-		*err = fail(ctx, MSC_ERR_HIP, "rank lists: size read-back failed");
+		*err = eager ? fail(ctx, MSC_ERR_OOM, "rank lists: out of device memory") : MSC_OK;
+		if (!eager) s->rkl_unavailable = true;
 		return false;
 	}
-	if (total + 4 > s->rkl_entries) {
-		if (s->rkl) (void)hipFree(s->rkl);
-		s->rkl = nullptr;
-		s->rkl_entries = total + total / 8 + 1024;
-		if (hipMalloc((void**)&s->rkl, s->rkl_entries * sizeof(uint32_t)) != hipSuccess) { s->rkl_entries = 0; return give_up(); }
-	}
-	if (msc_launch_rank_lists_fill(ctx->stream, s->ent, s->cum, s->hdr, s->capacity, s->rkl_n, s->rkl_off, s->L.nbins, s->rkl) != hipSuccess) {
-		*err = fail(ctx, MSC_ERR_HIP, "rank lists: fill failed");
-		return false;
-	}
+	if (*err) return false;
 	s->rkl_off_host.resize(s->capacity + 1);
 	if (hipMemcpyAsync(s->rkl_off_host.data(), s->rkl_off, (s->capacity + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
 		*err = fail(ctx, MSC_ERR_HIP, "rank lists: offsets read-back failed");
@@ -132,95 +136,88 @@ bool rank_lists_ready(msc_ctx* ctx, const msc_hist_set* s, int* err, bool eager)
 	return true;
 }
 
-// ... and its repeated-bin lists, which the long-list pass (k_pair_ranks_items) reads beside them: built at the first such pass of an epoch
-int rank_multi_ready(msc_ctx* ctx, const msc_hist_set* s) {
+// ... and its repeated-bin lists, which the long-list pass (k_pair_ranks_items) reads beside them: built at the first such pass of an epoch;
+// no memory for them is always an error
+static int rank_multi_ready(msc_ctx* ctx, const msc_hist_set* s) {
 	if (s->rkm && s->rkm_epoch == s->list_epoch) return MSC_OK;
-	if (!s->rkm_off && (hipMalloc((void**)&s->rkm_off, (s->capacity + 1) * sizeof(uint64_t)) != hipSuccess || hipMalloc((void**)&s->rkm_n, s->capacity * sizeof(uint32_t)) != hipSuccess)) {
+	bool no_memory = false;
+	const int r = build_slot_lists(
+	    ctx, s->capacity, s->rkm_off, s->rkm_n, s->rkm, s->rkm_entries, &no_memory,
+	    [&] { return msc_launch_rank_multi_sizes(ctx->stream, s->ent, s->hdr, s->capacity, s->rkm_n, s->rkm_off); },
+	    [&] { return msc_launch_rank_multi_fill(ctx->stream, s->ent, s->hdr, s->capacity, s->rkm_off, s->rkm); });
+	if (no_memory) {
 		(void)hipGetLastError();
 		return fail(ctx, MSC_ERR_OOM, "repeated-bin lists: out of device memory");
 	}
-	HIP_TRY(ctx, msc_launch_rank_multi_sizes(ctx->stream, s->ent, s->hdr, s->capacity, s->rkm_n, s->rkm_off));
-	uint64_t total = 0;
-	HIP_TRY(ctx, hipMemcpyAsync(&total, s->rkm_off + s->capacity, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
-	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-	if (total + 4 > s->rkm_entries) {
-		if (s->rkm) (void)hipFree(s->rkm);
-		s->rkm = nullptr;
-		s->rkm_entries = total + total / 8 + 1024;
-		if (hipMalloc((void**)&s->rkm, s->rkm_entries * sizeof(uint2)) != hipSuccess) {
-			(void)hipGetLastError();
-			s->rkm_entries = 0;
-			return fail(ctx, MSC_ERR_OOM, "repeated-bin lists: out of device memory");
-		}
-	}
-	HIP_TRY(ctx, msc_launch_rank_multi_fill(ctx->stream, s->ent, s->hdr, s->capacity, s->rkm_off, s->rkm));
+	if (r) return r;
 	s->rkm_epoch = s->list_epoch;
 	return MSC_OK;
 }
 
-// Streams the candidates once, then folds / evaluates per candidate. Chunked so the partial records stay <= 256 MiB.
-bool needs_wide(const msc_hist_set* a, const msc_hist_set* b) { return needs_wide_impl(a, b); }
-int run_score(msc_ctx* ctx, ScoreRequest& rq) {
-	const double t_call = g_profile_calls ? now_s() : 0;
-	int r = validate_pair(ctx, rq.cands, rq.qset, rq.q_slot, rq.cand_slots, rq.dev_slots ? 0 : rq.m);
-	if (r) return r;
-	if (rq.dev_slots && (rq.cand_slots || rq.reduce_mode < 0 || rq.m > 0xfffffff0ull)) return fail(ctx, MSC_ERR_INVALID_ARG, "run_score: a device slot list goes with a reduction only");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	const msc_hist_set* cs = rq.cands;
-	const MscLayout& L = cs->L;
-	const uint64_t m = rq.m;
-	const int nf = __builtin_popcountll(rq.feat_mask);
-	const int ns = rq.model ? rq.model->h.n_singles : 0;
-	const int nc = rq.model ? rq.model->h.n_combos : 0;
-	uint64_t want = rq.feat_mask;
-	if (rq.model) for (int i = 0; i < ns; i++) want |= rq.model->h.single_flag[i];
-	const bool need_div = (want & MSC_FEAT_DIV) != 0 && !rq.only_tiles;
-	const bool need_grp = (want & MSC_FEAT_GROUPS) != 0 && !rq.only_tiles;      // sim_mm / rre_k_r: 4-bin group statistics
-	const int tb = msc_div_table_dim(L);
-	const bool wide = needs_wide(rq.cands, rq.qset);
-	ctx->tiles_ms_accum = 0.f;
-	ctx->tiles_launches = 0;
-	ctx->have_timing = false;
-	ctx->last_kernel = cs->sparse ? "k_pair_sparse" : wide ? "k_pair_tiles_wide" : "k_pair_tiles";
-	ctx->last_query_tile = 1;
-	if (m == 0) {
-		if (rq.reduce_host) { rq.reduce_host->best_pos = rq.reduce_mode == MSC_REDUCE_GET_CLOSE ? -1 : 0; rq.reduce_host->best_sim = rq.reduce_mode == MSC_REDUCE_GET_CLOSE ? -1.0 : DBL_MIN;
-		                      rq.reduce_host->any_close = 0; rq.reduce_host->n_close = 0; rq.reduce_host->first_error = 0; }
-		return MSC_OK;
-	}
-	const bool sp = cs->sparse;
-	// The divergence statistics of a DENSE set are scored on its sparse mirror by the same merge kernels a sparse set uses (one
-	// evaluation order in every route); the dense streaming kernel then only produces the integer reductions. Histograms too small
-	// for the sparse layout (< 64 KiB) keep the table form inside the streaming kernel.
-	const msc_hist_set *c_sp = nullptr, *q_sp = nullptr;
-	// r04: a DENSE set's 1 x M pass runs over its sparse mirror too whenever the mirror exists (histograms of 64 KiB and more, narrow
-	// range): the merge kernels read 8 bytes per counted k-mer where k_pair_tiles streams 4^k bins (cfg2: ~8 KB against 1 MiB per
-	// candidate), and return the same integer reductions bit for bit (test_sparse_sets_equal_dense_sets). The streaming kernel keeps
-	// the histograms without a list form, the wide range, and msc_mean_nearest's pass against a mean (only_tiles).
+// ================================================================================================ the route of a 1 x M call
+
+bool mirror_pass_allowed(const msc_ctx* ctx, const MscLayout& L) {
 	static const bool no_mirror_env = getenv("MSC_NO_SPARSE_MIRROR") != nullptr;
-	const bool no_mirror_pass = no_mirror_env || !ctx->mirror_pass;
-	bool via = false;
-	if (sp) { c_sp = cs; q_sp = rq.qset; }
-	else if (need_div || need_grp || (!wide && !rq.only_tiles && !no_mirror_pass && L.nbins == L.padded_bins)) {
-		if ((r = ensure_sparse_mirror(ctx, cs, &c_sp)) || (r = ensure_sparse_mirror(ctx, rq.qset, &q_sp))) return r;
-		if (!c_sp || !q_sp) c_sp = q_sp = nullptr;
-		via = c_sp != nullptr && !wide && !rq.only_tiles && !no_mirror_pass;
-	}
-	const bool lists = sp || via;          // the pass is a merge of two lists
-	// sim_mm / rre_k_r: from the lists where they exist, else (histograms under 64 KiB) by the dense group kernels -- a given (k, dtype)
-	// always takes the same one of the two, so a pair has one evaluation order in every route
-	const bool grp_dense = need_grp && !c_sp;
-	if (grp_dense && std::max(rq.cands->max_count, rq.qset->max_count) > 0xffffffffull)
-		return fail(ctx, MSC_ERR_UNSUPPORTED, "sim_mm / rre_k_r: counts above 2^32 - 1 are not supported");
-	const bool mirror_div = need_div && !lists && c_sp != nullptr;      // (the mirror may be here for the group statistics alone)
-	const bool inline_div = need_div && !lists && !mirror_div;       // table form inside k_pair_tiles / direct form inside the wide kernel
-	const SparseKernel spk = c_sp ? pick_sparse_kernel(c_sp, q_sp, rq.q_slot, std::max(rq.cands->max_count, rq.qset->max_count), wide) : SPK_GENERIC;
-	if (lists) ctx->last_kernel = spk == SPK_MP && !need_div && msc_sparse_wl_fits(q_sp->hdr_host[rq.q_slot].nnz, c_sp->max_nnz) ? "k_pair_sparse_wl" : sparse_kernel_name(spk);
+	return !no_mirror_env && ctx->mirror_pass && L.nbins == L.padded_bins;
+}
+
+int pair_status(msc_ctx* ctx, int first_err) {
+	if (first_err == MSC_ERR_ZERO_LENGTH) return fail(ctx, first_err, "length_difference: a point has length 0 (the reference throws 123, predict/Feature.cpp:878-886)");
+	if (first_err == MSC_ERR_NAN) return fail(ctx, first_err, "normalisation produced NaN (the reference throws, predict/Feature.cpp:143-146)");
+	if (first_err < 0) return fail(ctx, first_err, "feature evaluation failed with status %d", first_err);
+	return MSC_OK;
+}
+
+namespace {
+
+enum PassKind { PASS_TILES, PASS_TILES_WIDE, PASS_MERGE, PASS_RANKS_1XM, PASS_RANKS_ITEMS };          // which kernel streams the candidates
+// where the two FP64 divergence sums come from: the table form inside k_pair_tiles / the direct form inside the wide kernel, a merge pass over
+// the mirror's lists beside the streaming kernel, the merge pass itself, the cells the items kernel counts
+enum DivForm { DIV_NONE, DIV_INLINE, DIV_MIRROR, DIV_LISTS, DIV_RANKS };
+enum GroupForm { GRP_NONE, GRP_DENSE, GRP_LISTS };          // sim_mm / rre_k_r: the dense group kernels, or from the lists
+
+// what pick_score_route decides for one call; the stages below read it and decide nothing
+struct ScoreRoute {
+	PassKind pass = PASS_TILES;
+	DivForm div = DIV_NONE;          // (DIV_MIRROR and up: c_sp exists and the sums reach the epilogue per {jd, js} record)
+	GroupForm grp = GRP_NONE;
+	const msc_hist_set *c_sp = nullptr, *q_sp = nullptr;          // the lists the pass or its side passes read: the sets themselves or their sparse mirrors
+	SparseKernel spk = SPK_GENERIC;                                // the merge kernel of the pass / of the mirror side pass
+	uint32_t mp_parts = 1;                                         // waves that share a candidate of the merge-path kernel
+	uint32_t PS = 0, SPN = 0, DVN = 0;                             // records per candidate: partials of the pass, of a merge pass, {jd, js}
+	uint32_t rank_rounds = 0;                                      // items pass: rounds of 1 024 entries that cover its longest list
+	uint64_t q_kmers = 0, chunk = 0;                               // bound on the k-mers of any histogram of the query's set; candidates per chunk
+	int nf = 0, ns = 0, nc = 0;                                    // raw statistics, singles, combos per candidate
+	bool need_po = false, fused = false;                           // the per-pair records go home; epilogue, first reduce stage and close pass in one kernel
+	const char* kernel = "";                                       // msc_last_kernel_info's name of the pass
+	bool lists() const { return pass >= PASS_MERGE; }              // the pass reads two lists, no bins
+	bool ranks() const { return pass >= PASS_RANKS_1XM; }
+};
+
+// one chunk of the candidates
+struct ScoreChunk {
+	uint64_t off = 0;
+	uint32_t mc = 0;
+	const uint32_t* d_slots = nullptr;
+	const uint8_t *c_bins = nullptr, *c_scal = nullptr, *q_bins = nullptr, *q_scal = nullptr;
+};
+
+// what the stages of a chunk hand on, and what the call keeps of its chunks
+struct ScoreHome {
+	std::vector<MscPairOut> po;
+	int first_err = 0;
+	bool fold_on_host = false;          // the fused kernel's parts sit in page-locked memory: the host folds them behind the wait
+	uint32_t n_parts = 0;
+};
+
+// May the pass run over RANK lists, and which of the two rank kernels takes it? Sets pass, rank_rounds and the kernel's name.
+int pick_rank_pass(msc_ctx* ctx, const ScoreRequest& rq, bool need_div, ScoreRoute* rt) {
+	const MscLayout& L = rq.cands->L;
+	const msc_hist_set *c_sp = rt->c_sp, *q_sp = rt->q_sp;
+	int r;
 	// r04: up to k = 9 the integer statistics of a list pass come from RANK lists -- no merge (msc_ranks_pass.hip): the query's histogram as
 	// two bits per bin in LDS, the candidates' k-mers streamed at 4 bytes each. Same records as the merge kernels, bit for bit.
 	const bool no_rank_pass = getenv("MSC_NO_RANKS_1XM") != nullptr;          // (read on every call: tests compare both routes in one process)
-	bool rank_pass = false;
-	const uint64_t q_kmers = rq.qset->max_sum >= L.nbins ? rq.qset->max_sum - L.nbins : ~0ull;          // bound on the k-mers of any histogram of the query's set
 	// (the divergence statistics too: bins counted per cell of (candidate's count, query's count) by k_pair_ranks_items, evaluated per
 	// candidate in one fixed order by k_rank_items_finish -- msc_ranks_pass.hip; MSC_NO_RANKS_DIV keeps such passes on the merge kernel)
 	const bool no_rank_div = getenv("MSC_NO_RANKS_DIV") != nullptr;
@@ -233,7 +230,7 @@ int run_score(msc_ctx* ctx, ScoreRequest& rq) {
 	// Long lists (more than 8 192 k-mers on either side) go through k_pair_ranks_items: the unit of work is a round of 1 024 entries of a
 	// candidate, so a window of a few thousand long candidates still fills the chip (MSC_NO_RANKS_ITEMS: such passes stay on the merge kernel
 	// when they carry divergence statistics, on k_pair_ranks_1xm otherwise).
-	const uint64_t c_kmers = c_sp && c_sp->max_sum >= L.nbins ? c_sp->max_sum - L.nbins : ~0ull;          // bound on the k-mers of any candidate
+	const uint64_t c_kmers = c_sp->max_sum >= L.nbins ? c_sp->max_sum - L.nbins : ~0ull;          // bound on the k-mers of any candidate
 	// (which of the two rank kernels takes a pass is decided by the QUERY alone -- its stored bins, the same number on every rank of a sharded
 	// run and in a one-rank run -- never by a bound of the set or shard at hand: the two kernels add the divergence terms in different orders,
 	// and two identical sequences scored for one query must not come out one bit apart because they sit on different ranks)
@@ -242,65 +239,122 @@ int run_score(msc_ctx* ctx, ScoreRequest& rq) {
 	// preparation kernels); without them a short query's pass stays with k_pair_ranks_1xm (1 kb +- 100, 13 300 candidates per pass: 31 us
 	// against 35 + 10 + 6.5). (MSC_RANKS_ITEMS_FROM=n: the bound for both.)
 	static const int items_from = [] { const char* e = getenv("MSC_RANKS_ITEMS_FROM"); return e ? atoi(e) : -1; }();
-	const bool long_lists = q_sp && q_sp->hdr_host[rq.q_slot].nnz > (uint32_t)(items_from >= 0 ? items_from : need_div ? 0 : 2000);
+	const bool long_lists = q_sp->hdr_host[rq.q_slot].nnz > (uint32_t)(items_from >= 0 ? items_from : need_div ? 0 : 2000);
 	// Rounds of 1 024 entries that cover the longest list THIS PASS can meet: a candidate the length window drops takes no
 	// round, so inside a window no list is longer than max_len k-mers (nor the query's own); only without a window does the set's bound
 	// count. One 50 Mb scaffold among short sequences used to size -- and clear, every step -- the accumulators of every pass for 50 000
 	// rounds per candidate. And a pass whose scratch would still pass 2 GiB stays with the merge kernels instead of failing with OOM.
-	uint64_t pass_kmers = std::max(q_kmers, c_kmers);
+	uint64_t pass_kmers = std::max(rt->q_kmers, c_kmers);
 	if (rq.use_window && long_lists) {
 		uint64_t q_len = 0;
 		if ((r = slot_length(ctx, rq.qset, rq.q_slot, &q_len))) return r;
 		pass_kmers = std::min(pass_kmers, std::max(rq.max_len, q_len));
 	}
 	const uint64_t pass_rounds = (pass_kmers + msc_ranks_items_round() - 1) / msc_ranks_items_round();
-	const bool items_ok = getenv("MSC_NO_RANKS_ITEMS") == nullptr && c_kmers < (1ull << 26) && pass_rounds < (1ull << 26) && m * (64 + pass_rounds * 3 * 280) <= (2048ull << 20);
+	const bool items_ok = getenv("MSC_NO_RANKS_ITEMS") == nullptr && c_kmers < (1ull << 26) && pass_rounds < (1ull << 26) && rq.m * (64 + pass_rounds * 3 * 280) <= (2048ull << 20);
 	const bool div_fits = !need_div || (!no_rank_div && rank_div_wanted && long_lists && items_ok);          // (only the items kernel carries the divergence statistics)
-	bool rank_items = false;
-	uint32_t rank_rounds = 0;
-	if (lists && div_fits && !rq.only_tiles && spk == SPK_MP && !no_rank_pass && q_kmers <= msc_ranks_pass_query_cap() && msc_ranks_pass_lds(L.nbins, q_kmers) != 0) {
-		int e = MSC_OK;
-		rank_pass = rank_lists_ready(ctx, c_sp, &e, rq.close_list.pos != nullptr);
-		if (e) return e;
-		if (rank_pass && !ctx->rk_guard) {
-			HIP_TRY(ctx, hipHostMalloc((void**)&ctx->rk_guard, 64, hipHostMallocDefault));
-			*ctx->rk_guard = 0;
-		}
-		rank_items = rank_pass && long_lists && items_ok;
-		if (rank_items) {
-			if ((r = rank_multi_ready(ctx, c_sp))) return r;
-			rank_rounds = (uint32_t)pass_rounds;
-			if ((r = ensure(ctx, ctx->rk_q, ((q_kmers + 255) & ~255ull) * sizeof(uint32_t) + 1024))) return r;
-		} else if (rank_pass && msc_ranks_pass_query_scratch(q_kmers) && (r = ensure(ctx, ctx->rk_q, msc_ranks_pass_query_scratch(q_kmers) * sizeof(uint32_t)))) return r;
-		if (rank_pass) ctx->last_kernel = rank_items ? "k_pair_ranks_items" : "k_pair_ranks_1xm";
+	if (!rt->lists() || !div_fits || rq.only_tiles || rt->spk != SPK_MP || no_rank_pass || rt->q_kmers > msc_ranks_pass_query_cap() || msc_ranks_pass_lds(L.nbins, rt->q_kmers) == 0)
+		return MSC_OK;
+	int e = MSC_OK;
+	if (!rank_lists_ready(ctx, c_sp, &e, rq.close_list.pos != nullptr)) return e;
+	if (!ctx->rk_guard) {
+		HIP_TRY(ctx, hipHostMalloc((void**)&ctx->rk_guard, 64, hipHostMallocDefault));
+		*ctx->rk_guard = 0;
 	}
+	rt->pass = PASS_RANKS_1XM;
+	rt->kernel = "k_pair_ranks_1xm";
+	if (long_lists && items_ok) {
+		if ((r = rank_multi_ready(ctx, c_sp))) return r;
+		rt->pass = PASS_RANKS_ITEMS;
+		rt->kernel = "k_pair_ranks_items";
+		rt->rank_rounds = (uint32_t)pass_rounds;
+	}
+	return MSC_OK;
+}
+
+// The one place that decides how a call runs -- and that reads MSC_NO_SPARSE_MIRROR, msc_set_mirror_pass, MSC_NO_RANKS_1XM, MSC_NO_RANKS_DIV,
+// MSC_RANKS_DIV, MSC_RANKS_ITEMS_FROM, MSC_NO_RANKS_ITEMS and MSC_NO_FUSED_REDUCE. It prepares what the decision depends on (the sparse mirrors,
+// the rank lists, which count their requests) and nothing else.
+int pick_score_route(msc_ctx* ctx, const ScoreRequest& rq, ScoreRoute* rt) {
+	const msc_hist_set* cs = rq.cands;
+	const MscLayout& L = cs->L;
+	int r;
+	rt->nf = __builtin_popcountll(rq.feat_mask);
+	rt->ns = rq.model ? rq.model->h.n_singles : 0;
+	rt->nc = rq.model ? rq.model->h.n_combos : 0;
+	uint64_t want = rq.feat_mask;
+	if (rq.model) for (int i = 0; i < rt->ns; i++) want |= rq.model->h.single_flag[i];
+	const bool need_div = (want & MSC_FEAT_DIV) != 0 && !rq.only_tiles;
+	const bool need_grp = (want & MSC_FEAT_GROUPS) != 0 && !rq.only_tiles;      // sim_mm / rre_k_r: 4-bin group statistics
+	const bool wide = needs_wide(rq.cands, rq.qset);
+	// The divergence statistics of a DENSE set are scored on its sparse mirror by the same merge kernels a sparse set uses (one
+	// evaluation order in every route); the dense streaming kernel then only produces the integer reductions. Histograms too small
+	// for the sparse layout (< 64 KiB) keep the table form inside the streaming kernel.
+	// r04: a DENSE set's 1 x M pass runs over its sparse mirror too whenever the mirror exists (histograms of 64 KiB and more, narrow
+	// range): the merge kernels read 8 bytes per counted k-mer where k_pair_tiles streams 4^k bins (cfg2: ~8 KB against 1 MiB per
+	// candidate), and return the same integer reductions bit for bit (test_sparse_sets_equal_dense_sets). The streaming kernel keeps
+	// the histograms without a list form, the wide range, and msc_mean_nearest's pass against a mean (only_tiles).
+	const bool mirror_pass = !cs->sparse && !wide && !rq.only_tiles && mirror_pass_allowed(ctx, L);
+	rt->pass = wide ? PASS_TILES_WIDE : PASS_TILES;
+	if (cs->sparse) { rt->c_sp = cs; rt->q_sp = rq.qset; rt->pass = PASS_MERGE; }
+	else if (need_div || need_grp || mirror_pass) {
+		if ((r = ensure_sparse_mirror(ctx, cs, &rt->c_sp)) || (r = ensure_sparse_mirror(ctx, rq.qset, &rt->q_sp))) return r;
+		if (!rt->c_sp || !rt->q_sp) rt->c_sp = rt->q_sp = nullptr;
+		if (rt->c_sp && mirror_pass) rt->pass = PASS_MERGE;          // (a padded histogram has no mirror: what exists passes the rule's layout test)
+	}
+	const msc_hist_set *c_sp = rt->c_sp, *q_sp = rt->q_sp;
+	// sim_mm / rre_k_r: from the lists where they exist, else (histograms under 64 KiB) by the dense group kernels -- a given (k, dtype)
+	// always takes the same one of the two, so a pair has one evaluation order in every route
+	rt->grp = !need_grp ? GRP_NONE : c_sp ? GRP_LISTS : GRP_DENSE;
+	if (rt->grp == GRP_DENSE && std::max(rq.cands->max_count, rq.qset->max_count) > 0xffffffffull)
+		return fail(ctx, MSC_ERR_UNSUPPORTED, "sim_mm / rre_k_r: counts above 2^32 - 1 are not supported");
+	rt->spk = c_sp ? pick_sparse_kernel(c_sp, q_sp, rq.q_slot, std::max(rq.cands->max_count, rq.qset->max_count), wide) : SPK_GENERIC;
+	const uint32_t q_nnz = c_sp ? q_sp->hdr_host[rq.q_slot].nnz : 0;
+	const bool whole_lists = c_sp && msc_sparse_wl_fits(q_nnz, c_sp->max_nnz);
+	rt->kernel = rt->lists() ? (rt->spk == SPK_MP && !need_div && whole_lists ? "k_pair_sparse_wl" : sparse_kernel_name(rt->spk)) : wide ? "k_pair_tiles_wide" : "k_pair_tiles";
+	rt->q_kmers = rq.qset->max_sum >= L.nbins ? rq.qset->max_sum - L.nbins : ~0ull;
+	if (c_sp && (r = pick_rank_pass(ctx, rq, need_div, rt))) return r;
+	// the divergence sums: the mirror may be here for the group statistics alone; without one, the table form inside k_pair_tiles / the direct
+	// form inside the wide kernel
+	rt->div = !need_div ? DIV_NONE : rt->ranks() ? DIV_RANKS : rt->lists() ? DIV_LISTS : c_sp ? DIV_MIRROR : DIV_INLINE;
 	// a sparse set's integer statistics through the merge-path kernel: a short window is shared out, several waves per candidate
 	// (never the divergence form: its FP64 sums keep one evaluation order whatever the window)
 	// ... and so is the divergence form (sparse sets and the mirror pass of dense ones): its FP64 sums leave per granule of the merged
 	// order and are added in granule order by the epilogue, whatever the number of waves that shared a pair
-	const uint64_t mp_entries = c_sp ? (uint64_t)q_sp->hdr_host[rq.q_slot].nnz + c_sp->max_nnz : 0;
-	const uint32_t mp_parts = c_sp && !rank_pass && spk == SPK_MP && (need_div ? true : lists && !msc_sparse_wl_fits(q_sp->hdr_host[rq.q_slot].nnz, c_sp->max_nnz))
-	                              ? msc_sparse_mp_parts((uint32_t)std::min<uint64_t>(m, 0xffffffffu), mp_entries, ctx->num_cus, need_div) : 1;
-	const uint32_t SPN = sparse_records(spk, mp_parts);               // records per candidate the merge kernel writes
-	const bool rank_div = rank_pass && need_div;
-	const uint32_t DVN = rank_div ? 1 : div_records(spk, mp_entries);                // ... and {jd, js} records per candidate
-	const uint32_t PS = lists ? SPN : L.S;                            // partial records per candidate
-	ctx->last_partial_stride = PS;
-	uint64_t chunk = (256ull << 20) / ((uint64_t)PS * sizeof(MscPartial));
-	chunk = std::max<uint64_t>(chunk, 1024);
-	if (rq.reduce_mode >= 0 || rq.only_tiles) chunk = m;      // reductions run over the whole window in one piece
-	chunk = std::min(chunk, m);
+	const uint64_t mp_entries = c_sp ? (uint64_t)q_nnz + c_sp->max_nnz : 0;
+	rt->mp_parts = c_sp && !rt->ranks() && rt->spk == SPK_MP && (need_div || (rt->lists() && !whole_lists))
+	                   ? msc_sparse_mp_parts((uint32_t)std::min<uint64_t>(rq.m, 0xffffffffu), mp_entries, ctx->num_cus, need_div) : 1;
+	rt->SPN = sparse_records(rt->spk, rt->mp_parts);
+	rt->DVN = rt->div == DIV_RANKS ? 1 : div_records(rt->spk, mp_entries);
+	rt->PS = rt->lists() ? rt->SPN : L.S;
+	rt->chunk = std::max<uint64_t>((256ull << 20) / ((uint64_t)rt->PS * sizeof(MscPartial)), 1024);          // the partial records of a chunk stay <= 256 MiB
+	if (rq.reduce_mode >= 0 || rq.only_tiles) rt->chunk = rq.m;      // reductions run over the whole window in one piece
+	rt->chunk = std::min(rt->chunk, rq.m);
+	rt->need_po = rq.sum_out || rq.csum_out || rq.combo0_out || rq.status_out || rq.reduce_mode < 0;
+	// a reduced pass that returns nothing per pair: epilogue, first reduce stage and the window's close pass in one kernel
+	rt->fused = rq.reduce_mode >= 0 && !rt->need_po && !rq.raw_out && !rq.singles_out && !rq.combos_out && rt->PS <= 4 && getenv("MSC_NO_FUSED_REDUCE") == nullptr;
+	return MSC_OK;
+}
 
-	if ((r = ensure(ctx, ctx->partials, chunk * PS * sizeof(MscPartial))) != MSC_OK) return r;
+// ================================================================================================ the stages of a call
+
+// the scratch of a chunk of rt.chunk candidates, the slot list on the device
+int ensure_score_scratch(msc_ctx* ctx, const ScoreRequest& rq, const ScoreRoute& rt) {
+	const MscLayout& L = rq.cands->L;
+	const uint64_t m = rq.m, chunk = rt.chunk;
+	int r;
+	if ((r = ensure(ctx, ctx->partials, chunk * rt.PS * sizeof(MscPartial)))) return r;
 	if (rq.cand_slots && !(rq.slots_uploaded && ctx->slots.cap >= m * sizeof(uint32_t))) {
-		if ((r = ensure(ctx, ctx->slots, m * sizeof(uint32_t))) != MSC_OK) return r;
-		if ((r = ensure_pinned(ctx, ctx->pin_up, m * sizeof(uint32_t))) != MSC_OK) return r;
+		if ((r = ensure(ctx, ctx->slots, m * sizeof(uint32_t))) || (r = ensure_pinned(ctx, ctx->pin_up, m * sizeof(uint32_t)))) return r;
 		memcpy(ctx->pin_up.p, rq.cand_slots, m * sizeof(uint32_t));      // the previous call's copy has completed: every call ends in a sync
 		HIP_TRY(ctx, hipMemcpyAsync(ctx->slots.p, ctx->pin_up.p, m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
 	}
+	// the query's rank list where a rank pass keeps it in global memory
+	const uint64_t rk_q_words = rt.pass == PASS_RANKS_ITEMS ? ((rt.q_kmers + 255) & ~255ull) + 256 : rt.pass == PASS_RANKS_1XM ? msc_ranks_pass_query_scratch(rt.q_kmers) : 0;
+	if (rk_q_words && (r = ensure(ctx, ctx->rk_q, rk_q_words * sizeof(uint32_t)))) return r;
 	// (long lists: a record and a spot-term slot per item, nothing to clear; the pass's counters in two sets used in turn, each pass clearing the other's)
-	if (rank_items) {
-		if ((r = ensure(ctx, ctx->rk_acc, msc_ranks_items_rec_bytes(chunk, rank_rounds))) || (r = ensure(ctx, ctx->rk_items, msc_ranks_items_list_bytes(chunk, rank_rounds)))) return r;
+	if (rt.pass == PASS_RANKS_ITEMS) {
+		if ((r = ensure(ctx, ctx->rk_acc, msc_ranks_items_rec_bytes(chunk, rt.rank_rounds))) || (r = ensure(ctx, ctx->rk_items, msc_ranks_items_list_bytes(chunk, rt.rank_rounds)))) return r;
 		if (!ctx->rk_counters.p) {
 			if ((r = ensure(ctx, ctx->rk_counters, 32 * sizeof(uint32_t)))) return r;
 			HIP_TRY(ctx, hipMemsetAsync(ctx->rk_counters.p, 0, 32 * sizeof(uint32_t), ctx->stream));
@@ -311,196 +365,248 @@ int run_score(msc_ctx* ctx, ScoreRequest& rq) {
 			HIP_TRY(ctx, hipMemsetAsync(ctx->rk_tables.p, 0, 2 * (size_t)ctx->rk_table_words * sizeof(uint32_t), ctx->stream));
 		}
 	}
-	if (rank_div && (r = ensure(ctx, ctx->rk_big, ((size_t)q_sp->hdr_host[rq.q_slot].nnz + 1) * sizeof(uint32_t)))) return r;
-	if (need_div) {
-		if (!rank_div && (r = ensure(ctx, ctx->div_tables, chunk * (c_sp ? 256 : tb * tb) * 16)) != MSC_OK) return r;
-		if ((r = ensure(ctx, ctx->div_partials, chunk * (c_sp ? DVN : PS) * 16)) != MSC_OK) return r;
-		if (mirror_div && (r = ensure(ctx, ctx->sp_partials, chunk * SPN * sizeof(MscPartial))) != MSC_OK) return r;
+	if (rt.div == DIV_RANKS && (r = ensure(ctx, ctx->rk_big, ((size_t)rt.q_sp->hdr_host[rq.q_slot].nnz + 1) * sizeof(uint32_t)))) return r;
+	if (rt.div != DIV_NONE) {
+		const int tb = msc_div_table_dim(L);
+		if (rt.div != DIV_RANKS && (r = ensure(ctx, ctx->div_tables, chunk * (rt.c_sp ? 256 : tb * tb) * 16))) return r;
+		if ((r = ensure(ctx, ctx->div_partials, chunk * (rt.c_sp ? rt.DVN : rt.PS) * 16))) return r;
+		if (rt.div == DIV_MIRROR && (r = ensure(ctx, ctx->sp_partials, chunk * rt.SPN * sizeof(MscPartial)))) return r;
 	}
-	if (need_grp) {
-		if ((r = ensure(ctx, ctx->grp_pairs, chunk * 32 * sizeof(double))) != MSC_OK) return r;
-		if ((r = ensure(ctx, ctx->grp_self, (chunk + 1) * 16 * sizeof(double))) != MSC_OK) return r;      // [candidates][16] then the query's 16
-	}
-	if (!rq.only_tiles) {
-		if ((r = ensure(ctx, ctx->pair_out, chunk * sizeof(MscPairOut))) != MSC_OK) return r;
-		if (rq.raw_out && (r = ensure(ctx, ctx->raw, chunk * nf * sizeof(double))) != MSC_OK) return r;
-		if (rq.singles_out && (r = ensure(ctx, ctx->singles, chunk * ns * sizeof(double))) != MSC_OK) return r;
-		if (rq.combos_out && (r = ensure(ctx, ctx->combos, chunk * nc * sizeof(double))) != MSC_OK) return r;
-		if ((r = ensure(ctx, ctx->flags, 64 + chunk)) != MSC_OK) return r;      // [reduce record (64 B)][close flags]: one copy back
-		if ((r = ensure(ctx, ctx->reduce_out, sizeof(MscReduceOut))) != MSC_OK) return r;
-	}
-	const uint8_t* q_bins = sp ? nullptr : rq.qset->bins + rq.q_slot * rq.qset->L.slot_bytes;
-	const uint8_t* q_scal = rq.qset->scalars + rq.q_slot * rq.qset->scalar_stride;
-	std::vector<MscPairOut> po_host;
-	int first_err = 0;
-	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_all0, ctx->stream));
-	if (g_profile_calls) { ctx->prof_calls++; ctx->prof_cands += m; ctx->prof_prep += now_s() - t_call; }
-	bool fold_on_host = false;
-	uint32_t n_parts_host = 0;
-	for (uint64_t off = 0; off < m; off += chunk) {
-		const double t_issue = g_profile_calls ? now_s() : 0;
-		const uint32_t mc = (uint32_t)std::min(chunk, m - off);
-		const uint32_t* d_slots = rq.dev_slots ? rq.dev_slots : rq.cand_slots ? (const uint32_t*)ctx->slots.p + off : nullptr;
-		const uint8_t* c_bins = sp ? nullptr : cs->bins + (d_slots ? 0 : off * L.slot_bytes);
-		const uint8_t* c_scal = cs->scalars + (d_slots ? 0 : off * cs->scalar_stride);
-		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_tiles0, ctx->stream));
-		if (lists && g_profile_calls) {
-			if (!ctx->prof_nnz.p) { if ((r = ensure(ctx, ctx->prof_nnz, 32))) return r; HIP_TRY(ctx, hipMemsetAsync(ctx->prof_nnz.p, 0, 32, ctx->stream)); }
-			HIP_TRY(ctx, msc_launch_sparse_nnz_sum(ctx->stream, c_sp->hdr, cs->scalars, cs->scalar_stride, d_slots, off, mc, rq.use_window, rq.min_len, rq.max_len,
-			                                       (uint64_t*)ctx->prof_nnz.p + (rank_pass ? 2 : 0)));
-			ctx->prof_q_nnz += q_sp->hdr_host[rq.q_slot].nnz;
-		}
-		if (lists && rank_items) {
-			MscRankDiv dv{(uint32_t*)ctx->rk_big.p, q_scal, rq.order, (double*)ctx->div_partials.p};
-			HIP_TRY(ctx, msc_launch_pair_ranks_items(ctx->stream, c_sp->rkl, c_sp->rkl_off, c_sp->rkl_n, c_sp->rkm, c_sp->rkm_off, c_sp->rkm_n, cs->scalars + (d_slots ? 0 : off * cs->scalar_stride),
-			                                         cs->scalar_stride, d_slots, off, mc, q_sp->ent, q_sp->cum, q_sp->hdr + rq.q_slot, L.nbins, rq.use_window, rq.min_len, rq.max_len,
-			                                         (MscPartial*)ctx->partials.p, ctx->num_cus, (uint32_t*)ctx->rk_q.p, rank_rounds, ctx->rk_acc.p, rank_div ? &dv : nullptr, q_kmers, ctx->rk_guard,
-			                                         ctx->rk_items.p, (uint32_t*)ctx->rk_counters.p, (uint32_t*)ctx->rk_tables.p, (int)(ctx->rk_turn++ & 1u),
-			                                         q_sp == c_sp && rq.q_slot < c_sp->capacity ? c_sp->rkl + c_sp->rkl_off_host[rq.q_slot] : nullptr));
-		} else if (lists && rank_pass) {
-			HIP_TRY(ctx, msc_launch_pair_ranks_1xm(ctx->stream, c_sp->rkl, c_sp->rkl_off, c_sp->rkl_n, cs->scalars + (d_slots ? 0 : off * cs->scalar_stride), cs->scalar_stride, d_slots, off, mc,
-			                                       q_sp->ent, q_sp->cum, q_sp->hdr + rq.q_slot, L.nbins, rq.use_window, rq.min_len, rq.max_len, (MscPartial*)ctx->partials.p, ctx->num_cus, q_kmers, ctx->rk_guard, (uint32_t*)ctx->rk_q.p));
-		} else if (lists) {
-			HIP_TRY(ctx, launch_sparse_pass(ctx, spk, c_sp, cs->scalars, cs->scalar_stride, d_slots, off, mc, q_sp, rq.q_slot, q_scal, L.nbins, rq.use_window, rq.min_len,
-			                                rq.max_len, (MscPartial*)ctx->partials.p, need_div ? ctx->div_tables.p : nullptr, need_div ? ctx->div_partials.p : nullptr, rq.order,
-			                                mp_parts, DVN));
-		} else if (wide) {
-			HIP_TRY(ctx, msc_launch_pair_tiles_wide(ctx->stream, L, cs->dtype, c_bins, c_scal, d_slots, mc, q_bins, q_scal, rq.use_window, rq.min_len,
-			                                        rq.max_len, (MscPartial*)ctx->partials.p, ctx->num_cus, inline_div ? ctx->div_partials.p : nullptr, rq.order));
-		} else {
-			HIP_TRY(ctx, msc_launch_pair_tiles(ctx->stream, L, cs->dtype, c_bins, c_scal, d_slots, mc, q_bins, q_scal, rq.use_window, rq.min_len,
-			                                   rq.max_len, (MscPartial*)ctx->partials.p, ctx->num_cus, inline_div ? ctx->div_tables.p : nullptr,
-			                                   inline_div ? ctx->div_partials.p : nullptr, rq.order));
-		}
-		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_tiles1, ctx->stream));
-		if (mirror_div)        // the divergence sums of this chunk, from the lists of the same slots (outside the streaming kernel's timing)
-			HIP_TRY(ctx, launch_sparse_pass(ctx, spk, c_sp, cs->scalars, cs->scalar_stride, d_slots, off, mc, q_sp, rq.q_slot, q_scal, L.nbins, rq.use_window, rq.min_len,
-			                                rq.max_len, (MscPartial*)ctx->sp_partials.p, ctx->div_tables.p, ctx->div_partials.p, rq.order, mp_parts, DVN));
-		if (grp_dense) {
-			HIP_TRY(ctx, msc_launch_pair_groups_dense(ctx->stream, L, cs->dtype, c_bins, c_scal, cs->scalar_stride, d_slots, mc, q_bins, rq.use_window, rq.min_len, rq.max_len,
-			                                          (double*)ctx->grp_pairs.p));
-			HIP_TRY(ctx, msc_launch_self_markov_dense(ctx->stream, L, cs->dtype, cs->bins, d_slots, off, mc, (double*)ctx->grp_self.p));
-			HIP_TRY(ctx, msc_launch_self_markov_dense(ctx->stream, rq.qset->L, rq.qset->dtype, rq.qset->bins, nullptr, rq.q_slot, 1, (double*)ctx->grp_self.p + (uint64_t)chunk * 16));
-		} else if (need_grp) {
-			HIP_TRY(ctx, msc_launch_pair_sparse_groups(ctx->stream, c_sp->ent, c_sp->hdr + (d_slots ? 0 : off), cs->scalars + (d_slots ? 0 : off * cs->scalar_stride),
-			                                           cs->scalar_stride, d_slots, mc, q_sp->ent, q_sp->hdr + rq.q_slot, rq.use_window, rq.min_len, rq.max_len,
-			                                           (double*)ctx->grp_pairs.p));
-			HIP_TRY(ctx, msc_launch_sparse_self_markov(ctx->stream, c_sp->ent, c_sp->hdr, d_slots, off, mc, (double*)ctx->grp_self.p));
-			HIP_TRY(ctx, msc_launch_sparse_self_markov(ctx->stream, q_sp->ent, q_sp->hdr, nullptr, rq.q_slot, 1, (double*)ctx->grp_self.p + (uint64_t)chunk * 16));
-		}
-		if (rq.only_tiles) {
-			if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_all1, ctx->stream));
-			break;
-		}
-		MscEpilogueArgs ea;
-		memset(&ea, 0, sizeof ea);
-		ea.partials = (const MscPartial*)ctx->partials.p;
-		ea.div_partials = inline_div ? ctx->div_partials.p : nullptr;
-		if (need_div && c_sp) { ea.div_direct = (const double*)ctx->div_partials.p; ea.div_direct_n = DVN; ea.div_base = L.nbins; }
-		if (need_grp) { ea.grp_pairs = (const double*)ctx->grp_pairs.p; ea.grp_self_c = (const double*)ctx->grp_self.p; ea.grp_self_q = (const double*)ctx->grp_self.p + (uint64_t)chunk * 16; }
-		ea.S = PS;
-		ea.sparse_base = lists ? L.nbins : 0;
-		ea.m = mc;
-		ea.cand_scalars = c_scal;
-		ea.cand_scalar_stride = cs->scalar_stride;
-		ea.cand_slots = d_slots;
-		ea.q_scalars = q_scal;
-		ea.nbins = L.nbins;
-		ea.dtype = cs->dtype;
-		ea.order = rq.order;
-		ea.use_window = rq.use_window;
-		ea.min_len = rq.min_len;
-		ea.max_len = rq.max_len;
-		ea.feat_mask = rq.feat_mask;
-		ea.raw_out = rq.raw_out ? (double*)ctx->raw.p : nullptr;
-		ea.model = rq.model ? rq.model->d : nullptr;
-		ea.singles_out = rq.singles_out ? (double*)ctx->singles.p : nullptr;
-		ea.combos_out = rq.combos_out ? (double*)ctx->combos.p : nullptr;
-		ea.pair_out = (MscPairOut*)ctx->pair_out.p;
-		const bool need_po = rq.sum_out || rq.csum_out || rq.combo0_out || rq.status_out || (rq.flags_out && rq.reduce_mode < 0) || rq.reduce_mode < 0;
-		// a reduced pass that returns nothing per pair: epilogue, first reduce stage and the window's close pass in one kernel
-		const bool fused = rq.reduce_mode >= 0 && !need_po && !rq.raw_out && !rq.singles_out && !rq.combos_out && PS <= 4 && getenv("MSC_NO_FUSED_REDUCE") == nullptr;
-		if (fused) ea.pair_out = nullptr;
-		else HIP_TRY(ctx, msc_launch_epilogue(ctx->stream, ea));
-		if (rq.reduce_mode >= 0) {
-			// the reduce kernel writes its record and the close flags straight into page-locked host memory the device can address
-			// (no copy command behind the kernel): [reduce record (64 B)][close flags]
-			constexpr size_t kRo = 64;
-			static_assert(sizeof(MscReduceOut) <= kRo, "the reduce record sits in front of the flags");
-			if ((r = ensure_pinned(ctx, ctx->pin_down, kRo + mc)) != MSC_OK) return r;
-			uint8_t* down = nullptr;
-			HIP_TRY(ctx, hipHostGetDevicePointer((void**)&down, ctx->pin_down.p, 0));
-			if ((r = ensure(ctx, ctx->reduce_parts, msc_reduce_scratch_bytes())) != MSC_OK) return r;
-			uint8_t* d_flags = rq.dev_flags_out ? rq.dev_flags_out : rq.flags_out ? down + kRo : nullptr;
-			if (fused) {
-				// (the step-serial loop's own call: the workgroups' parts go to page-locked memory and are folded here, behind the wait for the
-				// stream -- k_pair_reduce_fold2 was one of a pass's launches)
-				ReducePart* host_parts = nullptr;
-				if (rq.close_list.pos && rq.close_list.out_host && off == 0 && mc == m) {
-					if ((r = ensure_pinned(ctx, ctx->pin_parts, 1024 * sizeof(ReducePart))) != MSC_OK) return r;
-					HIP_TRY(ctx, hipHostGetDevicePointer((void**)&host_parts, ctx->pin_parts.p, 0));
-				}
-				fold_on_host = host_parts != nullptr;
-				HIP_TRY(ctx, msc_launch_epilogue_reduce(ctx->stream, ea, rq.reduce_mode, rq.reduce_begin, d_flags, (MscReduceOut*)down, ctx->reduce_parts.p, rq.close_list, host_parts, &n_parts_host));
-				if (rq.after_reduce && !rq.close_list.pos) HIP_TRY(ctx, rq.after_reduce((const MscReduceOut*)down));
-			} else {
-				HIP_TRY(ctx, msc_launch_reduce(ctx->stream, (const MscPairOut*)ctx->pair_out.p, mc, rq.reduce_mode, rq.reduce_begin, d_flags, (MscReduceOut*)down, ctx->reduce_parts.p,
-				                               rq.reduce_mode == MSC_REDUCE_GET_CLOSE ? rq.close_list.pos : nullptr));          // (a window pass: ties by window position)
-				if (rq.after_reduce) HIP_TRY(ctx, rq.after_reduce((const MscReduceOut*)down));
-			}
-		}
-		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_all1, ctx->stream));
-		if (rq.raw_out) HIP_TRY(ctx, hipMemcpyAsync(rq.raw_out + off * nf, ctx->raw.p, (size_t)mc * nf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-		if (rq.singles_out) HIP_TRY(ctx, hipMemcpyAsync(rq.singles_out + off * ns, ctx->singles.p, (size_t)mc * ns * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-		if (rq.combos_out) HIP_TRY(ctx, hipMemcpyAsync(rq.combos_out + off * nc, ctx->combos.p, (size_t)mc * nc * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-		if (need_po) {
-			po_host.resize(mc);
-			HIP_TRY(ctx, hipMemcpyAsync(po_host.data(), ctx->pair_out.p, (size_t)mc * sizeof(MscPairOut), hipMemcpyDeviceToHost, ctx->stream));
-		}
-		const double t_wait = g_profile_calls ? now_s() : 0;
-		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-		if (g_profile_calls) { ctx->prof_issue += t_wait - t_issue; ctx->prof_wait += now_s() - t_wait; }
-		if (rq.reduce_mode >= 0 && fold_on_host) {
-			uint32_t wpos = 0;
-			msc_reduce_fold_host((const ReducePart*)ctx->pin_parts.p, n_parts_host, rq.reduce_mode, rq.reduce_host, &wpos);
-			rq.close_list.out_host[0] = wpos;
-			if (rq.flags_out) memcpy(rq.flags_out, (const uint8_t*)ctx->pin_down.p + 64, mc);
-		} else if (rq.reduce_mode >= 0) {
-			constexpr size_t kRo = 64;
-			memcpy(rq.reduce_host, ctx->pin_down.p, sizeof(MscReduceOut));
-			if (rq.flags_out) memcpy(rq.flags_out, (const uint8_t*)ctx->pin_down.p + kRo, mc);
-		}
-		float t = 0;
-		if (ctx->timing && hipEventElapsedTime(&t, ctx->ev_tiles0, ctx->ev_tiles1) == hipSuccess) { ctx->tiles_ms_accum += t; ctx->tiles_launches++; ctx->have_timing = true; }
-		if (need_po) {
-			for (uint32_t i = 0; i < mc; i++) {
-				const MscPairOut& p = po_host[i];
-				if (rq.sum_out) rq.sum_out[off + i] = p.sum;
-				if (rq.csum_out) rq.csum_out[off + i] = p.csum;
-				if (rq.combo0_out) rq.combo0_out[off + i] = p.combo0;
-				if (rq.status_out) rq.status_out[off + i] = p.status;
-				if (rq.flags_out && rq.reduce_mode < 0) rq.flags_out[off + i] = (p.status == 0 && p.close) ? 1 : 0;
-				if (p.status < 0 && p.status < first_err) first_err = p.status;
-			}
-		}
+	if (rt.grp != GRP_NONE) {
+		if ((r = ensure(ctx, ctx->grp_pairs, chunk * 32 * sizeof(double)))) return r;
+		if ((r = ensure(ctx, ctx->grp_self, (chunk + 1) * 16 * sizeof(double)))) return r;      // [candidates][16] then the query's 16
 	}
 	if (rq.only_tiles) return MSC_OK;
-	if (rank_pass && *ctx->rk_guard) {
-		*ctx->rk_guard = 0;
-		return fail(ctx, MSC_ERR_HIP, "rank pass: the query's list is longer than its set's bound (max_sum not maintained by a writer of that set)");
+	if ((r = ensure(ctx, ctx->pair_out, chunk * sizeof(MscPairOut)))) return r;
+	if (rq.raw_out && (r = ensure(ctx, ctx->raw, chunk * rt.nf * sizeof(double)))) return r;
+	if (rq.singles_out && (r = ensure(ctx, ctx->singles, chunk * rt.ns * sizeof(double)))) return r;
+	if (rq.combos_out && (r = ensure(ctx, ctx->combos, chunk * rt.nc * sizeof(double)))) return r;
+	if ((r = ensure(ctx, ctx->flags, 64 + chunk))) return r;      // [reduce record (64 B)][close flags]: one copy back
+	return ensure(ctx, ctx->reduce_out, sizeof(MscReduceOut));
+}
+
+ScoreChunk score_chunk(const msc_ctx* ctx, const ScoreRequest& rq, const ScoreRoute& rt, uint64_t off) {
+	const msc_hist_set* cs = rq.cands;
+	ScoreChunk ck;
+	ck.off = off;
+	ck.mc = (uint32_t)std::min(rt.chunk, rq.m - off);
+	ck.d_slots = rq.dev_slots ? rq.dev_slots : rq.cand_slots ? (const uint32_t*)ctx->slots.p + off : nullptr;
+	ck.c_bins = cs->sparse ? nullptr : cs->bins + (ck.d_slots ? 0 : off * cs->L.slot_bytes);
+	ck.c_scal = cs->scalars + (ck.d_slots ? 0 : off * cs->scalar_stride);
+	ck.q_bins = cs->sparse ? nullptr : rq.qset->bins + rq.q_slot * rq.qset->L.slot_bytes;
+	ck.q_scal = rq.qset->scalars + rq.q_slot * rq.qset->scalar_stride;
+	return ck;
+}
+
+// the kernel that streams the candidates of a chunk
+hipError_t launch_pass_kernel(msc_ctx* ctx, const ScoreRequest& rq, const ScoreRoute& rt, const ScoreChunk& ck) {
+	const msc_hist_set *cs = rq.cands, *c_sp = rt.c_sp, *q_sp = rt.q_sp;
+	const MscLayout& L = cs->L;
+	MscPartial* partials = (MscPartial*)ctx->partials.p;
+	switch (rt.pass) {
+	case PASS_RANKS_ITEMS: {
+		MscRankDiv dv{(uint32_t*)ctx->rk_big.p, ck.q_scal, rq.order, (double*)ctx->div_partials.p};
+		return msc_launch_pair_ranks_items(ctx->stream, c_sp->rkl, c_sp->rkl_off, c_sp->rkl_n, c_sp->rkm, c_sp->rkm_off, c_sp->rkm_n, ck.c_scal, cs->scalar_stride, ck.d_slots, ck.off, ck.mc,
+		                                         q_sp->ent, q_sp->cum, q_sp->hdr + rq.q_slot, L.nbins, rq.use_window, rq.min_len, rq.max_len, partials, ctx->num_cus, (uint32_t*)ctx->rk_q.p,
+		                                         rt.rank_rounds, ctx->rk_acc.p, rt.div == DIV_RANKS ? &dv : nullptr, rt.q_kmers, ctx->rk_guard, ctx->rk_items.p, (uint32_t*)ctx->rk_counters.p,
+		                                         (uint32_t*)ctx->rk_tables.p, (int)(ctx->rk_turn++ & 1u),
+		                                         q_sp == c_sp && rq.q_slot < c_sp->capacity ? c_sp->rkl + c_sp->rkl_off_host[rq.q_slot] : nullptr);
 	}
-	if (rq.reduce_host && rq.reduce_host->first_error < first_err) first_err = rq.reduce_host->first_error;
-	if (first_err == MSC_ERR_ZERO_LENGTH) return fail(ctx, first_err, "length_difference: a point has length 0 (the reference throws 123, predict/Feature.cpp:878-886)");
-	if (first_err == MSC_ERR_NAN) return fail(ctx, first_err, "normalisation produced NaN (the reference throws, predict/Feature.cpp:143-146)");
-	if (first_err < 0) return fail(ctx, first_err, "feature evaluation failed with status %d", first_err);
+	case PASS_RANKS_1XM:
+		return msc_launch_pair_ranks_1xm(ctx->stream, c_sp->rkl, c_sp->rkl_off, c_sp->rkl_n, ck.c_scal, cs->scalar_stride, ck.d_slots, ck.off, ck.mc, q_sp->ent, q_sp->cum,
+		                                       q_sp->hdr + rq.q_slot, L.nbins, rq.use_window, rq.min_len, rq.max_len, partials, ctx->num_cus, rt.q_kmers, ctx->rk_guard, (uint32_t*)ctx->rk_q.p);
+	case PASS_MERGE:
+		return launch_sparse_pass(ctx, rt.spk, c_sp, cs->scalars, cs->scalar_stride, ck.d_slots, ck.off, ck.mc, q_sp, rq.q_slot, ck.q_scal, L.nbins, rq.use_window, rq.min_len, rq.max_len,
+		                                partials, rt.div == DIV_LISTS ? ctx->div_tables.p : nullptr, rt.div == DIV_LISTS ? ctx->div_partials.p : nullptr, rq.order, rt.mp_parts, rt.DVN);
+	case PASS_TILES_WIDE:
+		return msc_launch_pair_tiles_wide(ctx->stream, L, cs->dtype, ck.c_bins, ck.c_scal, ck.d_slots, ck.mc, ck.q_bins, ck.q_scal, rq.use_window, rq.min_len, rq.max_len, partials,
+		                                        ctx->num_cus, rt.div == DIV_INLINE ? ctx->div_partials.p : nullptr, rq.order);
+	case PASS_TILES:
+		return msc_launch_pair_tiles(ctx->stream, L, cs->dtype, ck.c_bins, ck.c_scal, ck.d_slots, ck.mc, ck.q_bins, ck.q_scal, rq.use_window, rq.min_len, rq.max_len, partials,
+		                                   ctx->num_cus, rt.div == DIV_INLINE ? ctx->div_tables.p : nullptr, rt.div == DIV_INLINE ? ctx->div_partials.p : nullptr, rq.order);
+	}
+	return hipErrorInvalidValue;
+}
+
+// ... between the two timing events
+int launch_score_pass(msc_ctx* ctx, const ScoreRequest& rq, const ScoreRoute& rt, const ScoreChunk& ck) {
+	const msc_hist_set* cs = rq.cands;
+	int r;
+	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_tiles0, ctx->stream));
+	if (rt.lists() && g_profile_calls) {
+		if (!ctx->prof_nnz.p) { if ((r = ensure(ctx, ctx->prof_nnz, 32))) return r; HIP_TRY(ctx, hipMemsetAsync(ctx->prof_nnz.p, 0, 32, ctx->stream)); }
+		HIP_TRY(ctx, msc_launch_sparse_nnz_sum(ctx->stream, rt.c_sp->hdr, cs->scalars, cs->scalar_stride, ck.d_slots, ck.off, ck.mc, rq.use_window, rq.min_len, rq.max_len,
+		                                       (uint64_t*)ctx->prof_nnz.p + (rt.ranks() ? 2 : 0)));
+		ctx->prof_q_nnz += rt.q_sp->hdr_host[rq.q_slot].nnz;
+	}
+	HIP_TRY(ctx, launch_pass_kernel(ctx, rq, rt, ck));
+	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_tiles1, ctx->stream));
 	return MSC_OK;
 }
 
+// what rides beside the pass (outside its timing): the divergence sums of a streamed chunk from the lists of the same slots, the group statistics
+int launch_side_passes(msc_ctx* ctx, const ScoreRequest& rq, const ScoreRoute& rt, const ScoreChunk& ck) {
+	const msc_hist_set *cs = rq.cands, *c_sp = rt.c_sp, *q_sp = rt.q_sp;
+	double *grp_pairs = (double*)ctx->grp_pairs.p, *grp_self = (double*)ctx->grp_self.p;
+	if (rt.div == DIV_MIRROR)
+		HIP_TRY(ctx, launch_sparse_pass(ctx, rt.spk, c_sp, cs->scalars, cs->scalar_stride, ck.d_slots, ck.off, ck.mc, q_sp, rq.q_slot, ck.q_scal, cs->L.nbins, rq.use_window, rq.min_len,
+		                                rq.max_len, (MscPartial*)ctx->sp_partials.p, ctx->div_tables.p, ctx->div_partials.p, rq.order, rt.mp_parts, rt.DVN));
+	if (rt.grp == GRP_DENSE) {
+		HIP_TRY(ctx, msc_launch_pair_groups_dense(ctx->stream, cs->L, cs->dtype, ck.c_bins, ck.c_scal, cs->scalar_stride, ck.d_slots, ck.mc, ck.q_bins, rq.use_window, rq.min_len, rq.max_len, grp_pairs));
+		HIP_TRY(ctx, msc_launch_self_markov_dense(ctx->stream, cs->L, cs->dtype, cs->bins, ck.d_slots, ck.off, ck.mc, grp_self));
+		HIP_TRY(ctx, msc_launch_self_markov_dense(ctx->stream, rq.qset->L, rq.qset->dtype, rq.qset->bins, nullptr, rq.q_slot, 1, grp_self + rt.chunk * 16));
+	} else if (rt.grp == GRP_LISTS) {
+		HIP_TRY(ctx, msc_launch_pair_sparse_groups(ctx->stream, c_sp->ent, c_sp->hdr + (ck.d_slots ? 0 : ck.off), ck.c_scal, cs->scalar_stride, ck.d_slots, ck.mc, q_sp->ent, q_sp->hdr + rq.q_slot,
+		                                           rq.use_window, rq.min_len, rq.max_len, grp_pairs));
+		HIP_TRY(ctx, msc_launch_sparse_self_markov(ctx->stream, c_sp->ent, c_sp->hdr, ck.d_slots, ck.off, ck.mc, grp_self));
+		HIP_TRY(ctx, msc_launch_sparse_self_markov(ctx->stream, q_sp->ent, q_sp->hdr, nullptr, rq.q_slot, 1, grp_self + rt.chunk * 16));
+	}
+	return MSC_OK;
+}
 
-static int run_score_fwd(msc_ctx* ctx, const msc_hist_set* set, const uint32_t* member_slots, uint64_t m, const msc_hist_set* rs) {
+// the epilogue's arguments for a chunk (one query: the fields of several queries and the error word stay clear, unlike fill_pair_args)
+void fill_score_args(MscEpilogueArgs& ea, const msc_ctx* ctx, const ScoreRequest& rq, const ScoreRoute& rt, const ScoreChunk& ck) {
+	const msc_hist_set* cs = rq.cands;
+	memset(&ea, 0, sizeof ea);
+	ea.partials = (const MscPartial*)ctx->partials.p;
+	if (rt.div == DIV_INLINE) ea.div_partials = ctx->div_partials.p;
+	else if (rt.div != DIV_NONE) { ea.div_direct = (const double*)ctx->div_partials.p; ea.div_direct_n = rt.DVN; ea.div_base = cs->L.nbins; }
+	if (rt.grp != GRP_NONE) { ea.grp_pairs = (const double*)ctx->grp_pairs.p; ea.grp_self_c = (const double*)ctx->grp_self.p; ea.grp_self_q = ea.grp_self_c + rt.chunk * 16; }
+	ea.S = rt.PS; ea.sparse_base = rt.lists() ? cs->L.nbins : 0; ea.m = ck.mc;
+	ea.cand_scalars = ck.c_scal; ea.cand_scalar_stride = cs->scalar_stride; ea.cand_slots = ck.d_slots; ea.q_scalars = ck.q_scal;
+	ea.nbins = cs->L.nbins; ea.dtype = cs->dtype; ea.order = rq.order;
+	ea.use_window = rq.use_window; ea.min_len = rq.min_len; ea.max_len = rq.max_len;
+	ea.feat_mask = rq.feat_mask; ea.model = rq.model ? rq.model->d : nullptr;
+	ea.raw_out = rq.raw_out ? (double*)ctx->raw.p : nullptr;
+	ea.singles_out = rq.singles_out ? (double*)ctx->singles.p : nullptr;
+	ea.combos_out = rq.combos_out ? (double*)ctx->combos.p : nullptr;
+	ea.pair_out = rt.fused ? nullptr : (MscPairOut*)ctx->pair_out.p;
+}
+
+// epilogue, then the reduction where the call asks for one -- or both in the fused kernel
+int launch_epilogue_reduce(msc_ctx* ctx, const ScoreRequest& rq, const ScoreRoute& rt, const ScoreChunk& ck, const MscEpilogueArgs& ea, ScoreHome* home) {
+	int r;
+	if (!rt.fused) HIP_TRY(ctx, msc_launch_epilogue(ctx->stream, ea));
+	if (rq.reduce_mode < 0) return MSC_OK;
+	// the reduce kernel writes its record and the close flags straight into page-locked host memory the device can address
+	// (no copy command behind the kernel): [reduce record (64 B)][close flags]
+	constexpr size_t kRo = 64;
+	static_assert(sizeof(MscReduceOut) <= kRo, "the reduce record sits in front of the flags");
+	if ((r = ensure_pinned(ctx, ctx->pin_down, kRo + ck.mc))) return r;
+	uint8_t* down = nullptr;
+	HIP_TRY(ctx, hipHostGetDevicePointer((void**)&down, ctx->pin_down.p, 0));
+	if ((r = ensure(ctx, ctx->reduce_parts, msc_reduce_scratch_bytes()))) return r;
+	uint8_t* d_flags = rq.dev_flags_out ? rq.dev_flags_out : rq.flags_out ? down + kRo : nullptr;
+	if (!rt.fused) {
+		HIP_TRY(ctx, msc_launch_reduce(ctx->stream, (const MscPairOut*)ctx->pair_out.p, ck.mc, rq.reduce_mode, rq.reduce_begin, d_flags, (MscReduceOut*)down, ctx->reduce_parts.p,
+		                               rq.reduce_mode == MSC_REDUCE_GET_CLOSE ? rq.close_list.pos : nullptr));          // (a window pass: ties by window position)
+		if (rq.after_reduce) HIP_TRY(ctx, rq.after_reduce((const MscReduceOut*)down));
+		return MSC_OK;
+	}
+	// (the step-serial loop's own call: the workgroups' parts go to page-locked memory and are folded by the host, behind the wait for the
+	// stream -- k_pair_reduce_fold2 was one of a pass's launches)
+	ReducePart* host_parts = nullptr;
+	if (rq.close_list.pos && rq.close_list.out_host && ck.off == 0 && ck.mc == rq.m) {
+		if ((r = ensure_pinned(ctx, ctx->pin_parts, 1024 * sizeof(ReducePart)))) return r;
+		HIP_TRY(ctx, hipHostGetDevicePointer((void**)&host_parts, ctx->pin_parts.p, 0));
+	}
+	home->fold_on_host = host_parts != nullptr;
+	HIP_TRY(ctx, msc_launch_epilogue_reduce(ctx->stream, ea, rq.reduce_mode, rq.reduce_begin, d_flags, (MscReduceOut*)down, ctx->reduce_parts.p, rq.close_list, host_parts, &home->n_parts));
+	if (rq.after_reduce && !rq.close_list.pos) HIP_TRY(ctx, rq.after_reduce((const MscReduceOut*)down));
+	return MSC_OK;
+}
+
+// the chunk's results home: the copies, the call's one wait for the stream, the host's fold of the reduction, the per-pair records scattered
+int bring_home(msc_ctx* ctx, const ScoreRequest& rq, const ScoreRoute& rt, const ScoreChunk& ck, ScoreHome* home, double t_issue) {
+	const uint64_t off = ck.off;
+	const uint32_t mc = ck.mc;
+	if (rq.raw_out) HIP_TRY(ctx, hipMemcpyAsync(rq.raw_out + off * rt.nf, ctx->raw.p, (size_t)mc * rt.nf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (rq.singles_out) HIP_TRY(ctx, hipMemcpyAsync(rq.singles_out + off * rt.ns, ctx->singles.p, (size_t)mc * rt.ns * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (rq.combos_out) HIP_TRY(ctx, hipMemcpyAsync(rq.combos_out + off * rt.nc, ctx->combos.p, (size_t)mc * rt.nc * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (rt.need_po) {
+		home->po.resize(mc);
+		HIP_TRY(ctx, hipMemcpyAsync(home->po.data(), ctx->pair_out.p, (size_t)mc * sizeof(MscPairOut), hipMemcpyDeviceToHost, ctx->stream));
+	}
+	const double t_wait = g_profile_calls ? now_s() : 0;
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	if (g_profile_calls) { ctx->prof_issue += t_wait - t_issue; ctx->prof_wait += now_s() - t_wait; }
+	if (rq.reduce_mode >= 0) {
+		if (home->fold_on_host) {
+			uint32_t wpos = 0;
+			msc_reduce_fold_host((const ReducePart*)ctx->pin_parts.p, home->n_parts, rq.reduce_mode, rq.reduce_host, &wpos);
+			rq.close_list.out_host[0] = wpos;
+		} else memcpy(rq.reduce_host, ctx->pin_down.p, sizeof(MscReduceOut));
+		if (rq.flags_out) memcpy(rq.flags_out, (const uint8_t*)ctx->pin_down.p + 64, mc);
+	}
+	float t = 0;
+	if (ctx->timing && hipEventElapsedTime(&t, ctx->ev_tiles0, ctx->ev_tiles1) == hipSuccess) { ctx->tiles_ms_accum += t; ctx->tiles_launches++; ctx->have_timing = true; }
+	if (!rt.need_po) return MSC_OK;
+	for (uint32_t i = 0; i < mc; i++) {
+		const MscPairOut& p = home->po[i];
+		if (rq.sum_out) rq.sum_out[off + i] = p.sum;
+		if (rq.csum_out) rq.csum_out[off + i] = p.csum;
+		if (rq.combo0_out) rq.combo0_out[off + i] = p.combo0;
+		if (rq.status_out) rq.status_out[off + i] = p.status;
+		if (rq.flags_out && rq.reduce_mode < 0) rq.flags_out[off + i] = (p.status == 0 && p.close) ? 1 : 0;
+		if (p.status < 0 && p.status < home->first_err) home->first_err = p.status;
+	}
+	return MSC_OK;
+}
+
+}  // namespace
+
+// One 1 x M call: streams the candidates once, then folds / evaluates per candidate, chunk by chunk.
+int run_score(msc_ctx* ctx, ScoreRequest& rq) {
+	const double t_call = g_profile_calls ? now_s() : 0;
+	int r = validate_pair(ctx, rq.cands, rq.qset, rq.q_slot, rq.cand_slots, rq.dev_slots ? 0 : rq.m);
+	if (r) return r;
+	if (rq.dev_slots && (rq.cand_slots || rq.reduce_mode < 0 || rq.m > 0xfffffff0ull)) return fail(ctx, MSC_ERR_INVALID_ARG, "run_score: a device slot list goes with a reduction only");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	ctx->tiles_ms_accum = 0.f;
+	ctx->tiles_launches = 0;
+	ctx->have_timing = false;
+	ctx->last_kernel = rq.cands->sparse ? "k_pair_sparse" : needs_wide(rq.cands, rq.qset) ? "k_pair_tiles_wide" : "k_pair_tiles";
+	ctx->last_query_tile = 1;
+	if (rq.m == 0) {
+		const bool gc = rq.reduce_mode == MSC_REDUCE_GET_CLOSE;
+		if (rq.reduce_host) *rq.reduce_host = MscReduceOut{gc ? -1.0 : DBL_MIN, gc ? -1 : 0, 0, 0, 0};
+		return MSC_OK;
+	}
+	ScoreRoute rt;
+	if ((r = pick_score_route(ctx, rq, &rt))) return r;
+	ctx->last_kernel = rt.kernel;
+	ctx->last_partial_stride = rt.PS;
+	if ((r = ensure_score_scratch(ctx, rq, rt))) return r;
+	ScoreHome home;
+	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_all0, ctx->stream));
+	if (g_profile_calls) { ctx->prof_calls++; ctx->prof_cands += rq.m; ctx->prof_prep += now_s() - t_call; }
+	for (uint64_t off = 0; off < rq.m; off += rt.chunk) {
+		const double t_issue = g_profile_calls ? now_s() : 0;
+		const ScoreChunk ck = score_chunk(ctx, rq, rt, off);
+		if ((r = launch_score_pass(ctx, rq, rt, ck)) || (r = launch_side_passes(ctx, rq, rt, ck))) return r;
+		if (!rq.only_tiles) {
+			MscEpilogueArgs ea;
+			fill_score_args(ea, ctx, rq, rt, ck);
+			if ((r = launch_epilogue_reduce(ctx, rq, rt, ck, ea, &home))) return r;
+		}
+		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_all1, ctx->stream));
+		if (rq.only_tiles) return MSC_OK;          // (one chunk; msc_mean_nearest folds the partial records itself)
+		if ((r = bring_home(ctx, rq, rt, ck, &home, t_issue))) return r;
+	}
+	if (rt.ranks() && *ctx->rk_guard) {
+		*ctx->rk_guard = 0;
+		return fail(ctx, MSC_ERR_HIP, "rank pass: the query's list is longer than its set's bound (max_sum not maintained by a writer of that set)");
+	}
+	if (rq.reduce_host && rq.reduce_host->first_error < home.first_err) home.first_err = rq.reduce_host->first_error;
+	return pair_status(ctx, home.first_err);
+}
+
+
+// members against their rounded mean in slot 0 of rs: the pass alone (only the |p - r| reduction is used; the slots are in ctx->slots already)
+static int score_against_mean(msc_ctx* ctx, const msc_hist_set* set, const uint32_t* member_slots, uint64_t m, const msc_hist_set* rs) {
 	ScoreRequest rq;
 	rq.cands = set; rq.cand_slots = member_slots; rq.m = m; rq.qset = rs; rq.q_slot = 0; rq.only_tiles = true;
-	rq.slots_uploaded = member_slots != nullptr;          // (mean_nearest_sparse copied them at its head)
+	rq.slots_uploaded = member_slots != nullptr;
 	return run_score(ctx, rq);
 }
 
@@ -640,7 +746,6 @@ extern "C" int msc_search(msc_ctx* ctx, const msc_model* cls, const msc_model* r
 // ================================================================================================ mean + nearest
 
 // msc_mean_nearest for sparse members (kernels and the derivation in sparse.hip)
-static int run_score_fwd(msc_ctx* ctx, const msc_hist_set* set, const uint32_t* member_slots, uint64_t m, const msc_hist_set* rs);
 namespace {
 __global__ void k_put_words(uint32_t* __restrict__ a, const uint32_t* __restrict__ a_src, uint32_t na, uint32_t* __restrict__ b, const uint32_t* __restrict__ b_src, uint32_t nb) {
 	for (uint32_t i = threadIdx.x; i < na; i += blockDim.x) a[i] = a_src[i];
@@ -753,8 +858,7 @@ static int mean_nearest_sparse(msc_ctx* ctx, const msc_hist_set* set, const uint
 	const uint64_t *d_off = (const uint64_t*)(pin_d + pl.off), *d_cb = (const uint64_t*)(pin_d + pl.cb), *d_floor = (const uint64_t*)(pin_d + pl.floor_sum);
 	HIP_TRY(ctx, msc_launch_sparse_mean_write_batch(ctx->stream, (uint32_t*)ctx->sp_acc.p, L.nbins, n_chunks, chunk_bins, 1, nullptr, (uint32_t)m, d_off, d_cb, rs->ent, rs->cum,
 	                                                touched));
-	// members vs the rounded mean: only the |p - r| reduction of the merge kernel is used
-	if ((r = run_score_fwd(ctx, set, member_slots, m, rs))) return r;
+	if ((r = score_against_mean(ctx, set, member_slots, m, rs))) return r;
 	if ((r = ensure(ctx, ctx->raw, m * sizeof(double)))) return r;
 	HIP_TRY(ctx, msc_launch_distance_d(ctx->stream, (const MscPartial*)ctx->partials.p, ctx->last_partial_stride, (uint32_t)m, set->scalars, set->scalar_stride, d_slots,
 	                                   rs->scalars, d_floor, (double*)ctx->raw.p, (MscReduceOut*)(pin_d + pl.ro)));
@@ -793,11 +897,7 @@ extern "C" int msc_mean_nearest(msc_ctx* ctx, const msc_hist_set* set, const uin
 	if ((r = ensure(ctx, ctx->tile_scratch, (size_t)L.S * 2 * sizeof(uint64_t)))) return r;
 	HIP_TRY(ctx, msc_launch_finalize(ctx->stream, rs->bins, rs->scalars, L, set->dtype, 0, 1, false, (uint64_t*)ctx->tile_scratch.p));      // one wave per tile
 	if ((r = refresh_bounds(ctx, rs, 0, 1))) return r;
-	// members vs the rounded mean through the streaming kernel (only the |p - r| reduction is used)
-	ScoreRequest rq;
-	rq.cands = set; rq.cand_slots = member_slots; rq.m = m; rq.qset = rs; rq.q_slot = 0; rq.only_tiles = true;
-	rq.slots_uploaded = member_slots != nullptr;          // (copied above, on this stream)
-	if ((r = run_score(ctx, rq))) return r;
+	if ((r = score_against_mean(ctx, set, member_slots, m, rs))) return r;
 	if ((r = ensure(ctx, ctx->reduce_out, sizeof(MscReduceOut)))) return r;
 	if ((r = ensure(ctx, ctx->raw, m * sizeof(double)))) return r;
 	HIP_TRY(ctx, msc_launch_distance_d(ctx->stream, (const MscPartial*)ctx->partials.p, L.S, (uint32_t)m, set->scalars, set->scalar_stride, d_slots,
