@@ -285,6 +285,22 @@ int msc_hist_copy_batch(msc_ctx* ctx, msc_hist_set* dst, const uint32_t* dst_slo
  * (cluster/ClusterFactory.cpp:560-575, cluster/Center.h:13-40) -- a centre is not read before the update stage, so a driver may
  * queue its clones and issue them together. */
 int msc_hist_clone_batch(msc_ctx* ctx, msc_hist_set* dst, const uint32_t* dst_slots, const msc_hist_set* src, const uint32_t* src_slots, uint64_t n);
+/* The reverse complement of n slots, on the device: the histogram of a reverse-complemented sequence is a fixed permutation of the bins, so
+ * the operator needs no sequence and applies to centres, means and uploaded bins alike. The reference has no counterpart: its users orient
+ * their input by hand before fastcar's work() compares histograms as stored (fastcar/FC_Runner.cpp:426-471).
+ * Index rule: A = 0, C = 1, G = 2, T = 3, a k-mer x0 .. x(k-1) has bin sum xi * 4^(k-1-i) (the order of msc_hist_download); rc(b) is the bin
+ * whose digit of weight 4^j is 3 - (the digit of weight 4^(k-1-j) of b), an involution, and bins'[b] = bins[rc(b)]. The operator is DEFINED as
+ * this permutation, not as a rebuild (for sequences of ACGT the two agree; the segment rules around runs of N are not mirror-symmetric).
+ * Record rule: the scalar record is an exact copy, as msc_hist_copy_batch's (every word, a stale mag included -- sum, sum_sq, max_count,
+ * overflow, length, n_kmers and stddev do not change under a permutation), except that one_mers is reversed (one_mers'[i] = one_mers[3 - i])
+ * and a dense slot's tile prefixes follow the new bins. A sparse slot's list is mapped, sorted by the new bin and gets its cum and sub-range
+ * table rebuilt: the slot the sparse builder writes for the reverse-complement sequence. Lists of more than 32 768 entries go through a dense
+ * scratch slot, as the builder's long sequences do, with that route's limits (k <= 13).
+ * Arguments as msc_hist_copy_batch: same ctx, k, dtype and layout; slots in range; destination slots distinct; n == 0 is MSC_OK; a sparse
+ * destination appends all the lists or none (MSC_ERR_OOM). There is no in-place form: dst == src with a slot in both lists is
+ * MSC_ERR_INVALID_ARG. Every mirror of the destination is rebuilt at its next use. msc_last_kernel_info names what ran ("k_hist_revcomp",
+ * "k_sparse_revcomp_sort" or "k_sparse_revcomp_scratch", queries_per_candidate_read = 0). */
+int msc_hist_revcomp_batch(msc_ctx* ctx, msc_hist_set* dst, const uint32_t* dst_slots, const msc_hist_set* src, const uint32_t* src_slots, uint64_t n);
 
 /* ------------------------------------------------------------------ a5/a7: model (Feature<T> + GLM weights) */
 /* Mirrors the state Predictor::read_from builds (predict/Predictor.cpp:125-185): combos are replayed through
@@ -445,6 +461,28 @@ int msc_search_pairs_top(msc_ctx* ctx, const msc_model* cls, const msc_model* re
                          const msc_hist_set* qset, const uint32_t* q_slots, uint64_t n_q,
                          const uint64_t* win_lo, const uint64_t* win_hi, uint32_t top_n,
                          uint64_t* offsets, uint64_t* close_counts, msc_pairs_info* info);
+
+/* msc_search_pairs on both strands: fastcar's work() (fastcar/FC_Runner.cpp:426-471) compares a query with a database entry as stored, so a
+ * read that is the reverse complement of an entry is an unrelated histogram to it, and the reference's users orient their input by hand.
+ * Let F be the list msc_search_pairs gives for these arguments and R the list it gives when every query is replaced by its reverse
+ * complement (msc_hist_revcomp_batch: bins'[b] = bins[rc(b)], rc(b) = the bin whose digit of weight 4^j is 3 - (the digit of weight
+ * 4^(k-1-j) of b); the record copied with one_mers reversed), same windows. The candidates are never permuted: the earth mover's distance
+ * depends on the bin order, so "the query's reverse complement against the stored candidate" is the definition.
+ * Merge rule, per query: the union of F_q and R_q over the candidate index i, ascending in i. A pair of one list keeps that list's similarity
+ * bits and gets strand 0 (forward) or 1 (reverse); a pair of both keeps the larger similarity, compared as doubles, and a tie goes to forward.
+ * offsets, msc_search_pairs_fetch (idx, sim) and msc_search_pairs_fetch_strands (one byte per pair) read the merged list;
+ * msc_search_pairs_fetch_strands after a search that was not this one is MSC_ERR_UNSUPPORTED.
+ * info: n_pairs = the merged count, fp64_pairs = the sum of both passes, route = MSC_PAIRS_ROUTE_MATRIX iff both passes report it (the reverse
+ * complements inherit the queries' bounds, so both take the same route). Argument checks and error statuses are msc_search_pairs's; n_q == 1
+ * is legal, m == 0 and n_q == 0 are MSC_OK with empty lists.
+ * Scratch size: the reverse complements live in a set of n_q slots of the query set's k, dtype and layout that the context owns (a sparse one
+ * with an arena of the queries' stored bins), reused and grown between calls and freed by msc_destroy; no device memory for it is MSC_ERR_OOM
+ * with the byte count in msc_last_error. A dense slot is 4^k * sizeof(T) bytes: the caller batches its queries where n_q slots matter. */
+int msc_search_pairs_strands(msc_ctx* ctx, const msc_model* cls, const msc_model* reg,
+                             const msc_hist_set* db, const uint32_t* db_slots, uint64_t m,
+                             const msc_hist_set* qset, const uint32_t* q_slots, uint64_t n_q,
+                             const uint64_t* win_lo, const uint64_t* win_hi, uint64_t* offsets, msc_pairs_info* info);
+int msc_search_pairs_fetch_strands(msc_ctx* ctx, uint64_t first, uint64_t n, uint8_t* strand);
 
 /* ------------------------------------------------------------------ a8 over a device-resident window
  * The accumulate loop (cluster/ClusterFactory.cpp:553-610) hands Trainer::get_close an iterator range of the length-sorted store

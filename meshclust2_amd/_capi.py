@@ -85,6 +85,7 @@ PROTOTYPES = {
     "msc_hist_assign_batch": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64]),
     "msc_hist_copy_batch": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64]),
     "msc_hist_clone_batch": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64]),
+    "msc_hist_revcomp_batch": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64]),
     "msc_model_create": (_int, [_vp, _int, _int, C.POINTER(_int), _pu64, _pdbl, _int, _pu64, _pdbl, _pdbl, _dbl, C.POINTER(_vp)]),
     "msc_model_load": (_int, [_vp, C.c_char_p, _int, C.POINTER(_vp)]),
     "msc_model_parse": (_int, [_vp, C.c_char_p, _int, C.POINTER(_vp)]),
@@ -105,6 +106,8 @@ PROTOTYPES = {
     "msc_search_pairs": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     "msc_search_pairs_top": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u32, _vp, _vp, _vp]),
     "msc_search_pairs_fetch": (_int, [_vp, _u64, _u64, _vp, _vp]),
+    "msc_search_pairs_strands": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "msc_search_pairs_fetch_strands": (_int, [_vp, _u64, _u64, _vp]),
     "msc_mean_nearest": (_int, [_vp, _vp, _vp, _u64, _pi64, _vp, _vp]),
     "msc_update_centres": (_int, [_vp, _vp, C.c_double, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "msc_merge_all": (_int, [_vp, _vp, C.c_double, _vp, _vp, C.c_uint64, _int, _vp]),

@@ -262,6 +262,14 @@ class HistogramSet:
         assert d.size == s_.size
         self.ctx.check(self.ctx.lib.msc_hist_copy_batch(self.ctx.h, self.h, _ptr(d), src.h, _ptr(s_), d.size))
 
+    def revcomp_batch(self, dst_slots, src, src_slots):
+        """slot dst_slots[i] of this set = the reverse complement of slot src_slots[i] of src (msc_hist_revcomp_batch): bins'[b] = bins[rc(b)],
+        the record an exact copy with its 1-mers reversed. Same k, dtype and layout; no in-place form."""
+        d = np.ascontiguousarray(dst_slots, dtype=np.uint32)
+        s_ = np.ascontiguousarray(src_slots, dtype=np.uint32)
+        assert d.size == s_.size
+        self.ctx.check(self.ctx.lib.msc_hist_revcomp_batch(self.ctx.h, self.h, _ptr(d), src.h, _ptr(s_), d.size))
+
     def device_view(self):
         b, s = C.c_void_p(), C.c_void_p()
         sb, ss = C.c_uint64(), C.c_uint64()
@@ -744,3 +752,30 @@ class Predictor:
         sim = np.zeros(max(n, 1))
         self.ctx.check(lib.msc_search_pairs_fetch(h, 0, n, _ptr(idx), _ptr(sim)))
         return offsets, idx[:n], sim[:n], dict(n_pairs=n, route=int(info.route), fp64_pairs=int(info.fp64_pairs), close_counts=counts[:nq])
+
+    def search_pairs_strands(self, db, db_slots, qset, q_slots, win_lo=None, win_hi=None, m=None):
+        """search_pairs on both strands (msc_search_pairs_strands): per query the union, ascending candidate index, of its list and of the list of
+        its reverse complement against the candidates as stored. A pair of both lists keeps the larger similarity (a tie goes to forward).
+        -> (offsets, cand_idx, sim, strand uint8 (0 forward, 1 reverse), info) with info as search_pairs: fp64_pairs summed over both passes, route
+        MATRIX iff both passes took it."""
+        sl, m = _slots(db_slots, m)
+        qs = np.ascontiguousarray(q_slots, dtype=np.uint32)
+        nq = qs.size
+        if (win_lo is None) != (win_hi is None):
+            raise ValueError("win_lo and win_hi are given together or not at all")
+        lo = None if win_lo is None else np.ascontiguousarray(win_lo, dtype=np.uint64)
+        hi = None if win_hi is None else np.ascontiguousarray(win_hi, dtype=np.uint64)
+        if lo is not None and (lo.size != nq or hi.size != nq):
+            raise ValueError("one window per query")
+        offsets = np.zeros(nq + 1, dtype=np.uint64)
+        info = _capi.PairsInfo()
+        lib, h = self.ctx.lib, self.ctx.h
+        self.ctx.check(lib.msc_search_pairs_strands(h, self.cls.h if self.cls else None, self.reg.h if self.reg else None, db.h, _ptr(sl), m, qset.h, _ptr(qs), nq,
+                                                    _ptr(lo), _ptr(hi), _ptr(offsets), C.byref(info)))
+        n = int(info.n_pairs)
+        idx = np.zeros(max(n, 1), dtype=np.uint32)
+        sim = np.zeros(max(n, 1))
+        strand = np.zeros(max(n, 1), dtype=np.uint8)
+        self.ctx.check(lib.msc_search_pairs_fetch(h, 0, n, _ptr(idx), _ptr(sim)))
+        self.ctx.check(lib.msc_search_pairs_fetch_strands(h, 0, n, _ptr(strand)))
+        return offsets, idx[:n], sim[:n], strand[:n], dict(n_pairs=n, route=int(info.route), fp64_pairs=int(info.fp64_pairs))

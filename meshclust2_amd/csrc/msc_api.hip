@@ -141,7 +141,7 @@ extern "C" void msc_destroy(msc_ctx* ctx) {
 			}
 		}
 	}
-	for (msc_hist_set* s : {ctx->scratch_set, ctx->sparse_scratch, ctx->sparse_mean_set, ctx->sparse_mean_batch, ctx->batch_scratch, ctx->shard_gather})
+	for (msc_hist_set* s : {ctx->scratch_set, ctx->sparse_scratch, ctx->sparse_mean_set, ctx->sparse_mean_batch, ctx->batch_scratch, ctx->shard_gather, ctx->strand_set})
 		if (s) msc_hist_set_destroy(s);
 	for (void* pinned : {ctx->pl_pin.p, (void*)ctx->rk_guard, ctx->pin_up.p, ctx->pin_down.p, ctx->pin_parts.p, ctx->pin_mean.p})
 		if (pinned) (void)hipHostFree(pinned);
@@ -153,7 +153,8 @@ extern "C" void msc_destroy(msc_ctx* ctx) {
 	                  &ctx->pl_counts, &ctx->pl_offsets, &ctx->pl_seg, &ctx->pl_dst, &ctx->pl_qslots, &ctx->pl_win, &ctx->pl_qcount, &ctx->pl_words,
 	                  &ctx->emd_out, &ctx->close_counts, &ctx->rk_bad, &ctx->prof_nnz, &ctx->segs, &ctx->pair_seg, &ctx->dist, &ctx->sp_counts,
 	                  &ctx->sp_cumbase, &ctx->sp_acc, &ctx->sp_chunk_off, &ctx->sp_chunk_cum, &ctx->sp_partials, &ctx->grp_pairs, &ctx->grp_self,
-	                  &ctx->tile_scratch, &ctx->reduce_parts, &ctx->sp_touched, &ctx->sp_acc_batch};
+	                  &ctx->tile_scratch, &ctx->reduce_parts, &ctx->sp_touched, &ctx->sp_acc_batch, &ctx->ps_idx, &ctx->ps_sim, &ctx->ps_m_idx, &ctx->ps_m_sim,
+	                  &ctx->pl_strand, &ctx->ps_off, &ctx->ps_only, &ctx->ps_counts};
 	for (DevBuf* b : bufs) release(*b);
 	for (hipEvent_t e : pipe.ev_pool) (void)hipEventDestroy(e);
 	for (hipEvent_t e : {ctx->ev_tiles0, ctx->ev_tiles1, ctx->ev_all0, ctx->ev_all1, pipe.ev_call}) (void)hipEventDestroy(e);
@@ -1246,6 +1247,130 @@ extern "C" int msc_hist_copy_batch(msc_ctx* ctx, msc_hist_set* dst, const uint32
 }
 extern "C" int msc_hist_clone_batch(msc_ctx* ctx, msc_hist_set* dst, const uint32_t* dst_slots, const msc_hist_set* src, const uint32_t* src_slots, uint64_t n) {
 	return assign_or_copy_batch(ctx, dst, dst_slots, src, src_slots, n, 2);
+}
+
+// A list of more than 32 768 entries, the way the builder takes a sequence of more than 32 768 k-mers: into the dense scratch slot (which has
+// that route's limits: k <= 13, a slot the device can hold), then k_sparse_count / k_sparse_write. The caller has checked the arena.
+static int revcomp_scratch_slot(msc_ctx* ctx, const msc_hist_set* src) {
+	if (ctx->sparse_scratch && ctx->sparse_scratch->k == src->k && ctx->sparse_scratch->dtype == src->dtype) return MSC_OK;
+	if (ctx->sparse_scratch) { msc_hist_set_destroy(ctx->sparse_scratch); ctx->sparse_scratch = nullptr; }
+	return msc_hist_set_create(ctx, src->k, src->dtype, 1, &ctx->sparse_scratch);
+}
+static int revcomp_sparse_scratch(msc_ctx* ctx, msc_hist_set* dst, uint32_t ds, const msc_hist_set* src, uint32_t ss) {
+	msc_hist_set* sc = ctx->sparse_scratch;
+	const MscSparseHdr sh = src->hdr_host[ss];
+	HIP_TRY(ctx, msc_launch_fill(ctx->stream, sc->bins, sc->L, 0, 1));
+	HIP_TRY(ctx, msc_launch_sparse_revcomp_scatter(ctx->stream, sc->L, src->k, src->dtype, sc->bins, src->ent + sh.off, sh.nnz));
+	return sparsify_slots(ctx, sc, 0, dst, ds, 1, nullptr);
+}
+
+// The reverse complement of n slots: bins'[b] = bins[msc_rc_bin(b)] (msc_revcomp.h), the record an exact copy with the 1-mers reversed and, in a
+// dense set, the tile prefixes of the new bins. The host side is msc_hist_copy_batch's; no mirror is written here (mark_stale / lists_written).
+extern "C" int msc_hist_revcomp_batch(msc_ctx* ctx, msc_hist_set* dst, const uint32_t* dst_slots, const msc_hist_set* src, const uint32_t* src_slots, uint64_t n) {
+	if (!ctx || !dst || !src || dst->ctx != ctx || src->ctx != ctx) return MSC_ERR_INVALID_ARG;
+	if (n == 0) return MSC_OK;
+	if (!dst_slots || !src_slots) return MSC_ERR_INVALID_ARG;
+	if (dst->k != src->k || dst->dtype != src->dtype || dst->sparse != src->sparse) return fail(ctx, MSC_ERR_INVALID_ARG, "sets differ in k, dtype or layout");
+	if (n > 0x7fffffffull) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_hist_revcomp_batch: at most 2^31 - 1 slots a call");
+	if (dst->sparse && src->scalar_stride != dst->scalar_stride) return fail(ctx, MSC_ERR_INVALID_ARG, "sets differ in layout");
+	uint32_t lo = ~0u, hi = 0;
+	for (uint64_t i = 0; i < n; i++) {
+		if (dst_slots[i] >= dst->capacity || src_slots[i] >= src->capacity) return fail(ctx, MSC_ERR_INVALID_ARG, "slot out of range");
+		lo = std::min(lo, dst_slots[i]);
+		hi = std::max(hi, dst_slots[i]);
+	}
+	{
+		std::vector<uint32_t> d(dst_slots, dst_slots + n);
+		std::sort(d.begin(), d.end());
+		if (std::adjacent_find(d.begin(), d.end()) != d.end()) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_hist_revcomp_batch: a destination slot is named twice");
+		if (dst == src)
+			for (uint64_t i = 0; i < n; i++)
+				if (std::binary_search(d.begin(), d.end(), src_slots[i]))
+					return fail(ctx, MSC_ERR_INVALID_ARG, "msc_hist_revcomp_batch: slot %u is a source and a destination (there is no in-place form)", src_slots[i]);
+	}
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	int r;
+	if ((r = ensure(ctx, ctx->slots, n * sizeof(uint32_t))) || (r = ensure(ctx, ctx->pair_seg, n * sizeof(uint32_t)))) return r;
+	const uint32_t* d_ds = (const uint32_t*)ctx->slots.p;
+	const uint32_t* d_ss = (const uint32_t*)ctx->pair_seg.p;
+	if (dst->sparse) {
+		// all lists or none: a list keeps its length
+		const uint32_t sort_max = msc_sparse_revcomp_sort_max();
+		uint64_t need = 0;
+		bool any_long = false;
+		for (uint64_t i = 0; i < n; i++) { need += src->hdr_host[src_slots[i]].nnz; any_long = any_long || src->hdr_host[src_slots[i]].nnz > sort_max; }
+		if (dst->ent_used + need > dst->ent_capacity)
+			return fail(ctx, MSC_ERR_OOM, "sparse set entry arena exhausted (%llu of %llu entries used, %llu needed)", (unsigned long long)dst->ent_used,
+			            (unsigned long long)dst->ent_capacity, (unsigned long long)need);
+		if (any_long && src->k > 13) return fail(ctx, MSC_ERR_UNSUPPORTED, "dense histograms support 1 <= k <= 13 (got %d): a list of more than %u entries goes through one", src->k, sort_max);
+		if (any_long && (r = revcomp_scratch_slot(ctx, src))) return r;          // (where the builder would refuse, before anything is written)
+		// the short lists first, in one launch; their places in the arena are known on the host
+		std::vector<uint32_t> s_ds, s_ss, longs;
+		std::vector<uint64_t> off;
+		uint64_t o = dst->ent_used;
+		uint32_t longest = 0;
+		for (uint64_t i = 0; i < n; i++) {
+			const uint32_t nnz = src->hdr_host[src_slots[i]].nnz;
+			if (nnz > sort_max) { longs.push_back((uint32_t)i); continue; }
+			s_ds.push_back(dst_slots[i]); s_ss.push_back(src_slots[i]); off.push_back(o);
+			o += nnz;
+			longest = std::max(longest, nnz);
+		}
+		const uint64_t ns = s_ds.size();
+		if (ns) {
+			if ((r = ensure(ctx, ctx->sp_chunk_off, ns * sizeof(uint64_t))) || (r = ensure(ctx, ctx->sp_counts, ns * sizeof(MscSparseHdr)))) return r;
+			HIP_TRY(ctx, hipMemcpyAsync(ctx->slots.p, s_ds.data(), ns * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+			HIP_TRY(ctx, hipMemcpyAsync(ctx->pair_seg.p, s_ss.data(), ns * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+			HIP_TRY(ctx, hipMemcpyAsync(ctx->sp_chunk_off.p, off.data(), ns * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+			HIP_TRY(ctx, msc_launch_sparse_revcomp_sort(ctx->stream, src->k, src->L.nbins, src->ent, src->hdr, d_ds, d_ss, (const uint64_t*)ctx->sp_chunk_off.p, (uint32_t)ns, longest,
+			                                            dst->ent, dst->cum, dst->hdr, (MscSparseHdr*)ctx->sp_counts.p));
+			std::vector<MscSparseHdr> hl(ns);          // the headers (the kernel's sub-range tables) for the host's mirror
+			HIP_TRY(ctx, hipMemcpyAsync(hl.data(), ctx->sp_counts.p, ns * sizeof(MscSparseHdr), hipMemcpyDeviceToHost, ctx->stream));
+			HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+			for (uint64_t i = 0; i < ns; i++) dst->hdr_host[s_ds[i]] = hl[i];
+			dst->ent_used = o;
+			ctx->last_kernel = "k_sparse_revcomp_sort";
+		}
+		for (const uint32_t i : longs) {
+			if ((r = revcomp_sparse_scratch(ctx, dst, dst_slots[i], src, src_slots[i]))) return r;
+			ctx->last_kernel = "k_sparse_revcomp_scratch";
+		}
+		// the records: an exact copy, the 1-mers reversed
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->slots.p, dst_slots, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->pair_seg.p, src_slots, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+		HIP_TRY(ctx, msc_launch_assign_scalars(ctx->stream, dst->scalars, src->scalars, dst->scalar_stride, d_ds, d_ss, (uint32_t)n, 1));
+		HIP_TRY(ctx, msc_launch_revcomp_one_mers(ctx->stream, dst->scalars, src->scalars, dst->scalar_stride, d_ds, d_ss, (uint32_t)n));
+		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // the caller's slot arrays may go away
+		for (uint64_t i = 0; i < n; i++) {
+			dst->max_nnz = std::max(dst->max_nnz, dst->hdr_host[dst_slots[i]].nnz);
+			if (src_slots[i] < src->len_known.size() && src->len_known[src_slots[i]]) learn_length(dst, dst_slots[i], src->len_host[src_slots[i]]);
+			else forget_lengths(dst, dst_slots[i], 1);
+		}
+		lists_written(dst, lo, (uint64_t)hi + 1 - lo);
+		dst->max_count = std::max(dst->max_count, src->max_count);
+		dst->max_sum = std::max(dst->max_sum, src->max_sum);
+		ctx->last_query_tile = 0;
+		ctx->have_timing = false;
+		return MSC_OK;
+	}
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->slots.p, dst_slots, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->pair_seg.p, src_slots, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+	HIP_TRY(ctx, msc_launch_assign_scalars(ctx->stream, dst->scalars, src->scalars, dst->scalar_stride, d_ds, d_ss, (uint32_t)n, 1));
+	HIP_TRY(ctx, msc_launch_hist_revcomp(ctx->stream, dst->L, dst->k, dst->dtype, dst->bins, dst->scalars, src->bins, src->scalars, d_ds, d_ss, (uint32_t)n));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // the caller's slot arrays may go away
+	dst->max_count = std::max(dst->max_count, src->max_count);
+	dst->max_sum = std::max(dst->max_sum, src->max_sum);
+	if (dst->written.size() < dst->capacity) dst->written.resize(dst->capacity, 0);
+	for (uint64_t i = 0; i < n; i++) {
+		dst->written[dst_slots[i]] = 1;
+		if (src_slots[i] < src->len_known.size() && src->len_known[src_slots[i]]) learn_length(dst, dst_slots[i], src->len_host[src_slots[i]]);
+		else forget_lengths(dst, dst_slots[i], 1);
+	}
+	mark_stale(dst, lo, (uint64_t)hi + 1 - lo);
+	ctx->last_kernel = "k_hist_revcomp";
+	ctx->last_query_tile = 0;
+	ctx->have_timing = false;
+	return MSC_OK;
 }
 
 extern "C" int msc_hist_set_device_view(const msc_hist_set* set, void** bins, uint64_t* slot_bytes, void** scalars, uint64_t* scalar_bytes) {

@@ -9,6 +9,8 @@
 //               there and copied up, so that msc_search_pairs_fetch reads one list whichever route ran.
 // msc_search_pairs_top is the same body with a cut behind each block's list: the block's pairs go to the staging list on either route, and
 // k_pair_top_plan / k_pair_top_select (pair_features.hip) write each query's top_n best from there to the call's list.
+// msc_search_pairs_strands is the body twice -- the queries as given, then their reverse complements (msc_hist_revcomp_batch into a scratch set of
+// the context) -- and a merge of the two lists on the device (k_pair_strand_count / _scan / _write).
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -312,6 +314,7 @@ int search_pairs(msc_ctx* ctx, const msc_model* cls, const msc_model* reg, const
 	if ((cls && cls->ctx != ctx) || (reg && reg->ctx != ctx)) return MSC_ERR_INVALID_ARG;
 	if (info) memset(info, 0, sizeof *info);
 	ctx->pl_n = 0;          // (the list of the call before is gone whatever happens next)
+	ctx->pl_strands = false;
 	if (!cls && !reg) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_search_pairs needs a classification or a regression model");
 	if (!win_lo != !win_hi) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_search_pairs: win_lo and win_hi are given together or not at all");
 	if (m > 0xffffffffull) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_search_pairs: candidate indices are 32-bit");
@@ -372,7 +375,99 @@ int search_pairs(msc_ctx* ctx, const msc_model* cls, const msc_model* reg, const
 	return MSC_OK;
 }
 
+// the context's scratch set for the reverse complements of n_q queries of qset's shape (a sparse one with an arena of `entries`), emptied
+int strand_scratch(msc_ctx* ctx, const msc_hist_set* qset, uint64_t n_q, uint64_t entries) {
+	msc_hist_set*& s = ctx->strand_set;
+	entries = std::max<uint64_t>(entries, 1);
+	if (s && (s->k != qset->k || s->dtype != qset->dtype || s->sparse != qset->sparse || s->capacity < n_q || (s->sparse && s->ent_capacity < entries))) {
+		msc_hist_set_destroy(s);
+		s = nullptr;
+	}
+	if (!s) {
+		const int r = qset->sparse ? msc_hist_set_create_sparse(ctx, qset->k, qset->dtype, n_q, entries, &s) : msc_hist_set_create(ctx, qset->k, qset->dtype, n_q, &s);
+		if (r) {
+			s = nullptr;
+			const unsigned long long bytes = qset->sparse ? entries * 12ull + n_q * (sizeof(MscSlotScalars) + sizeof(MscSparseHdr)) : n_q * (qset->L.slot_bytes + qset->scalar_stride);
+			return fail(ctx, r == MSC_ERR_OOM ? MSC_ERR_OOM : r, "msc_search_pairs_strands: no device memory for the reverse complements of %llu queries (%llu bytes)",
+			            (unsigned long long)n_q, bytes);
+		}
+	}
+	if (s->sparse) { if (const int r = msc_hist_set_clear(ctx, s)) return r; }
+	s->max_count = s->max_sum = 0;          // (the bounds are the queries' alone: both passes take one route)
+	return MSC_OK;
+}
+
 }  // namespace
+
+extern "C" int msc_search_pairs_strands(msc_ctx* ctx, const msc_model* cls, const msc_model* reg, const msc_hist_set* db, const uint32_t* db_slots, uint64_t m,
+                                        const msc_hist_set* qset, const uint32_t* q_slots, uint64_t n_q, const uint64_t* win_lo, const uint64_t* win_hi, uint64_t* offsets,
+                                        msc_pairs_info* info) {
+	// the forward pass: every argument check is its
+	msc_pairs_info fi{}, ri{};
+	int r = search_pairs(ctx, cls, reg, db, db_slots, m, qset, q_slots, n_q, win_lo, win_hi, 0, offsets, nullptr, &fi);
+	if (info) memset(info, 0, sizeof *info);
+	if (r) return r;
+	if (n_q == 0 || m == 0) { ctx->pl_strands = true; return MSC_OK; }
+	if (n_q > 0xffffffffull) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_search_pairs_strands: at most 2^32 - 1 queries a call");
+	hipStream_t st = ctx->stream;
+	std::vector<uint64_t> off_f(offsets, offsets + n_q + 1), off_r(n_q + 1, 0);
+	std::swap(ctx->pl_idx, ctx->ps_idx);          // the forward list aside
+	std::swap(ctx->pl_sim, ctx->ps_sim);
+	ctx->pl_n = 0;
+	// the queries' reverse complements, slot i of the scratch set for query i
+	uint64_t entries = 0;
+	if (qset->sparse) for (uint64_t i = 0; i < n_q; i++) entries += qset->hdr_host[q_slots[i]].nnz;
+	if ((r = strand_scratch(ctx, qset, n_q, entries))) return r;
+	std::vector<uint32_t> ids(n_q);
+	for (uint64_t i = 0; i < n_q; i++) ids[i] = (uint32_t)i;
+	if ((r = msc_hist_revcomp_batch(ctx, ctx->strand_set, ids.data(), qset, q_slots, n_q))) return r;
+	if ((r = search_pairs(ctx, cls, reg, db, db_slots, m, ctx->strand_set, ids.data(), n_q, win_lo, win_hi, 0, off_r.data(), nullptr, &ri))) return r;
+	const uint64_t n_f = off_f[n_q], n_r = off_r[n_q];
+	ctx->pl_n = 0;          // (until the merged list stands)
+	// the merge
+	if ((r = ensure(ctx, ctx->ps_off, 3 * (n_q + 1) * sizeof(uint64_t))) || (r = ensure(ctx, ctx->ps_counts, n_q * sizeof(uint64_t))) ||
+	    (r = ensure(ctx, ctx->ps_only, std::max<uint64_t>(n_r, 1) * sizeof(uint32_t))))
+		return r;
+	uint64_t* d_off_f = (uint64_t*)ctx->ps_off.p;
+	uint64_t *d_off_r = d_off_f + n_q + 1, *d_off_m = d_off_r + n_q + 1;
+	HIP_TRY(ctx, hipMemcpyAsync(d_off_f, off_f.data(), (n_q + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+	HIP_TRY(ctx, hipMemcpyAsync(d_off_r, off_r.data(), (n_q + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+	HIP_TRY(ctx, msc_launch_pair_strand_count(st, d_off_f, d_off_r, (uint32_t)n_q, (const uint32_t*)ctx->ps_idx.p, (const uint32_t*)ctx->pl_idx.p, (uint32_t*)ctx->ps_only.p,
+	                                          (uint64_t*)ctx->ps_counts.p, d_off_m));
+	HIP_TRY(ctx, hipMemcpyAsync(offsets, d_off_m, (n_q + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+	HIP_TRY(ctx, hipStreamSynchronize(st));
+	const uint64_t total = offsets[n_q];
+	if (total > n_f + n_r) return fail(ctx, MSC_ERR_HIP, "msc_search_pairs_strands: %llu pairs merged out of %llu + %llu", (unsigned long long)total, (unsigned long long)n_f, (unsigned long long)n_r);
+	if ((r = grow_list(ctx, ctx->ps_m_idx, ctx->ps_m_sim, 0, std::max<uint64_t>(total, 1))) || (r = ensure(ctx, ctx->pl_strand, std::max<uint64_t>(total, 1)))) return r;
+	HIP_TRY(ctx, msc_launch_pair_strand_write(st, d_off_f, d_off_r, d_off_m, (uint32_t)n_q, (const uint32_t*)ctx->ps_idx.p, (const double*)ctx->ps_sim.p, (const uint32_t*)ctx->pl_idx.p,
+	                                          (const double*)ctx->pl_sim.p, (const uint32_t*)ctx->ps_only.p, (uint32_t*)ctx->ps_m_idx.p, (double*)ctx->ps_m_sim.p,
+	                                          (uint8_t*)ctx->pl_strand.p));
+	HIP_TRY(ctx, hipStreamSynchronize(st));
+	std::swap(ctx->pl_idx, ctx->ps_m_idx);          // the merged list is the call's list
+	std::swap(ctx->pl_sim, ctx->ps_m_sim);
+	ctx->pl_n = total;
+	ctx->pl_strands = true;
+	if (info) {
+		info->n_pairs = total;
+		info->fp64_pairs = fi.fp64_pairs + ri.fp64_pairs;
+		info->route = fi.route == MSC_PAIRS_ROUTE_MATRIX && ri.route == MSC_PAIRS_ROUTE_MATRIX ? MSC_PAIRS_ROUTE_MATRIX : MSC_PAIRS_ROUTE_FALLBACK;
+	}
+	return MSC_OK;
+}
+
+extern "C" int msc_search_pairs_fetch_strands(msc_ctx* ctx, uint64_t first, uint64_t n, uint8_t* strand) {
+	if (!ctx) return MSC_ERR_INVALID_ARG;
+	if (!ctx->pl_strands) return fail(ctx, MSC_ERR_UNSUPPORTED, "msc_search_pairs_fetch_strands: the last search was not msc_search_pairs_strands");
+	if (first > ctx->pl_n || n > ctx->pl_n - first)
+		return fail(ctx, MSC_ERR_INVALID_ARG, "msc_search_pairs_fetch_strands: pairs [%llu, %llu) outside the list of %llu", (unsigned long long)first,
+		            (unsigned long long)(first + n), (unsigned long long)ctx->pl_n);
+	if (n == 0) return MSC_OK;
+	if (!strand) return MSC_ERR_INVALID_ARG;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipMemcpyAsync(strand, (const uint8_t*)ctx->pl_strand.p + first, n, hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return MSC_OK;
+}
 
 extern "C" int msc_search_pairs(msc_ctx* ctx, const msc_model* cls, const msc_model* reg, const msc_hist_set* db, const uint32_t* db_slots, uint64_t m,
                                 const msc_hist_set* qset, const uint32_t* q_slots, uint64_t n_q, const uint64_t* win_lo, const uint64_t* win_hi, uint64_t* offsets,

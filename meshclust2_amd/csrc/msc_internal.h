@@ -278,6 +278,12 @@ hipError_t msc_launch_pair_list_write(hipStream_t st, const MscEpilogueArgs& a, 
                                       const uint64_t* offsets, uint32_t* out_idx, double* out_sim);
 hipError_t msc_launch_pair_list_gather(hipStream_t st, const uint64_t* seg, uint32_t n_chunks, uint32_t n_q, uint64_t* base, uint64_t* dst, const uint32_t* s_idx,
                                        const double* s_sim, uint32_t* out_idx, double* out_sim);
+// the merge of msc_search_pairs_strands: the lists F and R of one call (offsets off_f / off_r per query, ascending candidate index inside a query) into
+// their union per query. count: r_only[entry of R] and counts[q], scanned into off_m[0 .. n_q]; write: the merged list with a strand byte per pair
+hipError_t msc_launch_pair_strand_count(hipStream_t st, const uint64_t* off_f, const uint64_t* off_r, uint32_t n_q, const uint32_t* f_idx, const uint32_t* r_idx, uint32_t* r_only,
+                                        uint64_t* counts, uint64_t* off_m);
+hipError_t msc_launch_pair_strand_write(hipStream_t st, const uint64_t* off_f, const uint64_t* off_r, const uint64_t* off_m, uint32_t n_q, const uint32_t* f_idx, const double* f_sim,
+                                        const uint32_t* r_idx, const double* r_sim, const uint32_t* r_only, uint32_t* out_idx, double* out_sim, uint8_t* out_strand);
 // the cut of msc_search_pairs_top: each query's place in the list (it keeps min(pairs, top_n); *base grows by their sum), then -- once the
 // list has that room -- the selection out of the block's staged pairs (seg[chunk][query] = {first, n}) straight to those places
 hipError_t msc_launch_pair_top_plan(hipStream_t st, const uint64_t* seg, uint32_t n_chunks, uint32_t n_q, uint32_t top_n, uint64_t* base, uint64_t* dst);
@@ -386,3 +392,17 @@ hipError_t msc_launch_distance_batch(hipStream_t st, const MscPartial* partials,
                                      double* dist_out);
 hipError_t msc_launch_assign_batch(hipStream_t st, const MscLayout& L, uint8_t* dst_bins, uint8_t* dst_scalars, const uint8_t* src_bins,
                                    const uint8_t* src_scalars, const uint32_t* dst_slots, const uint32_t* src_slots, uint32_t n, int exact = 0);
+// msc_revcomp.hip: the reverse complement of slots, bins'[b] = bins[msc_rc_bin(b)]. Dense: the bins (whole in LDS up to 64 KiB a slot, else as a
+// tiled transpose), the tile prefixes of the new bins and the reversed 1-mers; the rest of the record is the caller's (msc_launch_assign_scalars)
+bool msc_revcomp_whole_slot(const MscLayout& L);
+hipError_t msc_launch_hist_revcomp(hipStream_t st, const MscLayout& L, int k, int dtype, uint8_t* dst_bins, uint8_t* dst_scalars, const uint8_t* src_bins,
+                                   const uint8_t* src_scalars, const uint32_t* dst_slots, const uint32_t* src_slots, uint32_t n);
+hipError_t msc_launch_revcomp_one_mers(hipStream_t st, uint8_t* dst_scalars, const uint8_t* src_scalars, uint64_t stride, const uint32_t* dst_slots,
+                                       const uint32_t* src_slots, uint32_t n);
+// sparse: lists of at most msc_sparse_revcomp_sort_max() entries sorted in LDS (list i of the launch goes to dst_off[i] of the arena); a longer
+// one scattered into a dense slot that holds the pseudocount, for k_sparse_count / k_sparse_write
+uint32_t msc_sparse_revcomp_sort_max();
+hipError_t msc_launch_sparse_revcomp_sort(hipStream_t st, int k, uint64_t nbins, const void* s_ent, const MscSparseHdr* s_hdr, const uint32_t* dst_slots,
+                                          const uint32_t* src_slots, const uint64_t* dst_off, uint32_t n, uint32_t longest, void* d_ent, uint32_t* d_cum, MscSparseHdr* d_hdr,
+                                          MscSparseHdr* hdr_list);
+hipError_t msc_launch_sparse_revcomp_scatter(hipStream_t st, const MscLayout& L, int k, int dtype, void* scratch_bins, const void* ent, uint32_t n);

@@ -58,6 +58,15 @@ MSC_HD uint64_t msc_phys_index(uint64_t bin, uint32_t E, uint32_t R) {
 	return tile * tile_bins + (uint64_t)t * (64 * E) + lane * E + j;
 }
 
+// ... and back: physical element index inside the slot -> logical bin
+MSC_HD uint64_t msc_logical_index(uint64_t phys, uint32_t E, uint32_t R) {
+	const uint32_t tile_bins = 64 * R;
+	uint64_t tile = phys / tile_bins;
+	uint32_t e = (uint32_t)(phys % tile_bins);
+	uint32_t t = e / (64 * E), lane = (e / E) % 64, j = e % E;
+	return tile * tile_bins + (uint64_t)lane * R + t * E + j;
+}
+
 // Per-slot scalar record, followed in memory by S uint64 tile prefixes (exclusive sum of the bins of
 // all earlier tiles). One record per slot, stride = msc_scalar_stride(S).
 struct MscSlotScalars {

@@ -91,6 +91,11 @@ struct msc_ctx {
 	DevBuf pl_stage_idx, pl_stage_sim;     // a block's pairs chunk by chunk, when its candidates take several chunks
 	DevBuf pl_flags, pl_counts, pl_offsets, pl_seg, pl_dst, pl_qslots, pl_win, pl_qcount, pl_words;
 	DevBuf pl_pin;                         // page-locked: the running totals read back before a list grows
+	// msc_search_pairs_strands: the forward pass's list moved aside, the merged list before it takes the list's place, a strand byte per pair of the
+	// list (pl_strands: the last call left one), the three offset arrays, R's r_only words and the merged counts
+	DevBuf ps_idx, ps_sim, ps_m_idx, ps_m_sim, pl_strand, ps_off, ps_only, ps_counts;
+	bool pl_strands = false;
+	msc_hist_set* strand_set = nullptr;    // ... and the queries' reverse complements: n_q slots of the query set's shape, reused and grown between calls
 	uint64_t close_counts_n = 0;           // queries the counts on file cover (0: the last call kept none)
 	DevBuf qslots_all;                     // msc_score_multi: the query slots of a whole call whose blocks are queued
 	DevBuf emd_out, rk_bad;                // msc_emd_ranks.hip: the distances of a chunk, the build's error word

@@ -2765,6 +2765,92 @@ __global__ void __launch_bounds__(kBlock) k_pair_list_gather(const unsigned long
 	}
 }
 
+// ---------------------------------------------------------------------------------------- both strands (msc_search_pairs_strands)
+// Two lists of one call, F (the queries as given) and R (their reverse complements), each ascending in the candidate index inside a query, merged
+// per query into their union over the index: a pair of one list keeps its similarity and gets that list's strand (0 / 1), a pair of both the
+// larger similarity, forward on a tie. One wave per query; an entry's place is its own rank plus its rank in the other list, found by
+// bisection: no atomic, the output does not depend on the schedule. k_pair_strand_count leaves, for every entry of R, how many entries of R
+// before it F does not hold (r_only), and the merged count of the query.
+__device__ __forceinline__ uint32_t strand_lower_bound(const uint32_t* __restrict__ a, uint32_t n, uint32_t x) {
+	uint32_t lo = 0, hi = n;
+	while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (a[mid] < x) lo = mid + 1; else hi = mid; }
+	return lo;
+}
+
+__global__ void __launch_bounds__(64) k_pair_strand_count(const unsigned long long* __restrict__ off_f, const unsigned long long* __restrict__ off_r, const uint32_t* __restrict__ f_idx,
+                                                          const uint32_t* __restrict__ r_idx, uint32_t* __restrict__ r_only, unsigned long long* __restrict__ counts) {
+	const uint32_t q = blockIdx.x, lane = threadIdx.x;
+	const unsigned long long f0 = off_f[q], r0 = off_r[q];
+	const uint32_t nf = (uint32_t)(off_f[q + 1] - f0), nr = (uint32_t)(off_r[q + 1] - r0);
+	uint32_t carry = 0;
+	for (uint32_t base = 0; base < nr; base += 64) {
+		const uint32_t j = base + lane;
+		uint32_t only = 0;
+		if (j < nr) {
+			const uint32_t x = r_idx[r0 + j], lb = strand_lower_bound(f_idx + f0, nf, x);
+			only = !(lb < nf && f_idx[f0 + lb] == x);
+		}
+		uint32_t inc = only;
+#pragma unroll
+		for (int o = 1; o < 64; o <<= 1) {
+			const uint32_t up = __shfl_up(inc, o, 64);
+			if ((int)lane >= o) inc += up;
+		}
+		if (j < nr) r_only[r0 + j] = carry + inc - only;
+		carry += __shfl(inc, 63, 64);
+	}
+	if (lane == 0) counts[q] = (unsigned long long)nf + carry;
+}
+
+// one workgroup: off_m[0 .. n_q] = the exclusive prefix sums of counts
+__global__ void __launch_bounds__(kBlock) k_pair_strand_scan(const unsigned long long* __restrict__ counts, uint32_t n_q, unsigned long long* __restrict__ off_m) {
+	__shared__ unsigned long long part[kBlock];
+	const uint32_t per = (n_q + kBlock - 1) / kBlock, a = threadIdx.x * per, b = a + per < n_q ? a + per : n_q;
+	unsigned long long s = 0;
+	for (uint32_t i = a; i < b; i++) s += counts[i];
+	part[threadIdx.x] = s;
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		unsigned long long run = 0;
+		for (int i = 0; i < kBlock; i++) { const unsigned long long x = part[i]; part[i] = run; run += x; }
+		off_m[n_q] = run;
+	}
+	__syncthreads();
+	s = part[threadIdx.x];
+	for (uint32_t i = a; i < b; i++) { off_m[i] = s; s += counts[i]; }
+}
+
+__global__ void __launch_bounds__(64) k_pair_strand_write(const unsigned long long* __restrict__ off_f, const unsigned long long* __restrict__ off_r,
+                                                          const unsigned long long* __restrict__ off_m, const uint32_t* __restrict__ f_idx, const double* __restrict__ f_sim,
+                                                          const uint32_t* __restrict__ r_idx, const double* __restrict__ r_sim, const uint32_t* __restrict__ r_only,
+                                                          uint32_t* __restrict__ out_idx, double* __restrict__ out_sim, uint8_t* __restrict__ out_strand) {
+	const uint32_t q = blockIdx.x, lane = threadIdx.x;
+	const unsigned long long f0 = off_f[q], r0 = off_r[q], m0 = off_m[q];
+	const uint32_t nf = (uint32_t)(off_f[q + 1] - f0), nr = (uint32_t)(off_r[q + 1] - r0);
+	const uint32_t only_all = (uint32_t)(off_m[q + 1] - m0) - nf;
+	for (uint32_t i = lane; i < nf; i += 64) {
+		const uint32_t x = f_idx[f0 + i], lb = strand_lower_bound(r_idx + r0, nr, x);
+		double sim = f_sim[f0 + i];
+		uint8_t strand = 0;
+		if (lb < nr && r_idx[r0 + lb] == x) {
+			const double rs = r_sim[r0 + lb];
+			if (rs > sim) { sim = rs; strand = 1; }
+		}
+		const unsigned long long at = m0 + i + (lb < nr ? r_only[r0 + lb] : only_all);
+		out_idx[at] = x;
+		out_sim[at] = sim;
+		out_strand[at] = strand;
+	}
+	for (uint32_t j = lane; j < nr; j += 64) {
+		const uint32_t x = r_idx[r0 + j], lb = strand_lower_bound(f_idx + f0, nf, x);
+		if (lb < nf && f_idx[f0 + lb] == x) continue;
+		const unsigned long long at = m0 + lb + r_only[r0 + j];
+		out_idx[at] = x;
+		out_sim[at] = r_sim[r0 + j];
+		out_strand[at] = 1;
+	}
+}
+
 // ---------------------------------------------------------------------------------------- the cut (msc_search_pairs_top)
 // Each query's top_n pairs by similarity out of a block's staged pairs: chunk c's pairs of query q lie in the staging list at
 // seg[c][q] = {first, n}, chunks in ascending candidate order. k_pair_top_plan gives every query its place in the call's list (it keeps
@@ -3003,5 +3089,22 @@ hipError_t msc_launch_pair_list_gather(hipStream_t st, const uint64_t* seg, uint
 	hipLaunchKernelGGL(k_pair_list_plan, dim3(1), dim3(64), 0, st, (const unsigned long long*)seg, n_chunks, n_q, (unsigned long long*)base, (unsigned long long*)dst);
 	hipLaunchKernelGGL(k_pair_list_gather, dim3(n_chunks * n_q), dim3(kBlock), 0, st, (const unsigned long long*)seg, (const unsigned long long*)dst, s_idx, s_sim,
 	                   out_idx, out_sim);
+	return hipGetLastError();
+}
+
+hipError_t msc_launch_pair_strand_count(hipStream_t st, const uint64_t* off_f, const uint64_t* off_r, uint32_t n_q, const uint32_t* f_idx, const uint32_t* r_idx, uint32_t* r_only,
+                                        uint64_t* counts, uint64_t* off_m) {
+	if (n_q == 0) return hipSuccess;
+	hipLaunchKernelGGL(k_pair_strand_count, dim3(n_q), dim3(64), 0, st, (const unsigned long long*)off_f, (const unsigned long long*)off_r, f_idx, r_idx, r_only,
+	                   (unsigned long long*)counts);
+	hipLaunchKernelGGL(k_pair_strand_scan, dim3(1), dim3(kBlock), 0, st, (const unsigned long long*)counts, n_q, (unsigned long long*)off_m);
+	return hipGetLastError();
+}
+
+hipError_t msc_launch_pair_strand_write(hipStream_t st, const uint64_t* off_f, const uint64_t* off_r, const uint64_t* off_m, uint32_t n_q, const uint32_t* f_idx, const double* f_sim,
+                                        const uint32_t* r_idx, const double* r_sim, const uint32_t* r_only, uint32_t* out_idx, double* out_sim, uint8_t* out_strand) {
+	if (n_q == 0) return hipSuccess;
+	hipLaunchKernelGGL(k_pair_strand_write, dim3(n_q), dim3(64), 0, st, (const unsigned long long*)off_f, (const unsigned long long*)off_r, (const unsigned long long*)off_m, f_idx,
+	                   f_sim, r_idx, r_sim, r_only, out_idx, out_sim, out_strand);
 	return hipGetLastError();
 }

@@ -101,6 +101,12 @@ public:
 	void copy_batch(const std::vector<uint32_t>& dst, const PointSet& src, const std::vector<uint32_t>& src_slots) {
 		ctx_.check(msc_hist_copy_batch(ctx_.get(), h_, dst.data(), src.h_, src_slots.data(), dst.size()));
 	}
+	// slot dst[i] of this set = the reverse complement of slot src_slots[i] of src (msc_hist_revcomp_batch: bins'[b] = bins[rc(b)], the record
+	// copied with its 1-mers reversed); no in-place form
+	void revcomp_batch(const std::vector<uint32_t>& dst, const PointSet& src, const std::vector<uint32_t>& src_slots) {
+		if (dst.size() != src_slots.size()) throw Error(MSC_ERR_INVALID_ARG, "revcomp_batch: one source slot per destination slot");
+		ctx_.check(msc_hist_revcomp_batch(ctx_.get(), h_, dst.data(), src.h_, src_slots.data(), dst.size()));
+	}
 private:
 	Context& ctx_;
 	msc_hist_set* h_ = nullptr;
@@ -284,6 +290,26 @@ public:
 		cand_idx.resize(inf.n_pairs);
 		similarity.resize(inf.n_pairs);
 		ctx_.check(msc_search_pairs_fetch(ctx_.get(), 0, inf.n_pairs, cand_idx.data(), similarity.data()));
+		if (info) *info = inf;
+		return offsets;
+	}
+	// search_pairs on both strands (msc_search_pairs_strands): per query the union of its list and of its reverse complement's, ascending index;
+	// strand[p] = 0 (the query as given; also a tie) or 1 (its reverse complement gave the larger similarity, or the only one). Empty windows
+	// mean every candidate.
+	std::vector<uint64_t> search_pairs_strands(const PointSet& db, const std::vector<uint32_t>& slots, const PointSet& q, const std::vector<uint32_t>& q_slots,
+	                                           const std::vector<uint64_t>& win_lo, const std::vector<uint64_t>& win_hi, std::vector<uint32_t>& cand_idx,
+	                                           std::vector<double>& similarity, std::vector<uint8_t>& strand, msc_pairs_info* info = nullptr) const {
+		const bool windows = !win_lo.empty() || !win_hi.empty();
+		if (windows && (win_lo.size() != q_slots.size() || win_hi.size() != q_slots.size())) throw Error(MSC_ERR_INVALID_ARG, "search_pairs_strands: one window per query");
+		std::vector<uint64_t> offsets(q_slots.size() + 1, 0);
+		msc_pairs_info inf;
+		ctx_.check(msc_search_pairs_strands(ctx_.get(), cls_ ? cls_->get() : nullptr, reg_ ? reg_->get() : nullptr, db.get(), slots.data(), slots.size(), q.get(), q_slots.data(),
+		                                    q_slots.size(), windows ? win_lo.data() : nullptr, windows ? win_hi.data() : nullptr, offsets.data(), &inf));
+		cand_idx.resize(inf.n_pairs);
+		similarity.resize(inf.n_pairs);
+		strand.resize(inf.n_pairs);
+		ctx_.check(msc_search_pairs_fetch(ctx_.get(), 0, inf.n_pairs, cand_idx.data(), similarity.data()));
+		ctx_.check(msc_search_pairs_fetch_strands(ctx_.get(), 0, inf.n_pairs, strand.data()));
 		if (info) *info = inf;
 		return offsets;
 	}

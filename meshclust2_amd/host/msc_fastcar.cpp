@@ -6,7 +6,11 @@
 // std::sort by length, bin_search, format_header and the output formatting follow fastcar/FC_Runner.cpp:389-471,
 // 560-611 at one thread (one output file "<prefix>0"); training is out of scope, a two-block weights file is required.
 //
-//   msc_fastcar <db.fa> --query <q.fa> --recover weights.txt [--output output] [--chunk 10000] [--no-format] [--device 0] [--div-cells] [--top N]
+//   msc_fastcar <db.fa> --query <q.fa> --recover weights.txt [--output output] [--chunk 10000] [--no-format] [--device 0] [--div-cells] [--top N] [--both-strands]
+//
+// --both-strands: every block of queries, single-member blocks included, goes through msc_search_pairs_strands: a hit is reported when the query
+// or its reverse complement is close to the database entry as stored, with the larger of the two similarities (a tie goes to the query as
+// given) and a last column + or -. Not together with --top.
 //
 // --top N: each query's N best hits over the whole database (the rule of msc_search_pairs_top: largest similarity, ties to the earlier
 // database chunk and then to the lower position in the chunk's window order). Per database chunk the cut runs on the device; across
@@ -113,7 +117,7 @@ int main(int argc, char** argv) {
 	std::vector<std::string> files, qfiles;
 	std::string weights, output = "output";
 	size_t chunk = 10000, qblock = 16, top = 0;
-	bool format = true, sparse = false, report_kernels = false, div_cells = false, sparse_matrix = false;
+	bool format = true, sparse = false, report_kernels = false, div_cells = false, sparse_matrix = false, both_strands = false;
 	int device = 0;
 	for (int i = 1; i < argc; i++) {
 		std::string a = argv[i];
@@ -130,11 +134,16 @@ int main(int argc, char** argv) {
 		else if (a == "--div-cells") div_cells = true;  // msc_set_pairs_div_cells: a --feat slow model's query blocks on the matrix-core route
 		else if (a == "--sparse-matrix") sparse_matrix = true;  // msc_set_sparse_matrix_pass: with --sparse, the query blocks on the matrix-core route
 		else if (a == "--top") top = (size_t)std::max(0l, std::atol(need("--top").c_str()));          // each query's N best hits (0: all)
+		else if (a == "--both-strands") both_strands = true;          // msc_search_pairs_strands: the queries and their reverse complements
 		else if (a == "--device") device = std::atoi(need("--device").c_str());
 		else files.push_back(a);
 	}
 	if (files.empty() || qfiles.empty() || weights.empty()) {
-		std::fprintf(stderr, "usage: %s <db.fa> --query <q.fa> --recover weights.txt [--output prefix] [--chunk 10000] [--no-format] [--sparse] [--sparse-matrix] [--div-cells] [--top N]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s <db.fa> --query <q.fa> --recover weights.txt [--output prefix] [--chunk 10000] [--no-format] [--sparse] [--sparse-matrix] [--div-cells] [--top N] [--both-strands]\n", argv[0]);
+		return 1;
+	}
+	if (both_strands && top) {
+		std::fprintf(stderr, "--both-strands and --top cannot be combined: the cut is not defined over two strands\n");
 		return 1;
 	}
 	try {
@@ -194,7 +203,7 @@ int main(int argc, char** argv) {
 				// work() (:426-471) for every query of the chunk. Queries are taken in blocks of `qblock` neighbours in LENGTH order, so
 				// their length windows nearly coincide and one Q x M pass over the union window serves the block; each query then
 				// keeps only its own window, and the lines are written in the reference's order (query order, then window order).
-				struct Hit { size_t cand; double sim; };
+				struct Hit { size_t cand; double sim; uint8_t strand; };
 				std::vector<std::vector<Hit> > hits(qp.size());
 				std::vector<size_t> win_start(qp.size()), win_end(qp.size());
 				for (size_t qi = 0; qi < qp.size(); qi++) {
@@ -225,14 +234,14 @@ int main(int argc, char** argv) {
 					if (members.empty()) continue;
 					std::vector<uint32_t> window;
 					for (size_t i = lo; i < hi; i++) window.push_back(pts[i]->slot);
-					if (members.size() == 1) {          // pred->close / similarity, one query
+					if (members.size() == 1 && !both_strands) {          // pred->close / similarity, one query
 						std::vector<uint8_t> close;
 						std::vector<double> sim;
 						pred.search(dset, window, qset, q_slots[0], close, sim);
 						note_kernel();
 						const size_t before = hits[members[0]].size();
 						for (size_t i = win_start[members[0]]; i < win_end[members[0]]; i++)
-							if (close[i - lo]) hits[members[0]].push_back(Hit{i, sim[i - lo]});
+							if (close[i - lo]) hits[members[0]].push_back(Hit{i, sim[i - lo], 0});
 						num_pred_pos += hits[members[0]].size() - before;
 						cut_top(hits[members[0]], top);
 						continue;
@@ -243,12 +252,14 @@ int main(int argc, char** argv) {
 					std::vector<uint32_t> idx;
 					std::vector<double> sim;
 					std::vector<uint64_t> counts;
-					const std::vector<uint64_t> offsets = top ? pred.search_pairs_top(dset, window, qset, q_slots, wl, wh, (uint32_t)std::min<size_t>(top, 0xffffffffu), idx, sim, &counts)
+					std::vector<uint8_t> strand;
+					const std::vector<uint64_t> offsets = both_strands ? pred.search_pairs_strands(dset, window, qset, q_slots, wl, wh, idx, sim, strand)
+					                                      : top ? pred.search_pairs_top(dset, window, qset, q_slots, wl, wh, (uint32_t)std::min<size_t>(top, 0xffffffffu), idx, sim, &counts)
 					                                          : pred.search_pairs(dset, window, qset, q_slots, wl, wh, idx, sim);
 					note_kernel();
 					for (size_t j = 0; j < members.size(); j++) num_pred_pos += top ? counts[j] : offsets[j + 1] - offsets[j];
 					for (size_t j = 0; j < members.size(); j++)
-						for (uint64_t p = offsets[j]; p < offsets[j + 1]; p++) hits[members[j]].push_back(Hit{lo + idx[p], sim[p]});
+						for (uint64_t p = offsets[j]; p < offsets[j + 1]; p++) hits[members[j]].push_back(Hit{lo + idx[p], sim[p], both_strands ? strand[p] : (uint8_t)0});
 				}
 				if (top) {          // the chunk's survivors behind those of the chunks before, cut again: ties stay with the earlier chunk
 					for (size_t qi = 0; qi < qp.size(); qi++) {
@@ -261,8 +272,10 @@ int main(int argc, char** argv) {
 					const Pt& query = qp[qi];
 					for (const Hit& h : hits[qi]) {
 						if (h.sim > 0) {
-							if (format) out << format_header(query.header) << delim << format_header(pts[h.cand]->header) << delim << 100 * h.sim << std::endl;
-							else out << query.header << delim << pts[h.cand]->header << delim << 100 * h.sim << std::endl;
+							if (format) out << format_header(query.header) << delim << format_header(pts[h.cand]->header) << delim << 100 * h.sim;
+							else out << query.header << delim << pts[h.cand]->header << delim << 100 * h.sim;
+							if (both_strands) out << delim << (h.strand ? '-' : '+');
+							out << std::endl;
 						}
 					}
 				}
