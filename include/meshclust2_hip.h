@@ -159,6 +159,19 @@ int         msc_set_pairs_div_cells(msc_ctx* ctx, int on);
  * cells". msc_search_pairs's own matrix route follows msc_set_pairs_div_cells alone; its fallback IS a sequence of msc_score_multi calls
  * and follows this switch as they do. No other call is affected. Default: off. */
 int         msc_set_multi_div_cells(msc_ctx* ctx, int on);
+/* A msc_score_multi call that wants nothing but the close flags, on the matrix-core route with a model that holds
+ * earth_movers_distance: the flags are first decided from exact integer bounds of that distance (two moments per slot of the ranks
+ * mirror), and the rank lists are walked only for the pairs the bounds leave open -- a device list of at most 1/64 of a block's pairs,
+ * evaluated in FP64 with their exact distances. A block whose list overflows is scored as with the switch off, on the device, without a
+ * host round trip; a model more than half of whose blocks overflowed in one call is remembered, and later calls with it skip the bound
+ * pass. The flags are those of the switch-off call, pair for pair. on = 0: the distance of every pair of a block is formed first (the
+ * path before this switch existed). Default: on (off at start with MSC_NO_EMD_BOUNDS in the environment). Calls that want sums,
+ * classify sums or raw statistics, --feat slow models, msc_search_pairs* and msc_score_pair_list do not look at it. */
+int         msc_set_emd_bounds(msc_ctx* ctx, int on);
+/* What the last msc_score_multi call did about the earth mover's distance of its close-flag blocks (those the switch above is about):
+ * blocks = such blocks, dense_blocks = those whose every pair had its rank lists walked (switch off, a remembered model, sets of
+ * different list pitch, an overflowed list), listed_pairs = pairs walked one by one from the lists of the others. Any pointer may be null. */
+int         msc_last_emd_walk(const msc_ctx* ctx, uint64_t* listed_pairs, uint64_t* dense_blocks, uint64_t* blocks);
 /* A Q x M call over two SPARSE sets (msc_score_multi, msc_search_pairs) runs one 1 x M pass per query over the lists: the matrix-core
  * route reads a presence bit per bin, the lists of large bins and the sorted ranks of a set -- mirrors only dense sets used to carry.
  * on = 1 lets two sparse sets of equal k and dtype take that route as well, under its usual conditions (8/16/32-bit bins of the narrow

@@ -78,6 +78,18 @@ class Context:
         a model derives from them agree to rounding (1e-9 relative), not bit for bit"""
         self.check(self.lib.msc_set_multi_div_cells(self.h, 1 if on else 0))
 
+    def set_emd_bounds(self, on):
+        """score_multi's close flags with an earth_movers_distance model: decided from bounds of the distance, rank lists walked for the
+        pairs the bounds leave open only (default), or the distance of every pair formed first (off); the same flags"""
+        self.check(self.lib.msc_set_emd_bounds(self.h, 1 if on else 0))
+
+    def last_emd_walk(self):
+        """(listed_pairs, dense_blocks, blocks) of the last score_multi call: pairs whose rank lists were walked one by one, close-flag
+        blocks whose every pair was walked, and such blocks in all"""
+        v = [C.c_uint64(0) for _ in range(3)]
+        self.check(self.lib.msc_last_emd_walk(self.h, C.byref(v[0]), C.byref(v[1]), C.byref(v[2])))
+        return tuple(int(x.value) for x in v)
+
     def set_sparse_matrix_pass(self, on):
         """score_multi / search_pairs over two sparse sets: the matrix-core route over mirrors built from the lists (on) or one 1 x M pass
         per query (default); identical results"""

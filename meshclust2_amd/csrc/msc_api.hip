@@ -114,6 +114,7 @@ extern "C" int msc_create(int device, msc_ctx** out) {
 	}
 	ctx->mirror_pass = getenv("MSC_NO_MIRROR_1XM") == nullptr;
 	ctx->block_pipe = getenv("MSC_GEMM_NO_PIPE") == nullptr;
+	ctx->emd_bounds = getenv("MSC_NO_EMD_BOUNDS") == nullptr;
 	*out = ctx;
 	return MSC_OK;
 }
@@ -151,7 +152,7 @@ extern "C" void msc_destroy(msc_ctx* ctx) {
 	                  &ctx->seq_meta, &ctx->qslots_all, &ctx->shard_payload, &ctx->shard_hdrs, &ctx->rk_q, &ctx->rk_acc, &ctx->rk_counters,
 	                  &ctx->rk_tables, &ctx->rk_items, &ctx->rk_big, &ctx->pl_idx, &ctx->pl_sim, &ctx->pl_stage_idx, &ctx->pl_stage_sim, &ctx->pl_flags,
 	                  &ctx->pl_counts, &ctx->pl_offsets, &ctx->pl_seg, &ctx->pl_dst, &ctx->pl_qslots, &ctx->pl_win, &ctx->pl_qcount, &ctx->pl_words,
-	                  &ctx->emd_out, &ctx->close_counts, &ctx->rk_bad, &ctx->prof_nnz, &ctx->segs, &ctx->pair_seg, &ctx->dist, &ctx->sp_counts,
+	                  &ctx->emd_out, &ctx->open_list, &ctx->emd_list, &ctx->open_words, &ctx->close_counts, &ctx->rk_bad, &ctx->prof_nnz, &ctx->segs, &ctx->pair_seg, &ctx->dist, &ctx->sp_counts,
 	                  &ctx->sp_cumbase, &ctx->sp_acc, &ctx->sp_chunk_off, &ctx->sp_chunk_cum, &ctx->sp_partials, &ctx->grp_pairs, &ctx->grp_self,
 	                  &ctx->tile_scratch, &ctx->reduce_parts, &ctx->sp_touched, &ctx->sp_acc_batch, &ctx->ps_idx, &ctx->ps_sim, &ctx->ps_m_idx, &ctx->ps_m_sim,
 	                  &ctx->pl_strand, &ctx->ps_off, &ctx->ps_only, &ctx->ps_counts};
@@ -185,6 +186,20 @@ extern "C" int msc_synchronize(msc_ctx* ctx) {
 extern "C" int msc_set_block_pipe(msc_ctx* ctx, int on) {
 	if (!ctx) return MSC_ERR_INVALID_ARG;
 	ctx->block_pipe = on != 0;
+	return MSC_OK;
+}
+
+extern "C" int msc_set_emd_bounds(msc_ctx* ctx, int on) {
+	if (!ctx) return MSC_ERR_INVALID_ARG;
+	ctx->emd_bounds = on != 0;
+	return MSC_OK;
+}
+
+extern "C" int msc_last_emd_walk(const msc_ctx* ctx, uint64_t* listed_pairs, uint64_t* dense_blocks, uint64_t* blocks) {
+	if (!ctx) return MSC_ERR_INVALID_ARG;
+	if (listed_pairs) *listed_pairs = ctx->walk_listed;
+	if (dense_blocks) *dense_blocks = ctx->walk_dense;
+	if (blocks) *blocks = ctx->walk_blocks;
 	return MSC_OK;
 }
 
@@ -458,6 +473,7 @@ extern "C" void msc_hist_set_destroy(msc_hist_set* s) {
 	if (s->ranks) (void)hipFree(s->ranks);
 	if (s->ranks16) (void)hipFree(s->ranks16);
 	if (s->rk_n) (void)hipFree(s->rk_n);
+	if (s->rk_sum) (void)hipFree(s->rk_sum);
 	if (s->sp_mirror) msc_hist_set_destroy(s->sp_mirror);
 	if (s->ent) (void)hipFree(s->ent);
 	if (s->cum) (void)hipFree(s->cum);

@@ -119,6 +119,11 @@ int ensure_ranks(msc_ctx* ctx, const msc_hist_set* set) {
 		set->rk_n = (uint32_t*)pn;
 		set->rk_pitch = pitch;
 		set->rk_stale.all(set->capacity);
+		if (!set->rk_sum) {          // the two moments per slot (msc_emd_list.hip), built with the rows below; without them the close flags take the dense walk
+			void* pm = nullptr;
+			if (hipMalloc(&pm, 2 * sizeof(uint64_t) * set->capacity) != hipSuccess) (void)hipGetLastError();
+			else { set->rk_sum = (uint64_t*)pm; set->rk_dev = set->rk_sum + set->capacity; }
+		}
 	}
 	static const bool no_rk16 = getenv("MSC_NO_RANKS16") != nullptr;
 	if (!set->ranks16 && !set->rk16_off && !no_rk16 && set->rk_pitch % 1024 == 0) {          // the 16-bit form beside it (k_emd_ranks16)
@@ -133,7 +138,8 @@ int ensure_ranks(msc_ctx* ctx, const msc_hist_set* set) {
 		// runs of slots that hold a histogram (an unwritten slot's digest is whatever the allocation held)
 		const uint64_t lo = set->rk_stale.lo, hi = std::min<uint64_t>(set->rk_stale.hi, set->sparse ? set->capacity : set->written.size());
 		int32_t* bad_word = (int32_t*)ctx->rk_bad.p;
-		auto build16 = [&](uint64_t first, uint64_t n) {
+		auto build16 = [&](uint64_t first, uint64_t n) {          // (a dense set: and the moments of the same rows, msc_emd_list.hip)
+			if (set->rk_sum && !set->sparse) HIP_TRY(ctx, msc_launch_rank_moments(ctx->stream, set->L.nbins, set->ranks, set->rk_pitch, first, n, set->rk_sum, set->rk_dev));
 			if (set->ranks16) HIP_TRY(ctx, msc_launch_ranks16_build(ctx->stream, set->L.nbins, set->ranks, set->ranks16, set->rk_pitch, first, n, bad_word + 1));
 			return (int)MSC_OK;
 		};
@@ -142,6 +148,7 @@ int ensure_ranks(msc_ctx* ctx, const msc_hist_set* set) {
 			// runs that hold a list, as a dense set's unwritten slots are skipped: the ranks16 row of an empty slot is NOT maintained (all
 			// padding does not fit 16 bits and would switch the form off for the set; nothing reads a row past its rk_n = 0)
 			if (hi > lo) HIP_TRY(ctx, msc_launch_ranks_build_sparse(ctx->stream, set->L, set->ent, set->cum, set->hdr, set->ranks, set->rk_n, set->rk_pitch, lo, hi - lo, bad_word));
+			if (hi > lo && set->rk_sum) HIP_TRY(ctx, msc_launch_rank_moments(ctx->stream, set->L.nbins, set->ranks, set->rk_pitch, lo, hi - lo, set->rk_sum, set->rk_dev));
 			if ((r = for_each_run(lo, hi, [&](uint64_t i) { return set->hdr_host[i].nnz != 0; }, build16))) return r;
 		} else if ((r = for_each_run(lo, hi, [&](uint64_t i) { return set->written[i] != 0; }, [&](uint64_t first, uint64_t n) {
 			            HIP_TRY(ctx, msc_launch_ranks_build(ctx->stream, set->L, set->dtype, set->bins, set->scalars, set->ranks, set->rk_n, set->rk_pitch, first, n, bad_word));
@@ -230,11 +237,11 @@ void fill_matrix_args(MscEpilogueArgs& ea, const BlockPipe::Side& s, const msc_h
 	ea.emd_stride = rows; ea.emd_ranks = (const uint64_t*)emd_out;
 }
 
-hipError_t launch_emd_ranks(hipStream_t st, const msc_hist_set* cands, const msc_hist_set* qset, const uint32_t* d_slots, uint64_t off, uint32_t mc, const uint32_t* dq, uint32_t nq, uint64_t* out, uint32_t stride) {
+hipError_t launch_emd_ranks(hipStream_t st, const msc_hist_set* cands, const msc_hist_set* qset, const uint32_t* d_slots, uint64_t off, uint32_t mc, const uint32_t* dq, uint32_t nq, uint64_t* out, uint32_t stride, const uint32_t* run_if) {
 	const uint64_t nbins = cands->L.nbins;
 	if (cands->ranks16 && qset->ranks16 && cands->rk_pitch == qset->rk_pitch)          // every reduced rank of both sets fits 16 bits: two per v_sad_u16
-		return msc_launch_emd_ranks16(st, nbins, cands->ranks16, cands->rk_pitch, cands->rk_n, d_slots, off, mc, qset->ranks16, qset->rk_n, dq, nq, out, stride);
-	return msc_launch_emd_ranks(st, nbins, cands->ranks, cands->rk_pitch, cands->rk_n, d_slots, off, mc, qset->ranks, qset->rk_pitch, qset->rk_n, dq, nq, out, stride);
+		return msc_launch_emd_ranks16(st, nbins, cands->ranks16, cands->rk_pitch, cands->rk_n, d_slots, off, mc, qset->ranks16, qset->rk_n, dq, nq, out, stride, run_if);
+	return msc_launch_emd_ranks(st, nbins, cands->ranks, cands->rk_pitch, cands->rk_n, d_slots, off, mc, qset->ranks, qset->rk_pitch, qset->rk_n, dq, nq, out, stride, run_if);
 }
 
 void fill_pair_args(MscEpilogueArgs& ea, msc_ctx* ctx, const msc_hist_set* cands, const msc_hist_set* qset, const uint32_t* d_slots, uint64_t first, uint32_t mc, const uint32_t* dq, uint32_t q_slot0, uint32_t nq, uint32_t n_rec, int order) {
@@ -711,6 +718,8 @@ int run_streamed(MultiCall& c, Block& b, const BlockRoute& rt) {
 // walk of block i and the epilogue of block i - 1 on tail_stream, the queries' side of block i + 1 on prep_stream -- the product is bound by the matrix pipe,
 // the others by vector arithmetic and latency. Blocks take turns on the two sides of the pipe. (Single chunk, no divergence / group passes between the stages -- divergence sums from cells run none;
 // MSC_GEMM_NO_PREP: the queries' side on the product's stream, as in r04.) The close flags go into one of two buffers and home on the copy stream, under the next block's kernels.
+// A flags-only block whose distance comes from the ranks mirrors runs no walk beside the product: its tail is the bound screen, the walk and the FP64 evaluation of
+// the listed pairs, then the dense walk and the two older epilogue kernels predicated on the list's overflow word (msc_emd_list.hip).
 int run_matrix(MultiCall& c, Block& b, const BlockRoute& rt) {
 	msc_ctx* ctx = c.ctx;
 	BlockPipe& pipe = ctx->pipe;
@@ -769,7 +778,25 @@ int run_matrix(MultiCall& c, Block& b, const BlockRoute& rt) {
 		HIP_TRY(ctx, msc_launch_pair_gemm(ctx->stream, L.nbins, cands->kb, k.d_slots, off, k.mc, rows, slices, hot.ptr, s.hot.p, (int32_t*)s.min.p, (int32_t*)s.diff.p, (const uint8_t*)s.anib.p));
 		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ev_t1, ctx->stream));
 		if (piped) { HIP_TRY(ctx, hipEventRecord(s.ev_product, ctx->stream)); s.product_busy = true; }
-		if (rt.emd_ranks) HIP_TRY(ctx, launch_emd_ranks(b.tail, cands, qset, k.d_slots, off, k.mc, b.dq_slots, (uint32_t)n_q, (uint64_t*)ctx->emd_out.p, rows));
+		// only the close flags are wanted: k_pair_epilogue_bits decides them in f32 with an error bound and evaluates in FP64 only the
+		// pairs the bound leaves open -- the same flags (MSC_NO_SCREEN: FP64 for every pair)
+		static const bool no_screen = getenv("MSC_NO_SCREEN") != nullptr;
+		const bool screen = c.model && c.model->h.screen_ok && b.close && !b.sum && !b.csum && !b.raw && !c.want_div && !c.want_grp && !no_screen;
+		// ... and with the distance from the ranks mirrors of two sets of one pitch (what k_emd_ranks16 asks too), first from BOUNDS of the distance
+		// (msc_emd_list.hip): the ranks are walked only for the pairs the bounds leave open, up to 1 / 64 of the chunk's pairs -- past that share a
+		// walk per pair reads more than the dense walk. msc_set_emd_bounds(0), a model remembered for overflowing, sets without moments: today's path
+		const bool walk_counted = screen && rt.emd_ranks;
+		const bool bounds = walk_counted && ctx->emd_bounds && !c.model->emd_decides && cands->rk_pitch == qset->rk_pitch && cands->rk_sum && qset->rk_sum &&
+		                    n_q * (uint64_t)k.mc <= 0xffffffffull && n_q * (uint64_t)k.mc >= 64;          // (fewer than 64 pairs: a list of no entries)
+		const uint32_t open_cap = bounds ? (uint32_t)(n_q * k.mc / 64) : 0;
+		uint32_t* open_words = nullptr;
+		if (walk_counted) { ctx->walk_blocks++; if (!bounds) ctx->walk_dense++; }
+		if (bounds) {
+			if ((r = ensure(ctx, ctx->open_list, std::max<size_t>(1, open_cap) * sizeof(uint32_t))) || (r = ensure(ctx, ctx->emd_list, std::max<size_t>(1, open_cap) * sizeof(uint64_t)))) return r;
+			open_words = (uint32_t*)ctx->open_words.p;          // (allocated and cleared when the call began, on the product's stream: behind ev_head for a piped block)
+			ctx->walk_bound_blocks++;
+		} else if (rt.emd_ranks)
+			HIP_TRY(ctx, launch_emd_ranks(b.tail, cands, qset, k.d_slots, off, k.mc, b.dq_slots, (uint32_t)n_q, (uint64_t*)ctx->emd_out.p, rows));
 		MscEpilogueArgs ea;
 		fill_block_args(c, b, b.dq_slots, k, L.S, ea);
 		if ((r = side_passes(c, b, k, ea))) return r;
@@ -783,12 +810,25 @@ int run_matrix(MultiCall& c, Block& b, const BlockRoute& rt) {
 			if (pipe.close_pp_busy[pp]) HIP_TRY(ctx, hipStreamWaitEvent(b.tail, pipe.ev_copied[pp], 0));
 		}
 		ea.close_soa = d_close;
-		// only the close flags are wanted: k_pair_epilogue_bits decides them in f32 with an error bound and evaluates in FP64 only the
-		// pairs the bound leaves open -- the same flags (MSC_NO_SCREEN: FP64 for every pair)
-		static const bool no_screen = getenv("MSC_NO_SCREEN") != nullptr;
-		ea.screen = c.model && c.model->h.screen_ok && d_close && !b.sum && !b.csum && !b.raw && !c.want_div && !c.want_grp && !no_screen;
+		ea.screen = screen;
 		if (piped) HIP_TRY(ctx, hipStreamWaitEvent(b.tail, s.ev_product, 0));
+		if (bounds) {
+			// the bound screen, the walk of the listed pairs, their FP64 evaluation; then today's three kernels, which return at once unless the list
+			// overflowed (then they overwrite every flag of the chunk); then the list's words into the call's totals, cleared for the next block
+			MscEpilogueArgs eb = ea;
+			eb.emd_ranks = nullptr;
+			eb.rk_c_sum = cands->rk_sum; eb.rk_c_dev = cands->rk_dev; eb.rk_q_sum = qset->rk_sum; eb.rk_q_dev = qset->rk_dev;
+			eb.open_list = (uint32_t*)ctx->open_list.p; eb.open_words = open_words; eb.open_cap = open_cap; eb.emd_list = (const uint64_t*)ctx->emd_list.p;
+			HIP_TRY(ctx, msc_launch_epilogue_bound(b.tail, eb));
+			const bool u16 = cands->ranks16 && qset->ranks16;
+			HIP_TRY(ctx, msc_launch_emd_ranks_list(b.tail, u16, u16 ? (const void*)cands->ranks16 : (const void*)cands->ranks, u16 ? (const void*)qset->ranks16 : (const void*)qset->ranks,
+			                                       cands->rk_pitch, k.d_slots, off, k.mc, b.dq_slots, eb.open_list, open_words, open_cap, (uint64_t*)ctx->emd_list.p, ctx->num_cus));
+			HIP_TRY(ctx, msc_launch_epilogue_list(b.tail, eb, ctx->num_cus));
+			HIP_TRY(ctx, launch_emd_ranks(b.tail, cands, qset, k.d_slots, off, k.mc, b.dq_slots, (uint32_t)n_q, (uint64_t*)ctx->emd_out.p, rows, open_words + 1));
+			ea.run_if = open_words + 1;
+		}
 		HIP_TRY(ctx, msc_launch_epilogue(b.tail, ea));
+		if (bounds) HIP_TRY(ctx, msc_launch_emd_list_close(b.tail, open_words, open_cap, (uint64_t*)(open_words + 2)));
 		if (b.close && ctx->close_counts_n) HIP_TRY(ctx, msc_launch_close_counts(b.tail, d_close, (uint32_t)n_q, k.mc, (uint64_t*)ctx->close_counts.p + b.q0));
 		if (piped) {
 			HIP_TRY(ctx, hipEventRecord(s.ev_tail, b.tail));
@@ -861,6 +901,10 @@ int score_multi(MultiCall& c) {
 	// close candidates per query, kept on the device for msc_last_close_counts (a caller that only needs the counts of a block of the
 	// pairwise matrix does not have to add up n_q x m flags on the host)
 	ctx->close_counts_n = 0;
+	if (c.close_out && c.model) {          // the list of open pairs of the bound pass (run_matrix): {count, overflow}, then the call's two totals
+		if ((r = ensure(ctx, ctx->open_words, 2 * sizeof(uint32_t) + 2 * sizeof(uint64_t)))) return r;
+		HIP_TRY(ctx, hipMemsetAsync(ctx->open_words.p, 0, 2 * sizeof(uint32_t) + 2 * sizeof(uint64_t), ctx->stream));
+	}
 	if (c.close_out) {
 		if ((r = ensure(ctx, ctx->close_counts, n_q * sizeof(uint64_t)))) return r;
 		HIP_TRY(ctx, hipMemsetAsync(ctx->close_counts.p, 0, n_q * sizeof(uint64_t), ctx->stream));
@@ -920,7 +964,19 @@ extern "C" int msc_score_multi(msc_ctx* ctx, const msc_model* model, const msc_h
                                const msc_hist_set* qset, const uint32_t* q_slots, uint64_t n_q, int order, double* sum_out, double* csum_out,
                                uint8_t* close_out, uint64_t feat_mask, double* raw_out) {
 	MultiCall c{ctx, model, cands, cand_slots, m, qset, q_slots, n_q, order, sum_out, csum_out, close_out, feat_mask, raw_out};
-	const int r = score_multi(c);
+	if (ctx) ctx->walk_listed = ctx->walk_dense = ctx->walk_blocks = ctx->walk_bound_blocks = 0;
+	int r = score_multi(c);
+	if (ctx && r == MSC_OK && ctx->walk_bound_blocks) {          // the totals of the bound pass (every stream of the call is idle: the error word has been read)
+		uint64_t totals[2] = {0, 0};
+		const hipError_t e = hipMemcpy(totals, (const uint8_t*)ctx->open_words.p + 2 * sizeof(uint32_t), sizeof totals, hipMemcpyDeviceToHost);
+		if (e != hipSuccess) r = fail(ctx, MSC_ERR_HIP, "copy of the pair list's totals failed: %s", hipGetErrorString(e));
+		else {
+			ctx->walk_listed = totals[0];
+			ctx->walk_dense += totals[1];
+			// a model whose distance really decides: it does not pay the bound pass for ever
+			if (totals[1] * 2 > ctx->walk_bound_blocks) model->emd_decides = true;
+		}
+	}
 	if (ctx && ctx->pipe.copy_pending) {          // the flag copies of the last blocks (issued beside the kernels that followed them)
 		const hipError_t e = hipStreamSynchronize(ctx->pipe.copy_stream);
 		ctx->pipe.copy_pending = ctx->pipe.close_pp_busy[0] = ctx->pipe.close_pp_busy[1] = false;

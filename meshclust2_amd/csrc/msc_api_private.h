@@ -75,5 +75,5 @@ void fill_pair_args(MscEpilogueArgs& ea, msc_ctx* ctx, const msc_hist_set* cands
 // the kb_* and emd_* fields of the epilogue's arguments (first: the chunk's first candidate, 0 with a slot list; emd_out null: no emd)
 void fill_matrix_args(MscEpilogueArgs& ea, const BlockPipe::Side& s, const msc_hist_set* cands, const msc_hist_set* qset, uint32_t slices, uint32_t rows, uint64_t first, uint64_t n_hot, const void* emd_out);
 // the earth mover's distances of a chunk from the ranks mirrors: the 16-bit walk where both sets keep that form at one pitch
-hipError_t launch_emd_ranks(hipStream_t st, const msc_hist_set* cands, const msc_hist_set* qset, const uint32_t* d_slots, uint64_t off, uint32_t mc, const uint32_t* dq, uint32_t nq, uint64_t* out, uint32_t stride);
+hipError_t launch_emd_ranks(hipStream_t st, const msc_hist_set* cands, const msc_hist_set* qset, const uint32_t* d_slots, uint64_t off, uint32_t mc, const uint32_t* dq, uint32_t nq, uint64_t* out, uint32_t stride, const uint32_t* run_if = nullptr);
 void name_matrix_kernel(msc_ctx* ctx, uint32_t rows, bool emd, bool cells, bool from_lists);      // msc_last_kernel_info's name of the product kernel

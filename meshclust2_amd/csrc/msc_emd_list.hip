@@ -1,0 +1,129 @@
+// msc_emd_list.hip -- the earth mover's distance of the Q x M close-flag pass WITHOUT the dense rank walk (gfx950).
+//
+// msc_emd_ranks.hip forms emd(a, b) = sum_t | a_t - b_t | over the padded rows of the ranks mirror for every pair of a block. The close
+// flag of almost every pair does not depend on the exact value: with base_t = floor(t * 4^k / pitch) (k_ranks16_build's) the triangle
+// inequality gives, exactly in integers, for two rows of ONE pitch
+//     | sum_t a_t - sum_t b_t |  <=  emd(a, b)  <=  sum_t | a_t - base_t | + sum_t | b_t - base_t |
+// so two moments per slot bound it, and the screen (pair_features.hip, k_pair_epilogue_bits_bound) decides the flag from the interval.
+//
+//   k_rank_moments      one wave per slot: rk_sum = sum_t a_t, rk_dev = sum_t | a_t - base_t | over the whole padded row. Launched wherever
+//                       the ranks mirror is built or refreshed, over the same slots.
+//   k_emd_ranks_list    the pairs the interval leaves undecided arrive as a device list of pair indices (q * m_per_query + ci); one wave
+//                       per listed pair walks the two rows (v_sad_u16 over the 16-bit form when both sets have it, v_sad_u32 otherwise) and
+//                       writes the exact distance. The count is read on the device: no host round trip between the screen and the walk.
+#include <algorithm>
+
+#include "msc_internal.h"
+
+namespace {
+
+typedef int v4i_ __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
+#pragma unroll
+	for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+	return v;
+}
+
+__global__ void __launch_bounds__(256) k_rank_moments(const uint32_t* __restrict__ ranks, uint64_t pitch, uint64_t nbins, uint64_t first_slot, uint64_t n_slots,
+                                                      uint64_t* __restrict__ rk_sum, uint64_t* __restrict__ rk_dev) {
+	const uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+	const uint32_t lane = threadIdx.x & 63;
+	if (i >= n_slots) return;
+	const uint64_t slot = first_slot + i;
+	const uint32_t* row = ranks + slot * pitch;
+	uint64_t s = 0, d = 0;
+	for (uint64_t t = lane; t < pitch; t += 64) {
+		const int64_t a = row[t], base = (int64_t)(t * nbins / pitch);
+		s += (uint64_t)a;
+		d += (uint64_t)(a > base ? a - base : base - a);
+	}
+	s = wave_sum_u64(s);
+	d = wave_sum_u64(d);
+	if (lane == 0) { rk_sum[slot] = s; rk_dev[slot] = d; }
+}
+
+// words[0] = pairs appended, words[1] = the overflow word (an append found the list full: the block's flags come from the dense walk, and
+// nothing here is needed). Rounds of 1 024 ranks, as the dense kernels take them: a lane's terms of a round fit 32 bits (16 of <= 2^20),
+// the rounds add up in 64.
+template <bool kU16>
+__global__ void __launch_bounds__(256) k_emd_ranks_list(const void* __restrict__ c_rk, const void* __restrict__ q_rk, uint64_t pitch, const uint32_t* __restrict__ cand_slots, uint64_t first,
+                                                        uint32_t m_per_query, const uint32_t* __restrict__ q_slots, const uint32_t* __restrict__ list, const uint32_t* __restrict__ words,
+                                                        uint32_t cap, uint64_t* __restrict__ emd_list) {
+	if (words[1]) return;
+	const uint32_t n = words[0] < cap ? words[0] : cap;
+	const uint32_t lane = threadIdx.x & 63;
+	const uint32_t wave0 = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+	for (uint32_t i = wave0; i < n; i += gridDim.x * 4) {
+		const uint32_t idx = list[i], q = idx / m_per_query, ci = idx % m_per_query;
+		const uint64_t c_slot = cand_slots ? cand_slots[ci] : first + ci, q_slot = q_slots[q];
+		uint64_t total = 0;
+		if constexpr (kU16) {          // pitch is a multiple of 1 024 here; lane l: reduced ranks 512 j + 8 l .. + 7 of the round, two per register
+			const uint16_t *a = reinterpret_cast<const uint16_t*>(c_rk) + c_slot * pitch, *b = reinterpret_cast<const uint16_t*>(q_rk) + q_slot * pitch;
+			for (uint64_t base = 0; base < pitch; base += 1024) {
+				uint32_t t = 0;
+#pragma unroll
+				for (int j = 0; j < 2; j++) {
+					const v4i_ x = *reinterpret_cast<const v4i_*>(a + base + 512 * j + 8 * lane), y = *reinterpret_cast<const v4i_*>(b + base + 512 * j + 8 * lane);
+					asm("v_sad_u16 %0, %1, %2, %0" : "+v"(t) : "v"(x.x), "v"(y.x));
+					asm("v_sad_u16 %0, %1, %2, %0" : "+v"(t) : "v"(x.y), "v"(y.y));
+					asm("v_sad_u16 %0, %1, %2, %0" : "+v"(t) : "v"(x.z), "v"(y.z));
+					asm("v_sad_u16 %0, %1, %2, %0" : "+v"(t) : "v"(x.w), "v"(y.w));
+				}
+				total += t;
+			}
+		} else {          // pitch is a multiple of 256; lane l: ranks 256 j + 4 l .. + 3 of the round
+			const uint32_t *a = reinterpret_cast<const uint32_t*>(c_rk) + c_slot * pitch, *b = reinterpret_cast<const uint32_t*>(q_rk) + q_slot * pitch;
+			for (uint64_t base = 0; base < pitch; base += 1024) {
+				uint32_t t = 0;
+#pragma unroll
+				for (int j = 0; j < 4; j++) {
+					if (base + 256 * j >= pitch) break;
+					const v4i_ x = *reinterpret_cast<const v4i_*>(a + base + 256 * j + 4 * lane), y = *reinterpret_cast<const v4i_*>(b + base + 256 * j + 4 * lane);
+					asm("v_sad_u32 %0, %1, %2, %0" : "+v"(t) : "v"(x.x), "v"(y.x));
+					asm("v_sad_u32 %0, %1, %2, %0" : "+v"(t) : "v"(x.y), "v"(y.y));
+					asm("v_sad_u32 %0, %1, %2, %0" : "+v"(t) : "v"(x.z), "v"(y.z));
+					asm("v_sad_u32 %0, %1, %2, %0" : "+v"(t) : "v"(x.w), "v"(y.w));
+				}
+				total += t;
+			}
+		}
+		total = wave_sum_u64(total);
+		if (lane == 0) emd_list[i] = total;
+	}
+}
+
+// Behind a block's kernels: its count and overflow word go into the call's totals (totals[0] += pairs walked from the list, totals[1] +=
+// blocks whose list overflowed) and are cleared for the next block.
+__global__ void k_emd_list_close(uint32_t* __restrict__ words, uint32_t cap, unsigned long long* __restrict__ totals) {
+	if (threadIdx.x || blockIdx.x) return;
+	if (words[1]) totals[1] += 1;
+	else totals[0] += words[0] < cap ? words[0] : cap;
+	words[0] = 0;
+	words[1] = 0;
+}
+
+}  // namespace
+
+// the two moments of slots [first_slot, first_slot + n_slots) from their 32-bit ranks
+hipError_t msc_launch_rank_moments(hipStream_t st, uint64_t nbins, const uint32_t* ranks, uint64_t pitch, uint64_t first_slot, uint64_t n_slots, uint64_t* rk_sum, uint64_t* rk_dev) {
+	if (n_slots == 0) return hipSuccess;
+	k_rank_moments<<<dim3((unsigned)((n_slots + 3) / 4)), dim3(256), 0, st>>>(ranks, pitch, nbins, first_slot, n_slots, rk_sum, rk_dev);
+	return hipGetLastError();
+}
+
+// emd_list[i] = the distance of listed pair i, i < min(words[0], cap); two sets of one pitch. u16: both rows are the 16-bit form
+hipError_t msc_launch_emd_ranks_list(hipStream_t st, bool u16, const void* c_ranks, const void* q_ranks, uint64_t pitch, const uint32_t* cand_slots, uint64_t first, uint32_t m_per_query,
+                                     const uint32_t* q_slots_dev, const uint32_t* list, const uint32_t* words, uint32_t cap, uint64_t* emd_list, int num_cus) {
+	if (cap == 0) return hipSuccess;
+	if (pitch % (u16 ? 1024 : 256) || m_per_query == 0) return hipErrorInvalidValue;
+	const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)cap + 3) / 4, (uint64_t)num_cus * 8);
+	if (u16) k_emd_ranks_list<true><<<dim3(grid), dim3(256), 0, st>>>(c_ranks, q_ranks, pitch, cand_slots, first, m_per_query, q_slots_dev, list, words, cap, emd_list);
+	else k_emd_ranks_list<false><<<dim3(grid), dim3(256), 0, st>>>(c_ranks, q_ranks, pitch, cand_slots, first, m_per_query, q_slots_dev, list, words, cap, emd_list);
+	return hipGetLastError();
+}
+
+hipError_t msc_launch_emd_list_close(hipStream_t st, uint32_t* words, uint32_t cap, uint64_t* totals) {
+	k_emd_list_close<<<dim3(1), dim3(64), 0, st>>>(words, cap, (unsigned long long*)totals);
+	return hipGetLastError();
+}

@@ -163,8 +163,9 @@ __device__ __forceinline__ void dma_piece(uint64_t sbase, uint32_t lane_off, uin
 constexpr uint32_t kRound = 1024, kQGroup = 16, kQHalf = 8, kCandPerWave = 2, kWaves = 8;
 __global__ void __launch_bounds__(512, 2) k_emd_ranks(const uint32_t* __restrict__ c_rk, uint64_t c_pitch, const uint32_t* __restrict__ c_n, const uint32_t* __restrict__ cand_slots,
                                                       uint64_t first, uint32_t m, const uint32_t* __restrict__ q_rk, uint64_t q_pitch, const uint32_t* __restrict__ q_n,
-                                                      const uint32_t* __restrict__ q_slots, uint32_t n_q, uint32_t nbins, uint64_t* __restrict__ out, uint32_t out_stride) {
+                                                      const uint32_t* __restrict__ q_slots, uint32_t n_q, uint32_t nbins, uint64_t* __restrict__ out, uint32_t out_stride, const uint32_t* __restrict__ run_if) {
 	__shared__ v4i_ sQ[2][kQHalf][kRound / 4];          // 2 x 32 KiB
+	if (run_if && *run_if == 0) return;          // (a launch queued for a case that did not arise: msc_api_multi.hip, the overflow of the pair list. Uniform, before any barrier or DMA)
 	const uint32_t lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 	const uint32_t c0 = (blockIdx.x * kWaves + wave) * kCandPerWave;
 	const uint32_t n_groups = (n_q + kQGroup - 1) / kQGroup;
@@ -302,8 +303,9 @@ constexpr uint32_t kCand16 = 4;          // candidates per wave
 template <uint32_t NWV, uint32_t QS>
 __global__ void __launch_bounds__(64 * NWV, NWV == 8 ? 2 : 4) k_emd_ranks16(const uint16_t* __restrict__ c_rk, uint64_t pitch, const uint32_t* __restrict__ c_n, const uint32_t* __restrict__ cand_slots,
                                                         uint64_t first, uint32_t m, const uint16_t* __restrict__ q_rk, const uint32_t* __restrict__ q_n,
-                                                        const uint32_t* __restrict__ q_slots, uint32_t n_q, uint32_t nbins, uint64_t* __restrict__ out, uint32_t out_stride) {
+                                                        const uint32_t* __restrict__ q_slots, uint32_t n_q, uint32_t nbins, uint64_t* __restrict__ out, uint32_t out_stride, const uint32_t* __restrict__ run_if) {
 	static_assert(QS % NWV == 0 && 8 % QS == 0, "ring slots");
+	if (run_if && *run_if == 0) return;          // (as k_emd_ranks)
 	constexpr uint32_t SPG = 8 / QS;          // ring slots per group of 8 queries (one fold)
 	__shared__ v4i_ sQ[2][QS][kRound / 8];          // a list's round = 1 024 reduced ranks = 2 KiB
 	const uint32_t lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -430,13 +432,13 @@ hipError_t msc_launch_ranks_build_sparse(hipStream_t st, const MscLayout& L, con
 	return hipGetLastError();
 }
 
-// out[candidate][out_stride]: emd of (candidate, query q) at [q], q < n_q <= out_stride; nbins <= 2^20
+// out[candidate][out_stride]: emd of (candidate, query q) at [q], q < n_q <= out_stride; nbins <= 2^20. run_if: null, or a device word: the launch does nothing when it is 0
 hipError_t msc_launch_emd_ranks(hipStream_t st, uint64_t nbins, const uint32_t* c_ranks, uint64_t c_pitch, const uint32_t* c_n, const uint32_t* cand_slots, uint64_t first,
                                 uint32_t m, const uint32_t* q_ranks, uint64_t q_pitch, const uint32_t* q_n, const uint32_t* q_slots_dev, uint32_t n_q, uint64_t* out,
-                                uint32_t out_stride) {
+                                uint32_t out_stride, const uint32_t* run_if) {
 	if (m == 0 || n_q == 0) return hipSuccess;
 	if (n_q > out_stride || nbins > (1u << 20) || c_pitch % 256 || q_pitch % 256) return hipErrorInvalidValue;
-	k_emd_ranks<<<dim3((m + kWaves * kCandPerWave - 1) / (kWaves * kCandPerWave)), dim3(64 * kWaves), 0, st>>>(c_ranks, c_pitch, c_n, cand_slots, first, m, q_ranks, q_pitch, q_n, q_slots_dev, n_q, (uint32_t)nbins, out, out_stride);
+	k_emd_ranks<<<dim3((m + kWaves * kCandPerWave - 1) / (kWaves * kCandPerWave)), dim3(64 * kWaves), 0, st>>>(c_ranks, c_pitch, c_n, cand_slots, first, m, q_ranks, q_pitch, q_n, q_slots_dev, n_q, (uint32_t)nbins, out, out_stride, run_if);
 	return hipGetLastError();
 }
 
@@ -450,9 +452,9 @@ hipError_t msc_launch_ranks16_build(hipStream_t st, uint64_t nbins, const uint32
 
 // as msc_launch_emd_ranks over the 16-bit mirrors of two sets that share one pitch (a multiple of 1 024)
 hipError_t msc_launch_emd_ranks16(hipStream_t st, uint64_t nbins, const uint16_t* c_ranks, uint64_t pitch, const uint32_t* c_n, const uint32_t* cand_slots, uint64_t first,
-                                  uint32_t m, const uint16_t* q_ranks, const uint32_t* q_n, const uint32_t* q_slots_dev, uint32_t n_q, uint64_t* out, uint32_t out_stride) {
+                                  uint32_t m, const uint16_t* q_ranks, const uint32_t* q_n, const uint32_t* q_slots_dev, uint32_t n_q, uint64_t* out, uint32_t out_stride, const uint32_t* run_if) {
 	if (m == 0 || n_q == 0) return hipSuccess;
 	if (n_q > out_stride || nbins > (1u << 20) || pitch % kRound) return hipErrorInvalidValue;
-	k_emd_ranks16<8, 8><<<dim3((m + 8 * kCand16 - 1) / (8 * kCand16)), dim3(512), 0, st>>>(c_ranks, pitch, c_n, cand_slots, first, m, q_ranks, q_n, q_slots_dev, n_q, (uint32_t)nbins, out, out_stride);
+	k_emd_ranks16<8, 8><<<dim3((m + 8 * kCand16 - 1) / (8 * kCand16)), dim3(512), 0, st>>>(c_ranks, pitch, c_n, cand_slots, first, m, q_ranks, q_n, q_slots_dev, n_q, (uint32_t)nbins, out, out_stride, run_if);
 	return hipGetLastError();
 }

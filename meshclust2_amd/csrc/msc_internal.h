@@ -147,6 +147,17 @@ struct MscEpilogueArgs {
 	// msc_score_multi --, k_pair_list_write<true, true>); kb_c_bits = the candidates' presence mirror
 	const uint8_t* kb_c_bits;
 	int32_t  div_cells;
+	// msc_score_multi's close flags without the dense rank walk (msc_emd_list.hip; k_pair_epilogue_bits_bound / _list): the two moments per slot of both
+	// sets' ranks mirrors, the list of the pairs the bounds leave open (pair index q * m_per_query + ci), its words {count, overflow}, its capacity,
+	// and the exact distances of the listed pairs
+	const uint64_t *rk_c_sum, *rk_c_dev, *rk_q_sum, *rk_q_dev;
+	uint32_t* open_list;
+	uint32_t* open_words;
+	uint32_t open_cap;
+	const uint64_t* emd_list;
+	// k_pair_epilogue_bits_screen / _open: null, or a device word -- the launch does nothing when it is 0 (queued behind the list kernels for the case
+	// that the list overflowed)
+	const uint32_t* run_if;
 };
 
 // ---------------------------------------------------------------- launchers (defined in the .hip kernel files)
@@ -216,10 +227,16 @@ hipError_t msc_launch_ranks_build_sparse(hipStream_t st, const MscLayout& L, con
                                          uint64_t pitch, uint64_t first_slot, uint64_t n_slots, int32_t* bad);
 hipError_t msc_launch_emd_ranks(hipStream_t st, uint64_t nbins, const uint32_t* c_ranks, uint64_t c_pitch, const uint32_t* c_n, const uint32_t* cand_slots, uint64_t first,
                                 uint32_t m, const uint32_t* q_ranks, uint64_t q_pitch, const uint32_t* q_n, const uint32_t* q_slots_dev, uint32_t n_q, uint64_t* out,
-                                uint32_t out_stride = 64);
+                                uint32_t out_stride = 64, const uint32_t* run_if = nullptr);
 hipError_t msc_launch_ranks16_build(hipStream_t st, uint64_t nbins, const uint32_t* ranks, uint16_t* ranks16, uint64_t pitch, uint64_t first_slot, uint64_t n_slots, int32_t* bad);
 hipError_t msc_launch_emd_ranks16(hipStream_t st, uint64_t nbins, const uint16_t* c_ranks, uint64_t pitch, const uint32_t* c_n, const uint32_t* cand_slots, uint64_t first,
-                                  uint32_t m, const uint16_t* q_ranks, const uint32_t* q_n, const uint32_t* q_slots_dev, uint32_t n_q, uint64_t* out, uint32_t out_stride);
+                                  uint32_t m, const uint16_t* q_ranks, const uint32_t* q_n, const uint32_t* q_slots_dev, uint32_t n_q, uint64_t* out, uint32_t out_stride, const uint32_t* run_if = nullptr);
+// msc_emd_list.hip: two moments per slot of the ranks mirror that bound the distance of a pair, the exact distances of a device list of pairs, and the
+// bookkeeping of that list (words = {pairs appended, overflow}; totals = {pairs walked, blocks that overflowed} of a call)
+hipError_t msc_launch_rank_moments(hipStream_t st, uint64_t nbins, const uint32_t* ranks, uint64_t pitch, uint64_t first_slot, uint64_t n_slots, uint64_t* rk_sum, uint64_t* rk_dev);
+hipError_t msc_launch_emd_ranks_list(hipStream_t st, bool u16, const void* c_ranks, const void* q_ranks, uint64_t pitch, const uint32_t* cand_slots, uint64_t first, uint32_t m_per_query,
+                                     const uint32_t* q_slots_dev, const uint32_t* list, const uint32_t* words, uint32_t cap, uint64_t* emd_list, int num_cus);
+hipError_t msc_launch_emd_list_close(hipStream_t st, uint32_t* words, uint32_t cap, uint64_t* totals);
 // the r04 form of that pass (msc_pair_gemm.hip): presence-bit mirror + lists of large bins, the queries' side of a block, the product
 uint64_t msc_kb_bytes(const MscLayout& L, uint64_t capacity);
 hipError_t msc_launch_kb_build(hipStream_t st, const MscLayout& L, int dtype, const uint8_t* bins, uint8_t* kb, uint64_t first_slot, uint64_t n_slots, void* mb,
@@ -267,6 +284,8 @@ hipError_t msc_launch_pair_gemm_queries(hipStream_t st, uint64_t nbins, const ui
 hipError_t msc_launch_pair_gemm(hipStream_t st, uint64_t nbins, const uint8_t* cand_kb, const uint32_t* cand_slots, uint64_t first, uint32_t m, uint32_t qn,
                                 uint32_t k_slices, const uint32_t* hot_ptr, const void* hot, int32_t* out_min, int32_t* out_diff, const uint8_t* anib);
 hipError_t msc_launch_epilogue(hipStream_t st, const MscEpilogueArgs& a);
+hipError_t msc_launch_epilogue_bound(hipStream_t st, const MscEpilogueArgs& a);
+hipError_t msc_launch_epilogue_list(hipStream_t st, const MscEpilogueArgs& a, int num_cus);
 hipError_t msc_launch_close_counts(hipStream_t st, const uint8_t* flags, uint32_t n_q, uint32_t m, uint64_t* counts);
 // the list of close pairs of msc_search_pairs (pair_features.hip): records of (query, tile of candidates), counted, scanned, written
 uint32_t msc_pair_list_tiles(uint32_t mc);

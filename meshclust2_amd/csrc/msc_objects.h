@@ -99,6 +99,12 @@ struct msc_ctx {
 	uint64_t close_counts_n = 0;           // queries the counts on file cover (0: the last call kept none)
 	DevBuf qslots_all;                     // msc_score_multi: the query slots of a whole call whose blocks are queued
 	DevBuf emd_out, rk_bad;                // msc_emd_ranks.hip: the distances of a chunk, the build's error word
+	// msc_emd_list.hip: the pairs of a block whose close flag the bounds of the distance leave open, their exact distances, and the words
+	// {count, overflow} (uint32) + {pairs walked, blocks that overflowed} (uint64, the call's totals) of that list
+	DevBuf open_list, emd_list, open_words;
+	bool emd_bounds = true;                // msc_set_emd_bounds / MSC_NO_EMD_BOUNDS: close flags from bounds of the distance, rank walk for the open pairs only
+	uint64_t walk_listed = 0, walk_dense = 0, walk_blocks = 0;          // msc_last_emd_walk: the last msc_score_multi call
+	uint64_t walk_bound_blocks = 0;        // ... its blocks that took the bound pass (their overflows are on the device until the call ends)
 	msc_hist_set* shard_gather = nullptr;
 	// MSC_PROFILE_CALLS: host wall clock of the 1 x M scoring calls, split into preparing + queueing the slot list, issuing the
 	// launches, and waiting for the stream (printed by msc_destroy)
@@ -164,6 +170,7 @@ struct msc_hist_set {
 	// rk_stale: the slots written since
 	mutable uint32_t* ranks = nullptr;
 	mutable uint32_t* rk_n = nullptr;
+	mutable uint64_t *rk_sum = nullptr, *rk_dev = nullptr;          // two moments per slot of that mirror (msc_emd_list.hip): one allocation, [capacity] each; null: none to be had
 	mutable uint64_t rk_pitch = 0;
 	mutable StaleRange rk_stale;
 	mutable bool ranks_unavailable = false;
@@ -214,6 +221,7 @@ struct msc_model {
 	int k = 0;
 	MscDevModel h;
 	MscDevModel* d = nullptr;
+	mutable bool emd_decides = false;          // more than half the blocks of a msc_score_multi call overflowed the list of open pairs: later calls skip the bound pass (msc_emd_list.hip)
 };
 
 

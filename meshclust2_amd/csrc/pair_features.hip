@@ -820,6 +820,7 @@ struct PairTotals {
 	uint64_t manh, dot, emd;
 	double jd, js;
 	double markov_ab, markov_aa, markov_bb, rre;      // 4-bin group statistics (a = first argument of the reference call, b = second)
+	float emd_half;      // screen_close<true> only: emd then holds L + U of the bounds L <= emd <= U (msc_emd_list.hip), and this (U - L) / 2
 };
 
 struct Side {
@@ -1006,6 +1007,7 @@ __device__ void epilogue_eval(const MscEpilogueArgs& a, uint32_t c, uint32_t ci,
 // in FP64 as before, so the flags are those of the FP64 path, pair for pair (tests/test_gpu_qxm_direct.py compares them).
 constexpr float kScreenEps = 9.5367431640625e-07f;      // 2^-20
 
+template <bool kEmdBound = false>
 __device__ __forceinline__ float screen_raw(uint64_t flag, const PairTotals& t, const Side& a, const Side& b, uint64_t nbins, int dtype) {
 	const float N = (float)nbins;
 	switch (flag) {
@@ -1025,6 +1027,7 @@ __device__ __forceinline__ float screen_raw(uint64_t flag, const PairTotals& t, 
 	case MSC_FEAT_INTERSECTION:
 		return (float)(2 * ((a.sum + b.sum - t.manh) >> 1)) * __builtin_amdgcn_rcpf((float)(a.mag + b.mag));
 	case MSC_FEAT_EMD:
+		if constexpr (kEmdBound) return 0.5f * (float)t.emd;          // the midpoint of [L, U]
 		return (float)t.emd;
 	case MSC_FEAT_LENGTHD:
 		return (float)(a.len > b.len ? a.len - b.len : b.len - a.len);
@@ -1049,12 +1052,17 @@ __device__ __forceinline__ float screen_raw(uint64_t flag, const PairTotals& t, 
 // -> 1 close, 0 not close, -1 undecided. a / b = first / second argument of the reference call. Combo by combo, each one's one or two
 // normalised statistics formed on the spot (no array of them: indexed by a model's run-time positions it becomes chains of selects --
 // 350 v_cndmask in the first form of this function, more than its arithmetic; a statistic two combos share is formed twice).
+// kEmdBound (k_pair_epilogue_bits_bound): the earth mover's distance is known as an interval -- the statistic is taken at its midpoint and the
+// half-width, with one kScreenEps term for the conversions of the two, joins the bound of its error; the rest of the arithmetic is the same.
+template <bool kEmdBound = false>
 __device__ __forceinline__ int screen_close(const MscDevModel& md, const PairTotals& t, const Side& a, const Side& b, uint64_t nbins, int dtype) {
 	if (a.len == 0 || b.len == 0) return -1;          // (length_difference throws: the FP64 path reports it)
 	auto single = [&](int i, float& v, float& dv) {          // normalised statistic i and the bound of its error
-		const float r = screen_raw(md.single_flag[i], t, a, b, nbins, dtype);
+		const float r = screen_raw<kEmdBound>(md.single_flag[i], t, a, b, nbins, dtype);
 		const float u = (r - md.s_min[i]) * md.s_inv[i];
-		const float du = (kScreenEps * (fabsf(r) + fabsf(md.s_min[i])) + 1e-30f) * fabsf(md.s_inv[i]) + kScreenEps * fabsf(u);
+		float du = (kScreenEps * (fabsf(r) + fabsf(md.s_min[i])) + 1e-30f) * fabsf(md.s_inv[i]) + kScreenEps * fabsf(u);
+		if constexpr (kEmdBound)
+			if (md.single_flag[i] == MSC_FEAT_EMD) du += (t.emd_half + kScreenEps * (t.emd_half + fabsf(r))) * fabsf(md.s_inv[i]);
 		v = md.is_sim[i] ? u : 1.f - u;
 		dv = du + kScreenEps * fabsf(v);
 	};
@@ -1412,6 +1420,7 @@ __global__ void __launch_bounds__(kBlock) k_pair_epilogue_bits(const MscEpilogue
 constexpr uint32_t kScreenOpen = 2;          // flag byte of a pair the screen left undecided, until k_pair_epilogue_bits_open has evaluated it
 template <uint32_t kScreenChunk>
 __global__ void __launch_bounds__(kBlock, 4) k_pair_epilogue_bits_screen(const MscEpilogueArgs a) {
+	if (a.run_if && *a.run_if == 0) return;          // (queued for a case that did not arise: the overflow of k_pair_epilogue_bits_bound's list)
 	const uint32_t lane = threadIdx.x & 63;
 	const uint32_t groups = (a.n_queries + 63) / 64;
 	const uint32_t chunks = (a.m_per_query + kScreenChunk - 1) / kScreenChunk;
@@ -1474,6 +1483,7 @@ __global__ void __launch_bounds__(kBlock, 4) k_pair_epilogue_bits_screen(const M
 // 256 registers finds no room on a CU that holds three workgroups of the product kernel -- queued beside it, this 20 us scan waited a
 // millisecond for one to leave; the evaluation spills, and runs for one pair in thousands)
 __global__ void __launch_bounds__(kBlock, 5) k_pair_epilogue_bits_open(const MscEpilogueArgs a) {
+	if (a.run_if && *a.run_if == 0) return;          // (as k_pair_epilogue_bits_screen)
 	const uint64_t total = (uint64_t)a.n_queries * a.m_per_query;
 	const uint64_t at = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
 	if (at >= total) return;
@@ -1503,6 +1513,114 @@ __global__ void __launch_bounds__(kBlock, 5) k_pair_epilogue_bits_open(const Msc
 		PairTotals t{0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 		bits_pair_totals(a, ci, cmb, c_n, q, q_slot, min_e, diff_e, emd, cand, qry, t);
 		epilogue_eval(a, q * a.m_per_query + ci, ci, q, cand, qry, a.min_len, a.max_len, t);
+	}
+}
+
+// k_pair_epilogue_bits_screen WITHOUT the distances of the dense rank walk: the earth mover's distance of a pair enters as the interval
+// [L, U] = [| rk_sum_c - rk_sum_q |, rk_dev_c + rk_dev_q] of msc_emd_list.hip (the candidate's two moments wave-uniform through the scalar
+// cache, the query's fetched once per chunk beside its scalar record), and screen_close<true> carries its half-width into the bound. A pair
+// that stays undecided gets the byte kScreenOpen and its index q * m_per_query + ci goes onto open_list: a wave ballots its lanes and ONE
+// lane adds the wave's count to open_words[0]; an append past open_cap sets open_words[1] and writes nothing -- the caller has the dense
+// walk and k_pair_epilogue_bits_screen / _open queued behind the list kernels for that case.
+template <uint32_t kScreenChunk>
+__global__ void __launch_bounds__(kBlock, 4) k_pair_epilogue_bits_bound(const MscEpilogueArgs a) {
+	const uint32_t lane = threadIdx.x & 63;
+	const uint32_t groups = (a.n_queries + 63) / 64;
+	const uint32_t chunks = (a.m_per_query + kScreenChunk - 1) / kScreenChunk;
+	const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
+	if (w >= chunks * groups) return;
+	const uint32_t c0 = (w / groups) * kScreenChunk, q = (w % groups) * 64 + lane;
+	const uint32_t nc = a.m_per_query - c0 < kScreenChunk ? a.m_per_query - c0 : kScreenChunk;
+	const bool live = q < a.n_queries;
+	const uint32_t qq = live ? q : 0;
+	const uint32_t q_slot = a.q_slots[qq];
+	const MscSlotScalars* qs = reinterpret_cast<const MscSlotScalars*>(a.qset_scalars + (uint64_t)q_slot * a.q_scalar_stride);
+	const Side qry{qs->mag, qs->length, qs->sum, qs->sum_sq};
+	const uint64_t q_sum = a.rk_q_sum[q_slot], q_dev = a.rk_q_dev[q_slot];
+	const uint32_t ns = a.kb_slices;
+	uint32_t fl[4] = {0, 0, 0, 0};
+	auto totals_of = [&](uint32_t ci, int64_t min_e, int64_t diff_e, Side& cand, PairTotals& t) {
+		const uint32_t slot_rel = a.cand_slots ? a.cand_slots[ci] : ci;
+		const uint64_t slot = a.cand_slots ? (uint64_t)slot_rel : a.kb_first + ci;
+		const uint2* cmb = reinterpret_cast<const uint2*>(a.kb_c_mb) + slot * a.kb_c_pitch;
+		const uint32_t c_n = a.kb_c_mb_n[slot] < a.kb_c_pitch ? a.kb_c_mb_n[slot] : a.kb_c_pitch;
+		const MscSlotScalars* cs = reinterpret_cast<const MscSlotScalars*>(a.cand_scalars + (uint64_t)slot_rel * a.cand_scalar_stride);
+		cand = Side{cs->mag, cs->length, cs->sum, cs->sum_sq};
+		const uint64_t c_sum = a.rk_c_sum[slot], c_dev = a.rk_c_dev[slot];
+		const uint64_t lo = c_sum > q_sum ? c_sum - q_sum : q_sum - c_sum, hi = c_dev + q_dev;
+		bits_pair_totals(a, ci, cmb, c_n, qq, q_slot, min_e, diff_e, lo + hi, cand, qry, t);
+		t.emd_half = 0.5f * (float)(hi - lo);
+	};
+	auto sums_of = [&](uint32_t ci, int64_t& min_e, int64_t& diff_e) {
+		int64_t v = a.kb_min[(uint64_t)ci * a.kb_qn + qq];
+		for (uint32_t s_ = 1; s_ < ns; s_++) v += a.kb_min[((uint64_t)s_ * a.m_per_query + ci) * a.kb_qn + qq];
+		min_e = v;
+		diff_e = a.kb_diff ? a.kb_diff[(uint64_t)ci * a.kb_qn + qq] : 0;
+	};
+#pragma unroll 1
+	for (uint32_t j0 = 0; j0 < nc; j0 += 4) {
+		int64_t min4[4], diff4[4];          // four candidates' loads in flight together
+#pragma unroll
+		for (uint32_t j = 0; j < 4; j++) sums_of(c0 + (j0 + j < nc ? j0 + j : nc - 1), min4[j], diff4[j]);
+#pragma unroll
+		for (uint32_t j = 0; j < 4; j++) {
+			if (j0 + j >= nc) break;
+			Side cand;
+			PairTotals t{0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.f};
+			totals_of(c0 + j0 + j, min4[j], diff4[j], cand, t);
+			const int verdict = a.order == MSC_ORDER_CAND_FIRST ? screen_close<true>(*a.model, t, cand, qry, a.nbins, a.dtype) : screen_close<true>(*a.model, t, qry, cand, a.nbins, a.dtype);
+			fl[(j0 + j) >> 2] |= (uint32_t)(verdict < 0 ? kScreenOpen : verdict) << (8 * ((j0 + j) & 3));
+			__builtin_amdgcn_sched_barrier(0);          // (one candidate's evaluation at a time, as in k_pair_epilogue_bits_screen)
+		}
+	}
+	// the open pairs of the wave onto the list (the whole wave is here: nothing above returns for a single lane)
+	// (once the overflow word is up the block's flags come from the dense walk: no more appends, which would only queue on the counter --
+	// half a block's pairs appending took 9 ms per block against 0.3 ms for the rest of the kernel)
+	const bool some = live && ((fl[0] | fl[1] | fl[2] | fl[3]) & 0x02020202u);
+	if (__ballot(some) && !__builtin_nontemporal_load(a.open_words + 1)) {
+		for (uint32_t j = 0; j < nc; j++) {
+			const bool open = live && ((fl[j >> 2] >> (8 * (j & 3))) & 0xffu) == kScreenOpen;
+			const uint64_t mask = __ballot(open);
+			if (!mask) continue;
+			const uint32_t leader = (uint32_t)__ffsll((unsigned long long)mask) - 1;
+			uint32_t at = 0;
+			if (lane == leader) at = atomicAdd(a.open_words, (uint32_t)__popcll(mask));
+			at = __shfl(at, leader, 64) + (uint32_t)__popcll(mask & ((1ull << lane) - 1));
+			if (open) {
+				if (at < a.open_cap) a.open_list[at] = q * a.m_per_query + c0 + j;
+				else a.open_words[1] = 1;
+			}
+		}
+	}
+	if (!live) return;
+	uint8_t* row = a.close_soa + (uint64_t)q * a.m_per_query + c0;
+	if (kScreenChunk == 4 && nc == kScreenChunk && ((uintptr_t)row & 3) == 0) *reinterpret_cast<uint32_t*>(row) = fl[0];
+	else for (uint32_t j = 0; j < nc; j++) row[j] = (uint8_t)((fl[j >> 2] >> (8 * (j & 3))) & 0xffu);
+}
+
+// Behind k_pair_epilogue_bits_bound and k_emd_ranks_list (msc_emd_list.hip): one thread per listed pair forms the pair's integer reductions as
+// k_pair_epilogue_bits_open does, takes the exact distance from emd_list and evaluates in FP64 (epilogue_eval writes the flag). Nothing to do
+// when the list overflowed. (96 registers, for the reason given at k_pair_epilogue_bits_open.)
+__global__ void __launch_bounds__(kBlock, 5) k_pair_epilogue_bits_list(const MscEpilogueArgs a) {
+	if (a.open_words[1]) return;
+	const uint32_t n = a.open_words[0] < a.open_cap ? a.open_words[0] : a.open_cap;
+	const uint32_t ns = a.kb_slices;
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+		const uint32_t idx = a.open_list[i], q = idx / a.m_per_query, ci = idx % a.m_per_query;
+		const uint32_t q_slot = a.q_slots[q];
+		const uint32_t slot_rel = a.cand_slots ? a.cand_slots[ci] : ci;
+		const uint64_t slot = a.cand_slots ? (uint64_t)slot_rel : a.kb_first + ci;
+		const uint2* cmb = reinterpret_cast<const uint2*>(a.kb_c_mb) + slot * a.kb_c_pitch;
+		const uint32_t c_n = a.kb_c_mb_n[slot] < a.kb_c_pitch ? a.kb_c_mb_n[slot] : a.kb_c_pitch;
+		const MscSlotScalars* cs = reinterpret_cast<const MscSlotScalars*>(a.cand_scalars + (uint64_t)slot_rel * a.cand_scalar_stride);
+		const MscSlotScalars* qs = reinterpret_cast<const MscSlotScalars*>(a.qset_scalars + (uint64_t)q_slot * a.q_scalar_stride);
+		const Side cand{cs->mag, cs->length, cs->sum, cs->sum_sq}, qry{qs->mag, qs->length, qs->sum, qs->sum_sq};
+		int64_t min_e = 0;
+		for (uint32_t s_ = 0; s_ < ns; s_++) min_e += a.kb_min[((uint64_t)s_ * a.m_per_query + ci) * a.kb_qn + q];
+		const int64_t diff_e = a.kb_diff ? a.kb_diff[(uint64_t)ci * a.kb_qn + q] : 0;
+		PairTotals t{0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+		bits_pair_totals(a, ci, cmb, c_n, q, q_slot, min_e, diff_e, a.emd_list[i], cand, qry, t);
+		epilogue_eval(a, idx, ci, q, cand, qry, a.min_len, a.max_len, t);
 	}
 }
 
@@ -2292,6 +2410,29 @@ hipError_t msc_launch_epilogue(hipStream_t st, const MscEpilogueArgs& a) {
 		const unsigned blocks = (a.m + kBlock - 1) / kBlock;
 		hipLaunchKernelGGL(k_pair_epilogue_thread, dim3(blocks), dim3(kBlock), 0, st, a);
 	}
+	return hipGetLastError();
+}
+
+// The close flags of a block of the matrix-core pass from bounds of the earth mover's distance (k_pair_epilogue_bits_bound): what msc_launch_epilogue's
+// screen takes, and the moments, the list and its words instead of emd_ranks.
+hipError_t msc_launch_epilogue_bound(hipStream_t st, const MscEpilogueArgs& a) {
+	if (a.m == 0) return hipSuccess;
+	if (!a.kb_min || a.n_queries < 2 || a.n_queries > a.kb_qn || !a.kb_c_mb || !a.kb_q_mb || !a.kb_qT || !a.model || !a.close_soa || a.sum_soa || a.csum_soa || a.raw_out || a.singles_out ||
+	    a.combos_out || a.pair_out || a.use_window || a.div_direct || a.grp_pairs || a.sparse_base || a.div_cells || !a.rk_c_sum || !a.rk_c_dev || !a.rk_q_sum || !a.rk_q_dev || !a.open_words ||
+	    (a.open_cap && !a.open_list) || (uint64_t)a.n_queries * a.m_per_query > 0xffffffffull)
+		return hipErrorInvalidValue;
+	constexpr uint32_t chunk = 4;          // (as the screen of msc_launch_epilogue)
+	const uint64_t cw = (uint64_t)((a.m_per_query + chunk - 1) / chunk) * ((a.n_queries + 63) / 64);
+	hipLaunchKernelGGL(k_pair_epilogue_bits_bound<chunk>, dim3((unsigned)((cw + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, st, a);
+	return hipGetLastError();
+}
+
+// ... and the FP64 evaluation of the listed pairs with their exact distances (k_pair_epilogue_bits_list); a fixed grid, the count is on the device
+hipError_t msc_launch_epilogue_list(hipStream_t st, const MscEpilogueArgs& a, int num_cus) {
+	if (a.m == 0 || a.open_cap == 0) return hipSuccess;
+	if (!a.kb_min || !a.open_list || !a.open_words || !a.emd_list || !a.close_soa) return hipErrorInvalidValue;
+	const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)a.open_cap + kBlock - 1) / kBlock, (uint64_t)num_cus * 4);
+	hipLaunchKernelGGL(k_pair_epilogue_bits_list, dim3(grid), dim3(kBlock), 0, st, a);
 	return hipGetLastError();
 }
 

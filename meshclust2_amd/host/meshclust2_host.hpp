@@ -43,6 +43,7 @@ public:
 	void set_pairs_div_cells(bool on) { check(msc_set_pairs_div_cells(h_, on ? 1 : 0)); }
 	// score_multi with a divergence statistic on the matrix-core route, no merge pass per query (integer statistics bit-equal, the two sums to 1e-9)
 	void set_multi_div_cells(bool on) { check(msc_set_multi_div_cells(h_, on ? 1 : 0)); }
+	void set_emd_bounds(bool on) { check(msc_set_emd_bounds(h_, on ? 1 : 0)); }
 	// Q x M calls over two sparse sets on the matrix-core route, mirrors built from their lists (identical results)
 	void set_sparse_matrix_pass(bool on) { check(msc_set_sparse_matrix_pass(h_, on ? 1 : 0)); }
 	void check(int rc) const { if (rc != MSC_OK) throw Error(rc, msc_last_error(h_)); }
