@@ -172,6 +172,18 @@ int         msc_set_emd_bounds(msc_ctx* ctx, int on);
  * blocks = such blocks, dense_blocks = those whose every pair had its rank lists walked (switch off, a remembered model, sets of
  * different list pitch, an overflowed list), listed_pairs = pairs walked one by one from the lists of the others. Any pointer may be null. */
 int         msc_last_emd_walk(const msc_ctx* ctx, uint64_t* listed_pairs, uint64_t* dense_blocks, uint64_t* blocks);
+/* The blocks the switch above is about multiply presence bits of every pair of a block on the matrix cores to count its shared k-mers, which
+ * all but the related pairs' flags do not need exactly. fold = 8, 16 or 32 (default 16; 0 at start with MSC_NO_FOLD in the environment): the
+ * product of such a block runs over bits folded fold-to-1 -- an upper bound of the shared k-mers at 1/fold of the work --, the screen decides
+ * from intervals, and the pairs it leaves open get their exact counts one by one. A block whose list of open pairs overflows is scored
+ * again by the true product once the call's blocks are through; a model most of whose blocks do so is remembered. Sets whose histograms are too small to fold (k = 5) and
+ * every other call keep their route. The flags are those of fold = 0, pair for pair. Any other value of fold: MSC_ERR_INVALID_ARG. */
+int         msc_set_fold_screen(msc_ctx* ctx, int fold);
+/* What the last msc_score_multi call did about it: the fold used (0: none), the blocks whose product was folded, and those of them that fell
+ * back to the true product. Any pointer may be null. */
+int         msc_last_fold_screen(const msc_ctx* ctx, uint64_t* fold, uint64_t* folded_blocks, uint64_t* fell_back);
+/* The fold map: the folded bin of `bin` of a histogram of nbins = 4^k bins, bin mod (nbins / fold); fold a power of two (0, 1: bin). */
+uint64_t    msc_fold_bin(uint64_t bin, uint64_t nbins, uint32_t fold);
 /* A Q x M call over two SPARSE sets (msc_score_multi, msc_search_pairs) runs one 1 x M pass per query over the lists: the matrix-core
  * route reads a presence bit per bin, the lists of large bins and the sorted ranks of a set -- mirrors only dense sets used to carry.
  * on = 1 lets two sparse sets of equal k and dtype take that route as well, under its usual conditions (8/16/32-bit bins of the narrow

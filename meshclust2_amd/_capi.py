@@ -58,6 +58,9 @@ PROTOTYPES = {
     "msc_set_multi_div_cells": (_int, [_vp, _int]),
     "msc_set_emd_bounds": (_int, [_vp, _int]),
     "msc_last_emd_walk": (_int, [_vp, _pu64, _pu64, _pu64]),
+    "msc_set_fold_screen": (_int, [_vp, _int]),
+    "msc_last_fold_screen": (_int, [_vp, _pu64, _pu64, _pu64]),
+    "msc_fold_bin": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint32]),
     "msc_set_sparse_matrix_pass": (_int, [_vp, _int]),
     "msc_last_kernel_launches": (_int, [_vp]),
     "msc_last_kernel_info": (_int, [_vp, C.c_char_p, C.c_size_t, C.POINTER(_int)]),

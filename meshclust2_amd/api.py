@@ -90,6 +90,19 @@ class Context:
         self.check(self.lib.msc_last_emd_walk(self.h, C.byref(v[0]), C.byref(v[1]), C.byref(v[2])))
         return tuple(int(x.value) for x in v)
 
+    def set_fold_screen(self, fold):
+        """score_multi's close-flag blocks with an earth_movers_distance model: the matrix product over presence bits folded `fold`-to-1
+        (8, 16 -- the default -- or 32) with the screen deciding from intervals and exact counts for the pairs it leaves open, or the true
+        product (0); the same flags"""
+        self.check(self.lib.msc_set_fold_screen(self.h, int(fold)))
+
+    def last_fold_screen(self):
+        """(fold, folded_blocks, fell_back) of the last score_multi call: the fold used (0: none), the blocks whose product was folded and
+        those of them whose list of open pairs overflowed and were scored again with the true product"""
+        v = [C.c_uint64(0) for _ in range(3)]
+        self.check(self.lib.msc_last_fold_screen(self.h, C.byref(v[0]), C.byref(v[1]), C.byref(v[2])))
+        return tuple(int(x.value) for x in v)
+
     def set_sparse_matrix_pass(self, on):
         """score_multi / search_pairs over two sparse sets: the matrix-core route over mirrors built from the lists (on) or one 1 x M pass
         per query (default); identical results"""
@@ -417,6 +430,12 @@ def pair_features_raw(ctx, cands, cand_slots, qset, q_slot, feat_mask=FEAT_FAST,
     out = np.zeros((m, nf))
     ctx.check(ctx.lib.msc_pair_features_raw(ctx.h, cands.h, _ptr(sl), m, qset.h, q_slot, order, feat_mask, _ptr(out)))
     return out
+
+
+def fold_bin(bin, nbins, fold):
+    """msc_fold_bin: the folded bin of `bin` of a histogram of nbins = 4^k bins, bin mod (nbins / fold) (needs no device)"""
+    from . import _capi
+    return int(_capi.load_library().msc_fold_bin(int(bin), int(nbins), int(fold)))
 
 
 def pinned_array(ctx, shape, dtype):

@@ -21,6 +21,7 @@
 
 #include "msc_internal.h"
 
+#include "msc_fold.h"
 #include "msc_objects.h"
 #include "msc_api_private.h"
 
@@ -115,6 +116,7 @@ extern "C" int msc_create(int device, msc_ctx** out) {
 	ctx->mirror_pass = getenv("MSC_NO_MIRROR_1XM") == nullptr;
 	ctx->block_pipe = getenv("MSC_GEMM_NO_PIPE") == nullptr;
 	ctx->emd_bounds = getenv("MSC_NO_EMD_BOUNDS") == nullptr;
+	ctx->fold_screen = getenv("MSC_NO_FOLD") == nullptr ? 16 : 0;
 	*out = ctx;
 	return MSC_OK;
 }
@@ -152,7 +154,7 @@ extern "C" void msc_destroy(msc_ctx* ctx) {
 	                  &ctx->seq_meta, &ctx->qslots_all, &ctx->shard_payload, &ctx->shard_hdrs, &ctx->rk_q, &ctx->rk_acc, &ctx->rk_counters,
 	                  &ctx->rk_tables, &ctx->rk_items, &ctx->rk_big, &ctx->pl_idx, &ctx->pl_sim, &ctx->pl_stage_idx, &ctx->pl_stage_sim, &ctx->pl_flags,
 	                  &ctx->pl_counts, &ctx->pl_offsets, &ctx->pl_seg, &ctx->pl_dst, &ctx->pl_qslots, &ctx->pl_win, &ctx->pl_qcount, &ctx->pl_words,
-	                  &ctx->emd_out, &ctx->open_list, &ctx->emd_list, &ctx->open_words, &ctx->close_counts, &ctx->rk_bad, &ctx->prof_nnz, &ctx->segs, &ctx->pair_seg, &ctx->dist, &ctx->sp_counts,
+	                  &ctx->emd_out, &ctx->open_list, &ctx->emd_list, &ctx->open_words, &ctx->fold_over, &ctx->close_counts, &ctx->rk_bad, &ctx->prof_nnz, &ctx->segs, &ctx->pair_seg, &ctx->dist, &ctx->sp_counts,
 	                  &ctx->sp_cumbase, &ctx->sp_acc, &ctx->sp_chunk_off, &ctx->sp_chunk_cum, &ctx->sp_partials, &ctx->grp_pairs, &ctx->grp_self,
 	                  &ctx->tile_scratch, &ctx->reduce_parts, &ctx->sp_touched, &ctx->sp_acc_batch, &ctx->ps_idx, &ctx->ps_sim, &ctx->ps_m_idx, &ctx->ps_m_sim,
 	                  &ctx->pl_strand, &ctx->ps_off, &ctx->ps_only, &ctx->ps_counts};
@@ -194,6 +196,22 @@ extern "C" int msc_set_emd_bounds(msc_ctx* ctx, int on) {
 	ctx->emd_bounds = on != 0;
 	return MSC_OK;
 }
+
+extern "C" int msc_set_fold_screen(msc_ctx* ctx, int fold) {
+	if (!ctx || (fold != 0 && fold != 8 && fold != 16 && fold != 32)) return MSC_ERR_INVALID_ARG;
+	ctx->fold_screen = (uint32_t)fold;
+	return MSC_OK;
+}
+
+extern "C" int msc_last_fold_screen(const msc_ctx* ctx, uint64_t* fold, uint64_t* folded_blocks, uint64_t* fell_back) {
+	if (!ctx) return MSC_ERR_INVALID_ARG;
+	if (fold) *fold = ctx->fold_used;
+	if (folded_blocks) *folded_blocks = ctx->fold_blocks;
+	if (fell_back) *fell_back = ctx->fold_fell_back;
+	return MSC_OK;
+}
+
+extern "C" uint64_t msc_fold_bin(uint64_t bin, uint64_t nbins, uint32_t fold) { return msc_fold_bin_of(bin, nbins, fold); }
 
 extern "C" int msc_last_emd_walk(const msc_ctx* ctx, uint64_t* listed_pairs, uint64_t* dense_blocks, uint64_t* blocks) {
 	if (!ctx) return MSC_ERR_INVALID_ARG;
@@ -470,6 +488,8 @@ extern "C" void msc_hist_set_destroy(msc_hist_set* s) {
 	if (s->kb) (void)hipFree(s->kb);
 	if (s->mb) (void)hipFree(s->mb);
 	if (s->mb_n) (void)hipFree(s->mb_n);
+	if (s->kbf) (void)hipFree(s->kbf);
+	if (s->kbf_x) (void)hipFree(s->kbf_x);
 	if (s->ranks) (void)hipFree(s->ranks);
 	if (s->ranks16) (void)hipFree(s->ranks16);
 	if (s->rk_n) (void)hipFree(s->rk_n);

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "msc_internal.h"
+#include "msc_fold.h"
 
 #include "msc_objects.h"
 #include "msc_api_private.h"
@@ -36,14 +37,16 @@ static int ensure_digest(msc_ctx* ctx, const msc_hist_set* set) {
 // Q x M pass. A dense set's come from its bins, a sparse set's from its entry lists (the same bytes for the same sequences; every slot of
 // the stale range is rebuilt, a slot without a list as an all-zero image). MSC_OK with set->kb == nullptr when it cannot be had (no
 // memory): the older routes then run.
-int ensure_kb(msc_ctx* ctx, const msc_hist_set* set) {
+int ensure_kb(msc_ctx* ctx, const msc_hist_set* set, bool want_fold) {
 	if (set->kb_unavailable || set->dtype == 64) return MSC_OK;
 	auto give_up = [&] {
 		(void)hipGetLastError();
 		if (set->kb) (void)hipFree(set->kb);
 		if (set->mb) (void)hipFree(set->mb);
 		if (set->mb_n) (void)hipFree(set->mb_n);
-		set->kb = nullptr; set->mb = nullptr; set->mb_n = nullptr;
+		if (set->kbf) (void)hipFree(set->kbf);
+		if (set->kbf_x) (void)hipFree(set->kbf_x);
+		set->kb = nullptr; set->mb = nullptr; set->mb_n = nullptr; set->kbf = nullptr; set->kbf_x = nullptr; set->kbf_fold = 0;
 		set->kb_unavailable = true;
 		return MSC_OK;
 	};
@@ -80,6 +83,7 @@ int ensure_kb(msc_ctx* ctx, const msc_hist_set* set) {
 		if (hi > lo) HIP_TRY(ctx, hipMemcpyAsync(set->mb_n_host.data() + lo, set->mb_n + lo, (hi - lo) * 4, hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 		if (flags[0]) set->kb_has_zero = true;
+		if (set->kbf) set->kbf_stale.add(lo, hi > lo ? hi - lo : 0);          // (invalidated wherever kb is)
 		set->kb_stale.clear();
 		if ((uint32_t)flags[1] > set->mb_pitch) {
 			const uint32_t pitch = ((uint32_t)flags[1] + 15) / 16 * 16;
@@ -91,6 +95,31 @@ int ensure_kb(msc_ctx* ctx, const msc_hist_set* set) {
 			set->mb_pitch = pitch;
 			set->kb_stale.all(set->capacity);
 		}
+	}
+	// the folded mirror beside it (msc_fold.h), for the fold the context asks for: set-up work on a resident set, done once and refreshed with kb.
+	// Without memory for it the set is simply not folded. (want_fold: the call is one the folded screen serves -- msc_search_pairs builds none.)
+	if (!want_fold || !set->kb) return MSC_OK;
+	const uint32_t fold = msc_fold_fits(set->L, ctx->fold_screen) ? ctx->fold_screen : 0;
+	if (set->kbf && set->kbf_fold != fold) {
+		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+		(void)hipFree(set->kbf); (void)hipFree(set->kbf_x);
+		set->kbf = nullptr; set->kbf_x = nullptr; set->kbf_fold = 0;
+	}
+	if (fold && !set->kbf) {
+		MscLayout Lf = set->L;
+		Lf.padded_bins = Lf.nbins = set->L.nbins / fold;
+		void *p = nullptr, *px = nullptr;
+		if (hipMalloc(&p, msc_kb_bytes(Lf, set->capacity)) != hipSuccess || hipMalloc(&px, (set->capacity + 31) / 32 * 32 * sizeof(uint32_t)) != hipSuccess) {
+			(void)hipGetLastError();
+			if (p) (void)hipFree(p);
+			return MSC_OK;
+		}
+		set->kbf = (uint8_t*)p; set->kbf_x = (uint32_t*)px; set->kbf_fold = fold;
+		set->kbf_stale.all(set->capacity);
+	}
+	if (set->kbf && set->kbf_stale.any()) {
+		HIP_TRY(ctx, msc_launch_kb_fold(ctx->stream, set->L.nbins, fold, set->kb, set->kbf, set->kbf_x, set->kbf_stale.lo, set->kbf_stale.hi - set->kbf_stale.lo));
+		set->kbf_stale.clear();
 	}
 	return MSC_OK;
 }
@@ -212,6 +241,7 @@ MscCandChunks matrix_chunks(const msc_ctx* ctx, uint64_t nbins, uint64_t m, uint
 	return msc_cand_chunks(m, std::min(cap, limit));
 }
 
+// (a folded block passes the TRUE bin count -- its transposed planes are the true ones -- and the larger of the two slice counts: room for either form)
 int ensure_side(msc_ctx* ctx, BlockPipe::Side& s, uint64_t nbins, uint32_t rows, uint32_t slices, uint64_t chunk, uint64_t n_hot, HotList* hot) {
 	const uint64_t nsteps = nbins / 128;
 	int r;
@@ -254,15 +284,20 @@ void fill_pair_args(MscEpilogueArgs& ea, msc_ctx* ctx, const msc_hist_set* cands
 	ea.error_word = (int32_t*)ctx->err_word.p;
 }
 
-void name_matrix_kernel(msc_ctx* ctx, uint32_t rows, bool emd, bool cells, bool from_lists) {
-	snprintf(ctx->last_kernel_buf, sizeof ctx->last_kernel_buf, "%s<%u query rows, one matrix product per tile of presence bits%s%s%s>", msc_pair_gemm_kernel_name(), rows,
-	         emd ? ", emd by ranks" : ", no emd", cells ? ", divergence sums from cells" : "", from_lists ? ", mirrors from lists" : "");
+void name_matrix_kernel(msc_ctx* ctx, uint32_t rows, bool emd, bool cells, bool from_lists, uint32_t fold) {
+	char folded[24] = "";
+	if (fold) snprintf(folded, sizeof folded, ", folded x %u", fold);
+	snprintf(ctx->last_kernel_buf, sizeof ctx->last_kernel_buf, "%s<%u query rows, one matrix product per tile of presence bits%s%s%s%s>", msc_pair_gemm_kernel_name(), rows,
+	         emd ? ", emd by ranks" : ", no emd", cells ? ", divergence sums from cells" : "", from_lists ? ", mirrors from lists" : "", folded);
 	ctx->last_kernel = ctx->last_kernel_buf;
 }
 
 namespace {
 
 // ---- msc_score_multi: the call, its blocks, a route per block
+// ctx->open_words: {count, overflow} of a block's list of open pairs, then the call's three totals (pairs walked, blocks that overflowed, folded blocks
+// that fell back)
+constexpr size_t kOpenWordsBytes = 2 * sizeof(uint32_t) + 3 * sizeof(uint64_t);
 enum Route { R_MATRIX, R_DIGEST, R_RING, R_TILES, R_SPARSE_QUEUED, R_PER_QUERY };
 
 // what pick_route decides for one block
@@ -312,6 +347,8 @@ struct Block {
 	uint64_t chunk = 0;                          // candidates per launch
 	hipStream_t tail = nullptr;                  // where the epilogue and the copies home run
 	bool div_pass = false;                       // divergence statistics from a merge pass per query (not from cells)
+	uint32_t idx = 0;                            // the block's place in the call's plan
+	bool no_fold = false;                        // matrix: the block ran folded and its list overflowed -- this is its second run, with the true product
 	SparseKernel spk = SPK_MP;                   // ... one merge kernel for the whole block ...
 	uint32_t dvn = 1;                            // ... and its {jd, js} records per pair
 };
@@ -720,6 +757,7 @@ int run_streamed(MultiCall& c, Block& b, const BlockRoute& rt) {
 // MSC_GEMM_NO_PREP: the queries' side on the product's stream, as in r04.) The close flags go into one of two buffers and home on the copy stream, under the next block's kernels.
 // A flags-only block whose distance comes from the ranks mirrors runs no walk beside the product: its tail is the bound screen, the walk and the FP64 evaluation of
 // the listed pairs, then the dense walk and the two older epilogue kernels predicated on the list's overflow word (msc_emd_list.hip).
+// Such a block in one chunk runs its product over bits folded F-to-1 where both sets carry the folded mirror (msc_fold.h): `fold` below.
 int run_matrix(MultiCall& c, Block& b, const BlockRoute& rt) {
 	msc_ctx* ctx = c.ctx;
 	BlockPipe& pipe = ctx->pipe;
@@ -735,6 +773,23 @@ int run_matrix(MultiCall& c, Block& b, const BlockRoute& rt) {
 	b.div_pass = c.want_div && !c.cells;
 	if ((r = ensure_block_scratch(c, b, true))) return r;
 	const uint32_t slices = msc_pair_gemm_slices(L.nbins, (uint32_t)b.chunk, rows, ctx->num_cus);
+	// only the close flags are wanted: k_pair_epilogue_bits decides them in f32 with an error bound and evaluates in FP64 only the
+	// pairs the bound leaves open -- the same flags (MSC_NO_SCREEN: FP64 for every pair)
+	static const bool no_screen = getenv("MSC_NO_SCREEN") != nullptr;
+	const bool screen = c.model && c.model->h.screen_ok && b.close && !b.sum && !b.csum && !b.raw && !c.want_div && !c.want_grp && !no_screen;
+	// ... and with the distance from the ranks mirrors of two sets of one pitch (what k_emd_ranks16 asks too), first from BOUNDS of the distance
+	// (msc_emd_list.hip): the ranks are walked only for the pairs the bounds leave open, up to 1 / 64 of the chunk's pairs -- past that share a
+	// walk per pair reads more than the dense walk. msc_set_emd_bounds(0), a model remembered for overflowing, sets without moments: today's path
+	const bool walk_counted = screen && rt.emd_ranks;
+	const bool bounds_call = walk_counted && ctx->emd_bounds && !c.model->emd_decides && cands->rk_pitch == qset->rk_pitch && cands->rk_sum && qset->rk_sum;
+	// ... and there, in one chunk, with the PRODUCT over bits folded F-to-1 (msc_fold.h): 1 / F of the matrix operations for upper
+	// bounds of P1 and P2, which the screen takes as intervals; the listed pairs get their exact counts (k_fold_exact_list). msc_set_fold_screen(0),
+	// a model remembered for overflowing the folded stage's list, sets without a folded mirror (k = 5): the true product
+	const uint32_t fold = bounds_call && !b.no_fold && b.chunk == m && n_q * m <= 0xffffffffull && n_q * m >= 64 && !c.model->fold_overflows && cands->kbf && qset->kbf &&
+	                              cands->kbf_fold == ctx->fold_screen && qset->kbf_fold == ctx->fold_screen
+	                          ? ctx->fold_screen : 0;
+	const uint64_t nbins_f = fold ? L.nbins / fold : L.nbins;
+	const uint32_t slices_f = fold ? msc_pair_gemm_slices(nbins_f, (uint32_t)b.chunk, rows, ctx->num_cus) : slices;
 	const bool piped = queued && b.chunk == m && !b.div_pass && !c.want_grp && ctx->block_pipe;
 	const int pb = piped ? (int)(pipe.next++ & 1) : 0;
 	BlockPipe::Side& s = pipe.side[pb];
@@ -749,20 +804,26 @@ int run_matrix(MultiCall& c, Block& b, const BlockRoute& rt) {
 				if (!piped) pipe.side[i].tail_busy = false;
 			}
 	HotList hot;
-	if ((r = ensure_side(ctx, s, L.nbins, rows, slices, b.chunk, rt.n_hot, &hot))) return r;
+	if ((r = ensure_side(ctx, s, L.nbins, rows, std::max(slices, slices_f), b.chunk, rt.n_hot, &hot))) return r;
 	if (prep != ctx->stream) {
 		HIP_TRY(ctx, hipStreamWaitEvent(prep, pipe.ev_call, 0));          // the call's query slots are up
 		if (s.product_busy) HIP_TRY(ctx, hipStreamWaitEvent(prep, s.ev_product, 0));      // the product that read this side is through
 	}
 	// the queries' side of the block, once for all chunks of candidates
-	HIP_TRY(ctx, msc_launch_pair_gemm_queries(prep, L.nbins, qset->kb, qset->mb, qset->mb_n, qset->mb_pitch, b.dq_slots, (uint32_t)n_q, rows, (uint8_t*)s.qT.p, rt.n_hot, s.hot.p,
-	                                          hot.ptr, hot.cursor, hot.cnt, (uint8_t*)s.anib.p));
+	if (fold) {          // the transposed planes from the true mirror (the epilogue's walk of the candidate's large bins stays exact), the tiles and the hot list folded
+		HIP_TRY(ctx, msc_launch_kb_gather(prep, L.nbins, qset->kb, b.dq_slots, (uint32_t)n_q, rows, (uint8_t*)s.qT.p, nullptr));
+		HIP_TRY(ctx, msc_launch_kb_gather(prep, nbins_f, qset->kbf, b.dq_slots, (uint32_t)n_q, rows, nullptr, (uint8_t*)s.anib.p));
+		HIP_TRY(ctx, msc_launch_hot_list(prep, L.nbins, fold, qset->mb, qset->mb_n, qset->mb_pitch, b.dq_slots, (uint32_t)n_q, rows, (uint8_t*)s.qT.p, rt.n_hot, s.hot.p, hot.ptr,
+		                                 hot.cursor, hot.cnt));
+	} else
+		HIP_TRY(ctx, msc_launch_pair_gemm_queries(prep, L.nbins, qset->kb, qset->mb, qset->mb_n, qset->mb_pitch, b.dq_slots, (uint32_t)n_q, rows, (uint8_t*)s.qT.p, rt.n_hot, s.hot.p,
+		                                          hot.ptr, hot.cursor, hot.cnt, (uint8_t*)s.anib.p));
 	if (prep != ctx->stream) {
 		HIP_TRY(ctx, hipEventRecord(s.ev_prep, prep));
 		HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.ev_prep, 0));
 	}
 	if (rt.emd_ranks && (r = ensure(ctx, ctx->emd_out, b.chunk * rows * sizeof(uint64_t)))) return r;
-	name_matrix_kernel(ctx, rows, rt.emd_ranks, c.cells, cands->sparse);
+	name_matrix_kernel(ctx, rows, rt.emd_ranks, c.cells, cands->sparse, fold);
 	ctx->last_query_tile = (int)n_q;
 	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_all0, ctx->stream));
 	for (uint64_t off = 0; off < m; off += b.chunk) {
@@ -775,26 +836,18 @@ int run_matrix(MultiCall& c, Block& b, const BlockRoute& rt) {
 		}
 		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ev_t0, ctx->stream));
 		// the whole pass over the candidates' bins: products and level products on the matrix cores (timed as the streaming kernel)
-		HIP_TRY(ctx, msc_launch_pair_gemm(ctx->stream, L.nbins, cands->kb, k.d_slots, off, k.mc, rows, slices, hot.ptr, s.hot.p, (int32_t*)s.min.p, (int32_t*)s.diff.p, (const uint8_t*)s.anib.p));
+		HIP_TRY(ctx, msc_launch_pair_gemm(ctx->stream, nbins_f, fold ? cands->kbf : cands->kb, k.d_slots, off, k.mc, rows, slices_f, hot.ptr, s.hot.p, (int32_t*)s.min.p, (int32_t*)s.diff.p,
+		                                  (const uint8_t*)s.anib.p));
 		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ev_t1, ctx->stream));
 		if (piped) { HIP_TRY(ctx, hipEventRecord(s.ev_product, ctx->stream)); s.product_busy = true; }
-		// only the close flags are wanted: k_pair_epilogue_bits decides them in f32 with an error bound and evaluates in FP64 only the
-		// pairs the bound leaves open -- the same flags (MSC_NO_SCREEN: FP64 for every pair)
-		static const bool no_screen = getenv("MSC_NO_SCREEN") != nullptr;
-		const bool screen = c.model && c.model->h.screen_ok && b.close && !b.sum && !b.csum && !b.raw && !c.want_div && !c.want_grp && !no_screen;
-		// ... and with the distance from the ranks mirrors of two sets of one pitch (what k_emd_ranks16 asks too), first from BOUNDS of the distance
-		// (msc_emd_list.hip): the ranks are walked only for the pairs the bounds leave open, up to 1 / 64 of the chunk's pairs -- past that share a
-		// walk per pair reads more than the dense walk. msc_set_emd_bounds(0), a model remembered for overflowing, sets without moments: today's path
-		const bool walk_counted = screen && rt.emd_ranks;
-		const bool bounds = walk_counted && ctx->emd_bounds && !c.model->emd_decides && cands->rk_pitch == qset->rk_pitch && cands->rk_sum && qset->rk_sum &&
-		                    n_q * (uint64_t)k.mc <= 0xffffffffull && n_q * (uint64_t)k.mc >= 64;          // (fewer than 64 pairs: a list of no entries)
+		const bool bounds = bounds_call && n_q * (uint64_t)k.mc <= 0xffffffffull && n_q * (uint64_t)k.mc >= 64;          // (fewer than 64 pairs: a list of no entries)
 		const uint32_t open_cap = bounds ? (uint32_t)(n_q * k.mc / 64) : 0;
 		uint32_t* open_words = nullptr;
-		if (walk_counted) { ctx->walk_blocks++; if (!bounds) ctx->walk_dense++; }
+		if (walk_counted && !b.no_fold) { ctx->walk_blocks++; if (!bounds) ctx->walk_dense++; }          // (no_fold: the block was counted when it ran folded)
 		if (bounds) {
 			if ((r = ensure(ctx, ctx->open_list, std::max<size_t>(1, open_cap) * sizeof(uint32_t))) || (r = ensure(ctx, ctx->emd_list, std::max<size_t>(1, open_cap) * sizeof(uint64_t)))) return r;
 			open_words = (uint32_t*)ctx->open_words.p;          // (allocated and cleared when the call began, on the product's stream: behind ev_head for a piped block)
-			ctx->walk_bound_blocks++;
+			if (!b.no_fold) ctx->walk_bound_blocks++;
 		} else if (rt.emd_ranks)
 			HIP_TRY(ctx, launch_emd_ranks(b.tail, cands, qset, k.d_slots, off, k.mc, b.dq_slots, (uint32_t)n_q, (uint64_t*)ctx->emd_out.p, rows));
 		MscEpilogueArgs ea;
@@ -819,16 +872,36 @@ int run_matrix(MultiCall& c, Block& b, const BlockRoute& rt) {
 			eb.emd_ranks = nullptr;
 			eb.rk_c_sum = cands->rk_sum; eb.rk_c_dev = cands->rk_dev; eb.rk_q_sum = qset->rk_sum; eb.rk_q_dev = qset->rk_dev;
 			eb.open_list = (uint32_t*)ctx->open_list.p; eb.open_words = open_words; eb.open_cap = open_cap; eb.emd_list = (const uint64_t*)ctx->emd_list.p;
-			HIP_TRY(ctx, msc_launch_epilogue_bound(b.tail, eb));
 			const bool u16 = cands->ranks16 && qset->ranks16;
-			HIP_TRY(ctx, msc_launch_emd_ranks_list(b.tail, u16, u16 ? (const void*)cands->ranks16 : (const void*)cands->ranks, u16 ? (const void*)qset->ranks16 : (const void*)qset->ranks,
-			                                       cands->rk_pitch, k.d_slots, off, k.mc, b.dq_slots, eb.open_list, open_words, open_cap, (uint64_t*)ctx->emd_list.p, ctx->num_cus));
-			HIP_TRY(ctx, msc_launch_epilogue_list(b.tail, eb, ctx->num_cus));
-			HIP_TRY(ctx, launch_emd_ranks(b.tail, cands, qset, k.d_slots, off, k.mc, b.dq_slots, (uint32_t)n_q, (uint64_t*)ctx->emd_out.p, rows, open_words + 1));
-			ea.run_if = open_words + 1;
+			auto list_stage = [&](const MscEpilogueArgs& e) {          // screen, walk of the listed pairs, their FP64 evaluation, on e's words
+				HIP_TRY(ctx, msc_launch_epilogue_bound(b.tail, e));
+				if (e.fold_x_c) {          // (the listed pairs of a folded stage: their exact P1 / P2 into the product's arrays first)
+					const MscFoldExact fx{cands->ranks, cands->rk_pitch, L.nbins, L.E, L.R, k.d_slots, off, k.mc, b.dq_slots, e.open_list, e.open_words, open_cap, (const uint8_t*)s.qT.p, rows,
+					                      qset->mb, qset->mb_n, qset->mb_pitch, (int32_t*)s.min.p, e.kb_slices, rt.n_hot ? (int32_t*)s.diff.p : nullptr};
+					HIP_TRY(ctx, msc_launch_fold_exact_list(b.tail, fx, ctx->num_cus));
+				}
+				HIP_TRY(ctx, msc_launch_emd_ranks_list(b.tail, u16, u16 ? (const void*)cands->ranks16 : (const void*)cands->ranks, u16 ? (const void*)qset->ranks16 : (const void*)qset->ranks,
+				                                       cands->rk_pitch, k.d_slots, off, k.mc, b.dq_slots, e.open_list, e.open_words, open_cap, (uint64_t*)ctx->emd_list.p, ctx->num_cus));
+				HIP_TRY(ctx, msc_launch_epilogue_list(b.tail, e, ctx->num_cus));
+				return (int)MSC_OK;
+			};
+			if (fold) {
+				// The folded stage: the screen over intervals, the listed pairs' exact counts, their walk and FP64 evaluation. Should ITS list overflow -- every
+				// related pair is on it, the lower bound of P1 being 0 --, k_emd_list_close raises the block's word of ctx->fold_over and score_multi, once the call's
+				// blocks are through, scores the block again with the true product (no host wait here, and nothing queued for the case that did not arise)
+				MscEpilogueArgs ef = eb;
+				ef.kb_slices = slices_f; ef.fold_x_c = cands->kbf_x; ef.fold_x_q = qset->kbf_x;
+				if ((r = list_stage(ef))) return r;
+				ctx->fold_used = fold;
+				ctx->fold_blocks++;
+			} else {
+				if ((r = list_stage(eb))) return r;
+				HIP_TRY(ctx, launch_emd_ranks(b.tail, cands, qset, k.d_slots, off, k.mc, b.dq_slots, (uint32_t)n_q, (uint64_t*)ctx->emd_out.p, rows, open_words + 1));
+				ea.run_if = open_words + 1;
+			}
 		}
-		HIP_TRY(ctx, msc_launch_epilogue(b.tail, ea));
-		if (bounds) HIP_TRY(ctx, msc_launch_emd_list_close(b.tail, open_words, open_cap, (uint64_t*)(open_words + 2)));
+		if (!fold) HIP_TRY(ctx, msc_launch_epilogue(b.tail, ea));
+		if (bounds) HIP_TRY(ctx, msc_launch_emd_list_close(b.tail, open_words, open_cap, (uint64_t*)(open_words + 2), fold ? (uint32_t*)ctx->fold_over.p + b.idx : nullptr));
 		if (b.close && ctx->close_counts_n) HIP_TRY(ctx, msc_launch_close_counts(b.tail, d_close, (uint32_t)n_q, k.mc, (uint64_t*)ctx->close_counts.p + b.q0));
 		if (piped) {
 			HIP_TRY(ctx, hipEventRecord(s.ev_tail, b.tail));
@@ -894,7 +967,8 @@ int score_multi(MultiCall& c) {
 	const bool div_cells = ctx->multi_div_cells && c.want_div && !c.want_grp;
 	c.kb_fit = n_q >= 2 && kb_route_fits(cands, qset, c.need_emd) && !(cands->sparse && (c.want_grp || (c.want_div && !div_cells)));
 	if (c.kb_fit) {
-		if ((r = ensure_kb(ctx, cands)) || (r = ensure_kb(ctx, qset))) return r;
+		const bool flags_only = c.model && c.close_out && !c.sum_out && !c.csum_out && !c.raw_out && c.need_emd && !c.want_div && !c.want_grp;
+		if ((r = ensure_kb(ctx, cands, flags_only)) || (r = ensure_kb(ctx, qset, flags_only))) return r;
 		c.kb_fit = cands->kb && qset->kb && !cands->kb_has_zero && !qset->kb_has_zero;
 	}
 	c.cells = div_cells && c.kb_fit;
@@ -902,8 +976,12 @@ int score_multi(MultiCall& c) {
 	// pairwise matrix does not have to add up n_q x m flags on the host)
 	ctx->close_counts_n = 0;
 	if (c.close_out && c.model) {          // the list of open pairs of the bound pass (run_matrix): {count, overflow}, then the call's two totals
-		if ((r = ensure(ctx, ctx->open_words, 2 * sizeof(uint32_t) + 2 * sizeof(uint64_t)))) return r;
-		HIP_TRY(ctx, hipMemsetAsync(ctx->open_words.p, 0, 2 * sizeof(uint32_t) + 2 * sizeof(uint64_t), ctx->stream));
+		// (+ the third total, folded blocks that fell back; and per block of the plan a word that a folded block raises when its list overflows)
+		if ((r = ensure(ctx, ctx->open_words, kOpenWordsBytes))) return r;
+		HIP_TRY(ctx, hipMemsetAsync(ctx->open_words.p, 0, kOpenWordsBytes, ctx->stream));
+		const size_t over_bytes = ((n_q + 63) / 64 + 1) * sizeof(uint32_t);          // (a plan's blocks are of 64 queries or more, but for the last)
+		if ((r = ensure(ctx, ctx->fold_over, over_bytes))) return r;
+		HIP_TRY(ctx, hipMemsetAsync(ctx->fold_over.p, 0, over_bytes, ctx->stream));
 	}
 	if (c.close_out) {
 		if ((r = ensure(ctx, ctx->close_counts, n_q * sizeof(uint64_t)))) return r;
@@ -926,9 +1004,15 @@ int score_multi(MultiCall& c) {
 	}, c.blocks);
 	if (err) return err;
 	size_t next_taken = 0;
-	for (const MscMultiBlock& pb : c.blocks) {
+	std::vector<BlockRoute> route_of(c.blocks.size());
+	auto block_of = [&](const MscMultiBlock& pb) {
 		Block b{pb.q0, pb.nq, c.q_slots + pb.q0, c.sum_out ? c.sum_out + pb.q0 * m : nullptr, c.csum_out ? c.csum_out + pb.q0 * m : nullptr,
-		              c.raw_out ? c.raw_out + pb.q0 * m * c.nf : nullptr, c.close_out ? c.close_out + pb.q0 * m : nullptr};
+		        c.raw_out ? c.raw_out + pb.q0 * m * c.nf : nullptr, c.close_out ? c.close_out + pb.q0 * m : nullptr};
+		b.idx = (uint32_t)(&pb - c.blocks.data());
+		return b;
+	};
+	for (const MscMultiBlock& pb : c.blocks) {
+		Block b = block_of(pb);
 		// (blocks of the matrix-core pass are queued without a host wait between them: any other route first waits for them and reads their error word)
 		r = pb.matrix ? MSC_OK : flush_deferred(c);
 		BlockRoute rt;
@@ -944,6 +1028,7 @@ int score_multi(MultiCall& c) {
 				ctx->pipe.ev_used = 0; c.queue_up = true;
 			}
 		}
+		route_of[b.idx] = rt;
 		if (!r) switch (rt.kind) {
 			case R_MATRIX: r = run_matrix(c, b, rt); break;
 			case R_DIGEST: case R_RING: case R_TILES: r = run_streamed(c, b, rt); break;
@@ -954,6 +1039,21 @@ int score_multi(MultiCall& c) {
 		c.ms += ctx->tiles_ms_accum; c.launches += ctx->tiles_launches;
 	}
 	if ((r = flush_deferred(c))) return r;
+	if (ctx->fold_blocks) {
+		// the folded blocks whose list overflowed (msc_fold.h): once more, as the unfolded blocks they would have been -- the bounds of emd, the list, the dense
+		// walk behind it. The call's streams are idle; the block's close counts start again from zero, its flags go home over the first run's
+		std::vector<uint32_t> over(c.blocks.size());
+		HIP_TRY(ctx, hipMemcpy(over.data(), ctx->fold_over.p, over.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+		for (size_t i = 0; i < over.size(); i++) {
+			if (!over[i]) continue;
+			Block b = block_of(c.blocks[i]);
+			b.no_fold = true;
+			if (ctx->close_counts_n) HIP_TRY(ctx, hipMemsetAsync((uint64_t*)ctx->close_counts.p + b.q0, 0, b.nq * sizeof(uint64_t), ctx->stream));
+			if ((r = run_matrix(c, b, route_of[i]))) { (void)flush_deferred(c); return r; }
+			c.ms += ctx->tiles_ms_accum; c.launches += ctx->tiles_launches;
+		}
+		if ((r = flush_deferred(c))) return r;
+	}
 	ctx->tiles_ms_accum = c.ms; ctx->tiles_launches = c.launches;
 	return MSC_OK;
 }
@@ -964,10 +1064,10 @@ extern "C" int msc_score_multi(msc_ctx* ctx, const msc_model* model, const msc_h
                                const msc_hist_set* qset, const uint32_t* q_slots, uint64_t n_q, int order, double* sum_out, double* csum_out,
                                uint8_t* close_out, uint64_t feat_mask, double* raw_out) {
 	MultiCall c{ctx, model, cands, cand_slots, m, qset, q_slots, n_q, order, sum_out, csum_out, close_out, feat_mask, raw_out};
-	if (ctx) ctx->walk_listed = ctx->walk_dense = ctx->walk_blocks = ctx->walk_bound_blocks = 0;
+	if (ctx) ctx->walk_listed = ctx->walk_dense = ctx->walk_blocks = ctx->walk_bound_blocks = ctx->fold_used = ctx->fold_blocks = ctx->fold_fell_back = 0;
 	int r = score_multi(c);
 	if (ctx && r == MSC_OK && ctx->walk_bound_blocks) {          // the totals of the bound pass (every stream of the call is idle: the error word has been read)
-		uint64_t totals[2] = {0, 0};
+		uint64_t totals[3] = {0, 0, 0};
 		const hipError_t e = hipMemcpy(totals, (const uint8_t*)ctx->open_words.p + 2 * sizeof(uint32_t), sizeof totals, hipMemcpyDeviceToHost);
 		if (e != hipSuccess) r = fail(ctx, MSC_ERR_HIP, "copy of the pair list's totals failed: %s", hipGetErrorString(e));
 		else {
@@ -975,6 +1075,9 @@ extern "C" int msc_score_multi(msc_ctx* ctx, const msc_model* model, const msc_h
 			ctx->walk_dense += totals[1];
 			// a model whose distance really decides: it does not pay the bound pass for ever
 			if (totals[1] * 2 > ctx->walk_bound_blocks) model->emd_decides = true;
+			// ... nor, a model whose related pairs are too many for the list, the folded stage
+			ctx->fold_fell_back = totals[2];
+			if (totals[2] * 2 > ctx->fold_blocks) model->fold_overflows = true;
 		}
 	}
 	if (ctx && ctx->pipe.copy_pending) {          // the flag copies of the last blocks (issued beside the kernels that followed them)

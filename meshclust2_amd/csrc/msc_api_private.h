@@ -58,7 +58,7 @@ int batch_div_pass(msc_ctx* ctx, const msc_hist_set* cands, const msc_hist_set* 
                    MscPartial* partials, uint32_t* div_n);
 
 // ---- msc_api_multi.hip (shared with msc_api_pairs.hip)
-int ensure_kb(msc_ctx* ctx, const msc_hist_set* set);          // the presence-bit mirror and lists of large bins of a set, from its bins or its lists (set->kb null: unavailable)
+int ensure_kb(msc_ctx* ctx, const msc_hist_set* set, bool want_fold = false);          // the presence-bit mirror and lists of large bins of a set, from its bins or its lists (set->kb null: unavailable)
 int ensure_ranks(msc_ctx* ctx, const msc_hist_set* set);       // the ranks mirror, likewise (set->ranks null: unavailable)
 bool kb_route_fits(const msc_hist_set* cands, const msc_hist_set* qset, bool need_emd);          // host-side bounds of the matrix-core pass
 int read_error_word(msc_ctx* ctx);                             // the epilogue's error word as a status (the stream is idle)
@@ -76,4 +76,4 @@ void fill_pair_args(MscEpilogueArgs& ea, msc_ctx* ctx, const msc_hist_set* cands
 void fill_matrix_args(MscEpilogueArgs& ea, const BlockPipe::Side& s, const msc_hist_set* cands, const msc_hist_set* qset, uint32_t slices, uint32_t rows, uint64_t first, uint64_t n_hot, const void* emd_out);
 // the earth mover's distances of a chunk from the ranks mirrors: the 16-bit walk where both sets keep that form at one pitch
 hipError_t launch_emd_ranks(hipStream_t st, const msc_hist_set* cands, const msc_hist_set* qset, const uint32_t* d_slots, uint64_t off, uint32_t mc, const uint32_t* dq, uint32_t nq, uint64_t* out, uint32_t stride, const uint32_t* run_if = nullptr);
-void name_matrix_kernel(msc_ctx* ctx, uint32_t rows, bool emd, bool cells, bool from_lists);      // msc_last_kernel_info's name of the product kernel
+void name_matrix_kernel(msc_ctx* ctx, uint32_t rows, bool emd, bool cells, bool from_lists, uint32_t fold = 0);      // msc_last_kernel_info's name of the product kernel

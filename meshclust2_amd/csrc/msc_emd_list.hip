@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "msc_internal.h"
+#include "msc_kbits.h"
 
 namespace {
 
@@ -93,11 +94,48 @@ __global__ void __launch_bounds__(256) k_emd_ranks_list(const void* __restrict__
 	}
 }
 
+// The listed pairs of a FOLDED block (msc_fold.h): the product gave upper bounds of P1 (shared k-mers) and P2 (sum of e_q - 1 over the query's
+// large bins the candidate holds), and the list epilogue needs them exact. One wave per listed pair walks the candidate's row of the 32-bit ranks
+// mirror -- its k-mers as LOGICAL bins in order, a bin repeated per copy, padded with 4^k --, takes each distinct bin once, reads the query's two
+// bits at the bin's physical position from the transposed planes (plane 0: the query holds the k-mer; plane 1: more than once, and its own list
+// of large bins has the count), and stores P1 into slice 0 of the product's output (zeros into the other slices) and P2 beside it.
+__global__ void __launch_bounds__(256) k_fold_exact_list(const MscFoldExact a) {
+	if (a.words[1]) return;
+	const uint32_t n = a.words[0] < a.cap ? a.words[0] : a.cap;
+	const uint32_t lane = threadIdx.x & 63;
+	const uint32_t wave0 = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+	const uint32_t* qt = reinterpret_cast<const uint32_t*>(a.qT);
+	for (uint32_t i = wave0; i < n; i += gridDim.x * 4) {
+		const uint32_t idx = a.list[i], q = idx / a.m_per_query, ci = idx % a.m_per_query;
+		const uint64_t c_slot = a.cand_slots ? a.cand_slots[ci] : a.first + ci, q_slot = a.q_slots[q];
+		const uint32_t* row = a.c_ranks + c_slot * a.pitch;
+		const uint2* qmb = reinterpret_cast<const uint2*>(a.q_mb) + q_slot * a.q_pitch;
+		const uint32_t q_n = a.q_mb_n[q_slot] < a.q_pitch ? a.q_mb_n[q_slot] : a.q_pitch;
+		uint64_t p1 = 0, p2 = 0;
+		for (uint64_t t = lane; t < a.pitch; t += 64) {
+			const uint32_t bin = row[t];
+			if (bin >= a.nbins || (t && row[t - 1] == bin)) continue;          // padding; a further copy of the bin before
+			const uint32_t ph = (uint32_t)msc_phys_index(bin, a.E, a.R);
+			if (!((qt[msc_qt_word(ph, 0, q, a.qn)] >> (q & 31)) & 1u)) continue;
+			p1++;
+			if ((qt[msc_qt_word(ph, 1, q, a.qn)] >> (q & 31)) & 1u)
+				for (uint32_t j = 0; j < q_n; j++) if (qmb[j].x == ph) { p2 += qmb[j].y - 1; break; }
+		}
+		p1 = wave_sum_u64(p1);
+		p2 = wave_sum_u64(p2);
+		if (lane < a.slices) a.out_min[((uint64_t)lane * a.m_per_query + ci) * a.qn + q] = lane ? 0 : (int32_t)p1;
+		if (lane == 0 && a.out_diff) a.out_diff[(uint64_t)ci * a.qn + q] = (int32_t)p2;
+	}
+}
+
 // Behind a block's kernels: its count and overflow word go into the call's totals (totals[0] += pairs walked from the list, totals[1] +=
 // blocks whose list overflowed) and are cleared for the next block.
-__global__ void k_emd_list_close(uint32_t* __restrict__ words, uint32_t cap, unsigned long long* __restrict__ totals) {
+// fold_flag: the block's product was folded (msc_api_multi.hip). An overflow of ITS list is no dense block: totals[2] counts it and the flag tells the
+// host, when the call's blocks are through, to score the block again with the true product.
+__global__ void k_emd_list_close(uint32_t* __restrict__ words, uint32_t cap, unsigned long long* __restrict__ totals, uint32_t* __restrict__ fold_flag) {
 	if (threadIdx.x || blockIdx.x) return;
-	if (words[1]) totals[1] += 1;
+	if (fold_flag && words[1]) { totals[2] += 1; *fold_flag = 1; }
+	else if (words[1]) totals[1] += 1;
 	else totals[0] += words[0] < cap ? words[0] : cap;
 	words[0] = 0;
 	words[1] = 0;
@@ -123,7 +161,15 @@ hipError_t msc_launch_emd_ranks_list(hipStream_t st, bool u16, const void* c_ran
 	return hipGetLastError();
 }
 
-hipError_t msc_launch_emd_list_close(hipStream_t st, uint32_t* words, uint32_t cap, uint64_t* totals) {
-	k_emd_list_close<<<dim3(1), dim3(64), 0, st>>>(words, cap, (unsigned long long*)totals);
+hipError_t msc_launch_fold_exact_list(hipStream_t st, const MscFoldExact& a, int num_cus) {
+	if (a.cap == 0) return hipSuccess;
+	if (a.m_per_query == 0 || a.slices == 0 || a.slices > 64 || !a.c_ranks || !a.qT || !a.out_min) return hipErrorInvalidValue;
+	const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)a.cap + 3) / 4, (uint64_t)num_cus * 8);
+	k_fold_exact_list<<<dim3(grid), dim3(256), 0, st>>>(a);
+	return hipGetLastError();
+}
+
+hipError_t msc_launch_emd_list_close(hipStream_t st, uint32_t* words, uint32_t cap, uint64_t* totals, uint32_t* fold_flag) {
+	k_emd_list_close<<<dim3(1), dim3(64), 0, st>>>(words, cap, (unsigned long long*)totals, fold_flag);
 	return hipGetLastError();
 }

@@ -158,6 +158,9 @@ struct MscEpilogueArgs {
 	// k_pair_epilogue_bits_screen / _open: null, or a device word -- the launch does nothing when it is 0 (queued behind the list kernels for the case
 	// that the list overflowed)
 	const uint32_t* run_if;
+	// k_pair_epilogue_bits_bound on a FOLDED block (msc_fold.h): kb_min / kb_diff then hold P1' / P2' of the folded product, upper bounds of P1 / P2
+	// with each slot's own collisions added (fold_x_c: by candidate slot, fold_x_q: by query slot); null: the product was exact
+	const uint32_t *fold_x_c, *fold_x_q;
 };
 
 // ---------------------------------------------------------------- launchers (defined in the .hip kernel files)
@@ -236,7 +239,18 @@ hipError_t msc_launch_emd_ranks16(hipStream_t st, uint64_t nbins, const uint16_t
 hipError_t msc_launch_rank_moments(hipStream_t st, uint64_t nbins, const uint32_t* ranks, uint64_t pitch, uint64_t first_slot, uint64_t n_slots, uint64_t* rk_sum, uint64_t* rk_dev);
 hipError_t msc_launch_emd_ranks_list(hipStream_t st, bool u16, const void* c_ranks, const void* q_ranks, uint64_t pitch, const uint32_t* cand_slots, uint64_t first, uint32_t m_per_query,
                                      const uint32_t* q_slots_dev, const uint32_t* list, const uint32_t* words, uint32_t cap, uint64_t* emd_list, int num_cus);
-hipError_t msc_launch_emd_list_close(hipStream_t st, uint32_t* words, uint32_t cap, uint64_t* totals);
+// (fold_flag: null, or the word of a FOLDED block: set when its list overflowed, which totals[2] counts instead of totals[1])
+hipError_t msc_launch_emd_list_close(hipStream_t st, uint32_t* words, uint32_t cap, uint64_t* totals, uint32_t* fold_flag = nullptr);
+// the exact P1 / P2 of the listed pairs of a folded block, from the candidate's row of the 32-bit ranks mirror and the queries' transposed planes
+struct MscFoldExact {
+	const uint32_t* c_ranks; uint64_t pitch; uint64_t nbins; uint32_t E, R;
+	const uint32_t* cand_slots; uint64_t first; uint32_t m_per_query;
+	const uint32_t* q_slots; const uint32_t* list; const uint32_t* words; uint32_t cap;
+	const uint8_t* qT; uint32_t qn;
+	const void* q_mb; const uint32_t* q_mb_n; uint32_t q_pitch;
+	int32_t* out_min; uint32_t slices; int32_t* out_diff;
+};
+hipError_t msc_launch_fold_exact_list(hipStream_t st, const MscFoldExact& a, int num_cus);
 // the r04 form of that pass (msc_pair_gemm.hip): presence-bit mirror + lists of large bins, the queries' side of a block, the product
 uint64_t msc_kb_bytes(const MscLayout& L, uint64_t capacity);
 hipError_t msc_launch_kb_build(hipStream_t st, const MscLayout& L, int dtype, const uint8_t* bins, uint8_t* kb, uint64_t first_slot, uint64_t n_slots, void* mb,
@@ -283,6 +297,11 @@ hipError_t msc_launch_pair_gemm_queries(hipStream_t st, uint64_t nbins, const ui
                                         uint32_t* hot_cursor, uint32_t* hot_cnt, uint8_t* anib);
 hipError_t msc_launch_pair_gemm(hipStream_t st, uint64_t nbins, const uint8_t* cand_kb, const uint32_t* cand_slots, uint64_t first, uint32_t m, uint32_t qn,
                                 uint32_t k_slices, const uint32_t* hot_ptr, const void* hot, int32_t* out_min, int32_t* out_diff, const uint8_t* anib);
+// the folded mirror of a set (msc_fold.h) and the two parts of the queries' side on their own
+hipError_t msc_launch_kb_fold(hipStream_t st, uint64_t nbins, uint32_t fold, const uint8_t* kb, uint8_t* kbf, uint32_t* x, uint64_t first_slot, uint64_t n_slots);
+hipError_t msc_launch_kb_gather(hipStream_t st, uint64_t nbins, const uint8_t* q_kb, const uint32_t* q_slots_dev, uint32_t n_q, uint32_t qn, uint8_t* qT, uint8_t* anib);
+hipError_t msc_launch_hot_list(hipStream_t st, uint64_t nbins, uint32_t fold, const void* q_mb, const uint32_t* q_mb_n, uint32_t q_pitch, const uint32_t* q_slots_dev,
+                               uint32_t n_q, uint32_t qn, uint8_t* qT, uint64_t n_hot, void* hot, uint32_t* hot_ptr, uint32_t* hot_cursor, uint32_t* hot_cnt);
 hipError_t msc_launch_epilogue(hipStream_t st, const MscEpilogueArgs& a);
 hipError_t msc_launch_epilogue_bound(hipStream_t st, const MscEpilogueArgs& a);
 hipError_t msc_launch_epilogue_list(hipStream_t st, const MscEpilogueArgs& a, int num_cus);

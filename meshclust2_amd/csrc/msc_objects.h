@@ -102,9 +102,14 @@ struct msc_ctx {
 	// msc_emd_list.hip: the pairs of a block whose close flag the bounds of the distance leave open, their exact distances, and the words
 	// {count, overflow} (uint32) + {pairs walked, blocks that overflowed} (uint64, the call's totals) of that list
 	DevBuf open_list, emd_list, open_words;
+	DevBuf fold_over;                      // msc_fold.h: per block of a msc_score_multi call a word its folded stage raises when its list overflows
 	bool emd_bounds = true;                // msc_set_emd_bounds / MSC_NO_EMD_BOUNDS: close flags from bounds of the distance, rank walk for the open pairs only
 	uint64_t walk_listed = 0, walk_dense = 0, walk_blocks = 0;          // msc_last_emd_walk: the last msc_score_multi call
 	uint64_t walk_bound_blocks = 0;        // ... its blocks that took the bound pass (their overflows are on the device until the call ends)
+	// msc_set_fold_screen / MSC_NO_FOLD (msc_fold.h): 0, or the fold of the product of such blocks (8, 16, 32); msc_last_fold_screen: the last call's
+	// fold, its blocks whose product was folded, and those of them whose list overflowed (scored again with the true product)
+	uint32_t fold_screen = 16;
+	uint64_t fold_used = 0, fold_blocks = 0, fold_fell_back = 0;
 	msc_hist_set* shard_gather = nullptr;
 	// MSC_PROFILE_CALLS: host wall clock of the 1 x M scoring calls, split into preparing + queueing the slot list, issuing the
 	// launches, and waiting for the stream (printed by msc_destroy)
@@ -161,6 +166,12 @@ struct msc_hist_set {
 	mutable StaleRange kb_stale;
 	mutable bool kb_unavailable = false;
 	mutable bool kb_has_zero = false;         // a slot with a zero count went into the mirror (never the case for built histograms and their means)
+	// ... and the mirror folded F-to-1 (msc_fold.h; k_kb_fold): a bit per folded bin in kb's own layout at 4^k / kbf_fold bins, and per slot its own
+	// collisions kbf_x. Built from kb in ensure_kb wherever kb is (re)built: kbf_stale = the slots kb has been rebuilt for since.
+	mutable uint8_t* kbf = nullptr;
+	mutable uint32_t* kbf_x = nullptr;
+	mutable uint32_t kbf_fold = 0;
+	mutable StaleRange kbf_stale;
 	mutable void* mb = nullptr;
 	mutable uint32_t* mb_n = nullptr;
 	mutable uint32_t mb_pitch = 0;
@@ -221,6 +232,7 @@ struct msc_model {
 	int k = 0;
 	MscDevModel h;
 	MscDevModel* d = nullptr;
+	mutable bool fold_overflows = false;       // ... overflowed the list of their FOLDED stage (msc_fold.h): later calls run the true product
 	mutable bool emd_decides = false;          // more than half the blocks of a msc_score_multi call overflowed the list of open pairs: later calls skip the bound pass (msc_emd_list.hip)
 };
 

@@ -36,6 +36,7 @@
 #include "msc_internal.h"
 #include "msc_wave.h"
 #include "msc_kbits.h"
+#include "msc_fold.h"
 
 namespace {
 
@@ -167,6 +168,39 @@ __global__ void __launch_bounds__(256) k_mb_build_sparse(const uint2* __restrict
 	}
 }
 
+// ------------------------------------------------------------------------------------------------ the folded mirror
+// kbf = the mirror folded F-to-1 (msc_fold.h), in kb's own blocked layout at nbins / F bins: super-step s of a block of 32 slots is the OR
+// of super-steps s + j nss_f (j < F) of the true block, KiB for KiB. x[slot] = the slot's own collisions, its distinct k-mers minus its
+// distinct folded bins = popcount(true row) - popcount(folded row): with P1' the product of two folded rows,
+//     P1 <= P1' + min(x_q, x_c)
+// (the shared k-mers fall into the folded bins both rows hold -- at most P1' of them -- and every k-mer of a row beyond the first in its
+// folded bin is one of that row's x). One workgroup per block of 32 slots; whole blocks are rebuilt (a neighbour's row comes out as its kb
+// row says, which is what it held before).
+__global__ void __launch_bounds__(256) k_kb_fold(const uint8_t* __restrict__ kb, uint8_t* __restrict__ kbf, uint32_t* __restrict__ x, uint64_t nbins, uint32_t fold,
+                                                 uint64_t first_block) {
+	__shared__ uint32_t cnt[32];
+	const uint64_t blk = first_block + blockIdx.x, nbf = nbins / fold;
+	const uint32_t nss_f = (uint32_t)(nbf / 256), tid = threadIdx.x;
+	if (tid < 32) cnt[tid] = 0;
+	__syncthreads();
+	const uint4* src = reinterpret_cast<const uint4*>(kb + blk * msc_kb_block_bytes(nbins));
+	uint4* dst = reinterpret_cast<uint4*>(kbf + blk * msc_kb_block_bytes(nbf));
+	for (uint32_t p = tid; p < nss_f * 64; p += 256) {          // 16-byte piece p of the folded block: super-step p / 64, slot (p % 64) / 2
+		uint4 o = make_uint4(0, 0, 0, 0);
+		int own = 0;
+		for (uint32_t j = 0; j < fold; j++) {
+			const uint4 v = src[(uint64_t)j * nss_f * 64 + p];
+			own += __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w);
+			o.x |= v.x; o.y |= v.y; o.z |= v.z; o.w |= v.w;
+		}
+		dst[p] = o;
+		own -= __popc(o.x) + __popc(o.y) + __popc(o.z) + __popc(o.w);
+		if (own) atomicAdd(&cnt[(p & 63) >> 1], (uint32_t)own);
+	}
+	__syncthreads();
+	if (tid < 32) x[blk * 32 + tid] = cnt[tid];
+}
+
 // ------------------------------------------------------------------------------------------------ the queries' side of a block
 // One workgroup per 128-bin step, one thread per query row (rows past n_q are zero). anib = the queries' tile of each 256-bin super-step
 // as k_pair_gemm_fp4_dma copies it into LDS: [super-step][row][16-byte segment (2 t + h) ^ ((row >> 1) & 7)] = the nibbles lane half h
@@ -190,7 +224,7 @@ __global__ void __launch_bounds__(256) k_kb_gather(const uint8_t* __restrict__ k
 				hwv[2 * kc + 1] = ((uint32_t)hi[kc >> 1] >> (16 * (kc & 1))) & 0xffffu;
 			}
 		}
-		{          // the queries' tile as k_pair_gemm_fp4_dma copies it into LDS: nibbles, segments already swizzled
+		if (anib) {          // the queries' tile as k_pair_gemm_fp4_dma copies it into LDS: nibbles, segments already swizzled (null: not wanted)
 			v4i* tile_row = reinterpret_cast<v4i*>(anib) + ((uint64_t)(step >> 1) * QN + row) * 8;
 #pragma unroll
 			for (uint32_t x = 0; x < 4; x++) {          // x = 2 (t & 1) + h of this step's two products
@@ -204,6 +238,7 @@ __global__ void __launch_bounds__(256) k_kb_gather(const uint8_t* __restrict__ k
 	// transposed, as BITS: bin p of the step (halfword p / 16 of the row, bit p % 16) -> one ballot per bin and wave of 64 rows; lane l of a
 	// wave keeps the ballots of bins l and l + 64. Record of a bin = [plane][QN / 32 words]: plane 0 = "the query holds this k-mer"
 	// (e >= 1), plane 1 = "... more than once" (e >= 2: set by k_hot_fill; the epilogue then reads the count in the query's own list).
+	if (!qT) return;          // (null: only the tiles are wanted; uniform, in front of the barrier)
 	if (row < ((QN + 63u) & ~63u)) {          // (whole waves: a lane past QN holds zeros and keeps the ballots of its two bins like any other)
 		const uint32_t lane = row & 63, wv = row >> 6;
 		uint32_t lo[2] = {0, 0}, hi[2] = {0, 0};
@@ -238,15 +273,17 @@ __global__ void __launch_bounds__(256) k_kb_gather(const uint8_t* __restrict__ k
 	}
 }
 
-// The queries' large bins, bucketed by step: count, exclusive scan, fill. An entry = (bin, row << 16 | e - 1); the fill also puts
-// min(e, 127) at [bin][row] of the transposed image (behind k_kb_gather on the stream).
+// The queries' large bins, bucketed by step: count, exclusive scan, fill. An entry = (bin, row << 16 | e - 1); the fill also sets
+// the entry's bit of plane 1 of the transposed image (behind k_kb_gather on the stream; qT null: not wanted). fold > 1: the list of a FOLDED
+// block -- buckets and entries by msc_fold_bin_of(bin) over nbins / fold bins, so that the product adds e - 1 wherever the candidate's
+// folded bit is set: P2' = sum g_q(i) f'_c(fold(i)) >= P2.
 __global__ void __launch_bounds__(256) k_hot_count(const uint2* __restrict__ mb, const uint32_t* __restrict__ mb_n, uint32_t pitch, const uint32_t* __restrict__ q_slots,
-                                                   uint32_t n_q, uint32_t* __restrict__ cnt) {
+                                                   uint32_t n_q, uint32_t* __restrict__ cnt, uint64_t nbins, uint32_t fold) {
 	const uint32_t row = blockIdx.x;
 	if (row >= n_q) return;
 	const uint32_t slot = q_slots[row];
 	const uint32_t n = mb_n[slot] < pitch ? mb_n[slot] : pitch;
-	for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) atomicAdd(&cnt[mb[(uint64_t)slot * pitch + i].x / kStep], 1u);
+	for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) atomicAdd(&cnt[msc_fold_bin_of(mb[(uint64_t)slot * pitch + i].x, nbins, fold) / kStep], 1u);
 }
 __global__ void __launch_bounds__(1024) k_hot_scan(const uint32_t* __restrict__ cnt, uint32_t nsteps, uint32_t* __restrict__ ptr, uint32_t* __restrict__ cursor) {
 	__shared__ uint32_t part[1024];
@@ -266,7 +303,8 @@ __global__ void __launch_bounds__(1024) k_hot_scan(const uint32_t* __restrict__ 
 	if (threadIdx.x == 1023) ptr[nsteps] = part[1023];
 }
 __global__ void __launch_bounds__(256) k_hot_fill(const uint2* __restrict__ mb, const uint32_t* __restrict__ mb_n, uint32_t pitch, const uint32_t* __restrict__ q_slots,
-                                                  uint32_t n_q, uint32_t qn, uint32_t* __restrict__ cursor, uint2* __restrict__ hot, uint8_t* __restrict__ qT) {
+                                                  uint32_t n_q, uint32_t qn, uint32_t* __restrict__ cursor, uint2* __restrict__ hot, uint8_t* __restrict__ qT, uint64_t nbins,
+                                                  uint32_t fold) {
 	const uint32_t row = blockIdx.x;
 	if (row >= n_q) return;
 	const uint32_t slot = q_slots[row];
@@ -274,8 +312,9 @@ __global__ void __launch_bounds__(256) k_hot_fill(const uint2* __restrict__ mb, 
 	for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
 		const uint2 en = mb[(uint64_t)slot * pitch + i];
 		const uint32_t g = en.y - 1 > 0xffffu ? 0xffffu : en.y - 1;          // (counts of the narrow range are <= 8191)
-		hot[atomicAdd(&cursor[en.x / kStep], 1u)] = make_uint2(en.x, (row << 16) | g);
-		atomicOr(reinterpret_cast<uint32_t*>(qT) + msc_qt_word(en.x, 1, row, qn), 1u << (row & 31));
+		const uint32_t fb = (uint32_t)msc_fold_bin_of(en.x, nbins, fold);          // the product looks the entry up at its FOLDED bin; the plane keeps the true one
+		hot[atomicAdd(&cursor[fb / kStep], 1u)] = make_uint2(fb, (row << 16) | g);
+		if (qT) atomicOr(reinterpret_cast<uint32_t*>(qT) + msc_qt_word(en.x, 1, row, qn), 1u << (row & 31));
 	}
 }
 
@@ -503,28 +542,57 @@ uint64_t msc_pair_gemm_qt_bytes(uint64_t nbins, uint32_t qn) { return nbins * 2 
 // ... and the nibble image of the queries' tiles
 uint64_t msc_pair_gemm_anib_bytes(uint64_t nbins, uint32_t qn) { return nbins / 2 * qn; }
 
-// The queries' side: anib and qT of rows q_slots[0 .. n_q) of the mirror q_kb; when n_hot > 0 also the hot list (hot: n_hot entries;
-// hot_ptr, hot_cursor, hot_cnt: nbins / 128 + 1 words each) from the queries' lists of large bins.
-hipError_t msc_launch_pair_gemm_queries(hipStream_t st, uint64_t nbins, const uint8_t* q_kb, const void* q_mb, const uint32_t* q_mb_n, uint32_t q_pitch,
-                                        const uint32_t* q_slots_dev, uint32_t n_q, uint32_t qn, uint8_t* qT, uint64_t n_hot, void* hot, uint32_t* hot_ptr,
-                                        uint32_t* hot_cursor, uint32_t* hot_cnt, uint8_t* anib) {
-	if (n_q == 0 || n_q > qn || nbins % 256 || !anib || !qT) return hipErrorInvalidValue;
+// The folded mirror and the collisions of slots [first_slot, first_slot + n_slots) from kb (whole blocks of 32 slots around them;
+// x: room for the capacity rounded up to 32). kbf: msc_kb_bytes of a layout of nbins / fold bins.
+hipError_t msc_launch_kb_fold(hipStream_t st, uint64_t nbins, uint32_t fold, const uint8_t* kb, uint8_t* kbf, uint32_t* x, uint64_t first_slot, uint64_t n_slots) {
+	if (n_slots == 0) return hipSuccess;
+	if (fold < 2 || nbins % ((uint64_t)fold * 256)) return hipErrorInvalidValue;
+	const uint64_t b0 = first_slot >> 5, b1 = (first_slot + n_slots - 1) >> 5;
+	if (b1 - b0 + 1 > 0x7fffffffull) return hipErrorInvalidValue;
+	k_kb_fold<<<dim3((unsigned)(b1 - b0 + 1)), dim3(256), 0, st>>>(kb, kbf, x, nbins, fold, b0);
+	return hipGetLastError();
+}
+
+// The queries' side, in its two parts. The images of rows q_slots[0 .. n_q) of a mirror of nbins bins: qT (the transposed bit planes) and
+// anib (the nibble tiles), either of them null when not wanted -- a folded block takes its tiles from the folded mirror and its planes from
+// the true one.
+hipError_t msc_launch_kb_gather(hipStream_t st, uint64_t nbins, const uint8_t* q_kb, const uint32_t* q_slots_dev, uint32_t n_q, uint32_t qn, uint8_t* qT, uint8_t* anib) {
+	if (n_q == 0 || n_q > qn || nbins % 256 || (!anib && !qT)) return hipErrorInvalidValue;
 	const uint32_t nsteps = (uint32_t)(nbins / kStep);
 	if (qn == 32) k_kb_gather<32><<<dim3(nsteps), dim3(256), 0, st>>>(q_kb, q_slots_dev, n_q, nbins, qT, anib);
 	else if (qn == 64) k_kb_gather<64><<<dim3(nsteps), dim3(256), 0, st>>>(q_kb, q_slots_dev, n_q, nbins, qT, anib);
 	else if (qn == 128) k_kb_gather<128><<<dim3(nsteps), dim3(256), 0, st>>>(q_kb, q_slots_dev, n_q, nbins, qT, anib);
 	else return hipErrorInvalidValue;
-	hipError_t e = hipGetLastError();
-	if (e != hipSuccess || n_hot == 0) return e;
-	if ((e = hipMemsetAsync(hot_cnt, 0, (nsteps + 1) * sizeof(uint32_t), st)) != hipSuccess) return e;
-	k_hot_count<<<dim3(n_q), dim3(256), 0, st>>>((const uint2*)q_mb, q_mb_n, q_pitch, q_slots_dev, n_q, hot_cnt);
-	k_hot_scan<<<dim3(1), dim3(1024), 0, st>>>(hot_cnt, nsteps, hot_ptr, hot_cursor);
-	k_hot_fill<<<dim3(n_q), dim3(256), 0, st>>>((const uint2*)q_mb, q_mb_n, q_pitch, q_slots_dev, n_q, qn, hot_cursor, (uint2*)hot, qT);
 	return hipGetLastError();
 }
 
+// ... and the hot list (hot: n_hot entries; hot_ptr, hot_cursor, hot_cnt: nbins / fold / 128 + 1 words each) from the queries' lists of
+// large bins, by FOLDED bin when fold > 1; the fill sets plane 1 of qT (of the TRUE bins) unless qT is null.
+hipError_t msc_launch_hot_list(hipStream_t st, uint64_t nbins, uint32_t fold, const void* q_mb, const uint32_t* q_mb_n, uint32_t q_pitch, const uint32_t* q_slots_dev,
+                               uint32_t n_q, uint32_t qn, uint8_t* qT, uint64_t n_hot, void* hot, uint32_t* hot_ptr, uint32_t* hot_cursor, uint32_t* hot_cnt) {
+	if (n_hot == 0) return hipSuccess;
+	if (fold == 0 || nbins % ((uint64_t)fold * 256)) return hipErrorInvalidValue;
+	const uint32_t nsteps = (uint32_t)(nbins / fold / kStep);
+	const hipError_t e = hipMemsetAsync(hot_cnt, 0, (nsteps + 1) * sizeof(uint32_t), st);
+	if (e != hipSuccess) return e;
+	k_hot_count<<<dim3(n_q), dim3(256), 0, st>>>((const uint2*)q_mb, q_mb_n, q_pitch, q_slots_dev, n_q, hot_cnt, nbins, fold);
+	k_hot_scan<<<dim3(1), dim3(1024), 0, st>>>(hot_cnt, nsteps, hot_ptr, hot_cursor);
+	k_hot_fill<<<dim3(n_q), dim3(256), 0, st>>>((const uint2*)q_mb, q_mb_n, q_pitch, q_slots_dev, n_q, qn, hot_cursor, (uint2*)hot, qT, nbins, fold);
+	return hipGetLastError();
+}
+
+// Both parts for an unfolded block: anib and qT of rows q_slots[0 .. n_q) of the mirror q_kb; when n_hot > 0 also the hot list.
+hipError_t msc_launch_pair_gemm_queries(hipStream_t st, uint64_t nbins, const uint8_t* q_kb, const void* q_mb, const uint32_t* q_mb_n, uint32_t q_pitch,
+                                        const uint32_t* q_slots_dev, uint32_t n_q, uint32_t qn, uint8_t* qT, uint64_t n_hot, void* hot, uint32_t* hot_ptr,
+                                        uint32_t* hot_cursor, uint32_t* hot_cnt, uint8_t* anib) {
+	if (!anib || !qT) return hipErrorInvalidValue;
+	const hipError_t e = msc_launch_kb_gather(st, nbins, q_kb, q_slots_dev, n_q, qn, qT, anib);
+	if (e != hipSuccess) return e;
+	return msc_launch_hot_list(st, nbins, 1, q_mb, q_mb_n, q_pitch, q_slots_dev, n_q, qn, qT, n_hot, hot, hot_ptr, hot_cursor, hot_cnt);
+}
+
 // P1 [k_slices][m][qn] and, with a hot list, P2 [m][qn] (zeroed here) of the block's queries against m candidates (slot list, or slots
-// first .. first + m - 1) of the mirror cand_kb
+// first .. first + m - 1) of the mirror cand_kb (a folded block: of the folded mirror, nbins = its bin count)
 hipError_t msc_launch_pair_gemm(hipStream_t st, uint64_t nbins, const uint8_t* cand_kb, const uint32_t* cand_slots, uint64_t first, uint32_t m, uint32_t qn,
                                 uint32_t k_slices, const uint32_t* hot_ptr, const void* hot, int32_t* out_min, int32_t* out_diff, const uint8_t* anib) {
 	if (m == 0) return hipSuccess;

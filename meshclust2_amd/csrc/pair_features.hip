@@ -1049,18 +1049,72 @@ __device__ __forceinline__ float screen_raw(uint64_t flag, const PairTotals& t, 
 	}
 }
 
+// A FOLDED block (msc_fold.h, k_pair_epilogue_bits_bound<.., true>): the two reductions that come from the product are known as intervals,
+//     manh in [t1.manh, t0.manh]        dot in [t0.dot, t1.dot]
+// t0 = the corner P1 = P2 = 0, t1 = the corner P1 = U1, P2 = P2' (sum min and sum products at their upper ends; the caller has cut U1 to
+// min(sum e_a, sum e_b) - the lists' part, so t1.manh >= | sum_a - sum_b |, and t1.dot to (sq_a + sq_b) / 2, so sq_a + sq_b - 2 dot >= 0 --
+// both hold for the true values). Every statistic that reads one of the two is monotone in it, so its value lies between its values at the
+// two corners; -> their midpoint, and *half = half their distance, which joins the bound of the statistic's error as the emd's does:
+//   manhattan            = manh: increasing in manh.
+//   intersection         = 2 floor((sum_a + sum_b - manh) / 2) / (mag_a + mag_b): non-increasing in manh (floor is monotone, the divisor positive).
+//   kulczynski2          = coeff floor((sum_a + sum_b - manh) / 2) with coeff = N (ap + aq) / (2 ap aq) > 0: non-increasing in manh.
+//   euclidean            = sqrt(sq_a + sq_b - 2 dot): decreasing in dot while the argument is >= 0 (it is, at both corners, by the cut above).
+//   normalized_vectors   = dot / sqrt(sq_a sq_b): increasing in dot.
+//   pearson_coefficient  = (dot - const) / sqrt(np nq) with np, nq > 0 independent of the pair's products: increasing in dot.
+//   similarity_ratio     = dot / (dot + sqrt(W)), W = (sq_a + sq_b - 2 dot - 2^33 neg) mod 2^64 with neg = (manh - (sum_a - sum_b)) / 2 for 32-bit
+//                          bins and 0 otherwise. It reads BOTH reductions, so it is bounded over the box, not along a path: for dot > 0, W >= 0 it
+//                          is increasing in dot at fixed W and decreasing in W at fixed dot, hence within [f(dot_lo, W_hi), f(dot_hi, W_lo)]
+//                          once W_lo <= W <= W_hi holds as NUMBERS. E = sq_a + sq_b - 2 dot lies in [E_lo, E_hi] >= 0. neg = 0 over the whole
+//                          box: W = E. 1 <= neg < 2^30 over the whole box and E_hi < 2^33: E - 2^33 neg lies in (-2^64, 0) everywhere, W = 2^64
+//                          + E - 2^33 neg wraps exactly once at every point, increasing in E and decreasing in neg. Any other case (neg = 0 at
+//                          one corner only: the corners lie on two sides of a wrap) -> NaN, which leaves the pair open.
+//   earth_movers_distance, length_difference read neither: *half = 0 (the emd's own interval is screen_close's kEmdBound).
+__device__ __forceinline__ float screen_raw_box(uint64_t flag, const PairTotals& t0, const PairTotals& t1, const Side& a, const Side& b, uint64_t nbins, int dtype, float* half) {
+	float r0, r1;
+	if (flag == MSC_FEAT_SIMRATIO) {
+		const uint64_t sq = a.sq + b.sq;
+		const uint64_t e_hi = sq - 2 * t0.dot, e_lo = sq - 2 * t1.dot;
+		uint64_t w_lo = e_lo, w_hi = e_hi;
+		if (dtype == 32) {
+			const int64_t sdiff = (int64_t)a.sum - (int64_t)b.sum;
+			const uint64_t neg_hi = (uint64_t)(((int64_t)t0.manh - sdiff) >> 1), neg_lo = (uint64_t)(((int64_t)t1.manh - sdiff) >> 1);
+			if (neg_hi != 0) {
+				if (neg_lo == 0 || neg_hi >= (1ull << 30) || e_hi >= (1ull << 33)) { *half = 0.f; return NAN; }
+				w_lo = e_lo - (neg_hi << 33);
+				w_hi = e_hi - (neg_lo << 33);
+			}
+		}
+		const float d0 = (float)t0.dot, d1 = (float)t1.dot;
+		r0 = d0 * __builtin_amdgcn_rcpf(d0 + __builtin_amdgcn_sqrtf((float)w_hi));
+		r1 = d1 * __builtin_amdgcn_rcpf(d1 + __builtin_amdgcn_sqrtf((float)w_lo));
+	} else if (flag == MSC_FEAT_EMD || flag == MSC_FEAT_LENGTHD) {
+		*half = 0.f;
+		return screen_raw<true>(flag, t0, a, b, nbins, dtype);
+	} else {
+		r0 = screen_raw<true>(flag, t0, a, b, nbins, dtype);
+		r1 = screen_raw<true>(flag, t1, a, b, nbins, dtype);
+	}
+	*half = 0.5f * fabsf(r1 - r0);
+	return 0.5f * (r0 + r1);
+}
+
 // -> 1 close, 0 not close, -1 undecided. a / b = first / second argument of the reference call. Combo by combo, each one's one or two
 // normalised statistics formed on the spot (no array of them: indexed by a model's run-time positions it becomes chains of selects --
 // 350 v_cndmask in the first form of this function, more than its arithmetic; a statistic two combos share is formed twice).
 // kEmdBound (k_pair_epilogue_bits_bound): the earth mover's distance is known as an interval -- the statistic is taken at its midpoint and the
 // half-width, with one kScreenEps term for the conversions of the two, joins the bound of its error; the rest of the arithmetic is the same.
-template <bool kEmdBound = false>
-__device__ __forceinline__ int screen_close(const MscDevModel& md, const PairTotals& t, const Side& a, const Side& b, uint64_t nbins, int dtype) {
+// kBox (with kEmdBound; a folded block): t and *t1 are the two corners of screen_raw_box; the statistic is taken at the midpoint of its two corner
+// values, and the half-width -- with one kScreenEps term for each corner value's own rounding and for the midpoint's -- joins the bound.
+template <bool kEmdBound = false, bool kBox = false>
+__device__ __forceinline__ int screen_close(const MscDevModel& md, const PairTotals& t, const Side& a, const Side& b, uint64_t nbins, int dtype, const PairTotals* t1 = nullptr) {
 	if (a.len == 0 || b.len == 0) return -1;          // (length_difference throws: the FP64 path reports it)
 	auto single = [&](int i, float& v, float& dv) {          // normalised statistic i and the bound of its error
-		const float r = screen_raw<kEmdBound>(md.single_flag[i], t, a, b, nbins, dtype);
+		float r, box_half = 0.f;
+		if constexpr (kBox) r = screen_raw_box(md.single_flag[i], t, *t1, a, b, nbins, dtype, &box_half);
+		else r = screen_raw<kEmdBound>(md.single_flag[i], t, a, b, nbins, dtype);
 		const float u = (r - md.s_min[i]) * md.s_inv[i];
 		float du = (kScreenEps * (fabsf(r) + fabsf(md.s_min[i])) + 1e-30f) * fabsf(md.s_inv[i]) + kScreenEps * fabsf(u);
+		if constexpr (kBox) du += (box_half + 3.f * kScreenEps * (box_half + fabsf(r))) * fabsf(md.s_inv[i]);          // (|r0|, |r1| <= |r| + half)
 		if constexpr (kEmdBound)
 			if (md.single_flag[i] == MSC_FEAT_EMD) du += (t.emd_half + kScreenEps * (t.emd_half + fabsf(r))) * fabsf(md.s_inv[i]);
 		v = md.is_sim[i] ? u : 1.f - u;
@@ -1522,7 +1576,13 @@ __global__ void __launch_bounds__(kBlock, 5) k_pair_epilogue_bits_open(const Msc
 // that stays undecided gets the byte kScreenOpen and its index q * m_per_query + ci goes onto open_list: a wave ballots its lanes and ONE
 // lane adds the wave's count to open_words[0]; an append past open_cap sets open_words[1] and writes nothing -- the caller has the dense
 // walk and k_pair_epilogue_bits_screen / _open queued behind the list kernels for that case.
-template <uint32_t kScreenChunk>
+// kFold: the block's product ran over FOLDED bits (msc_fold.h): kb_min = P1' and kb_diff = P2' bound the true sums from above,
+//     0 <= P1 <= U1 = P1' + min(x_q, x_c)          0 <= P2 <= P2'
+// (x = a slot's own collisions, k_kb_fold), while the terms from the candidate's list of large bins stay exact (they read the queries' TRUE planes).
+// bits_pair_totals forms the corner P1 = P2 = 0; the other corner adds U1 -- cut to min(sum e_c, sum e_q) less the lists' part of sum min, which
+// sum min cannot pass -- to sum min and U1 + P2' to the sum of products -- cut to (sq_c + sq_q) / 2, which sum c_i q_i cannot pass --, and
+// screen_close<true, true> evaluates every statistic at both (screen_raw_box). The open pairs get their exact P1 / P2 from k_fold_exact_list.
+template <uint32_t kScreenChunk, bool kFold>
 __global__ void __launch_bounds__(kBlock, 4) k_pair_epilogue_bits_bound(const MscEpilogueArgs a) {
 	const uint32_t lane = threadIdx.x & 63;
 	const uint32_t groups = (a.n_queries + 63) / 64;
@@ -1538,8 +1598,10 @@ __global__ void __launch_bounds__(kBlock, 4) k_pair_epilogue_bits_bound(const Ms
 	const Side qry{qs->mag, qs->length, qs->sum, qs->sum_sq};
 	const uint64_t q_sum = a.rk_q_sum[q_slot], q_dev = a.rk_q_dev[q_slot];
 	const uint32_t ns = a.kb_slices;
+	uint32_t x_q = 0;
+	if constexpr (kFold) x_q = a.fold_x_q[q_slot];
 	uint32_t fl[4] = {0, 0, 0, 0};
-	auto totals_of = [&](uint32_t ci, int64_t min_e, int64_t diff_e, Side& cand, PairTotals& t) {
+	auto totals_of = [&](uint32_t ci, int64_t min_e, int64_t diff_e, Side& cand, PairTotals& t, PairTotals& t1) {
 		const uint32_t slot_rel = a.cand_slots ? a.cand_slots[ci] : ci;
 		const uint64_t slot = a.cand_slots ? (uint64_t)slot_rel : a.kb_first + ci;
 		const uint2* cmb = reinterpret_cast<const uint2*>(a.kb_c_mb) + slot * a.kb_c_pitch;
@@ -1548,8 +1610,21 @@ __global__ void __launch_bounds__(kBlock, 4) k_pair_epilogue_bits_bound(const Ms
 		cand = Side{cs->mag, cs->length, cs->sum, cs->sum_sq};
 		const uint64_t c_sum = a.rk_c_sum[slot], c_dev = a.rk_c_dev[slot];
 		const uint64_t lo = c_sum > q_sum ? c_sum - q_sum : q_sum - c_sum, hi = c_dev + q_dev;
-		bits_pair_totals(a, ci, cmb, c_n, qq, q_slot, min_e, diff_e, lo + hi, cand, qry, t);
-		t.emd_half = 0.5f * (float)(hi - lo);
+		if constexpr (kFold) {
+			bits_pair_totals(a, ci, cmb, c_n, qq, q_slot, 0, 0, lo + hi, cand, qry, t);
+			t.emd_half = 0.5f * (float)(hi - lo);
+			const uint32_t x_c = a.fold_x_c[slot];
+			const uint64_t ex_c = cand.sum - a.nbins, ex_q = qry.sum - a.nbins, gap = ex_c > ex_q ? ex_c - ex_q : ex_q - ex_c;
+			const uint64_t u1 = (uint64_t)min_e + (x_c < x_q ? x_c : x_q), room = (t.manh - gap) >> 1;          // (t.manh = ex_c + ex_q - 2 (the lists' part) >= gap)
+			const uint64_t u1c = u1 < room ? u1 : room, dot_top = (cand.sq + qry.sq) >> 1, dot_hi = t.dot + u1c + (uint64_t)diff_e;
+			t1 = t;
+			t1.manh = t.manh - 2 * u1c;
+			t1.dot = dot_hi < dot_top ? dot_hi : dot_top;
+			if (t1.dot < t.dot) t1.dot = t.dot;          // (never for true histograms: t.dot is a lower bound of a sum that dot_top bounds)
+		} else {
+			bits_pair_totals(a, ci, cmb, c_n, qq, q_slot, min_e, diff_e, lo + hi, cand, qry, t);
+			t.emd_half = 0.5f * (float)(hi - lo);
+		}
 	};
 	auto sums_of = [&](uint32_t ci, int64_t& min_e, int64_t& diff_e) {
 		int64_t v = a.kb_min[(uint64_t)ci * a.kb_qn + qq];
@@ -1566,9 +1641,10 @@ __global__ void __launch_bounds__(kBlock, 4) k_pair_epilogue_bits_bound(const Ms
 		for (uint32_t j = 0; j < 4; j++) {
 			if (j0 + j >= nc) break;
 			Side cand;
-			PairTotals t{0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.f};
-			totals_of(c0 + j0 + j, min4[j], diff4[j], cand, t);
-			const int verdict = a.order == MSC_ORDER_CAND_FIRST ? screen_close<true>(*a.model, t, cand, qry, a.nbins, a.dtype) : screen_close<true>(*a.model, t, qry, cand, a.nbins, a.dtype);
+			PairTotals t{0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.f}, t1;
+			totals_of(c0 + j0 + j, min4[j], diff4[j], cand, t, t1);
+			const int verdict = a.order == MSC_ORDER_CAND_FIRST ? screen_close<true, kFold>(*a.model, t, cand, qry, a.nbins, a.dtype, &t1)
+			                                                    : screen_close<true, kFold>(*a.model, t, qry, cand, a.nbins, a.dtype, &t1);
 			fl[(j0 + j) >> 2] |= (uint32_t)(verdict < 0 ? kScreenOpen : verdict) << (8 * ((j0 + j) & 3));
 			__builtin_amdgcn_sched_barrier(0);          // (one candidate's evaluation at a time, as in k_pair_epilogue_bits_screen)
 		}
@@ -2423,7 +2499,10 @@ hipError_t msc_launch_epilogue_bound(hipStream_t st, const MscEpilogueArgs& a) {
 		return hipErrorInvalidValue;
 	constexpr uint32_t chunk = 4;          // (as the screen of msc_launch_epilogue)
 	const uint64_t cw = (uint64_t)((a.m_per_query + chunk - 1) / chunk) * ((a.n_queries + 63) / 64);
-	hipLaunchKernelGGL(k_pair_epilogue_bits_bound<chunk>, dim3((unsigned)((cw + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, st, a);
+	if (a.fold_x_c || a.fold_x_q) {
+		if (!a.fold_x_c || !a.fold_x_q) return hipErrorInvalidValue;
+		hipLaunchKernelGGL((k_pair_epilogue_bits_bound<chunk, true>), dim3((unsigned)((cw + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, st, a);
+	} else hipLaunchKernelGGL((k_pair_epilogue_bits_bound<chunk, false>), dim3((unsigned)((cw + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, st, a);
 	return hipGetLastError();
 }
 

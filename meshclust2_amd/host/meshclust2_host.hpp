@@ -44,6 +44,8 @@ public:
 	// score_multi with a divergence statistic on the matrix-core route, no merge pass per query (integer statistics bit-equal, the two sums to 1e-9)
 	void set_multi_div_cells(bool on) { check(msc_set_multi_div_cells(h_, on ? 1 : 0)); }
 	void set_emd_bounds(bool on) { check(msc_set_emd_bounds(h_, on ? 1 : 0)); }
+	// ... and their product over presence bits folded fold-to-1 (0: off; 8, 16 or 32), exact counts for the pairs the screen leaves open (identical flags)
+	void set_fold_screen(int fold) { check(msc_set_fold_screen(h_, fold)); }
 	// Q x M calls over two sparse sets on the matrix-core route, mirrors built from their lists (identical results)
 	void set_sparse_matrix_pass(bool on) { check(msc_set_sparse_matrix_pass(h_, on ? 1 : 0)); }
 	void check(int rc) const { if (rc != MSC_OK) throw Error(rc, msc_last_error(h_)); }
