@@ -1,6 +1,7 @@
 // msc_api.hip -- the C ABI of libmeshclust2_hip.so (include/meshclust2_hip.h) and the host logic behind it: the context, histogram sets
 // and their builds -- sequence encoding, 2-bit packing --, copies, weights-file parsing. The scoring calls live in
-// msc_api_score.hip (1 x M), msc_api_multi.hip (Q x M), msc_api_batch.hip (the update stage); r05 split.
+// msc_api_score.hip (1 x M), msc_api_multi.hip (Q x M), msc_api_batch.hip (the update stage); r05 split. The mirrors a set carries for the
+// Q x M calls -- their builds, frees, stale marks and sizes -- live in msc_mirrors.hip.
 // All compute on histograms happens in the gfx950 kernels (hist_build.hip, pair_features.hip); there is no CPU
 // fallback: without a usable HIP device msc_create() fails and nothing else can be called.
 #include <algorithm>
@@ -484,16 +485,7 @@ extern "C" void msc_hist_set_destroy(msc_hist_set* s) {
 	(void)hipStreamSynchronize(s->ctx->stream);
 	if (s->bins) (void)hipFree(s->bins);
 	if (s->scalars) (void)hipFree(s->scalars);
-	if (s->digest) (void)hipFree(s->digest);
-	if (s->kb) (void)hipFree(s->kb);
-	if (s->mb) (void)hipFree(s->mb);
-	if (s->mb_n) (void)hipFree(s->mb_n);
-	if (s->kbf) (void)hipFree(s->kbf);
-	if (s->kbf_x) (void)hipFree(s->kbf_x);
-	if (s->ranks) (void)hipFree(s->ranks);
-	if (s->ranks16) (void)hipFree(s->ranks16);
-	if (s->rk_n) (void)hipFree(s->rk_n);
-	if (s->rk_sum) (void)hipFree(s->rk_sum);
+	free_mirrors(s);          // (msc_mirrors.hip)
 	if (s->sp_mirror) msc_hist_set_destroy(s->sp_mirror);
 	if (s->ent) (void)hipFree(s->ent);
 	if (s->cum) (void)hipFree(s->cum);
@@ -514,8 +506,8 @@ extern "C" uint64_t msc_hist_set_bytes(const msc_hist_set* s) {
 	if (!s) return 0;
 	if (s->sparse)
 		return s->ent_capacity * 12 + (s->scalar_stride + sizeof(MscSparseHdr)) * s->capacity + (s->rkl ? s->rkl_entries * 4 + s->capacity * 12 : 0) + (s->rkm ? s->rkm_entries * 8 + s->capacity * 12 : 0) +
-		       ((s->kb ? s->L.padded_bins / 8 + 32 + (uint64_t)s->mb_pitch * 8 + 4 : 0) + (s->ranks ? (s->rk_pitch + 1) * 4 : 0) + (s->ranks16 ? s->rk_pitch * 2 : 0)) * s->capacity;
-	return (s->L.slot_bytes + (s->digest ? msc_digest_slot_bytes(s->L) : 0) + (s->kb ? s->L.padded_bins / 8 + 32 + (uint64_t)s->mb_pitch * 8 + 4 : 0) + (s->ranks ? (s->rk_pitch + 1) * 4 : 0) + s->scalar_stride) * s->capacity;
+		       mirror_bytes_per_slot(s) * s->capacity;
+	return (s->L.slot_bytes + mirror_bytes_per_slot(s) + s->scalar_stride) * s->capacity;
 }
 
 extern "C" int msc_hist_set_build_info(const msc_hist_set* s, char* builder, size_t cap, uint64_t* max_count, uint64_t* max_sum, uint64_t* max_nnz) {
@@ -525,15 +517,6 @@ extern "C" int msc_hist_set_build_info(const msc_hist_set* s, char* builder, siz
 	if (max_sum) *max_sum = s->max_sum;
 	if (max_nnz) *max_nnz = s->sparse ? s->max_nnz : 0;
 	return MSC_OK;
-}
-
-// every writer of slots ends here: the mirrors the set has (dense: digest, sparse lists, presence bits, ranks; sparse: presence bits,
-// ranks) are stale for [first, first + n)
-static void mark_stale(msc_hist_set* s, uint64_t first, uint64_t n) {
-	if (s->digest) s->dg_stale.add(first, n);
-	if (s->sp_mirror) s->sm_stale.add(first, n);
-	if (s->kb) s->kb_stale.add(first, n);
-	if (s->ranks) s->rk_stale.add(first, n);
 }
 
 static void forget_lengths(const msc_hist_set* s, uint64_t first, uint64_t n) {

@@ -1,5 +1,7 @@
-// msc_api_multi.hip -- msc_score_multi, the Q x M all-pairs call (fastcar's loop, fastcar/FC_Runner.cpp:426-471): the mirrors of a dense set it
-// reads (digest, presence bits, ranks), the routes, the block pipe over three streams. Split from msc_api.hip in r05.
+// msc_api_multi.hip -- msc_score_multi, the Q x M all-pairs call (fastcar's loop, fastcar/FC_Runner.cpp:426-471): the block plan, a route per
+// block, one function per route and, for the matrix cores, one per stage of the block pipe over three streams (the stage decisions themselves are
+// plain arithmetic in msc_multi_plan.h). The mirrors of a set it reads (digest, presence bits, ranks) are built in msc_mirrors.hip. Split from
+// msc_api.hip in r05.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -11,214 +13,6 @@
 
 #include "msc_objects.h"
 #include "msc_api_private.h"
-
-// The digest mirror of a dense 32-bit set (pair_digest.hip): allocated on first use, refreshed for the slots written since.
-// Returns MSC_OK with set->digest == nullptr when the mirror cannot be had (no memory): the caller then streams the raw bins.
-static int ensure_digest(msc_ctx* ctx, const msc_hist_set* set) {
-	if (set->sparse || !msc_digest_supported(set->L) || set->digest_unavailable) return MSC_OK;
-	if (!set->digest) {
-		void* p = nullptr;
-		if (hipMalloc(&p, msc_digest_slot_bytes(set->L) * set->capacity) != hipSuccess) {
-			(void)hipGetLastError();
-			set->digest_unavailable = true;
-			return MSC_OK;
-		}
-		set->digest = (uint8_t*)p;
-		set->dg_stale.all(set->capacity);
-	}
-	if (set->dg_stale.any()) {
-		HIP_TRY(ctx, msc_launch_digest_build(ctx->stream, set->L, set->bins, set->scalars, set->digest, set->dg_stale.lo, set->dg_stale.hi - set->dg_stale.lo));
-		set->dg_stale.clear();
-	}
-	return MSC_OK;
-}
-
-// The presence-bit mirror of a set and its lists of large bins (msc_pair_gemm.hip): the operands of the int8 product that takes the
-// Q x M pass. A dense set's come from its bins, a sparse set's from its entry lists (the same bytes for the same sequences; every slot of
-// the stale range is rebuilt, a slot without a list as an all-zero image). MSC_OK with set->kb == nullptr when it cannot be had (no
-// memory): the older routes then run.
-int ensure_kb(msc_ctx* ctx, const msc_hist_set* set, bool want_fold) {
-	if (set->kb_unavailable || set->dtype == 64) return MSC_OK;
-	auto give_up = [&] {
-		(void)hipGetLastError();
-		if (set->kb) (void)hipFree(set->kb);
-		if (set->mb) (void)hipFree(set->mb);
-		if (set->mb_n) (void)hipFree(set->mb_n);
-		if (set->kbf) (void)hipFree(set->kbf);
-		if (set->kbf_x) (void)hipFree(set->kbf_x);
-		set->kb = nullptr; set->mb = nullptr; set->mb_n = nullptr; set->kbf = nullptr; set->kbf_x = nullptr; set->kbf_fold = 0;
-		set->kb_unavailable = true;
-		return MSC_OK;
-	};
-	if (!set->kb) {
-		void *p = nullptr, *pm = nullptr, *pn = nullptr;
-		set->mb_pitch = 16;
-		if (hipMalloc(&p, msc_kb_bytes(set->L, set->capacity)) != hipSuccess) return give_up();
-		set->kb = (uint8_t*)p;
-		if (hipMalloc(&pm, (size_t)set->capacity * set->mb_pitch * 8) != hipSuccess) return give_up();
-		set->mb = pm;
-		if (hipMalloc(&pn, (size_t)set->capacity * 4) != hipSuccess) return give_up();
-		set->mb_n = (uint32_t*)pn;
-		HIP_TRY(ctx, hipMemsetAsync(set->mb_n, 0, (size_t)set->capacity * 4, ctx->stream));
-		set->mb_n_host.assign(set->capacity, 0);
-		set->kb_stale.all(set->capacity);
-	}
-	auto written = [&](uint64_t i) { return set->written[i] != 0; };
-	while (set->kb_stale.any()) {
-		// runs of slots that hold a histogram; the build reports a zero count (sticky: the pass's identities take count - 1 of every
-		// bin) and the longest list of large bins it met: past the pitch, the lists are laid out again and every written slot rebuilt
-		int r;
-		if ((r = ensure(ctx, ctx->rk_bad, 2 * sizeof(int32_t)))) return r;
-		HIP_TRY(ctx, hipMemsetAsync(ctx->rk_bad.p, 0, 2 * sizeof(int32_t), ctx->stream));
-		const uint64_t lo = set->kb_stale.lo, hi = std::min<uint64_t>(set->kb_stale.hi, set->sparse ? set->capacity : set->written.size());
-		if (set->sparse) {          // every slot of the range: one without a list gets an all-zero image and an empty list
-			if (hi > lo) HIP_TRY(ctx, msc_launch_kb_build_sparse(ctx->stream, set->L, set->ent, set->hdr, set->kb, lo, hi - lo, set->mb, set->mb_n, set->mb_pitch, (int32_t*)ctx->rk_bad.p));
-		} else if ((r = for_each_run(lo, hi, written, [&](uint64_t first, uint64_t n) {
-			            HIP_TRY(ctx, msc_launch_kb_build(ctx->stream, set->L, set->dtype, set->bins, set->kb, first, n, set->mb, set->mb_n, set->mb_pitch, (int32_t*)ctx->rk_bad.p));
-			            return (int)MSC_OK;
-		            })))
-			return r;
-		int32_t flags[2] = {0, 0};
-		HIP_TRY(ctx, hipMemcpyAsync(flags, ctx->rk_bad.p, sizeof flags, hipMemcpyDeviceToHost, ctx->stream));
-		if (hi > lo) HIP_TRY(ctx, hipMemcpyAsync(set->mb_n_host.data() + lo, set->mb_n + lo, (hi - lo) * 4, hipMemcpyDeviceToHost, ctx->stream));
-		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-		if (flags[0]) set->kb_has_zero = true;
-		if (set->kbf) set->kbf_stale.add(lo, hi > lo ? hi - lo : 0);          // (invalidated wherever kb is)
-		set->kb_stale.clear();
-		if ((uint32_t)flags[1] > set->mb_pitch) {
-			const uint32_t pitch = ((uint32_t)flags[1] + 15) / 16 * 16;
-			void* pm = nullptr;
-			(void)hipFree(set->mb);
-			set->mb = nullptr;
-			if (hipMalloc(&pm, (size_t)set->capacity * pitch * 8) != hipSuccess) return give_up();
-			set->mb = pm;
-			set->mb_pitch = pitch;
-			set->kb_stale.all(set->capacity);
-		}
-	}
-	// the folded mirror beside it (msc_fold.h), for the fold the context asks for: set-up work on a resident set, done once and refreshed with kb.
-	// Without memory for it the set is simply not folded. (want_fold: the call is one the folded screen serves -- msc_search_pairs builds none.)
-	if (!want_fold || !set->kb) return MSC_OK;
-	const uint32_t fold = msc_fold_fits(set->L, ctx->fold_screen) ? ctx->fold_screen : 0;
-	if (set->kbf && set->kbf_fold != fold) {
-		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-		(void)hipFree(set->kbf); (void)hipFree(set->kbf_x);
-		set->kbf = nullptr; set->kbf_x = nullptr; set->kbf_fold = 0;
-	}
-	if (fold && !set->kbf) {
-		MscLayout Lf = set->L;
-		Lf.padded_bins = Lf.nbins = set->L.nbins / fold;
-		void *p = nullptr, *px = nullptr;
-		if (hipMalloc(&p, msc_kb_bytes(Lf, set->capacity)) != hipSuccess || hipMalloc(&px, (set->capacity + 31) / 32 * 32 * sizeof(uint32_t)) != hipSuccess) {
-			(void)hipGetLastError();
-			if (p) (void)hipFree(p);
-			return MSC_OK;
-		}
-		set->kbf = (uint8_t*)p; set->kbf_x = (uint32_t*)px; set->kbf_fold = fold;
-		set->kbf_stale.all(set->capacity);
-	}
-	if (set->kbf && set->kbf_stale.any()) {
-		HIP_TRY(ctx, msc_launch_kb_fold(ctx->stream, set->L.nbins, fold, set->kb, set->kbf, set->kbf_x, set->kbf_stale.lo, set->kbf_stale.hi - set->kbf_stale.lo));
-		set->kbf_stale.clear();
-	}
-	return MSC_OK;
-}
-
-// The ranks mirror of a set (msc_emd_ranks.hip), from a dense set's bins or a sparse set's lists. MSC_OK with set->ranks == nullptr when
-// it cannot be had (no memory, or a slot holds a zero count): the digest kernel then keeps the prefixes.
-int ensure_ranks(msc_ctx* ctx, const msc_hist_set* set) {
-	if (set->dtype == 64 || !msc_digest_supported(set->L) || set->ranks_unavailable || set->max_sum < set->L.nbins) return MSC_OK;
-	const uint64_t pitch = msc_ranks_pitch(set->max_sum - set->L.nbins);
-	if (set->ranks && pitch > set->rk_pitch) {          // a longer list than any before: lay the mirror out again
-		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-		(void)hipFree(set->ranks);
-		set->ranks = nullptr;
-		if (set->ranks16) { (void)hipFree(set->ranks16); set->ranks16 = nullptr; }
-		set->rk16_off = false;
-	}
-	if (!set->ranks) {
-		void *p = nullptr, *pn = set->rk_n;
-		if (hipMalloc(&p, pitch * 4 * set->capacity) != hipSuccess || (!pn && hipMalloc(&pn, 4 * set->capacity) != hipSuccess)) {
-			(void)hipGetLastError();
-			if (p) (void)hipFree(p);
-			set->ranks_unavailable = true;
-			return MSC_OK;
-		}
-		set->ranks = (uint32_t*)p;
-		set->rk_n = (uint32_t*)pn;
-		set->rk_pitch = pitch;
-		set->rk_stale.all(set->capacity);
-		if (!set->rk_sum) {          // the two moments per slot (msc_emd_list.hip), built with the rows below; without them the close flags take the dense walk
-			void* pm = nullptr;
-			if (hipMalloc(&pm, 2 * sizeof(uint64_t) * set->capacity) != hipSuccess) (void)hipGetLastError();
-			else { set->rk_sum = (uint64_t*)pm; set->rk_dev = set->rk_sum + set->capacity; }
-		}
-	}
-	static const bool no_rk16 = getenv("MSC_NO_RANKS16") != nullptr;
-	if (!set->ranks16 && !set->rk16_off && !no_rk16 && set->rk_pitch % 1024 == 0) {          // the 16-bit form beside it (k_emd_ranks16)
-		void* p16 = nullptr;
-		if (hipMalloc(&p16, set->rk_pitch * 2 * set->capacity) != hipSuccess) { (void)hipGetLastError(); set->rk16_off = true; }
-		else { set->ranks16 = (uint16_t*)p16; set->rk_stale.all(set->capacity); }
-	}
-	if (set->rk_stale.any()) {
-		int r;
-		if ((r = ensure(ctx, ctx->rk_bad, 2 * sizeof(int32_t)))) return r;
-		HIP_TRY(ctx, hipMemsetAsync(ctx->rk_bad.p, 0, 2 * sizeof(int32_t), ctx->stream));
-		// runs of slots that hold a histogram (an unwritten slot's digest is whatever the allocation held)
-		const uint64_t lo = set->rk_stale.lo, hi = std::min<uint64_t>(set->rk_stale.hi, set->sparse ? set->capacity : set->written.size());
-		int32_t* bad_word = (int32_t*)ctx->rk_bad.p;
-		auto build16 = [&](uint64_t first, uint64_t n) {          // (a dense set: and the moments of the same rows, msc_emd_list.hip)
-			if (set->rk_sum && !set->sparse) HIP_TRY(ctx, msc_launch_rank_moments(ctx->stream, set->L.nbins, set->ranks, set->rk_pitch, first, n, set->rk_sum, set->rk_dev));
-			if (set->ranks16) HIP_TRY(ctx, msc_launch_ranks16_build(ctx->stream, set->L.nbins, set->ranks, set->ranks16, set->rk_pitch, first, n, bad_word + 1));
-			return (int)MSC_OK;
-		};
-		if (set->sparse) {
-			// the 32-bit ranks of every slot of the range from its list (one without a list: all padding, n = 0); the 16-bit form only of the
-			// runs that hold a list, as a dense set's unwritten slots are skipped: the ranks16 row of an empty slot is NOT maintained (all
-			// padding does not fit 16 bits and would switch the form off for the set; nothing reads a row past its rk_n = 0)
-			if (hi > lo) HIP_TRY(ctx, msc_launch_ranks_build_sparse(ctx->stream, set->L, set->ent, set->cum, set->hdr, set->ranks, set->rk_n, set->rk_pitch, lo, hi - lo, bad_word));
-			if (hi > lo && set->rk_sum) HIP_TRY(ctx, msc_launch_rank_moments(ctx->stream, set->L.nbins, set->ranks, set->rk_pitch, lo, hi - lo, set->rk_sum, set->rk_dev));
-			if ((r = for_each_run(lo, hi, [&](uint64_t i) { return set->hdr_host[i].nnz != 0; }, build16))) return r;
-		} else if ((r = for_each_run(lo, hi, [&](uint64_t i) { return set->written[i] != 0; }, [&](uint64_t first, uint64_t n) {
-			            HIP_TRY(ctx, msc_launch_ranks_build(ctx->stream, set->L, set->dtype, set->bins, set->scalars, set->ranks, set->rk_n, set->rk_pitch, first, n, bad_word));
-			            return build16(first, n);
-		            })))
-			return r;
-		int32_t bad[2] = {0, 0};
-		HIP_TRY(ctx, hipMemcpyAsync(bad, ctx->rk_bad.p, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
-		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-		set->rk_stale.clear();
-		if (bad[0]) {
-			(void)hipFree(set->ranks);
-			set->ranks = nullptr;
-			set->ranks_unavailable = true;
-		}
-		if ((bad[0] || bad[1]) && set->ranks16) {          // a reduced rank that does not fit 16 bits: this set keeps the 32-bit walk
-			(void)hipFree(set->ranks16);
-			set->ranks16 = nullptr;
-			set->rk16_off = true;
-		}
-	}
-	return MSC_OK;
-}
-
-// Whether the pass on the matrix cores (msc_pair_gemm.hip) can take a Q x M call over these sets -- host-side bounds only: dense 8/16/32-bit
-// sets of the narrow range whose histograms are whole 4 KiB tiles, P1 / P2 within int32 and, when
-// the earth mover's distance is wanted, lists short enough for the ranks mirror (msc_emd_ranks.hip). Two sparse sets under the same
-// bounds with msc_set_sparse_matrix_pass on, up to 2^20 bins (their mirrors come from the lists); never one of each.
-bool kb_route_fits(const msc_hist_set* cands, const msc_hist_set* qset, bool need_emd) {
-	static const bool off = getenv("MSC_MULTI_NO_GEMM") != nullptr;
-	static const bool no_ranks = getenv("MSC_MULTI_NO_RANKS") != nullptr;
-	const MscLayout& L = cands->L;
-	if (cands->sparse != qset->sparse || (cands->sparse && (!cands->ctx->sparse_matrix_pass || L.nbins > (1ull << 20)))) return false;
-	// (what msc_launch_kb_build_sparse asks of the layout, so that a set it cannot serve stays on the list passes instead of failing the call)
-	if (cands->sparse && !msc_kb_build_sparse_fits(L)) return false;
-	if (off || cands->dtype == 64 || L.nbins != L.padded_bins || !msc_digest_supported(L) || needs_wide(cands, qset)) return false;
-	const uint64_t ms_ = std::max(cands->max_sum, qset->max_sum);
-	if (ms_ < L.nbins || ms_ - L.nbins >= (1ull << 24)) return false;          // (P1 <= the k-mers of either sequence is summed in f32: exact below 2^24; the corrections stay within int32)
-	if (need_emd && (no_ranks || L.nbins > (1ull << 20) || (ms_ - L.nbins) * 4 > L.nbins)) return false;
-	return true;
-}
 
 
 // the epilogue's error word (the stream is idle)
@@ -348,7 +142,6 @@ struct Block {
 	hipStream_t tail = nullptr;                  // where the epilogue and the copies home run
 	bool div_pass = false;                       // divergence statistics from a merge pass per query (not from cells)
 	uint32_t idx = 0;                            // the block's place in the call's plan
-	bool no_fold = false;                        // matrix: the block ran folded and its list overflowed -- this is its second run, with the true product
 	SparseKernel spk = SPK_MP;                   // ... one merge kernel for the whole block ...
 	uint32_t dvn = 1;                            // ... and its {jd, js} records per pair
 };
@@ -389,7 +182,9 @@ int flush_deferred(MultiCall& c) {
 	return read_error_word(ctx);
 }
 
-// The route of block [q_slots, q_slots + nq) -- the only reader of the MSC_MULTI_*, MSC_GEMM_NO_QUEUE, MSC_SPARSE_NO_* and MSC_DIGEST_* switches.
+// The route of block [q_slots, q_slots + nq) -- the only reader of the MSC_MULTI_*, MSC_GEMM_NO_QUEUE, MSC_SPARSE_NO_* and MSC_DIGEST_* switches
+// (a route's own switches are read where its facts are gathered: matrix_facts reads MSC_NO_SCREEN and MSC_GEMM_NO_PREP, run_sparse_queued
+// MSC_NO_RANKS_1XM; msc_mirrors.hip reads MSC_MULTI_NO_GEMM / _NO_RANKS and MSC_NO_RANKS16 for the mirrors).
 // may_matrix: the plan offers the block to the matrix cores and only asks whether they take it; otherwise the choice is among the other routes.
 //   matrix  EVERYTHING on the matrix cores (msc_pair_gemm.hip): one int8 product per tile of bins over the presence-bit mirrors + corrections from
 //           the lists of large bins -- exact for any counts of the narrow range. The queries' large bins become the block's hot list (its size is
@@ -757,171 +552,297 @@ int run_streamed(MultiCall& c, Block& b, const BlockRoute& rt) {
 // MSC_GEMM_NO_PREP: the queries' side on the product's stream, as in r04.) The close flags go into one of two buffers and home on the copy stream, under the next block's kernels.
 // A flags-only block whose distance comes from the ranks mirrors runs no walk beside the product: its tail is the bound screen, the walk and the FP64 evaluation of
 // the listed pairs, then the dense walk and the two older epilogue kernels predicated on the list's overflow word (msc_emd_list.hip).
-// Such a block in one chunk runs its product over bits folded F-to-1 where both sets carry the folded mirror (msc_fold.h): `fold` below.
-int run_matrix(MultiCall& c, Block& b, const BlockRoute& rt) {
+// Such a block in one chunk runs its product over bits folded F-to-1 where both sets carry the folded mirror (msc_fold.h).
+// What a block decides is plain arithmetic (msc_matrix_stages, msc_multi_plan.h) over facts gathered in one place (matrix_facts); run_matrix is the order of the
+// stages, one function each. A stage issues, in its own order, everything it puts on a stream: a re-cut of what was one body, in the same order.
+
+// the facts of a block on the matrix cores -- beside pick_route the only reader of environment switches here: MSC_NO_SCREEN (FP64 for every pair of
+// a flags-only block), MSC_GEMM_NO_PREP. second_run: rerun_overflowed's
+MscMatrixFacts matrix_facts(const MultiCall& c, const Block& b, const BlockRoute& rt, bool second_run) {
+	static const bool no_screen = getenv("MSC_NO_SCREEN") != nullptr;
+	static const bool no_prep = getenv("MSC_GEMM_NO_PREP") != nullptr;
+	const msc_ctx* ctx = c.ctx;
+	const msc_hist_set *cands = c.cands, *qset = c.qset;
+	MscMatrixFacts f;
+	f.model = c.model != nullptr; f.screen_ok = c.model && c.model->h.screen_ok;
+	f.close = b.close != nullptr; f.sum = b.sum != nullptr; f.csum = b.csum != nullptr; f.raw = b.raw != nullptr;
+	f.want_div = c.want_div; f.want_grp = c.want_grp; f.div_pass = b.div_pass;
+	f.no_screen = no_screen; f.no_prep = no_prep;
+	f.queued = rt.queued; f.emd_ranks = rt.emd_ranks;
+	f.block_pipe = ctx->block_pipe; f.emd_bounds = ctx->emd_bounds; f.fold_screen = ctx->fold_screen;
+	f.emd_decides = c.model && c.model->emd_decides; f.fold_overflows = c.model && c.model->fold_overflows;
+	f.rk_pitch_c = cands->rk_pitch; f.rk_pitch_q = qset->rk_pitch; f.moments_c = cands->rk_sum != nullptr; f.moments_q = qset->rk_sum != nullptr;
+	f.kbf_c = cands->kbf != nullptr; f.kbf_q = qset->kbf != nullptr; f.kbf_fold_c = cands->kbf_fold; f.kbf_fold_q = qset->kbf_fold;
+	f.second_run = second_run;
+	f.n_q = b.nq; f.m = c.m; f.chunk = b.chunk;
+	return f;
+}
+
+// a block on the matrix cores: what is settled before anything of it is issued, and what its stages hand one another
+struct MatrixBlock {
+	MscMatrixStages st;                               // the decisions
+	const BlockRoute* rt = nullptr;
+	uint32_t rows = 0, slices = 0, slices_f = 0;      // query rows of the product; slices of its array over the true bins, and over the bins it runs on
+	uint64_t nbins_f = 0;                             // the bins the product runs on: 4^k, folded 4^k / fold
+	int pb = 0;                                       // the side of the pipe the block takes
+	BlockPipe::Side* s = nullptr;
+	hipStream_t prep = nullptr;                       // where the queries' side runs
+	HotList hot;
+};
+// a chunk's tail: the epilogue's arguments, and the one of the two buffers its close flags go into
+struct Tail { MscEpilogueArgs ea; int pp = 0; uint8_t* d_close = nullptr; };
+
+// (b.chunk and b.div_pass are set) -- takes the block's turn on the pipe and names its streams
+MatrixBlock plan_matrix(const MultiCall& c, Block& b, const BlockRoute& rt, uint32_t rows, bool second_run) {
 	msc_ctx* ctx = c.ctx;
 	BlockPipe& pipe = ctx->pipe;
-	const msc_hist_set *cands = c.cands, *qset = c.qset;
-	const MscLayout& L = cands->L;
-	const uint64_t n_q = b.nq, m = c.m;
-	const bool queued = rt.queued;
-	int r;
-	if ((r = begin_block(ctx))) return r;
-	if ((r = block_uploads(c, b, queued))) return r;
-	const uint32_t rows = msc_pair_gemm_rows((uint32_t)n_q);
-	b.chunk = matrix_chunks(ctx, L.nbins, m, rows, group_chunk_limit(c, n_q)).chunk;
-	b.div_pass = c.want_div && !c.cells;
-	if ((r = ensure_block_scratch(c, b, true))) return r;
-	const uint32_t slices = msc_pair_gemm_slices(L.nbins, (uint32_t)b.chunk, rows, ctx->num_cus);
-	// only the close flags are wanted: k_pair_epilogue_bits decides them in f32 with an error bound and evaluates in FP64 only the
-	// pairs the bound leaves open -- the same flags (MSC_NO_SCREEN: FP64 for every pair)
-	static const bool no_screen = getenv("MSC_NO_SCREEN") != nullptr;
-	const bool screen = c.model && c.model->h.screen_ok && b.close && !b.sum && !b.csum && !b.raw && !c.want_div && !c.want_grp && !no_screen;
-	// ... and with the distance from the ranks mirrors of two sets of one pitch (what k_emd_ranks16 asks too), first from BOUNDS of the distance
-	// (msc_emd_list.hip): the ranks are walked only for the pairs the bounds leave open, up to 1 / 64 of the chunk's pairs -- past that share a
-	// walk per pair reads more than the dense walk. msc_set_emd_bounds(0), a model remembered for overflowing, sets without moments: today's path
-	const bool walk_counted = screen && rt.emd_ranks;
-	const bool bounds_call = walk_counted && ctx->emd_bounds && !c.model->emd_decides && cands->rk_pitch == qset->rk_pitch && cands->rk_sum && qset->rk_sum;
-	// ... and there, in one chunk, with the PRODUCT over bits folded F-to-1 (msc_fold.h): 1 / F of the matrix operations for upper
-	// bounds of P1 and P2, which the screen takes as intervals; the listed pairs get their exact counts (k_fold_exact_list). msc_set_fold_screen(0),
-	// a model remembered for overflowing the folded stage's list, sets without a folded mirror (k = 5): the true product
-	const uint32_t fold = bounds_call && !b.no_fold && b.chunk == m && n_q * m <= 0xffffffffull && n_q * m >= 64 && !c.model->fold_overflows && cands->kbf && qset->kbf &&
-	                              cands->kbf_fold == ctx->fold_screen && qset->kbf_fold == ctx->fold_screen
-	                          ? ctx->fold_screen : 0;
-	const uint64_t nbins_f = fold ? L.nbins / fold : L.nbins;
-	const uint32_t slices_f = fold ? msc_pair_gemm_slices(nbins_f, (uint32_t)b.chunk, rows, ctx->num_cus) : slices;
-	const bool piped = queued && b.chunk == m && !b.div_pass && !c.want_grp && ctx->block_pipe;
-	const int pb = piped ? (int)(pipe.next++ & 1) : 0;
-	BlockPipe::Side& s = pipe.side[pb];
-	b.tail = piped ? pipe.tail_stream : ctx->stream;
-	static const bool no_prep = getenv("MSC_GEMM_NO_PREP") != nullptr;
-	hipStream_t prep = piped && !no_prep ? pipe.prep_stream : ctx->stream;
-	if (pipe.tail_used)          // a block on ONE stream after piped ones waits for every epilogue in flight; a piped one for the epilogue that read its side
-		for (int i = 0; i < 2; i++)
-			if (pipe.side[i].tail_busy && (!piped || i == pb)) {
-				HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, pipe.side[i].ev_tail, 0));
-				if (prep != ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(prep, pipe.side[i].ev_tail, 0));          // (it rewrites the transposed image that epilogue read)
-				if (!piped) pipe.side[i].tail_busy = false;
-			}
-	HotList hot;
-	if ((r = ensure_side(ctx, s, L.nbins, rows, std::max(slices, slices_f), b.chunk, rt.n_hot, &hot))) return r;
+	const uint64_t nbins = c.cands->L.nbins;
+	MatrixBlock p;
+	p.st = msc_matrix_stages(matrix_facts(c, b, rt, second_run));
+	p.rt = &rt;
+	p.rows = rows;
+	p.slices = msc_pair_gemm_slices(nbins, (uint32_t)b.chunk, rows, ctx->num_cus);
+	p.nbins_f = p.st.fold ? nbins / p.st.fold : nbins;
+	p.slices_f = p.st.fold ? msc_pair_gemm_slices(p.nbins_f, (uint32_t)b.chunk, rows, ctx->num_cus) : p.slices;
+	p.pb = p.st.piped ? (int)(pipe.next++ & 1) : 0;
+	p.s = &pipe.side[p.pb];
+	b.tail = p.st.piped ? pipe.tail_stream : ctx->stream;
+	p.prep = p.st.own_prep_stream ? pipe.prep_stream : ctx->stream;
+	return p;
+}
+
+// before a side is reused: a block on ONE stream after piped ones waits for every epilogue in flight; a piped one for the epilogue that read its side
+int wait_side_free(msc_ctx* ctx, const MatrixBlock& p) {
+	BlockPipe& pipe = ctx->pipe;
+	if (!pipe.tail_used) return MSC_OK;
+	for (int i = 0; i < 2; i++)
+		if (pipe.side[i].tail_busy && (!p.st.piped || i == p.pb)) {
+			HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, pipe.side[i].ev_tail, 0));
+			if (p.prep != ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(p.prep, pipe.side[i].ev_tail, 0));          // (it rewrites the transposed image that epilogue read)
+			if (!p.st.piped) pipe.side[i].tail_busy = false;
+		}
+	return MSC_OK;
+}
+
+// the queries' side of the block, once for all chunks of candidates, on its stream; the product's stream waits for it (ev_prep)
+int queries_side(const MultiCall& c, const Block& b, const MatrixBlock& p) {
+	msc_ctx* ctx = c.ctx;
+	const msc_hist_set* qset = c.qset;
+	const uint64_t nbins = c.cands->L.nbins, n_hot = p.rt->n_hot;
+	const uint32_t n_q = (uint32_t)b.nq, rows = p.rows;
+	BlockPipe::Side& s = *p.s;
+	hipStream_t prep = p.prep;
 	if (prep != ctx->stream) {
-		HIP_TRY(ctx, hipStreamWaitEvent(prep, pipe.ev_call, 0));          // the call's query slots are up
+		HIP_TRY(ctx, hipStreamWaitEvent(prep, ctx->pipe.ev_call, 0));          // the call's query slots are up
 		if (s.product_busy) HIP_TRY(ctx, hipStreamWaitEvent(prep, s.ev_product, 0));      // the product that read this side is through
 	}
-	// the queries' side of the block, once for all chunks of candidates
-	if (fold) {          // the transposed planes from the true mirror (the epilogue's walk of the candidate's large bins stays exact), the tiles and the hot list folded
-		HIP_TRY(ctx, msc_launch_kb_gather(prep, L.nbins, qset->kb, b.dq_slots, (uint32_t)n_q, rows, (uint8_t*)s.qT.p, nullptr));
-		HIP_TRY(ctx, msc_launch_kb_gather(prep, nbins_f, qset->kbf, b.dq_slots, (uint32_t)n_q, rows, nullptr, (uint8_t*)s.anib.p));
-		HIP_TRY(ctx, msc_launch_hot_list(prep, L.nbins, fold, qset->mb, qset->mb_n, qset->mb_pitch, b.dq_slots, (uint32_t)n_q, rows, (uint8_t*)s.qT.p, rt.n_hot, s.hot.p, hot.ptr,
-		                                 hot.cursor, hot.cnt));
+	if (p.st.fold) {          // the transposed planes from the true mirror (the epilogue's walk of the candidate's large bins stays exact), the tiles and the hot list folded
+		HIP_TRY(ctx, msc_launch_kb_gather(prep, nbins, qset->kb, b.dq_slots, n_q, rows, (uint8_t*)s.qT.p, nullptr));
+		HIP_TRY(ctx, msc_launch_kb_gather(prep, p.nbins_f, qset->kbf, b.dq_slots, n_q, rows, nullptr, (uint8_t*)s.anib.p));
+		HIP_TRY(ctx, msc_launch_hot_list(prep, nbins, p.st.fold, qset->mb, qset->mb_n, qset->mb_pitch, b.dq_slots, n_q, rows, (uint8_t*)s.qT.p, n_hot, s.hot.p, p.hot.ptr,
+		                                 p.hot.cursor, p.hot.cnt));
 	} else
-		HIP_TRY(ctx, msc_launch_pair_gemm_queries(prep, L.nbins, qset->kb, qset->mb, qset->mb_n, qset->mb_pitch, b.dq_slots, (uint32_t)n_q, rows, (uint8_t*)s.qT.p, rt.n_hot, s.hot.p,
-		                                          hot.ptr, hot.cursor, hot.cnt, (uint8_t*)s.anib.p));
+		HIP_TRY(ctx, msc_launch_pair_gemm_queries(prep, nbins, qset->kb, qset->mb, qset->mb_n, qset->mb_pitch, b.dq_slots, n_q, rows, (uint8_t*)s.qT.p, n_hot, s.hot.p,
+		                                          p.hot.ptr, p.hot.cursor, p.hot.cnt, (uint8_t*)s.anib.p));
 	if (prep != ctx->stream) {
 		HIP_TRY(ctx, hipEventRecord(s.ev_prep, prep));
 		HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.ev_prep, 0));
 	}
-	if (rt.emd_ranks && (r = ensure(ctx, ctx->emd_out, b.chunk * rows * sizeof(uint64_t)))) return r;
-	name_matrix_kernel(ctx, rows, rt.emd_ranks, c.cells, cands->sparse, fold);
-	ctx->last_query_tile = (int)n_q;
-	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_all0, ctx->stream));
-	for (uint64_t off = 0; off < m; off += b.chunk) {
-		const Chunk k = chunk_at(c, b, off);
-		hipEvent_t ev_t0 = ctx->ev_tiles0, ev_t1 = ctx->ev_tiles1;
-		if (queued && ctx->timing && ((r = pool_event(ctx, &ev_t0)) || (r = pool_event(ctx, &ev_t1)))) return r;      // (read when the call's last block is through)
-		if (piped) {          // everything the tail needs from this stream so far (slot lists, the cleared error word) is behind this mark
-			HIP_TRY(ctx, hipEventRecord(s.ev_head, ctx->stream));
-			HIP_TRY(ctx, hipStreamWaitEvent(b.tail, s.ev_head, 0));
-		}
-		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ev_t0, ctx->stream));
-		// the whole pass over the candidates' bins: products and level products on the matrix cores (timed as the streaming kernel)
-		HIP_TRY(ctx, msc_launch_pair_gemm(ctx->stream, nbins_f, fold ? cands->kbf : cands->kb, k.d_slots, off, k.mc, rows, slices_f, hot.ptr, s.hot.p, (int32_t*)s.min.p, (int32_t*)s.diff.p,
-		                                  (const uint8_t*)s.anib.p));
-		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ev_t1, ctx->stream));
-		if (piped) { HIP_TRY(ctx, hipEventRecord(s.ev_product, ctx->stream)); s.product_busy = true; }
-		const bool bounds = bounds_call && n_q * (uint64_t)k.mc <= 0xffffffffull && n_q * (uint64_t)k.mc >= 64;          // (fewer than 64 pairs: a list of no entries)
-		const uint32_t open_cap = bounds ? (uint32_t)(n_q * k.mc / 64) : 0;
-		uint32_t* open_words = nullptr;
-		if (walk_counted && !b.no_fold) { ctx->walk_blocks++; if (!bounds) ctx->walk_dense++; }          // (no_fold: the block was counted when it ran folded)
-		if (bounds) {
-			if ((r = ensure(ctx, ctx->open_list, std::max<size_t>(1, open_cap) * sizeof(uint32_t))) || (r = ensure(ctx, ctx->emd_list, std::max<size_t>(1, open_cap) * sizeof(uint64_t)))) return r;
-			open_words = (uint32_t*)ctx->open_words.p;          // (allocated and cleared when the call began, on the product's stream: behind ev_head for a piped block)
-			if (!b.no_fold) ctx->walk_bound_blocks++;
-		} else if (rt.emd_ranks)
-			HIP_TRY(ctx, launch_emd_ranks(b.tail, cands, qset, k.d_slots, off, k.mc, b.dq_slots, (uint32_t)n_q, (uint64_t*)ctx->emd_out.p, rows));
-		MscEpilogueArgs ea;
-		fill_block_args(c, b, b.dq_slots, k, L.S, ea);
-		if ((r = side_passes(c, b, k, ea))) return r;
-		fill_matrix_args(ea, s, cands, qset, slices, rows, c.cand_slots ? 0 : off, rt.n_hot, rt.emd_ranks ? ctx->emd_out.p : nullptr);
-		ea.cq_group = 16;
-		if (c.cells) { ea.div_cells = 1; ea.kb_c_bits = cands->kb; }          // the two sums in the epilogue, as msc_search_pairs sets them (msc_api_pairs.hip)
-		const int pp = pipe.close_pp_next;
-		uint8_t* d_close = b.close ? (uint8_t*)pipe.close_pp[pp].p : nullptr;
-		if (b.close) {
-			pipe.close_pp_next ^= 1;
-			if (pipe.close_pp_busy[pp]) HIP_TRY(ctx, hipStreamWaitEvent(b.tail, pipe.ev_copied[pp], 0));
-		}
-		ea.close_soa = d_close;
-		ea.screen = screen;
-		if (piped) HIP_TRY(ctx, hipStreamWaitEvent(b.tail, s.ev_product, 0));
-		if (bounds) {
-			// the bound screen, the walk of the listed pairs, their FP64 evaluation; then today's three kernels, which return at once unless the list
-			// overflowed (then they overwrite every flag of the chunk); then the list's words into the call's totals, cleared for the next block
-			MscEpilogueArgs eb = ea;
-			eb.emd_ranks = nullptr;
-			eb.rk_c_sum = cands->rk_sum; eb.rk_c_dev = cands->rk_dev; eb.rk_q_sum = qset->rk_sum; eb.rk_q_dev = qset->rk_dev;
-			eb.open_list = (uint32_t*)ctx->open_list.p; eb.open_words = open_words; eb.open_cap = open_cap; eb.emd_list = (const uint64_t*)ctx->emd_list.p;
-			const bool u16 = cands->ranks16 && qset->ranks16;
-			auto list_stage = [&](const MscEpilogueArgs& e) {          // screen, walk of the listed pairs, their FP64 evaluation, on e's words
-				HIP_TRY(ctx, msc_launch_epilogue_bound(b.tail, e));
-				if (e.fold_x_c) {          // (the listed pairs of a folded stage: their exact P1 / P2 into the product's arrays first)
-					const MscFoldExact fx{cands->ranks, cands->rk_pitch, L.nbins, L.E, L.R, k.d_slots, off, k.mc, b.dq_slots, e.open_list, e.open_words, open_cap, (const uint8_t*)s.qT.p, rows,
-					                      qset->mb, qset->mb_n, qset->mb_pitch, (int32_t*)s.min.p, e.kb_slices, rt.n_hot ? (int32_t*)s.diff.p : nullptr};
-					HIP_TRY(ctx, msc_launch_fold_exact_list(b.tail, fx, ctx->num_cus));
-				}
-				HIP_TRY(ctx, msc_launch_emd_ranks_list(b.tail, u16, u16 ? (const void*)cands->ranks16 : (const void*)cands->ranks, u16 ? (const void*)qset->ranks16 : (const void*)qset->ranks,
-				                                       cands->rk_pitch, k.d_slots, off, k.mc, b.dq_slots, e.open_list, e.open_words, open_cap, (uint64_t*)ctx->emd_list.p, ctx->num_cus));
-				HIP_TRY(ctx, msc_launch_epilogue_list(b.tail, e, ctx->num_cus));
-				return (int)MSC_OK;
-			};
-			if (fold) {
-				// The folded stage: the screen over intervals, the listed pairs' exact counts, their walk and FP64 evaluation. Should ITS list overflow -- every
-				// related pair is on it, the lower bound of P1 being 0 --, k_emd_list_close raises the block's word of ctx->fold_over and score_multi, once the call's
-				// blocks are through, scores the block again with the true product (no host wait here, and nothing queued for the case that did not arise)
-				MscEpilogueArgs ef = eb;
-				ef.kb_slices = slices_f; ef.fold_x_c = cands->kbf_x; ef.fold_x_q = qset->kbf_x;
-				if ((r = list_stage(ef))) return r;
-				ctx->fold_used = fold;
-				ctx->fold_blocks++;
-			} else {
-				if ((r = list_stage(eb))) return r;
-				HIP_TRY(ctx, launch_emd_ranks(b.tail, cands, qset, k.d_slots, off, k.mc, b.dq_slots, (uint32_t)n_q, (uint64_t*)ctx->emd_out.p, rows, open_words + 1));
-				ea.run_if = open_words + 1;
-			}
-		}
-		if (!fold) HIP_TRY(ctx, msc_launch_epilogue(b.tail, ea));
-		if (bounds) HIP_TRY(ctx, msc_launch_emd_list_close(b.tail, open_words, open_cap, (uint64_t*)(open_words + 2), fold ? (uint32_t*)ctx->fold_over.p + b.idx : nullptr));
-		if (b.close && ctx->close_counts_n) HIP_TRY(ctx, msc_launch_close_counts(b.tail, d_close, (uint32_t)n_q, k.mc, (uint64_t*)ctx->close_counts.p + b.q0));
-		if (piped) {
-			HIP_TRY(ctx, hipEventRecord(s.ev_tail, b.tail));
-			s.tail_busy = true;
-			pipe.tail_used = true;
-		}
-		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_all1, ctx->stream));
-		if ((r = results_home(c, b, k))) return r;
-		if (b.close) {
-			HIP_TRY(ctx, hipEventRecord(pipe.ev_scored[pp], b.tail));
-			HIP_TRY(ctx, hipStreamWaitEvent(pipe.copy_stream, pipe.ev_scored[pp], 0));
-			HIP_TRY(ctx, rows_home(b.close + off, m, d_close, (size_t)k.mc, n_q, pipe.copy_stream));
-			HIP_TRY(ctx, hipEventRecord(pipe.ev_copied[pp], pipe.copy_stream));
-			pipe.close_pp_busy[pp] = true;
-			pipe.copy_pending = true;
-		}
-		if (queued) ctx->tiles_launches++;
-		else if ((r = chunk_done(ctx, ev_t0, ev_t1))) return r;
+	return MSC_OK;
+}
+
+// the whole pass over a chunk's bins: products and level products on the matrix cores, timed as the streaming kernel between ev_t0 and ev_t1
+int product_stage(const MultiCall& c, const Block& b, const MatrixBlock& p, const Chunk& k, hipEvent_t ev_t0, hipEvent_t ev_t1) {
+	msc_ctx* ctx = c.ctx;
+	BlockPipe::Side& s = *p.s;
+	if (p.st.piped) {          // everything the tail needs from this stream so far (slot lists, the cleared error word) is behind this mark
+		HIP_TRY(ctx, hipEventRecord(s.ev_head, ctx->stream));
+		HIP_TRY(ctx, hipStreamWaitEvent(b.tail, s.ev_head, 0));
 	}
-	return queued ? MSC_OK : read_error_word(ctx);
+	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ev_t0, ctx->stream));
+	HIP_TRY(ctx, msc_launch_pair_gemm(ctx->stream, p.nbins_f, p.st.fold ? c.cands->kbf : c.cands->kb, k.d_slots, k.off, k.mc, p.rows, p.slices_f, p.hot.ptr, s.hot.p, (int32_t*)s.min.p,
+	                                  (int32_t*)s.diff.p, (const uint8_t*)s.anib.p));
+	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ev_t1, ctx->stream));
+	if (p.st.piped) { HIP_TRY(ctx, hipEventRecord(s.ev_product, ctx->stream)); s.product_busy = true; }
+	return MSC_OK;
+}
+
+// What every tail does ahead of its epilogue kernels: the epilogue's arguments (the divergence / group passes with them, on the context's stream), a buffer for
+// the flags once its last copy home is through, and the wait for the product. (A tail's kernels that read nothing of the product are queued BEFORE this.)
+int tail_ready(MultiCall& c, Block& b, const MatrixBlock& p, const Chunk& k, Tail& t) {
+	msc_ctx* ctx = c.ctx;
+	BlockPipe& pipe = ctx->pipe;
+	const BlockRoute& rt = *p.rt;
+	MscEpilogueArgs& ea = t.ea;
+	int r;
+	fill_block_args(c, b, b.dq_slots, k, c.cands->L.S, ea);
+	if ((r = side_passes(c, b, k, ea))) return r;
+	fill_matrix_args(ea, *p.s, c.cands, c.qset, p.slices, p.rows, c.cand_slots ? 0 : k.off, rt.n_hot, rt.emd_ranks ? ctx->emd_out.p : nullptr);
+	ea.cq_group = 16;
+	if (c.cells) { ea.div_cells = 1; ea.kb_c_bits = c.cands->kb; }          // the two sums in the epilogue, as msc_search_pairs sets them (msc_api_pairs.hip)
+	t.pp = pipe.close_pp_next;
+	t.d_close = b.close ? (uint8_t*)pipe.close_pp[t.pp].p : nullptr;
+	if (b.close) {
+		pipe.close_pp_next ^= 1;
+		if (pipe.close_pp_busy[t.pp]) HIP_TRY(ctx, hipStreamWaitEvent(b.tail, pipe.ev_copied[t.pp], 0));
+	}
+	ea.close_soa = t.d_close;
+	ea.screen = p.st.screen;
+	if (p.st.piped) HIP_TRY(ctx, hipStreamWaitEvent(b.tail, p.s->ev_product, 0));
+	return MSC_OK;
+}
+
+// the scored tail: the rank walk of every pair where the distance comes from the ranks mirrors (beside the product), then the epilogue
+int tail_scored(MultiCall& c, Block& b, const MatrixBlock& p, const Chunk& k, Tail& t) {
+	msc_ctx* ctx = c.ctx;
+	int r;
+	if (p.rt->emd_ranks) HIP_TRY(ctx, launch_emd_ranks(b.tail, c.cands, c.qset, k.d_slots, k.off, k.mc, b.dq_slots, (uint32_t)b.nq, (uint64_t*)ctx->emd_out.p, p.rows));
+	if ((r = tail_ready(c, b, p, k, t))) return r;
+	HIP_TRY(ctx, msc_launch_epilogue(b.tail, t.ea));
+	return MSC_OK;
+}
+
+// the list of open pairs of a chunk and their distances (the list's words were allocated and cleared when the call began, on the product's stream: behind ev_head
+// for a piped block)
+int ensure_open_list(msc_ctx* ctx, uint32_t open_cap) {
+	int r;
+	if ((r = ensure(ctx, ctx->open_list, std::max<size_t>(1, open_cap) * sizeof(uint32_t))) || (r = ensure(ctx, ctx->emd_list, std::max<size_t>(1, open_cap) * sizeof(uint64_t)))) return r;
+	return MSC_OK;
+}
+
+// the arguments of the bound screen: the epilogue's, with the moments and the list in place of the distances
+MscEpilogueArgs bound_args(const MultiCall& c, const MscEpilogueArgs& ea, uint32_t open_cap) {
+	msc_ctx* ctx = c.ctx;
+	MscEpilogueArgs eb = ea;
+	eb.emd_ranks = nullptr;
+	eb.rk_c_sum = c.cands->rk_sum; eb.rk_c_dev = c.cands->rk_dev; eb.rk_q_sum = c.qset->rk_sum; eb.rk_q_dev = c.qset->rk_dev;
+	eb.open_list = (uint32_t*)ctx->open_list.p; eb.open_words = (uint32_t*)ctx->open_words.p; eb.open_cap = open_cap; eb.emd_list = (const uint64_t*)ctx->emd_list.p;
+	return eb;
+}
+
+// the list stage, on e's words: the bound screen, the walk of the listed pairs, their FP64 evaluation
+int list_stage(const MultiCall& c, const Block& b, const MatrixBlock& p, const Chunk& k, const MscEpilogueArgs& e, uint32_t open_cap) {
+	msc_ctx* ctx = c.ctx;
+	const msc_hist_set *cands = c.cands, *qset = c.qset;
+	const MscLayout& L = cands->L;
+	const BlockPipe::Side& s = *p.s;
+	const bool u16 = cands->ranks16 && qset->ranks16;
+	HIP_TRY(ctx, msc_launch_epilogue_bound(b.tail, e));
+	if (e.fold_x_c) {          // (the listed pairs of a folded stage: their exact P1 / P2 into the product's arrays first)
+		const MscFoldExact fx{cands->ranks, cands->rk_pitch, L.nbins, L.E, L.R, k.d_slots, k.off, k.mc, b.dq_slots, e.open_list, e.open_words, open_cap, (const uint8_t*)s.qT.p, p.rows,
+		                      qset->mb, qset->mb_n, qset->mb_pitch, (int32_t*)s.min.p, e.kb_slices, p.rt->n_hot ? (int32_t*)s.diff.p : nullptr};
+		HIP_TRY(ctx, msc_launch_fold_exact_list(b.tail, fx, ctx->num_cus));
+	}
+	HIP_TRY(ctx, msc_launch_emd_ranks_list(b.tail, u16, u16 ? (const void*)cands->ranks16 : (const void*)cands->ranks, u16 ? (const void*)qset->ranks16 : (const void*)qset->ranks,
+	                                       cands->rk_pitch, k.d_slots, k.off, k.mc, b.dq_slots, e.open_list, e.open_words, open_cap, (uint64_t*)ctx->emd_list.p, ctx->num_cus));
+	HIP_TRY(ctx, msc_launch_epilogue_list(b.tail, e, ctx->num_cus));
+	return MSC_OK;
+}
+
+// the bounds tail: the list stage; then today's three kernels, which return at once unless the list overflowed (then they overwrite every flag of the chunk);
+// then the list's words into the call's totals, cleared for the next block
+int tail_bounds(MultiCall& c, Block& b, const MatrixBlock& p, const Chunk& k, uint32_t open_cap, Tail& t) {
+	msc_ctx* ctx = c.ctx;
+	uint32_t* open_words = (uint32_t*)ctx->open_words.p;
+	int r;
+	if ((r = ensure_open_list(ctx, open_cap)) || (r = tail_ready(c, b, p, k, t)) || (r = list_stage(c, b, p, k, bound_args(c, t.ea, open_cap), open_cap))) return r;
+	HIP_TRY(ctx, launch_emd_ranks(b.tail, c.cands, c.qset, k.d_slots, k.off, k.mc, b.dq_slots, (uint32_t)b.nq, (uint64_t*)ctx->emd_out.p, p.rows, open_words + 1));
+	t.ea.run_if = open_words + 1;
+	HIP_TRY(ctx, msc_launch_epilogue(b.tail, t.ea));
+	HIP_TRY(ctx, msc_launch_emd_list_close(b.tail, open_words, open_cap, (uint64_t*)(open_words + 2), nullptr));
+	return MSC_OK;
+}
+
+// The folded tail: the screen over intervals, the listed pairs' exact counts, their walk and FP64 evaluation. Should ITS list overflow -- every related pair is
+// on it, the lower bound of P1 being 0 --, k_emd_list_close raises the block's word of ctx->fold_over and rerun_overflowed, once the call's blocks are through,
+// scores the block again with the true product (no host wait here, and nothing queued for the case that did not arise)
+int tail_folded(MultiCall& c, Block& b, const MatrixBlock& p, const Chunk& k, uint32_t open_cap, Tail& t) {
+	msc_ctx* ctx = c.ctx;
+	uint32_t* open_words = (uint32_t*)ctx->open_words.p;
+	int r;
+	if ((r = ensure_open_list(ctx, open_cap)) || (r = tail_ready(c, b, p, k, t))) return r;
+	MscEpilogueArgs ef = bound_args(c, t.ea, open_cap);
+	ef.kb_slices = p.slices_f; ef.fold_x_c = c.cands->kbf_x; ef.fold_x_q = c.qset->kbf_x;
+	if ((r = list_stage(c, b, p, k, ef, open_cap))) return r;
+	HIP_TRY(ctx, msc_launch_emd_list_close(b.tail, open_words, open_cap, (uint64_t*)(open_words + 2), (uint32_t*)ctx->fold_over.p + b.idx));
+	return MSC_OK;
+}
+
+// the flags' way home: from the chunk's buffer on the copy stream, under the next block's kernels
+int flags_home(MultiCall& c, Block& b, const Chunk& k, const Tail& t) {
+	msc_ctx* ctx = c.ctx;
+	BlockPipe& pipe = ctx->pipe;
+	HIP_TRY(ctx, hipEventRecord(pipe.ev_scored[t.pp], b.tail));
+	HIP_TRY(ctx, hipStreamWaitEvent(pipe.copy_stream, pipe.ev_scored[t.pp], 0));
+	HIP_TRY(ctx, rows_home(b.close + k.off, c.m, t.d_close, (size_t)k.mc, b.nq, pipe.copy_stream));
+	HIP_TRY(ctx, hipEventRecord(pipe.ev_copied[t.pp], pipe.copy_stream));
+	pipe.close_pp_busy[t.pp] = true;
+	pipe.copy_pending = true;
+	return MSC_OK;
+}
+
+// msc_last_emd_walk / msc_last_fold_screen: what a chunk adds to the call's counters (the overflows are on the device until the call ends)
+void count_chunk(msc_ctx* ctx, const MscMatrixStages& st, const MscMatrixChunk& ck) {
+	if (!st.counted) return;
+	if (st.walk_counted) { ctx->walk_blocks++; if (ck.bounds) ctx->walk_bound_blocks++; else ctx->walk_dense++; }
+	if (ck.tail == MSC_TAIL_FOLDED) { ctx->fold_used = st.fold; ctx->fold_blocks++; }
+}
+
+// candidates [off, off + b.chunk) of the block: the product, one of the three tails, the results' way home
+int matrix_chunk(MultiCall& c, Block& b, const MatrixBlock& p, uint64_t off) {
+	msc_ctx* ctx = c.ctx;
+	BlockPipe& pipe = ctx->pipe;
+	BlockPipe::Side& s = *p.s;
+	const bool queued = p.rt->queued;
+	int r;
+	const Chunk k = chunk_at(c, b, off);
+	hipEvent_t ev_t0 = ctx->ev_tiles0, ev_t1 = ctx->ev_tiles1;
+	if (queued && ctx->timing && ((r = pool_event(ctx, &ev_t0)) || (r = pool_event(ctx, &ev_t1)))) return r;      // (read when the call's last block is through)
+	if ((r = product_stage(c, b, p, k, ev_t0, ev_t1))) return r;
+	const MscMatrixChunk ck = msc_matrix_chunk(p.st, b.nq, k.mc);
+	count_chunk(ctx, p.st, ck);
+	Tail t;
+	switch (ck.tail) {
+		case MSC_TAIL_SCORED: r = tail_scored(c, b, p, k, t); break;
+		case MSC_TAIL_BOUNDS: r = tail_bounds(c, b, p, k, ck.open_cap, t); break;
+		case MSC_TAIL_FOLDED: r = tail_folded(c, b, p, k, ck.open_cap, t); break;
+	}
+	if (r) return r;
+	if (b.close && ctx->close_counts_n) HIP_TRY(ctx, msc_launch_close_counts(b.tail, t.d_close, (uint32_t)b.nq, k.mc, (uint64_t*)ctx->close_counts.p + b.q0));
+	if (p.st.piped) {
+		HIP_TRY(ctx, hipEventRecord(s.ev_tail, b.tail));
+		s.tail_busy = true;
+		pipe.tail_used = true;
+	}
+	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_all1, ctx->stream));
+	if ((r = results_home(c, b, k))) return r;
+	if (b.close && (r = flags_home(c, b, k, t))) return r;
+	if (queued) ctx->tiles_launches++;
+	else if ((r = chunk_done(ctx, ev_t0, ev_t1))) return r;
+	return MSC_OK;
+}
+
+// second_run: the block ran folded and its list overflowed -- it runs again with the true product (rerun_overflowed)
+int run_matrix(MultiCall& c, Block& b, const BlockRoute& rt, bool second_run = false) {
+	msc_ctx* ctx = c.ctx;
+	const uint64_t nbins = c.cands->L.nbins;
+	int r;
+	if ((r = begin_block(ctx)) || (r = block_uploads(c, b, rt.queued))) return r;
+	const uint32_t rows = msc_pair_gemm_rows((uint32_t)b.nq);
+	b.chunk = matrix_chunks(ctx, nbins, c.m, rows, group_chunk_limit(c, b.nq)).chunk;
+	b.div_pass = c.want_div && !c.cells;
+	if ((r = ensure_block_scratch(c, b, true))) return r;
+	MatrixBlock p = plan_matrix(c, b, rt, rows, second_run);
+	if ((r = wait_side_free(ctx, p))) return r;
+	// (a folded block passes the true bin count and the larger of the two slice counts)
+	if ((r = ensure_side(ctx, *p.s, nbins, rows, std::max(p.slices, p.slices_f), b.chunk, rt.n_hot, &p.hot)) || (r = queries_side(c, b, p))) return r;
+	if (rt.emd_ranks && (r = ensure(ctx, ctx->emd_out, b.chunk * rows * sizeof(uint64_t)))) return r;
+	name_matrix_kernel(ctx, rows, rt.emd_ranks, c.cells, c.cands->sparse, p.st.fold);
+	ctx->last_query_tile = (int)b.nq;
+	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_all0, ctx->stream));
+	for (uint64_t off = 0; off < c.m; off += b.chunk)
+		if ((r = matrix_chunk(c, b, p, off))) return r;
+	return rt.queued ? MSC_OK : read_error_word(ctx);
 }
 
 // What the older routes need of two dense sets when a divergence or group statistic is wanted: the sparse mirrors, both or neither, and with them
@@ -939,6 +860,77 @@ int settle_mirrors(MultiCall& c) {
 	}
 	c.grp_dense = c.want_grp && !c.c_sp;
 	c.simple = !cands->sparse && (!c.grp_dense || c.mc_ <= 0xffffffffull) && (!c.want_div || c.c_sp) && whole_tiles;
+	return MSC_OK;
+}
+
+// block i of the call's plan
+Block block_of(const MultiCall& c, size_t i) {
+	const MscMultiBlock& pb = c.blocks[i];
+	const uint64_t m = c.m;
+	Block b{pb.q0, pb.nq, c.q_slots + pb.q0, c.sum_out ? c.sum_out + pb.q0 * m : nullptr, c.csum_out ? c.csum_out + pb.q0 * m : nullptr,
+	        c.raw_out ? c.raw_out + pb.q0 * m * c.nf : nullptr, c.close_out ? c.close_out + pb.q0 * m : nullptr};
+	b.idx = (uint32_t)i;
+	return b;
+}
+
+// The folded blocks whose list overflowed (msc_fold.h): once more, as the unfolded blocks they would have been -- the bounds of emd, the list, the dense
+// walk behind it. The call's streams are idle; the block's close counts start again from zero, its flags go home over the first run's
+int rerun_overflowed(MultiCall& c, const std::vector<BlockRoute>& route_of) {
+	msc_ctx* ctx = c.ctx;
+	int r;
+	std::vector<uint32_t> over(c.blocks.size());
+	HIP_TRY(ctx, hipMemcpy(over.data(), ctx->fold_over.p, over.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	for (size_t i = 0; i < over.size(); i++) {
+		if (!over[i]) continue;
+		Block b = block_of(c, i);
+		if (ctx->close_counts_n) HIP_TRY(ctx, hipMemsetAsync((uint64_t*)ctx->close_counts.p + b.q0, 0, b.nq * sizeof(uint64_t), ctx->stream));
+		if ((r = run_matrix(c, b, route_of[i], true))) { (void)flush_deferred(c); return r; }
+		c.ms += ctx->tiles_ms_accum; c.launches += ctx->tiles_launches;
+	}
+	return flush_deferred(c);
+}
+
+// The call's counters (msc_last_emd_walk, msc_last_fold_screen) start from zero ...
+void clear_call_counters(msc_ctx* ctx) {
+	ctx->walk_listed = ctx->walk_dense = ctx->walk_blocks = ctx->walk_bound_blocks = ctx->fold_used = ctx->fold_blocks = ctx->fold_fell_back = 0;
+}
+
+// ... and take the totals of the bound pass when the call is through (every stream of the call is idle: the error word has been read)
+int read_call_totals(msc_ctx* ctx, const msc_model* model) {
+	if (!ctx->walk_bound_blocks) return MSC_OK;
+	uint64_t totals[3] = {0, 0, 0};
+	const hipError_t e = hipMemcpy(totals, (const uint8_t*)ctx->open_words.p + 2 * sizeof(uint32_t), sizeof totals, hipMemcpyDeviceToHost);
+	if (e != hipSuccess) return fail(ctx, MSC_ERR_HIP, "copy of the pair list's totals failed: %s", hipGetErrorString(e));
+	ctx->walk_listed = totals[0];
+	ctx->walk_dense += totals[1];
+	// a model whose distance really decides: it does not pay the bound pass for ever
+	if (totals[1] * 2 > ctx->walk_bound_blocks) model->emd_decides = true;
+	// ... nor, a model whose related pairs are too many for the list, the folded stage
+	ctx->fold_fell_back = totals[2];
+	if (totals[2] * 2 > ctx->fold_blocks) model->fold_overflows = true;
+	return MSC_OK;
+}
+
+// The device words the call's blocks add into, cleared on the context's stream: close candidates per query, kept for msc_last_close_counts (a caller that
+// only needs the counts of a block of the pairwise matrix does not have to add up n_q x m flags on the host) ...
+int clear_call_words(MultiCall& c) {
+	msc_ctx* ctx = c.ctx;
+	const uint64_t n_q = c.n_q;
+	int r;
+	ctx->close_counts_n = 0;
+	if (c.close_out && c.model) {          // the list of open pairs of the bound pass (run_matrix): {count, overflow}, then the call's two totals
+		// (+ the third total, folded blocks that fell back; and per block of the plan a word that a folded block raises when its list overflows)
+		if ((r = ensure(ctx, ctx->open_words, kOpenWordsBytes))) return r;
+		HIP_TRY(ctx, hipMemsetAsync(ctx->open_words.p, 0, kOpenWordsBytes, ctx->stream));
+		const size_t over_bytes = ((n_q + 63) / 64 + 1) * sizeof(uint32_t);          // (a plan's blocks are of 64 queries or more, but for the last)
+		if ((r = ensure(ctx, ctx->fold_over, over_bytes))) return r;
+		HIP_TRY(ctx, hipMemsetAsync(ctx->fold_over.p, 0, over_bytes, ctx->stream));
+	}
+	if (c.close_out) {
+		if ((r = ensure(ctx, ctx->close_counts, n_q * sizeof(uint64_t)))) return r;
+		HIP_TRY(ctx, hipMemsetAsync(ctx->close_counts.p, 0, n_q * sizeof(uint64_t), ctx->stream));
+		ctx->close_counts_n = n_q;
+	}
 	return MSC_OK;
 }
 
@@ -972,22 +964,7 @@ int score_multi(MultiCall& c) {
 		c.kb_fit = cands->kb && qset->kb && !cands->kb_has_zero && !qset->kb_has_zero;
 	}
 	c.cells = div_cells && c.kb_fit;
-	// close candidates per query, kept on the device for msc_last_close_counts (a caller that only needs the counts of a block of the
-	// pairwise matrix does not have to add up n_q x m flags on the host)
-	ctx->close_counts_n = 0;
-	if (c.close_out && c.model) {          // the list of open pairs of the bound pass (run_matrix): {count, overflow}, then the call's two totals
-		// (+ the third total, folded blocks that fell back; and per block of the plan a word that a folded block raises when its list overflows)
-		if ((r = ensure(ctx, ctx->open_words, kOpenWordsBytes))) return r;
-		HIP_TRY(ctx, hipMemsetAsync(ctx->open_words.p, 0, kOpenWordsBytes, ctx->stream));
-		const size_t over_bytes = ((n_q + 63) / 64 + 1) * sizeof(uint32_t);          // (a plan's blocks are of 64 queries or more, but for the last)
-		if ((r = ensure(ctx, ctx->fold_over, over_bytes))) return r;
-		HIP_TRY(ctx, hipMemsetAsync(ctx->fold_over.p, 0, over_bytes, ctx->stream));
-	}
-	if (c.close_out) {
-		if ((r = ensure(ctx, ctx->close_counts, n_q * sizeof(uint64_t)))) return r;
-		HIP_TRY(ctx, hipMemsetAsync(ctx->close_counts.p, 0, n_q * sizeof(uint64_t), ctx->stream));
-		ctx->close_counts_n = n_q;
-	}
+	if ((r = clear_call_words(c))) return r;
 	c.mc_ = std::max(cands->max_count, qset->max_count); c.ms_ = std::max(cands->max_sum, qset->max_sum);
 	// (sums from cells read no sparse mirror: a call whose blocks all stay with the matrix cores builds none; the first block that falls back settles them)
 	if (c.cells) c.simple = !cands->sparse;
@@ -1005,14 +982,9 @@ int score_multi(MultiCall& c) {
 	if (err) return err;
 	size_t next_taken = 0;
 	std::vector<BlockRoute> route_of(c.blocks.size());
-	auto block_of = [&](const MscMultiBlock& pb) {
-		Block b{pb.q0, pb.nq, c.q_slots + pb.q0, c.sum_out ? c.sum_out + pb.q0 * m : nullptr, c.csum_out ? c.csum_out + pb.q0 * m : nullptr,
-		        c.raw_out ? c.raw_out + pb.q0 * m * c.nf : nullptr, c.close_out ? c.close_out + pb.q0 * m : nullptr};
-		b.idx = (uint32_t)(&pb - c.blocks.data());
-		return b;
-	};
-	for (const MscMultiBlock& pb : c.blocks) {
-		Block b = block_of(pb);
+	for (size_t i = 0; i < c.blocks.size(); i++) {
+		const MscMultiBlock& pb = c.blocks[i];
+		Block b = block_of(c, i);
 		// (blocks of the matrix-core pass are queued without a host wait between them: any other route first waits for them and reads their error word)
 		r = pb.matrix ? MSC_OK : flush_deferred(c);
 		BlockRoute rt;
@@ -1039,21 +1011,7 @@ int score_multi(MultiCall& c) {
 		c.ms += ctx->tiles_ms_accum; c.launches += ctx->tiles_launches;
 	}
 	if ((r = flush_deferred(c))) return r;
-	if (ctx->fold_blocks) {
-		// the folded blocks whose list overflowed (msc_fold.h): once more, as the unfolded blocks they would have been -- the bounds of emd, the list, the dense
-		// walk behind it. The call's streams are idle; the block's close counts start again from zero, its flags go home over the first run's
-		std::vector<uint32_t> over(c.blocks.size());
-		HIP_TRY(ctx, hipMemcpy(over.data(), ctx->fold_over.p, over.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-		for (size_t i = 0; i < over.size(); i++) {
-			if (!over[i]) continue;
-			Block b = block_of(c.blocks[i]);
-			b.no_fold = true;
-			if (ctx->close_counts_n) HIP_TRY(ctx, hipMemsetAsync((uint64_t*)ctx->close_counts.p + b.q0, 0, b.nq * sizeof(uint64_t), ctx->stream));
-			if ((r = run_matrix(c, b, route_of[i]))) { (void)flush_deferred(c); return r; }
-			c.ms += ctx->tiles_ms_accum; c.launches += ctx->tiles_launches;
-		}
-		if ((r = flush_deferred(c))) return r;
-	}
+	if (ctx->fold_blocks && (r = rerun_overflowed(c, route_of))) return r;
 	ctx->tiles_ms_accum = c.ms; ctx->tiles_launches = c.launches;
 	return MSC_OK;
 }
@@ -1064,22 +1022,9 @@ extern "C" int msc_score_multi(msc_ctx* ctx, const msc_model* model, const msc_h
                                const msc_hist_set* qset, const uint32_t* q_slots, uint64_t n_q, int order, double* sum_out, double* csum_out,
                                uint8_t* close_out, uint64_t feat_mask, double* raw_out) {
 	MultiCall c{ctx, model, cands, cand_slots, m, qset, q_slots, n_q, order, sum_out, csum_out, close_out, feat_mask, raw_out};
-	if (ctx) ctx->walk_listed = ctx->walk_dense = ctx->walk_blocks = ctx->walk_bound_blocks = ctx->fold_used = ctx->fold_blocks = ctx->fold_fell_back = 0;
+	if (ctx) clear_call_counters(ctx);
 	int r = score_multi(c);
-	if (ctx && r == MSC_OK && ctx->walk_bound_blocks) {          // the totals of the bound pass (every stream of the call is idle: the error word has been read)
-		uint64_t totals[3] = {0, 0, 0};
-		const hipError_t e = hipMemcpy(totals, (const uint8_t*)ctx->open_words.p + 2 * sizeof(uint32_t), sizeof totals, hipMemcpyDeviceToHost);
-		if (e != hipSuccess) r = fail(ctx, MSC_ERR_HIP, "copy of the pair list's totals failed: %s", hipGetErrorString(e));
-		else {
-			ctx->walk_listed = totals[0];
-			ctx->walk_dense += totals[1];
-			// a model whose distance really decides: it does not pay the bound pass for ever
-			if (totals[1] * 2 > ctx->walk_bound_blocks) model->emd_decides = true;
-			// ... nor, a model whose related pairs are too many for the list, the folded stage
-			ctx->fold_fell_back = totals[2];
-			if (totals[2] * 2 > ctx->fold_blocks) model->fold_overflows = true;
-		}
-	}
+	if (ctx && r == MSC_OK) r = read_call_totals(ctx, model);
 	if (ctx && ctx->pipe.copy_pending) {          // the flag copies of the last blocks (issued beside the kernels that followed them)
 		const hipError_t e = hipStreamSynchronize(ctx->pipe.copy_stream);
 		ctx->pipe.copy_pending = ctx->pipe.close_pp_busy[0] = ctx->pipe.close_pp_busy[1] = false;

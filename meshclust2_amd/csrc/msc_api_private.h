@@ -1,5 +1,5 @@
 // msc_api_private.h -- what the translation units of the C ABI's host side (msc_api.hip: context, sets, builds, models; msc_api_score.hip: the
-// scoring driver and the 1 x M calls; msc_api_multi.hip: msc_score_multi; msc_api_batch.hip: the batched update stage; msc_api_pairlist.hip: msc_score_pair_list) share beyond
+// scoring driver and the 1 x M calls; msc_api_multi.hip: msc_score_multi; msc_mirrors.hip: the mirrors of a set the Q x M calls read; msc_api_batch.hip: the batched update stage; msc_api_pairlist.hip: msc_score_pair_list) share beyond
 // msc_objects.h / msc_internal.h.
 #pragma once
 #include <algorithm>
@@ -57,10 +57,16 @@ int batch_div_lists(msc_ctx* ctx, const msc_hist_set* cands, const msc_hist_set*
 int batch_div_pass(msc_ctx* ctx, const msc_hist_set* cands, const msc_hist_set* queries, const msc_hist_set* c_sp, const msc_hist_set* q_sp, uint64_t P, int order,
                    MscPartial* partials, uint32_t* div_n);
 
-// ---- msc_api_multi.hip (shared with msc_api_pairs.hip)
-int ensure_kb(msc_ctx* ctx, const msc_hist_set* set, bool want_fold = false);          // the presence-bit mirror and lists of large bins of a set, from its bins or its lists (set->kb null: unavailable)
+// ---- msc_mirrors.hip: the mirrors of a set that the Q x M calls read (msc_api_multi.hip, msc_api_pairs.hip), each built on first use
+int ensure_digest(msc_ctx* ctx, const msc_hist_set* set);      // the digest mirror of a dense set (set->digest null: unavailable)
+int ensure_kb(msc_ctx* ctx, const msc_hist_set* set, bool want_fold = false);          // the presence-bit mirror and lists of large bins of a set, from its bins or its lists (set->kb null: unavailable); want_fold: and its folded form
 int ensure_ranks(msc_ctx* ctx, const msc_hist_set* set);       // the ranks mirror, likewise (set->ranks null: unavailable)
 bool kb_route_fits(const msc_hist_set* cands, const msc_hist_set* qset, bool need_emd);          // host-side bounds of the matrix-core pass
+void mark_stale(msc_hist_set* s, uint64_t first, uint64_t n);  // slots [first, first + n) were written: the mirrors the set has are stale there
+void free_mirrors(const msc_hist_set* set);                    // msc_hist_set_destroy
+uint64_t mirror_bytes_per_slot(const msc_hist_set* s);         // the mirrors' term of msc_hist_set_bytes
+
+// ---- msc_api_multi.hip (shared with msc_api_pairs.hip)
 int read_error_word(msc_ctx* ctx);                             // the epilogue's error word as a status (the stream is idle)
 // ... and what a block on the matrix cores needs in either driver (the drivers themselves stay apart: msc_score_multi pipes its blocks over three
 // streams and scores every pair, msc_search_pairs lists the close ones on one stream)

@@ -1,5 +1,5 @@
 // msc_multi_plan.h -- the host arithmetic of the Q x M calls (msc_api_multi.hip, msc_api_pairs.hip): how msc_score_multi cuts its queries
-// into blocks, and how a block's candidates are cut into chunks. Free of HIP, so that tests/multi_plan_check.cpp builds it with g++ alone.
+// into blocks, how a block's candidates are cut into chunks, and what a block on the matrix cores decides about its stages. Free of HIP, so that tests/multi_plan_check.cpp builds it with g++ alone.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -31,4 +31,62 @@ inline MscCandChunks msc_cand_chunks(uint64_t m, uint64_t cap) {
 	const uint64_t c0 = std::min(std::max<uint64_t>(cap, 256), m);
 	const uint64_t n = (m + c0 - 1) / c0;
 	return MscCandChunks{(m + n - 1) / n, n};
+}
+
+// ---- a block on the matrix cores (run_matrix, msc_api_multi.hip): the plain facts its stage decisions rest on, the decisions, and one
+// function between them. The facts are filled where the block begins (matrix_facts), the two environment switches among them.
+struct MscMatrixFacts {
+	bool model = false, screen_ok = false;                        // a model is given; its statistics admit the f32 screen (MscDevModel::screen_ok)
+	bool close = false, sum = false, csum = false, raw = false;   // what the caller wants of the block
+	bool want_div = false, want_grp = false;                      // a divergence / group statistic is wanted ...
+	bool div_pass = false;                                        // ... and the divergence sums come from a merge pass per query (not from cells)
+	bool no_screen = false, no_prep = false;                      // MSC_NO_SCREEN, MSC_GEMM_NO_PREP
+	bool queued = false, emd_ranks = false;                       // the route: queued behind the block before; the distance from the ranks mirrors
+	bool block_pipe = false, emd_bounds = false;                  // the context: msc_set_block_pipe, msc_set_emd_bounds
+	uint32_t fold_screen = 0;                                     // ... msc_set_fold_screen
+	bool emd_decides = false, fold_overflows = false;             // the model is remembered for overflowing the list of open pairs / the folded stage's
+	uint64_t rk_pitch_c = 0, rk_pitch_q = 0;                      // the ranks mirrors of the candidates' and the queries' set: pitch,
+	bool moments_c = false, moments_q = false;                    // ... whether the two moments per slot stand beside it,
+	bool kbf_c = false, kbf_q = false;                            // ... whether the set carries a folded mirror,
+	uint32_t kbf_fold_c = 0, kbf_fold_q = 0;                      // ... and of which fold
+	bool second_run = false;                                      // the block ran folded and its list overflowed: this is its second run, with the true product
+	uint64_t n_q = 0, m = 0, chunk = 0;                           // queries of the block, candidates of the call, candidates per launch
+};
+
+struct MscMatrixStages {
+	bool screen = false;             // only the close flags are wanted: decided in f32 with an error bound, FP64 for the pairs the bound leaves open
+	bool walk_counted = false;       // ... with the distance from the ranks mirrors: the block counts in msc_last_emd_walk
+	bool bounds_call = false;        // ... from bounds of the distance first (msc_emd_list.hip), in every chunk of 64 pairs and more
+	uint32_t fold = 0;               // ... with the product over bits folded fold-to-1 (msc_fold.h); 0: the true product
+	bool piped = false;              // the block's stages on the three streams of the pipe
+	bool own_prep_stream = false;    // ... the queries' side on the prep stream
+	bool counted = false;            // the block's counters are bumped (not in a second run: it was counted when it ran folded)
+};
+
+inline bool msc_list_pairs_fit(uint64_t pairs) { return pairs >= 64 && pairs <= 0xffffffffull; }          // (fewer than 64 pairs: a list of no entries; the list holds 32-bit pair indices)
+
+inline MscMatrixStages msc_matrix_stages(const MscMatrixFacts& f) {
+	MscMatrixStages s;
+	s.screen = f.model && f.screen_ok && f.close && !f.sum && !f.csum && !f.raw && !f.want_div && !f.want_grp && !f.no_screen;
+	s.walk_counted = s.screen && f.emd_ranks;
+	s.bounds_call = s.walk_counted && f.emd_bounds && !f.emd_decides && f.rk_pitch_c == f.rk_pitch_q && f.moments_c && f.moments_q;
+	const bool folds = s.bounds_call && !f.second_run && f.chunk == f.m && msc_list_pairs_fit(f.n_q * f.m) && !f.fold_overflows && f.kbf_c && f.kbf_q &&
+	                   f.kbf_fold_c == f.fold_screen && f.kbf_fold_q == f.fold_screen;
+	s.fold = folds ? f.fold_screen : 0;
+	s.piped = f.queued && f.chunk == f.m && !f.div_pass && !f.want_grp && f.block_pipe;
+	s.own_prep_stream = s.piped && !f.no_prep;
+	s.counted = !f.second_run;
+	return s;
+}
+
+// The tail of a chunk of mc candidates, one of three forms:
+//   scored  the optional rank walk of every pair, then the epilogue
+//   bounds  the list stage (bound screen, walk and FP64 evaluation of the listed pairs), then the dense walk and the epilogue predicated on the
+//           list's overflow word, then the kernel that closes the list
+//   folded  the list stage on the folded words (with the listed pairs' exact counts), then the closing kernel with the block's fold_over word
+enum MscMatrixTail { MSC_TAIL_SCORED, MSC_TAIL_BOUNDS, MSC_TAIL_FOLDED };
+struct MscMatrixChunk { bool bounds; uint32_t open_cap; MscMatrixTail tail; };
+inline MscMatrixChunk msc_matrix_chunk(const MscMatrixStages& s, uint64_t n_q, uint64_t mc) {
+	const bool bounds = s.bounds_call && msc_list_pairs_fit(n_q * mc);
+	return MscMatrixChunk{bounds, bounds ? (uint32_t)(n_q * mc / 64) : 0, !bounds ? MSC_TAIL_SCORED : s.fold ? MSC_TAIL_FOLDED : MSC_TAIL_BOUNDS};
 }

@@ -13,7 +13,7 @@ struct DevBuf {
 	size_t cap = 0;
 };
 
-// The matrix-core block pipe (msc_pair_gemm.hip, msc_api_multi.hip). msc_score_multi queues the blocks of its matrix-core pass in stages on three
+// The matrix-core block pipe (msc_pair_gemm.hip; run_matrix and its stage functions, msc_api_multi.hip). msc_score_multi queues the blocks of its matrix-core pass in stages on three
 // streams: the queries' side of block i + 1 (prep_stream) under the product of block i (the context's stream), beside the rank walk of block i and the
 // epilogue of block i - 1 (tail_stream). What two stages touch exists twice and blocks take turns; msc_search_pairs, on one stream, uses side[0] alone.
 struct BlockPipe {
@@ -160,14 +160,14 @@ struct msc_hist_set {
 	// presence-bit mirror (msc_pair_gemm.hip, msc_kbits.h): one BIT per bin = [count >= 2], slots blocked by 32 -- the B operand of the
 	// int8 product of the Q x M pass -- and beside it the lists of large bins (count - 1 >= 2) that make the pass exact for any counts:
 	// mb[slot][mb_pitch] = (bin, count - 1), sorted by bin; mb_n = entries per slot (also on the host: the size of a query block's hot list is
-	// known without a read-back). kb_stale: the slots written since (mark_stale). A sparse set carries the same mirror, built from its lists
+	// known without a read-back). kb_stale: the slots written since (mark_stale, msc_mirrors.hip). A sparse set carries the same mirror, built from its lists
 	// (msc_set_sparse_matrix_pass; lists_written keeps the stale range)
 	mutable uint8_t* kb = nullptr;
 	mutable StaleRange kb_stale;
 	mutable bool kb_unavailable = false;
 	mutable bool kb_has_zero = false;         // a slot with a zero count went into the mirror (never the case for built histograms and their means)
 	// ... and the mirror folded F-to-1 (msc_fold.h; k_kb_fold): a bit per folded bin in kb's own layout at 4^k / kbf_fold bins, and per slot its own
-	// collisions kbf_x. Built from kb in ensure_kb wherever kb is (re)built: kbf_stale = the slots kb has been rebuilt for since.
+	// collisions kbf_x. Built from kb in ensure_kb_folded (msc_mirrors.hip) wherever kb is (re)built: kbf_stale = the slots kb has been rebuilt for since.
 	mutable uint8_t* kbf = nullptr;
 	mutable uint32_t* kbf_x = nullptr;
 	mutable uint32_t kbf_fold = 0;

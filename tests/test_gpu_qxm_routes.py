@@ -45,3 +45,18 @@ def test_slow_model_sums_match_the_per_query_passes():
                 assert np.all(np.abs(multi[key][i] - single[key]) <= atol + rtol * np.abs(single[key])), (nq, i, key)
             assert np.array_equal(multi["close"][i], (np.round(single["csum"]) > 0).astype(np.uint8)), (nq, i)
     ctx.close()
+
+
+def test_flag_routes_and_results_match_the_recorded_table():
+    """the second table of tools/qxm_routes.py (--flags): calls that ask for the close flags alone with an earth_movers_distance model -- the
+    bound tail, the folded tail, a folded block's second run, the dense walk, one stream, no timing events, a block that is not queued, fewer
+    than 64 pairs, mirrors from lists. tests/golden/qxm_flag_routes.json holds the lines (kernel, launches, SHA-256 of flags and counts,
+    msc_last_emd_walk, msc_last_fold_screen) of the library before run_matrix became a driver over stage functions. (A process of its own,
+    as the first table: the switches are read once per process, and a model remembers its overflows.)"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "qxm_routes.py"), "--flags"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
+    got = [json.loads(ln) for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
+    want = [json.loads(ln) for ln in open(os.path.join(ROOT, "tests", "golden", "qxm_flag_routes.json")).read().splitlines()]
+    assert [g["case"] for g in got] == [w["case"] for w in want]
+    for g, w in zip(got, want):
+        assert g == w, (w["case"], {k: (g[k], w[k]) for k in w if g[k] != w[k]})

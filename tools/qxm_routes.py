@@ -8,7 +8,15 @@ became a block plan with one function per route, and tests/test_gpu_qxm_routes.p
 The table: the shapes of tests/ring_variant_check.py (32-bit k = 9, 64-bit k = 6; digest, ring, raw tiles, matrix cores), three dense k = 7
 sets and two sparse sets (with and without msc_set_sparse_matrix_pass) at n_q = 2, 64, 65, 129, 130, 257 over a slot list and over a range,
 and a `--feat slow` model (jensen_shannon: the divergence sums ride behind the streaming kernel). The slow model's weighted sums hold FP64
-divergence sums and are not hashed: --dump DIR writes them as .npy files to be compared with a tolerance."""
+divergence sums and are not hashed: --dump DIR writes them as .npy files to be compared with a tolerance.
+
+    python tools/qxm_routes.py --flags [--lib PATH/libmeshclust2_hip.so]
+
+A second table, of calls that ask for the close flags alone (want = close, counts) with an earth_movers_distance model: the tails of a
+matrix-core block that the first table never reaches -- the bound screen of the distance, the folded product, the second run of a block
+whose folded list overflowed. A line holds the kernel, the launches, a SHA-256 of the flags and of the counts, msc_last_emd_walk and
+msc_last_fold_screen. tests/golden/qxm_flag_routes.json holds the lines of the build before run_matrix became a driver over stage
+functions."""
 import argparse
 import hashlib
 import json
@@ -27,8 +35,82 @@ def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
+def flag_table(ctx, api, synth):
+    """the flags-only calls: one JSON line each. A fresh Feature per case (a model remembers that its lists overflowed) unless the case is
+    about that memory."""
+    text = open(os.path.join(GOLDEN, "weights_k9_u32.txt")).read()
+    lines = []
+
+    def call(case, feat, cands, slots, qset, qs, m=None):
+        got = api.score_multi(ctx, feat, cands, slots, qset, qs, m=m, want=("close", "counts"))
+        lines.append(json.dumps(dict(case=case, kernel=ctx.last_kernel_info()[0], launches=ctx.last_kernel_launches(), emd_walk=ctx.last_emd_walk(),
+                                     fold_screen=ctx.last_fold_screen(), sha=dict(close=sha(got["close"]), counts=sha(got["counts"]))), sort_keys=True))
+        return got
+
+    def fresh():
+        return api.Feature.from_text(ctx, text, 0)
+
+    def shifted(by):          # the model with its intercept (the line after the first `n_combos:`) lowered by `by`
+        ls = text.splitlines()
+        at = next(i for i, ln in enumerate(ls) if ln.startswith("n_combos:")) + 1
+        ls[at] = repr(float(ls[at]) - float(by))
+        return api.Feature.from_text(ctx, "\n".join(ls) + "\n", 0)
+
+    # the set of tests/test_gpu_fold_screen.py: 640 sequences of 1 000 bases in families of four, k = 9, 32-bit
+    seqs = synth.families(20260002, 640, 1000, family=4)[0]
+    n = len(seqs)
+    hs = api.HistogramSet(ctx, 9, 32, n)
+    hs.build(seqs)
+    qs = np.arange(200, dtype=np.uint32)
+    call("200 x 640 range: two queued blocks, piped, folded", fresh(), hs, None, hs, qs, m=n)
+    call("200 x 640 shuffled slot list", fresh(), hs, np.random.default_rng(7).permutation(n).astype(np.uint32), hs, qs)
+    ctx.set_fold_screen(0)
+    call("fold screen off: the unfolded bound tail", fresh(), hs, None, hs, qs, m=n)
+    ctx.set_fold_screen(16)
+    ctx.set_emd_bounds(False)
+    call("emd bounds off: the scored tail, dense walk", fresh(), hs, None, hs, qs, m=n)
+    ctx.set_emd_bounds(True)
+    ctx.set_block_pipe(False)
+    call("block pipe off: queued on one stream", fresh(), hs, None, hs, qs, m=n)
+    ctx.set_block_pipe(True)
+    ctx.set_kernel_timing(False)
+    call("kernel timing off: queued without timing events", fresh(), hs, None, hs, qs, m=n)
+    ctx.set_kernel_timing(True)
+    call("3 x 200: one block, not queued", fresh(), hs, None, hs, np.array([3, 129, 130], dtype=np.uint32), m=200)
+    call("3 x 20: under 64 pairs, no list", fresh(), hs, None, hs, np.array([3, 129, 130], dtype=np.uint32), m=20)
+    hs.close()
+    # the set of tests/test_gpu_emd_bounds.py (families of 20): every folded list overflows and the blocks run again, unfolded; the model
+    # is remembered for it. Then with the intercept moved by the median sum of all pairs: the unfolded lists overflow too (the dense walk)
+    seqs = synth.families(20260002, 800, 1000)[0]
+    n = len(seqs)
+    hs = api.HistogramSet(ctx, 9, 32, n)
+    hs.build(seqs)
+    qs = np.arange(130, dtype=np.uint32)
+    feat = fresh()
+    call("families of 20, 130 x 800, first call", feat, hs, None, hs, qs, m=n)
+    call("families of 20, 130 x 800, second call: model remembered", feat, hs, None, hs, qs, m=n)
+    sums = api.score_multi(ctx, feat, hs, None, hs, qs, m=n, want=("sum",))["sum"]
+    feat = shifted(np.median(sums))
+    call("families of 20, intercept at the median, first call", feat, hs, None, hs, qs, m=n)
+    call("families of 20, intercept at the median, second call: model remembered", feat, hs, None, hs, qs, m=n)
+    hs.close()
+    # two sparse sets, mirrors from the lists
+    seqs = synth.families(20260002, 640, 1000, family=4)[0]
+    sp = api.HistogramSet(ctx, 9, 32, len(seqs), sparse_entries=sum(len(s) for s in seqs) + 1024)
+    sp.build(seqs)
+    sq = api.HistogramSet(ctx, 9, 32, 130, sparse_entries=sum(len(s) for s in seqs[:130]) + 1024)
+    sq.build(seqs[:130])
+    ctx.set_sparse_matrix_pass(True)
+    call("two sparse sets, 130 x 640", fresh(), sp, None, sq, np.arange(130, dtype=np.uint32), m=len(seqs))
+    ctx.set_sparse_matrix_pass(False)
+    sq.close()
+    sp.close()
+    print("\n".join(lines))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--flags", action="store_true", help="the second table: flags-only calls (the bound and folded tails of a matrix-core block)")
     ap.add_argument("--lib", help="run against this build of the library instead of the tree's")
     ap.add_argument("--dump", help="directory for the arrays that are not hashed")
     args = ap.parse_args()
@@ -37,6 +119,10 @@ def main():
         _capi.LIB_PATH = os.path.abspath(args.lib)
     from meshclust2_amd import api, synth
     ctx = api.Context(0)
+    if args.flags:
+        flag_table(ctx, api, synth)
+        ctx.close()
+        return
     lines = []
 
     def call(case, feat, hs, cands, qs, m=None, feat_mask=api.FEAT_FAST, hashed=("sum", "csum", "close", "raw"), dumped=()):
