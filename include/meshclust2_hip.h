@@ -179,6 +179,10 @@ int         msc_last_emd_walk(const msc_ctx* ctx, uint64_t* listed_pairs, uint64
  * again by the true product once the call's blocks are through; a model most of whose blocks do so is remembered. Sets whose histograms are too small to fold (k = 5) and
  * every other call keep their route. The flags are those of fold = 0, pair for pair. Any other value of fold: MSC_ERR_INVALID_ARG. */
 int         msc_set_fold_screen(msc_ctx* ctx, int fold);
+/* The queries' side of the matrix-core blocks of msc_score_multi (their bits as the product's tiles and transposed, their lists of large bins by step) is
+ * built for up to `cap` consecutive full blocks in one set of launches, a group ahead of the blocks that read it (default 32; 0 at start with
+ * MSC_NO_QUERY_GROUPS in the environment). cap = 0 or 1: block by block. Identical results. cap < 0: MSC_ERR_INVALID_ARG. */
+int         msc_set_query_groups(msc_ctx* ctx, int cap);
 /* What the last msc_score_multi call did about it: the fold used (0: none), the blocks whose product was folded, and those of them that fell
  * back to the true product. Any pointer may be null. */
 int         msc_last_fold_screen(const msc_ctx* ctx, uint64_t* fold, uint64_t* folded_blocks, uint64_t* fell_back);

@@ -96,6 +96,11 @@ class Context:
         product (0); the same flags"""
         self.check(self.lib.msc_set_fold_screen(self.h, int(fold)))
 
+    def set_query_groups(self, cap):
+        """score_multi's matrix-core blocks: the queries' side of up to `cap` consecutive full blocks in one set of launches (default 32), or
+        block by block (0 or 1); identical results"""
+        self.check(self.lib.msc_set_query_groups(self.h, int(cap)))
+
     def last_fold_screen(self):
         """(fold, folded_blocks, fell_back) of the last score_multi call: the fold used (0: none), the blocks whose product was folded and
         those of them whose list of open pairs overflowed and were scored again with the true product"""

@@ -110,6 +110,7 @@ extern "C" int msc_create(int device, msc_ctx** out) {
 	for (int i = 0; i < 2; i++)
 		for (hipEvent_t* e : {&pipe.side[i].ev_head, &pipe.side[i].ev_product, &pipe.side[i].ev_tail, &pipe.side[i].ev_prep, &pipe.ev_scored[i], &pipe.ev_copied[i]})
 			ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+	for (int i = 0; i < 2; i++) ok = ok && hipEventCreateWithFlags(&pipe.arena[i].ev_ready, hipEventDisableTiming) == hipSuccess;
 	if (!ok || hipEventCreateWithFlags(&pipe.ev_call, hipEventDisableTiming) != hipSuccess) {
 		delete ctx;
 		return fail(nullptr, MSC_ERR_HIP, "msc_create: stream/event creation failed");
@@ -118,6 +119,7 @@ extern "C" int msc_create(int device, msc_ctx** out) {
 	ctx->block_pipe = getenv("MSC_GEMM_NO_PIPE") == nullptr;
 	ctx->emd_bounds = getenv("MSC_NO_EMD_BOUNDS") == nullptr;
 	ctx->fold_screen = getenv("MSC_NO_FOLD") == nullptr ? 16 : 0;
+	ctx->query_groups = getenv("MSC_NO_QUERY_GROUPS") == nullptr ? 32 : 0;
 	*out = ctx;
 	return MSC_OK;
 }
@@ -164,7 +166,8 @@ extern "C" void msc_destroy(msc_ctx* ctx) {
 	for (hipEvent_t e : {ctx->ev_tiles0, ctx->ev_tiles1, ctx->ev_all0, ctx->ev_all1, pipe.ev_call}) (void)hipEventDestroy(e);
 	for (int i = 0; i < 2; i++) {
 		BlockPipe::Side& sd = pipe.side[i];
-		for (DevBuf* b : {&sd.qT, &sd.min, &sd.diff, &sd.anib, &sd.hot, &sd.hot_idx, &pipe.close_pp[i]}) release(*b);
+		for (DevBuf* b : {&sd.qT, &sd.min, &sd.diff, &sd.anib, &sd.hot, &sd.hot_idx, &pipe.close_pp[i], &pipe.arena[i].buf}) release(*b);
+		if (pipe.arena[i].ev_ready) (void)hipEventDestroy(pipe.arena[i].ev_ready);
 		for (hipEvent_t e : {sd.ev_head, sd.ev_product, sd.ev_tail, sd.ev_prep, pipe.ev_scored[i], pipe.ev_copied[i]}) (void)hipEventDestroy(e);
 	}
 	for (hipStream_t s : {pipe.copy_stream, pipe.tail_stream, pipe.prep_stream}) (void)hipStreamDestroy(s);
@@ -195,6 +198,12 @@ extern "C" int msc_set_block_pipe(msc_ctx* ctx, int on) {
 extern "C" int msc_set_emd_bounds(msc_ctx* ctx, int on) {
 	if (!ctx) return MSC_ERR_INVALID_ARG;
 	ctx->emd_bounds = on != 0;
+	return MSC_OK;
+}
+
+extern "C" int msc_set_query_groups(msc_ctx* ctx, int cap) {
+	if (!ctx || cap < 0) return MSC_ERR_INVALID_ARG;
+	ctx->query_groups = (uint32_t)cap;
 	return MSC_OK;
 }
 

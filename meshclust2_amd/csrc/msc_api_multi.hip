@@ -129,6 +129,10 @@ struct MultiCall {
 	int launches = 0;
 	std::vector<MscMultiBlock> blocks;
 	std::vector<BlockRoute> taken;          // the routes of the blocks the matrix cores take, in the order of `blocks`
+	// msc_set_query_groups: the groups of two blocks and more (msc_query_groups), the arena each was built in (-1: not yet), and per block of the plan
+	// its group (-1: the block builds its own queries' side)
+	std::vector<MscQueryGroup> groups;
+	std::vector<int> group_arena, group_of;
 };
 
 // one block of the call: its queries, its rows of the caller's arrays, and what its route's steps hand one another while it runs
@@ -173,6 +177,7 @@ int flush_deferred(MultiCall& c) {
 		pipe.tail_used = false;
 		for (BlockPipe::Side& s : pipe.side) s.tail_busy = s.product_busy = false;          // (every product waited for its queries' side: the prep stream is idle too)
 	}
+	for (BlockPipe::Arena& a : pipe.arena) a.busy = false;          // (what read them is through; a group built ahead of its blocks stays as it is)
 	for (size_t i = 0; i + 1 < pipe.ev_used; i += 2) {
 		float t = 0;
 		if (e == hipSuccess && hipEventElapsedTime(&t, pipe.ev_pool[i], pipe.ev_pool[i + 1]) == hipSuccess) { c.ms += t; ctx->have_timing = true; }
@@ -553,8 +558,25 @@ int run_streamed(MultiCall& c, Block& b, const BlockRoute& rt) {
 // A flags-only block whose distance comes from the ranks mirrors runs no walk beside the product: its tail is the bound screen, the walk and the FP64 evaluation of
 // the listed pairs, then the dense walk and the two older epilogue kernels predicated on the list's overflow word (msc_emd_list.hip).
 // Such a block in one chunk runs its product over bits folded F-to-1 where both sets carry the folded mirror (msc_fold.h).
+// Consecutive piped blocks of 128 rows share ONE build of the queries' side (plan_query_groups, group_side; msc_set_query_groups): a group's images and lists lie in one of
+// two arenas, built on the prep stream a group ahead of the blocks that read them; such a block's qT, anib and hot list are views into the arena.
 // What a block decides is plain arithmetic (msc_matrix_stages, msc_multi_plan.h) over facts gathered in one place (matrix_facts); run_matrix is the order of the
 // stages, one function each. A stage issues, in its own order, everything it puts on a stream: a re-cut of what was one body, in the same order.
+
+// what a block on the matrix cores settles first: its query rows, its candidates per launch, whether a merge pass serves the divergence sums
+uint32_t settle_matrix_block(const MultiCall& c, Block& b) {
+	const uint32_t rows = msc_pair_gemm_rows((uint32_t)b.nq);
+	b.chunk = matrix_chunks(c.ctx, c.cands->L.nbins, c.m, rows, group_chunk_limit(c, b.nq)).chunk;
+	b.div_pass = c.want_div && !c.cells;
+	return rows;
+}
+
+// the product arrays of a side alone (a grouped block: its images and lists are views into its group's arena)
+int ensure_products(msc_ctx* ctx, BlockPipe::Side& s, uint32_t rows, uint32_t slices, uint64_t chunk, uint64_t n_hot) {
+	int r;
+	if ((r = ensure(ctx, s.min, (size_t)slices * chunk * rows * sizeof(int32_t)))) return r;
+	return n_hot ? ensure(ctx, s.diff, chunk * rows * sizeof(int32_t)) : MSC_OK;
+}
 
 // the facts of a block on the matrix cores -- beside pick_route the only reader of environment switches here: MSC_NO_SCREEN (FP64 for every pair of
 // a flags-only block), MSC_GEMM_NO_PREP. second_run: rerun_overflowed's
@@ -578,6 +600,36 @@ MscMatrixFacts matrix_facts(const MultiCall& c, const Block& b, const BlockRoute
 	return f;
 }
 
+Block block_of(const MultiCall& c, size_t i);
+
+// msc_set_query_groups: the groups of the call's plan (msc_query_groups, msc_multi_plan.h) -- a block joins on the stage decisions it will take when it runs
+// (its route, the call and the context's switches settle them: nothing a block before it does changes them)
+constexpr uint64_t kArenaBudget = 512ull << 20;
+void plan_query_groups(MultiCall& c) {
+	msc_ctx* ctx = c.ctx;
+	c.groups.clear(); c.group_arena.clear(); c.group_of.clear();
+	if (ctx->query_groups < 2) return;
+	std::vector<MscGroupBlock> gb(c.blocks.size(), MscGroupBlock{false, 0, 0});
+	size_t next_taken = 0;
+	for (size_t i = 0; i < c.blocks.size(); i++) {
+		if (!c.blocks[i].matrix) continue;
+		const BlockRoute& rt = c.taken[next_taken++];
+		Block b = block_of(c, i);
+		const uint32_t rows = settle_matrix_block(c, b);
+		const MscMatrixStages st = msc_matrix_stages(matrix_facts(c, b, rt, false));
+		gb[i] = MscGroupBlock{st.piped && rows == 128, st.fold, rt.n_hot};
+	}
+	std::vector<MscQueryGroup> all;
+	msc_query_groups(gb, c.cands->L.nbins, ctx->query_groups, kArenaBudget, all);
+	c.group_of.assign(c.blocks.size(), -1);
+	for (const MscQueryGroup& g : all) {
+		if (g.n < 2) continue;          // (a group of one block: the per-block path)
+		for (size_t i = g.first; i < g.first + g.n; i++) c.group_of[i] = (int)c.groups.size();
+		c.groups.push_back(g);
+	}
+	c.group_arena.assign(c.groups.size(), -1);
+}
+
 // a block on the matrix cores: what is settled before anything of it is issued, and what its stages hand one another
 struct MatrixBlock {
 	MscMatrixStages st;                               // the decisions
@@ -588,6 +640,9 @@ struct MatrixBlock {
 	BlockPipe::Side* s = nullptr;
 	hipStream_t prep = nullptr;                       // where the queries' side runs
 	HotList hot;
+	int group = -1;                                   // the block's group of the call (-1: none: the images below are its side's own)
+	const uint8_t *qT = nullptr, *anib = nullptr;     // the queries' images and the entries of the hot list: the side's buffers, or views into the group's arena
+	const void* hot_entries = nullptr;
 };
 // a chunk's tail: the epilogue's arguments, and the one of the two buffers its close flags go into
 struct Tail { MscEpilogueArgs ea; int pp = 0; uint8_t* d_close = nullptr; };
@@ -618,7 +673,7 @@ int wait_side_free(msc_ctx* ctx, const MatrixBlock& p) {
 	for (int i = 0; i < 2; i++)
 		if (pipe.side[i].tail_busy && (!p.st.piped || i == p.pb)) {
 			HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, pipe.side[i].ev_tail, 0));
-			if (p.prep != ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(p.prep, pipe.side[i].ev_tail, 0));          // (it rewrites the transposed image that epilogue read)
+			if (p.prep != ctx->stream && p.group < 0) HIP_TRY(ctx, hipStreamWaitEvent(p.prep, pipe.side[i].ev_tail, 0));          // (it rewrites the transposed image that epilogue read; a grouped block's image is its arena's)
 			if (!p.st.piped) pipe.side[i].tail_busy = false;
 		}
 	return MSC_OK;
@@ -651,6 +706,64 @@ int queries_side(const MultiCall& c, const Block& b, const MatrixBlock& p) {
 	return MSC_OK;
 }
 
+// the queries' side of group g of the call, in the arena whose turn it is, on the prep stream (or the context's): once the call's query slots are up and
+// the last block that read the arena is through with its product and its tail (both streams run their blocks in order: the last block's events cover the group)
+int build_group_side(MultiCall& c, int g, hipStream_t prep) {
+	msc_ctx* ctx = c.ctx;
+	BlockPipe& pipe = ctx->pipe;
+	const msc_hist_set* qset = c.qset;
+	const MscQueryGroup& G = c.groups[g];
+	const int ai = (int)(pipe.arena_next++ & 1);
+	BlockPipe::Arena& A = pipe.arena[ai];
+	int r;
+	if ((r = ensure(ctx, A.buf, G.bytes))) return r;
+	if (prep != ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(prep, pipe.ev_call, 0));
+	if (A.busy) {
+		if (prep != ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(prep, A.last->ev_product, 0));
+		HIP_TRY(ctx, hipStreamWaitEvent(prep, A.last->ev_tail, 0));
+		A.busy = false;
+	}
+	uint8_t* base = (uint8_t*)A.buf.p;
+	const MscMultiBlock& last = c.blocks[G.first + G.n - 1];
+	HIP_TRY(ctx, msc_launch_query_group(prep, c.cands->L.nbins, G.fold, qset->kb, qset->kbf, qset->mb, qset->mb_n, qset->mb_pitch, (const uint32_t*)ctx->qslots_all.p + c.blocks[G.first].q0,
+	                                    (uint32_t)G.n, (uint32_t)last.nq, base + G.qt_off, G.qt_stride, base + G.anib_off, G.anib_stride, G.hot_stride, base + G.hot_off,
+	                                    (uint32_t*)(base + G.ptr_off), (uint32_t*)(base + G.cursor_off), (uint32_t*)(base + G.cnt_off), G.idx_stride));
+	if (prep != ctx->stream) HIP_TRY(ctx, hipEventRecord(A.ev_ready, prep));
+	c.group_arena[g] = ai;
+	return MSC_OK;
+}
+
+// The queries' side of a block of a group: views into the group's arena. The group's first block sees to it that the side is built -- and, on a prep stream
+// of its own, the next group's too, under this group's blocks -- and has the product's stream wait for it, once for the group.
+int group_side(MultiCall& c, const Block& b, MatrixBlock& p) {
+	msc_ctx* ctx = c.ctx;
+	BlockPipe& pipe = ctx->pipe;
+	const int g = p.group;
+	const MscQueryGroup& G = c.groups[g];
+	int r;
+	if (b.idx == G.first) {
+		if (c.group_arena[g] < 0 && (r = build_group_side(c, g, p.prep))) return r;
+		if (p.prep != ctx->stream) {
+			HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, pipe.arena[c.group_arena[g]].ev_ready, 0));
+			if (g + 1 < (int)c.groups.size() && (r = build_group_side(c, g + 1, p.prep))) return r;
+		}
+	}
+	BlockPipe::Arena& A = pipe.arena[c.group_arena[g]];
+	const uint64_t j = b.idx - G.first;
+	uint8_t* base = (uint8_t*)A.buf.p;
+	p.qT = base + G.qt_off + j * G.qt_stride;
+	p.anib = base + G.anib_off + j * G.anib_stride;
+	p.hot = HotList();
+	if (p.rt->n_hot) {
+		p.hot_entries = base + G.hot_off + j * G.hot_stride * 8;
+		p.hot.ptr = (uint32_t*)(base + G.ptr_off) + j * G.idx_stride;
+		p.hot.cursor = (uint32_t*)(base + G.cursor_off) + j * G.idx_stride;
+		p.hot.cnt = (uint32_t*)(base + G.cnt_off) + j * G.idx_stride;
+	}
+	A.last = p.s; A.busy = true;          // (this block's product and tail are queued before anything asks)
+	return MSC_OK;
+}
+
 // the whole pass over a chunk's bins: products and level products on the matrix cores, timed as the streaming kernel between ev_t0 and ev_t1
 int product_stage(const MultiCall& c, const Block& b, const MatrixBlock& p, const Chunk& k, hipEvent_t ev_t0, hipEvent_t ev_t1) {
 	msc_ctx* ctx = c.ctx;
@@ -660,8 +773,8 @@ int product_stage(const MultiCall& c, const Block& b, const MatrixBlock& p, cons
 		HIP_TRY(ctx, hipStreamWaitEvent(b.tail, s.ev_head, 0));
 	}
 	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ev_t0, ctx->stream));
-	HIP_TRY(ctx, msc_launch_pair_gemm(ctx->stream, p.nbins_f, p.st.fold ? c.cands->kbf : c.cands->kb, k.d_slots, k.off, k.mc, p.rows, p.slices_f, p.hot.ptr, s.hot.p, (int32_t*)s.min.p,
-	                                  (int32_t*)s.diff.p, (const uint8_t*)s.anib.p));
+	HIP_TRY(ctx, msc_launch_pair_gemm(ctx->stream, p.nbins_f, p.st.fold ? c.cands->kbf : c.cands->kb, k.d_slots, k.off, k.mc, p.rows, p.slices_f, p.hot.ptr, p.hot_entries, (int32_t*)s.min.p,
+	                                  (int32_t*)s.diff.p, p.anib));
 	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ev_t1, ctx->stream));
 	if (p.st.piped) { HIP_TRY(ctx, hipEventRecord(s.ev_product, ctx->stream)); s.product_busy = true; }
 	return MSC_OK;
@@ -678,6 +791,7 @@ int tail_ready(MultiCall& c, Block& b, const MatrixBlock& p, const Chunk& k, Tai
 	fill_block_args(c, b, b.dq_slots, k, c.cands->L.S, ea);
 	if ((r = side_passes(c, b, k, ea))) return r;
 	fill_matrix_args(ea, *p.s, c.cands, c.qset, p.slices, p.rows, c.cand_slots ? 0 : k.off, rt.n_hot, rt.emd_ranks ? ctx->emd_out.p : nullptr);
+	ea.kb_qT = p.qT;
 	ea.cq_group = 16;
 	if (c.cells) { ea.div_cells = 1; ea.kb_c_bits = c.cands->kb; }          // the two sums in the epilogue, as msc_search_pairs sets them (msc_api_pairs.hip)
 	t.pp = pipe.close_pp_next;
@@ -729,7 +843,7 @@ int list_stage(const MultiCall& c, const Block& b, const MatrixBlock& p, const C
 	const bool u16 = cands->ranks16 && qset->ranks16;
 	HIP_TRY(ctx, msc_launch_epilogue_bound(b.tail, e));
 	if (e.fold_x_c) {          // (the listed pairs of a folded stage: their exact P1 / P2 into the product's arrays first)
-		const MscFoldExact fx{cands->ranks, cands->rk_pitch, L.nbins, L.E, L.R, k.d_slots, k.off, k.mc, b.dq_slots, e.open_list, e.open_words, open_cap, (const uint8_t*)s.qT.p, p.rows,
+		const MscFoldExact fx{cands->ranks, cands->rk_pitch, L.nbins, L.E, L.R, k.d_slots, k.off, k.mc, b.dq_slots, e.open_list, e.open_words, open_cap, p.qT, p.rows,
 		                      qset->mb, qset->mb_n, qset->mb_pitch, (int32_t*)s.min.p, e.kb_slices, p.rt->n_hot ? (int32_t*)s.diff.p : nullptr};
 		HIP_TRY(ctx, msc_launch_fold_exact_list(b.tail, fx, ctx->num_cus));
 	}
@@ -828,14 +942,19 @@ int run_matrix(MultiCall& c, Block& b, const BlockRoute& rt, bool second_run = f
 	const uint64_t nbins = c.cands->L.nbins;
 	int r;
 	if ((r = begin_block(ctx)) || (r = block_uploads(c, b, rt.queued))) return r;
-	const uint32_t rows = msc_pair_gemm_rows((uint32_t)b.nq);
-	b.chunk = matrix_chunks(ctx, nbins, c.m, rows, group_chunk_limit(c, b.nq)).chunk;
-	b.div_pass = c.want_div && !c.cells;
+	const uint32_t rows = settle_matrix_block(c, b);
 	if ((r = ensure_block_scratch(c, b, true))) return r;
 	MatrixBlock p = plan_matrix(c, b, rt, rows, second_run);
+	p.group = second_run || c.group_of.empty() ? -1 : c.group_of[b.idx];
+	if (p.group >= 0 && (!p.st.piped || rows != 128 || p.st.fold != c.groups[p.group].fold)) return fail(ctx, MSC_ERR_HIP, "a grouped block's stages are not those its group was planned with");
 	if ((r = wait_side_free(ctx, p))) return r;
 	// (a folded block passes the true bin count and the larger of the two slice counts)
-	if ((r = ensure_side(ctx, *p.s, nbins, rows, std::max(p.slices, p.slices_f), b.chunk, rt.n_hot, &p.hot)) || (r = queries_side(c, b, p))) return r;
+	if (p.group >= 0) {
+		if ((r = ensure_products(ctx, *p.s, rows, std::max(p.slices, p.slices_f), b.chunk, rt.n_hot)) || (r = group_side(c, b, p))) return r;
+	} else {
+		if ((r = ensure_side(ctx, *p.s, nbins, rows, std::max(p.slices, p.slices_f), b.chunk, rt.n_hot, &p.hot)) || (r = queries_side(c, b, p))) return r;
+		p.qT = (const uint8_t*)p.s->qT.p; p.anib = (const uint8_t*)p.s->anib.p; p.hot_entries = p.s->hot.p;
+	}
 	if (rt.emd_ranks && (r = ensure(ctx, ctx->emd_out, b.chunk * rows * sizeof(uint64_t)))) return r;
 	name_matrix_kernel(ctx, rows, rt.emd_ranks, c.cells, c.cands->sparse, p.st.fold);
 	ctx->last_query_tile = (int)b.nq;
@@ -980,6 +1099,7 @@ int score_multi(MultiCall& c) {
 		return rt.kind != R_MATRIX;
 	}, c.blocks);
 	if (err) return err;
+	plan_query_groups(c);
 	size_t next_taken = 0;
 	std::vector<BlockRoute> route_of(c.blocks.size());
 	for (size_t i = 0; i < c.blocks.size(); i++) {

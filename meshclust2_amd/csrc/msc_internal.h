@@ -302,6 +302,10 @@ hipError_t msc_launch_kb_fold(hipStream_t st, uint64_t nbins, uint32_t fold, con
 hipError_t msc_launch_kb_gather(hipStream_t st, uint64_t nbins, const uint8_t* q_kb, const uint32_t* q_slots_dev, uint32_t n_q, uint32_t qn, uint8_t* qT, uint8_t* anib);
 hipError_t msc_launch_hot_list(hipStream_t st, uint64_t nbins, uint32_t fold, const void* q_mb, const uint32_t* q_mb_n, uint32_t q_pitch, const uint32_t* q_slots_dev,
                                uint32_t n_q, uint32_t qn, uint8_t* qT, uint64_t n_hot, void* hot, uint32_t* hot_ptr, uint32_t* hot_cursor, uint32_t* hot_cnt);
+// ... and both parts for a group of blocks of 128 rows in one set of launches (msc_query_groups, msc_multi_plan.h): images and lists a stride apart
+hipError_t msc_launch_query_group(hipStream_t st, uint64_t nbins, uint32_t fold, const uint8_t* q_kb, const uint8_t* q_kbf, const void* q_mb, const uint32_t* q_mb_n,
+                                  uint32_t q_pitch, const uint32_t* q_slots_dev, uint32_t n_blocks, uint32_t n_q_last, uint8_t* qT, uint64_t qt_stride, uint8_t* anib,
+                                  uint64_t anib_stride, uint64_t hot_stride, void* hot, uint32_t* hot_ptr, uint32_t* hot_cursor, uint32_t* hot_cnt, uint64_t idx_stride);
 hipError_t msc_launch_epilogue(hipStream_t st, const MscEpilogueArgs& a);
 hipError_t msc_launch_epilogue_bound(hipStream_t st, const MscEpilogueArgs& a);
 hipError_t msc_launch_epilogue_list(hipStream_t st, const MscEpilogueArgs& a, int num_cus);

@@ -90,3 +90,54 @@ inline MscMatrixChunk msc_matrix_chunk(const MscMatrixStages& s, uint64_t n_q, u
 	const bool bounds = s.bounds_call && msc_list_pairs_fit(n_q * mc);
 	return MscMatrixChunk{bounds, bounds ? (uint32_t)(n_q * mc / 64) : 0, !bounds ? MSC_TAIL_SCORED : s.fold ? MSC_TAIL_FOLDED : MSC_TAIL_BOUNDS};
 }
+
+// ---- the queries' side of several blocks in one set of launches (msc_set_query_groups; group_side, msc_api_multi.hip). Consecutive blocks of
+// a call form a GROUP when each of them `joins` (it takes the matrix cores piped, with 128 query rows, and is not a second run) and they agree
+// on the fold. A group's images lie in one arena, region by region, block j of the group at a region's offset + j strides:
+//   qT      the transposed planes of the TRUE bins                           nbins x 32 bytes a block
+//   anib    the nibble tiles of the bins the product runs on                 nbins / fold x 64 bytes
+//   hot     the hot lists, one stride for all: the group's longest list      8 bytes an entry
+//   ptr, cursor, cnt   the lists' step arrays                                nbins / fold / 128 + 1 words each
+// Size of a group: the blocks left of the run, at most `cap`, at most what `budget` bytes hold (never fewer than one: a group of one block is
+// left to the per-block path, as is every block with cap < 2). Every offset and stride is a multiple of 16 bytes.
+struct MscGroupBlock { bool joins; uint32_t fold; uint64_t n_hot; };
+struct MscQueryGroup {
+	size_t first = 0, n = 0;                 // blocks [first, first + n) of the plan
+	uint32_t fold = 0;
+	uint64_t hot_stride = 0, idx_stride = 0; // entries of a block's hot list; words of each of its three step arrays (0, 0: no block of the group has a list)
+	uint64_t qt_stride = 0, anib_stride = 0; // bytes
+	uint64_t qt_off = 0, anib_off = 0, hot_off = 0, ptr_off = 0, cursor_off = 0, cnt_off = 0, bytes = 0;          // byte offsets of the regions; the arena's size
+};
+
+inline uint64_t msc_group_block_bytes(uint64_t nbins, uint32_t fold, uint64_t hot_stride) {
+	const uint64_t nbins_f = fold ? nbins / fold : nbins, idx = hot_stride ? (nbins_f / 128 + 1 + 3) / 4 * 4 : 0;
+	return nbins * 32 + nbins_f * 64 + hot_stride * 8 + 3 * idx * sizeof(uint32_t);
+}
+
+inline void msc_query_groups(const std::vector<MscGroupBlock>& blocks, uint64_t nbins, uint32_t cap, uint64_t budget, std::vector<MscQueryGroup>& out) {
+	out.clear();
+	const size_t limit = std::max<uint32_t>(cap, 1);
+	for (size_t i = 0; i < blocks.size();) {
+		if (!blocks[i].joins) { i++; continue; }
+		size_t end = i;
+		while (end < blocks.size() && end - i < limit && blocks[end].joins && blocks[end].fold == blocks[i].fold) end++;
+		auto longest = [&](size_t n) { uint64_t h = 0; for (size_t j = i; j < i + n; j++) h = std::max(h, blocks[j].n_hot); return (h + 1) / 2 * 2; };
+		MscQueryGroup g;
+		g.first = i; g.fold = blocks[i].fold;
+		const uint64_t fit = budget / msc_group_block_bytes(nbins, g.fold, longest(end - i));          // (with the longest list of the whole run: a shorter group's is no longer)
+		g.n = (size_t)std::min<uint64_t>(end - i, std::max<uint64_t>(fit, 1));
+		const uint64_t nbins_f = g.fold ? nbins / g.fold : nbins;
+		g.hot_stride = longest(g.n);
+		g.idx_stride = g.hot_stride ? (nbins_f / 128 + 1 + 3) / 4 * 4 : 0;
+		g.qt_stride = nbins * 32; g.anib_stride = nbins_f * 64;
+		g.qt_off = 0;
+		g.anib_off = g.qt_off + g.n * g.qt_stride;
+		g.hot_off = g.anib_off + g.n * g.anib_stride;
+		g.ptr_off = g.hot_off + g.n * g.hot_stride * 8;
+		g.cursor_off = g.ptr_off + g.n * g.idx_stride * sizeof(uint32_t);
+		g.cnt_off = g.cursor_off + g.n * g.idx_stride * sizeof(uint32_t);
+		g.bytes = g.cnt_off + g.n * g.idx_stride * sizeof(uint32_t);
+		out.push_back(g);
+		i += g.n;
+	}
+}

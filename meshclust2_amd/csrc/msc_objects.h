@@ -16,6 +16,14 @@ struct DevBuf {
 // The matrix-core block pipe (msc_pair_gemm.hip; run_matrix and its stage functions, msc_api_multi.hip). msc_score_multi queues the blocks of its matrix-core pass in stages on three
 // streams: the queries' side of block i + 1 (prep_stream) under the product of block i (the context's stream), beside the rank walk of block i and the
 // epilogue of block i - 1 (tail_stream). What two stages touch exists twice and blocks take turns; msc_search_pairs, on one stream, uses side[0] alone.
+// Consecutive piped blocks of 128 rows form GROUPS (msc_set_query_groups, msc_query_groups in msc_multi_plan.h): the queries' side of a whole group is one
+// set of launches into one of two arenas, issued once on prep_stream while the blocks of the group before run -- the products of the group wait for it
+// once (ev_ready), and the arena is rewritten behind the product and the tail of the last block that read it. A grouped block's qT, anib and hot list are
+// views into the arena; its side keeps min and diff, and what remains per block is the product, the tail and the flags' way home:
+//
+//   prep_stream   | side of group g + 1 (arena 1)          | side of group g + 2 (arena 0) ...
+//   the stream    | product g.0 | product g.1 | ... | product g.n-1 | product g+1.0 | ...
+//   tail_stream   |             | tail g.0    | tail g.1 ...
 struct BlockPipe {
 	struct Side {
 		// bit image transposed, P1 per slice, P2, the queries' tiles as nibbles (what the product copies into LDS), hot list + its three step arrays
@@ -24,6 +32,15 @@ struct BlockPipe {
 		hipEvent_t ev_head = nullptr, ev_product = nullptr, ev_tail = nullptr, ev_prep = nullptr;
 		bool product_busy = false, tail_busy = false;          // a product that reads this side / an epilogue that read it has been queued
 	} side[2];
+	// the queries' side of a group of blocks: its images and lists (msc_query_groups lays them out); ready: the group's side is through; last: the side of
+	// the pipe the last block that reads the arena took (its ev_product and ev_tail), busy: such a block has been queued
+	struct Arena {
+		DevBuf buf;
+		hipEvent_t ev_ready = nullptr;
+		Side* last = nullptr;
+		bool busy = false;
+	} arena[2];
+	uint32_t arena_next = 0;               // the arena the next group takes (its low bit)
 	hipStream_t tail_stream = nullptr, prep_stream = nullptr, copy_stream = nullptr;
 	hipEvent_t ev_call = nullptr;          // the call's query slots are on the device
 	// the close flags of a block go back to the host on copy_stream, under the next block's kernels: two device buffers take turns, and
@@ -79,6 +96,7 @@ struct msc_ctx {
 	DevBuf shard_payload, shard_hdrs;
 	BlockPipe pipe;                        // msc_pair_gemm.hip: the queries' side of a block and the streams its stages run on
 	bool block_pipe = true;                // msc_set_block_pipe: the blocks of msc_score_multi on three streams
+	uint32_t query_groups = 32;            // msc_set_query_groups / MSC_NO_QUERY_GROUPS: most blocks whose queries' side one set of launches builds (0, 1: block by block)
 	bool pairs_div_cells = false;          // msc_set_pairs_div_cells: msc_search_pairs keeps divergence-statistic models on the matrix-core route
 	bool multi_div_cells = false;          // msc_set_multi_div_cells: msc_score_multi keeps blocks that want a divergence statistic on the matrix-core route, no merge pass
 	bool sparse_matrix_pass = false;       // msc_set_sparse_matrix_pass: two sparse sets may take the matrix-core Q x M route (mirrors built from their lists)

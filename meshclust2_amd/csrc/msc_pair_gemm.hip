@@ -23,6 +23,8 @@
 //   k_kb_gather          the queries' side of a block of <= QN queries: their bits as the nibble tiles the product copies into LDS, and
 //                        transposed as two bit planes per bin ("the query holds this k-mer", "... more than once") for the epilogue
 //   k_hot_*              the queries' large bins bucketed by 128-bin step: (bin, query row, e - 1); the fill also sets the second plane
+//   k_kb_gather_group, k_hot_*_group   the same images and lists for a GROUP of blocks of 128 rows in one set of launches (msc_launch_query_group;
+//                        msc_query_groups in msc_multi_plan.h lays them out in one arena)
 //   k_pair_gemm_fp4_dma  the product on v_mfma_f32_32x32x64_f8f6f4 with E2M1 operands: workgroup = 128 candidates x QN queries, wave = 32
 //                        candidates x QN queries (QN / 32 accumulators of 32 x 32); both operands arrive in LDS by LDS-DMA. Roofline: the
 //                        FP4 matrix pipe (~10 POPS dense at 2.4 GHz; 8.7 measured back to back, tools/ubench/mfma_rate.hip) --
@@ -318,6 +320,114 @@ __global__ void __launch_bounds__(256) k_hot_fill(const uint2* __restrict__ mb, 
 	}
 }
 
+// ------------------------------------------------------------------------------------------------ the queries' side of a GROUP of blocks
+// The same images for several blocks of 128 query rows in one launch (msc_query_groups, msc_multi_plan.h): blockIdx.y = block of the
+// group, its query slots at q_slots + 128 y, its images a stride behind the block's before it (the last block may hold fewer than 128
+// queries: n_q_last). A workgroup takes one block and a run of kGatherRun super-steps and reads the mirror as it lies: lane l of wave w
+// loads the 16-byte half l / 32 of row 32 w + l % 32 of a super-step -- the whole 32-byte record of a (row, super-step) in one
+// instruction, every byte of a row once per block, and 1 KiB in a piece per wave where the rows are neighbours in the mirror (a record
+// is all the mirror keeps contiguous of one row: its super-steps lie a KiB apart). The load of the next super-step is in flight while
+// this one is transposed. Bit p of a half h is bin 32 (p / 16) + 16 h + p % 16 of the super-step, so one ballot is the 32 rows of the
+// wave at TWO bins (low word: h = 0, high word: the bin 16 further on); lane l keeps ballots l and l + 64, and the 16-byte pieces of the
+// planes leave through LDS, 4 KiB contiguous per store instruction. The images are k_kb_gather's, byte for byte.
+constexpr uint32_t kGatherRun = 8;
+__global__ void __launch_bounds__(256) k_kb_gather_group(const uint8_t* __restrict__ kb, const uint32_t* __restrict__ q_slots, uint32_t n_q_last, uint64_t nbins,
+                                                         uint8_t* __restrict__ qT, uint64_t qt_stride, uint8_t* __restrict__ anib, uint64_t anib_stride) {
+	__shared__ uint32_t qbits[2][4][256];          // [turn][word of 32 rows][bin of the super-step]
+	const uint32_t blk = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, row = 32 * wv + (lane & 31), h = lane >> 5;
+	const uint32_t n_q = blk + 1 == gridDim.y ? n_q_last : 128, nss = (uint32_t)(nbins / 256), ss0 = blockIdx.x * kGatherRun;
+	const uint32_t n_run = nss - ss0 < kGatherRun ? nss - ss0 : kGatherRun;
+	const bool live = row < n_q;          // (rows past n_q are zero)
+	const uint8_t* src = live ? kb + msc_kb_offset(q_slots[(uint64_t)blk * 128 + row], (uint64_t)ss0 * 256, nbins) + 16 * h : kb;
+	if (qT) qT += (uint64_t)blk * qt_stride;
+	if (anib) anib += (uint64_t)blk * anib_stride;
+	v4i next = v4i{0, 0, 0, 0};
+	if (live) next = *reinterpret_cast<const v4i*>(src);
+#pragma unroll 1
+	for (uint32_t r = 0; r < n_run; r++) {
+		const v4i v = next;
+		if (live && r + 1 < n_run) next = *reinterpret_cast<const v4i*>(src + (uint64_t)(r + 1) * 1024);
+		const uint32_t ss = ss0 + r;
+		if (anib) {          // word t of half h = the nibbles lane half h feeds the super-step's product t (k_kb_gather's w)
+			v4i* tile_row = reinterpret_cast<v4i*>(anib) + ((uint64_t)ss * 128 + row) * 8;
+#pragma unroll
+			for (uint32_t t = 0; t < 4; t++) {
+				const uint32_t w = (uint32_t)v[t];
+				tile_row[(2 * t + h) ^ ((row >> 1) & 7)] = v4i{(int)((w << 2) & 0x44444444u), (int)(w & 0x22222222u), (int)((w >> 2) & 0x11111111u), (int)((w >> 1) & 0x44444444u)};
+			}
+		}
+		if (!qT) continue;          // (uniform)
+		uint32_t lo[2] = {0, 0}, hi[2] = {0, 0};
+#pragma unroll
+		for (uint32_t p = 0; p < 128; p++) {
+			const unsigned long long b = __builtin_amdgcn_ballot_w64(((uint32_t)v[p >> 5] >> (p & 31)) & 1u);
+			const bool mine = lane == (p & 63);          // (a select, as in k_kb_gather)
+			lo[p >> 6] = mine ? (uint32_t)b : lo[p >> 6];
+			hi[p >> 6] = mine ? (uint32_t)(b >> 32) : hi[p >> 6];
+		}
+		uint32_t* qb = &qbits[r & 1][0][0];
+#pragma unroll
+		for (uint32_t g = 0; g < 2; g++) {
+			const uint32_t p = 64 * g + lane, bin = 32 * (p >> 4) + (p & 15);
+			qb[wv * 256 + bin] = lo[g];
+			qb[wv * 256 + bin + 16] = hi[g];
+		}
+		__syncthreads();          // (one barrier a super-step: turn r & 1 is written again two barriers on, behind every read of it)
+		uint4* rec = reinterpret_cast<uint4*>(qT + (uint64_t)ss * 256 * 32);
+#pragma unroll
+		for (uint32_t it = tid; it < 512; it += 256) {          // 16-byte piece `it` of the super-step: bin it / 2, plane it % 2; plane 1 leaves as zeros
+			const uint32_t bin = it >> 1;
+			rec[it] = it & 1 ? make_uint4(0, 0, 0, 0) : make_uint4(qb[bin], qb[256 + bin], qb[512 + bin], qb[768 + bin]);
+		}
+	}
+}
+
+// the hot lists of a group: k_hot_count / _scan / _fill with blockIdx.y = block of the group, its step arrays idx_stride words and its entries hot_stride
+// entries behind those of the block before it
+__global__ void __launch_bounds__(256) k_hot_count_group(const uint2* __restrict__ mb, const uint32_t* __restrict__ mb_n, uint32_t pitch, const uint32_t* __restrict__ q_slots,
+                                                         uint32_t n_q_last, uint32_t* __restrict__ cnt, uint64_t idx_stride, uint64_t nbins, uint32_t fold) {
+	const uint32_t row = blockIdx.x, blk = blockIdx.y;
+	if (row >= (blk + 1 == gridDim.y ? n_q_last : 128u)) return;
+	const uint32_t slot = q_slots[(uint64_t)blk * 128 + row];
+	const uint32_t n = mb_n[slot] < pitch ? mb_n[slot] : pitch;
+	cnt += blk * idx_stride;
+	for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) atomicAdd(&cnt[msc_fold_bin_of(mb[(uint64_t)slot * pitch + i].x, nbins, fold) / kStep], 1u);
+}
+__global__ void __launch_bounds__(1024) k_hot_scan_group(const uint32_t* __restrict__ cnt, uint32_t nsteps, uint32_t* __restrict__ ptr, uint32_t* __restrict__ cursor, uint64_t idx_stride) {
+	__shared__ uint32_t part[1024];
+	cnt += blockIdx.x * idx_stride; ptr += blockIdx.x * idx_stride; cursor += blockIdx.x * idx_stride;
+	const uint32_t per = (nsteps + 1023) / 1024, lo = threadIdx.x * per < nsteps ? threadIdx.x * per : nsteps, hi = lo + per < nsteps ? lo + per : nsteps;
+	uint32_t s = 0;
+	for (uint32_t i = lo; i < hi; i++) s += cnt[i];
+	part[threadIdx.x] = s;
+	__syncthreads();
+	for (uint32_t d = 1; d < 1024; d <<= 1) {
+		const uint32_t v = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
+		__syncthreads();
+		part[threadIdx.x] += v;
+		__syncthreads();
+	}
+	uint32_t run = part[threadIdx.x] - s;
+	for (uint32_t i = lo; i < hi; i++) { ptr[i] = run; cursor[i] = run; run += cnt[i]; }
+	if (threadIdx.x == 1023) ptr[nsteps] = part[1023];
+}
+__global__ void __launch_bounds__(256) k_hot_fill_group(const uint2* __restrict__ mb, const uint32_t* __restrict__ mb_n, uint32_t pitch, const uint32_t* __restrict__ q_slots,
+                                                        uint32_t n_q_last, uint32_t* __restrict__ cursor, uint64_t idx_stride, uint2* __restrict__ hot, uint64_t hot_stride,
+                                                        uint8_t* __restrict__ qT, uint64_t qt_stride, uint64_t nbins, uint32_t fold) {
+	const uint32_t row = blockIdx.x, blk = blockIdx.y;
+	if (row >= (blk + 1 == gridDim.y ? n_q_last : 128u)) return;
+	const uint32_t slot = q_slots[(uint64_t)blk * 128 + row];
+	const uint32_t n = mb_n[slot] < pitch ? mb_n[slot] : pitch;
+	cursor += blk * idx_stride; hot += blk * hot_stride; qT += blk * qt_stride;
+	for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+		const uint2 en = mb[(uint64_t)slot * pitch + i];
+		const uint32_t g = en.y - 1 > 0xffffu ? 0xffffu : en.y - 1;
+		const uint32_t fb = (uint32_t)msc_fold_bin_of(en.x, nbins, fold);
+		hot[atomicAdd(&cursor[fb / kStep], 1u)] = make_uint2(fb, (row << 16) | g);
+		atomicOr(reinterpret_cast<uint32_t*>(qT) + msc_qt_word(en.x, 1, row, 128), 1u << (row & 31));
+	}
+}
+
 // ------------------------------------------------------------------------------------------------ the product
 // v_mfma_f32_32x32x64_f8f6f4 with both operands in FP4 (E2M1): 64 bins per instruction (MI355X: ~10 POPS dense), and an expansion of bits
 // that costs a v_and per EIGHT bins: the product only needs both operands to agree on which bin sits in which K position, so nibble i of
@@ -589,6 +699,35 @@ hipError_t msc_launch_pair_gemm_queries(hipStream_t st, uint64_t nbins, const ui
 	const hipError_t e = msc_launch_kb_gather(st, nbins, q_kb, q_slots_dev, n_q, qn, qT, anib);
 	if (e != hipSuccess) return e;
 	return msc_launch_hot_list(st, nbins, 1, q_mb, q_mb_n, q_pitch, q_slots_dev, n_q, qn, qT, n_hot, hot, hot_ptr, hot_cursor, hot_cnt);
+}
+
+// The queries' side of a group of n_blocks blocks of 128 rows (msc_query_groups, msc_multi_plan.h): block j reads the slots q_slots_dev[128 j ..], the last
+// one n_q_last of them. qT and anib: the first block's images, the others' a stride behind; fold > 1: the tiles from the folded mirror q_kbf, the lists by
+// folded bin. hot_stride > 0: also the hot lists -- hot, hot_ptr, hot_cursor, hot_cnt of the first block, the others' hot_stride entries / idx_stride
+// words behind (hot_cnt of the whole group contiguous: one clear); the fill runs behind the gather, whose plane 1 it sets.
+hipError_t msc_launch_query_group(hipStream_t st, uint64_t nbins, uint32_t fold, const uint8_t* q_kb, const uint8_t* q_kbf, const void* q_mb, const uint32_t* q_mb_n,
+                                  uint32_t q_pitch, const uint32_t* q_slots_dev, uint32_t n_blocks, uint32_t n_q_last, uint8_t* qT, uint64_t qt_stride, uint8_t* anib,
+                                  uint64_t anib_stride, uint64_t hot_stride, void* hot, uint32_t* hot_ptr, uint32_t* hot_cursor, uint32_t* hot_cnt, uint64_t idx_stride) {
+	const uint64_t nbins_f = fold > 1 ? nbins / fold : nbins;
+	if (n_blocks == 0 || n_blocks > 65535 || n_q_last == 0 || n_q_last > 128 || !qT || !anib || nbins % 256 || nbins_f % 256 || (fold > 1 && (!q_kbf || nbins % ((uint64_t)fold * 256))))
+		return hipErrorInvalidValue;
+	auto runs = [](uint64_t nb) { return (unsigned)((nb / 256 + kGatherRun - 1) / kGatherRun); };
+	if (fold > 1) {
+		k_kb_gather_group<<<dim3(runs(nbins), n_blocks), dim3(256), 0, st>>>(q_kb, q_slots_dev, n_q_last, nbins, qT, qt_stride, nullptr, 0);
+		k_kb_gather_group<<<dim3(runs(nbins_f), n_blocks), dim3(256), 0, st>>>(q_kbf, q_slots_dev, n_q_last, nbins_f, nullptr, 0, anib, anib_stride);
+	} else
+		k_kb_gather_group<<<dim3(runs(nbins), n_blocks), dim3(256), 0, st>>>(q_kb, q_slots_dev, n_q_last, nbins, qT, qt_stride, anib, anib_stride);
+	if (hot_stride) {
+		const uint32_t nsteps = (uint32_t)(nbins_f / kStep);
+		if (idx_stride < nsteps + 1) return hipErrorInvalidValue;
+		const hipError_t e = hipMemsetAsync(hot_cnt, 0, (size_t)n_blocks * idx_stride * sizeof(uint32_t), st);
+		if (e != hipSuccess) return e;
+		k_hot_count_group<<<dim3(128, n_blocks), dim3(256), 0, st>>>((const uint2*)q_mb, q_mb_n, q_pitch, q_slots_dev, n_q_last, hot_cnt, idx_stride, nbins, fold ? fold : 1);
+		k_hot_scan_group<<<dim3(n_blocks), dim3(1024), 0, st>>>(hot_cnt, nsteps, hot_ptr, hot_cursor, idx_stride);
+		k_hot_fill_group<<<dim3(128, n_blocks), dim3(256), 0, st>>>((const uint2*)q_mb, q_mb_n, q_pitch, q_slots_dev, n_q_last, hot_cursor, idx_stride, (uint2*)hot, hot_stride, qT,
+		                                                            qt_stride, nbins, fold ? fold : 1);
+	}
+	return hipGetLastError();
 }
 
 // P1 [k_slices][m][qn] and, with a hot list, P2 [m][qn] (zeroed here) of the block's queries against m candidates (slot list, or slots
