@@ -330,6 +330,29 @@ int msc_hist_clone_batch(msc_ctx* ctx, msc_hist_set* dst, const uint32_t* dst_sl
  * MSC_ERR_INVALID_ARG. Every mirror of the destination is rebuilt at its next use. msc_last_kernel_info names what ran ("k_hist_revcomp",
  * "k_sparse_revcomp_sort" or "k_sparse_revcomp_scratch", queries_per_candidate_read = 0). */
 int msc_hist_revcomp_batch(msc_ctx* ctx, msc_hist_set* dst, const uint32_t* dst_slots, const msc_hist_set* src, const uint32_t* src_slots, uint64_t n);
+/* The strand-neutral (canonical) form of n slots, on the device: every k-mer counted together with its reverse complement, so that a sequence and
+ * its reverse complement become the SAME point and the mean-shift stages need not know about strands. The reference has no counterpart: fastcar's
+ * work() compares histograms as stored (fastcar/FC_Runner.cpp:426-471), the loader counts the strand it is given (clutil/Loader.cpp:138-179), and
+ * its users orient their input by hand. Like msc_hist_revcomp_batch the operator needs no sequence: centres, means and uploaded bins alike.
+ * Definition: D is the slot as msc_hist_download returns it (natural order, the pseudocount of 1 in every bin), T the set's bin type, rc the index
+ * rule stated at msc_hist_revcomp_batch:
+ *     canon(D)[b] = clamp(D[b] + D[rc(b)] - 1, 0, max(T)),   the sum computed without wrap-around.
+ * A k-mer counted c times forward and c' times in reverse holds 1 + c + c'; a palindromic bin (b == rc(b), even k only) holds 2 * D[b] - 1. The
+ * result is symmetric under rc; a second application applies the formula again (it is not special-cased).
+ * Record rule: length and id are copied from the source; one_mers'[i] = one_mers[i] + one_mers[3 - i] - 1; mag, sum, sum_sq, max_count, stddev and
+ * a dense slot's tile prefixes are recomputed from the new bins, the bits msc_hist_upload gives for those bins (mag fresh, as after
+ * msc_hist_clone); overflow' = the source's overflow OR some bin's exact sum exceeded max(T). The set's bounds (msc_hist_set_build_info) are
+ * refreshed: a canonical slot can double them. A sparse slot's list is the merge by bin of the source's list and of its rc-mapped list, cum and
+ * the sub-range table rebuilt: the slot the sparse builder would have written for those bins. Lists of more than 16 384 entries go through a
+ * dense scratch slot, with that route's limits (k <= 13).
+ * Arguments as msc_hist_copy_batch: same ctx, k, dtype and layout; slots in range; destination slots distinct; n == 0 is MSC_OK. A sparse
+ * destination appends all the lists or none (MSC_ERR_OOM, the destination untouched); a canonical list has up to twice the source's entries.
+ * Unlike the reverse complement there IS an in-place form: with dst == src, dst_slots[i] == src_slots[i] is legal for every i, and in-place and
+ * out-of-place results are byte-identical. A slot that is the destination of one i and the source of a different i is MSC_ERR_INVALID_ARG. On a
+ * sparse set the in-place form appends the new list and leaves the old one behind in the arena, as msc_hist_assign_batch does.
+ * Every mirror of the destination is rebuilt at its next use. msc_last_kernel_info names what ran ("k_hist_canonical",
+ * "k_sparse_canonical_sort" or "k_sparse_canonical_scratch", queries_per_candidate_read = 0). */
+int msc_hist_canonical_batch(msc_ctx* ctx, msc_hist_set* dst, const uint32_t* dst_slots, const msc_hist_set* src, const uint32_t* src_slots, uint64_t n);
 
 /* ------------------------------------------------------------------ a5/a7: model (Feature<T> + GLM weights) */
 /* Mirrors the state Predictor::read_from builds (predict/Predictor.cpp:125-185): combos are replayed through

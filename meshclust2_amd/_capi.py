@@ -92,6 +92,7 @@ PROTOTYPES = {
     "msc_hist_copy_batch": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64]),
     "msc_hist_clone_batch": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64]),
     "msc_hist_revcomp_batch": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64]),
+    "msc_hist_canonical_batch": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64]),
     "msc_model_create": (_int, [_vp, _int, _int, C.POINTER(_int), _pu64, _pdbl, _int, _pu64, _pdbl, _pdbl, _dbl, C.POINTER(_vp)]),
     "msc_model_load": (_int, [_vp, C.c_char_p, _int, C.POINTER(_vp)]),
     "msc_model_parse": (_int, [_vp, C.c_char_p, _int, C.POINTER(_vp)]),

@@ -300,6 +300,16 @@ class HistogramSet:
         assert d.size == s_.size
         self.ctx.check(self.ctx.lib.msc_hist_revcomp_batch(self.ctx.h, self.h, _ptr(d), src.h, _ptr(s_), d.size))
 
+    def canonical_batch(self, dst_slots, src, src_slots):
+        """slot dst_slots[i] of this set = the strand-neutral form of slot src_slots[i] of src (msc_hist_canonical_batch):
+        bins'[b] = clamp(bins[b] + bins[rc(b)] - 1, 0, max(T)), so that a sequence and its reverse complement give the same slot. length and id
+        are copied, the 1-mers added up the same way, everything else of the record recomputed. Same k, dtype and layout; with src is self,
+        dst_slots[i] == src_slots[i] is the in-place form."""
+        d = np.ascontiguousarray(dst_slots, dtype=np.uint32)
+        s_ = np.ascontiguousarray(src_slots, dtype=np.uint32)
+        assert d.size == s_.size
+        self.ctx.check(self.ctx.lib.msc_hist_canonical_batch(self.ctx.h, self.h, _ptr(d), src.h, _ptr(s_), d.size))
+
     def device_view(self):
         b, s = C.c_void_p(), C.c_void_p()
         sb, ss = C.c_uint64(), C.c_uint64()

@@ -1401,6 +1401,144 @@ extern "C" int msc_hist_revcomp_batch(msc_ctx* ctx, msc_hist_set* dst, const uin
 	return MSC_OK;
 }
 
+// refresh_bounds over a list of slots: one call per run of consecutive slots
+static int refresh_bounds_list(msc_ctx* ctx, msc_hist_set* s, std::vector<uint32_t> slots) {
+	std::sort(slots.begin(), slots.end());
+	int r;
+	for (size_t i = 0; i < slots.size();) {
+		size_t j = i + 1;
+		while (j < slots.size() && slots[j] == slots[j - 1] + 1) j++;
+		if ((r = refresh_bounds(ctx, s, slots[i], j - i))) return r;
+		i = j;
+	}
+	return MSC_OK;
+}
+
+// A list of more than 16 384 entries: its reverse complement scattered into the dense scratch slot (revcomp's long-list route), the dense kernel in
+// place on that slot -- canon(rc(D)) = canon(D) -- with the source's record beside it, msc_launch_finalize, then k_sparse_count / k_sparse_write and the
+// record carried over. The caller has checked the arena against the exact entry count.
+static int canonical_sparse_scratch(msc_ctx* ctx, msc_hist_set* dst, uint32_t ds, const msc_hist_set* src, uint32_t ss) {
+	msc_hist_set* sc = ctx->sparse_scratch;
+	const MscSparseHdr sh = src->hdr_host[ss];
+	int r;
+	if ((r = ensure(ctx, ctx->sp_chunk_off, 16))) return r;
+	HIP_TRY(ctx, hipMemsetAsync(ctx->sp_chunk_off.p, 0, 16, ctx->stream));          // slot 0 onto slot 0
+	HIP_TRY(ctx, msc_launch_fill(ctx->stream, sc->bins, sc->L, 0, 1));
+	HIP_TRY(ctx, msc_launch_sparse_revcomp_scatter(ctx->stream, sc->L, src->k, src->dtype, sc->bins, src->ent + sh.off, sh.nnz));
+	HIP_TRY(ctx, hipMemcpyAsync(sc->scalars, src->scalars + (uint64_t)ss * src->scalar_stride, sizeof(MscSlotScalars), hipMemcpyDeviceToDevice, ctx->stream));
+	HIP_TRY(ctx, msc_launch_hist_canonical(ctx->stream, sc->L, sc->k, sc->dtype, sc->bins, sc->scalars, sc->bins, sc->scalars, (const uint32_t*)ctx->sp_chunk_off.p,
+	                                       (const uint32_t*)ctx->sp_chunk_off.p, 1));
+	HIP_TRY(ctx, msc_launch_finalize(ctx->stream, sc->bins, sc->scalars, sc->L, sc->dtype, 0, 1, false));
+	if ((r = sparsify_slots(ctx, sc, 0, dst, ds, 1, nullptr))) return r;
+	HIP_TRY(ctx, hipMemcpyAsync(dst->scalars + (uint64_t)ds * dst->scalar_stride, sc->scalars, sizeof(MscSlotScalars), hipMemcpyDeviceToDevice, ctx->stream));
+	return MSC_OK;
+}
+
+// canon(D)[b] = clamp(D[b] + D[msc_rc_bin(b)] - 1, 0, max(T)) for n slots (msc_canonical.hip). length and id are the source's, the 1-mers are added up
+// the same way, the overflow flag is the source's or a sum's; everything else of the record follows from the new bins, and the set's bounds are read
+// back from the records. With dst == src a pair may name one slot twice (in place); no mirror is written here (mark_stale / lists_written).
+extern "C" int msc_hist_canonical_batch(msc_ctx* ctx, msc_hist_set* dst, const uint32_t* dst_slots, const msc_hist_set* src, const uint32_t* src_slots, uint64_t n) {
+	if (!ctx || !dst || !src || dst->ctx != ctx || src->ctx != ctx) return MSC_ERR_INVALID_ARG;
+	if (n == 0) return MSC_OK;
+	if (!dst_slots || !src_slots) return MSC_ERR_INVALID_ARG;
+	if (dst->k != src->k || dst->dtype != src->dtype || dst->sparse != src->sparse) return fail(ctx, MSC_ERR_INVALID_ARG, "sets differ in k, dtype or layout");
+	if (n > 0x7fffffffull) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_hist_canonical_batch: at most 2^31 - 1 slots a call");
+	if (dst->sparse && src->scalar_stride != dst->scalar_stride) return fail(ctx, MSC_ERR_INVALID_ARG, "sets differ in layout");
+	uint32_t lo = ~0u, hi = 0;
+	for (uint64_t i = 0; i < n; i++) {
+		if (dst_slots[i] >= dst->capacity || src_slots[i] >= src->capacity) return fail(ctx, MSC_ERR_INVALID_ARG, "slot out of range");
+		lo = std::min(lo, dst_slots[i]);
+		hi = std::max(hi, dst_slots[i]);
+	}
+	{
+		std::vector<std::pair<uint32_t, uint64_t>> d(n);          // (destination slot, its pair)
+		for (uint64_t i = 0; i < n; i++) d[i] = {dst_slots[i], i};
+		std::sort(d.begin(), d.end());
+		for (uint64_t i = 1; i < n; i++)
+			if (d[i].first == d[i - 1].first) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_hist_canonical_batch: a destination slot is named twice");
+		if (dst == src)
+			for (uint64_t i = 0; i < n; i++) {
+				const auto it = std::lower_bound(d.begin(), d.end(), std::make_pair(src_slots[i], (uint64_t)0));
+				if (it != d.end() && it->first == src_slots[i] && it->second != i)
+					return fail(ctx, MSC_ERR_INVALID_ARG, "msc_hist_canonical_batch: slot %u is the source of one pair and the destination of another", src_slots[i]);
+			}
+	}
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	int r;
+	if ((r = ensure(ctx, ctx->slots, n * sizeof(uint32_t))) || (r = ensure(ctx, ctx->pair_seg, n * sizeof(uint32_t)))) return r;
+	const uint32_t* d_ds = (const uint32_t*)ctx->slots.p;
+	const uint32_t* d_ss = (const uint32_t*)ctx->pair_seg.p;
+	ctx->last_query_tile = 0;
+	ctx->have_timing = false;
+	if (dst->sparse) {
+		// all lists or none: the merged lists are counted before anything is written
+		const uint32_t sort_max = msc_sparse_canonical_sort_max();
+		if ((r = ensure(ctx, ctx->sp_touched, n * sizeof(uint32_t)))) return r;
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->pair_seg.p, src_slots, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+		HIP_TRY(ctx, msc_launch_sparse_canonical_count(ctx->stream, src->k, src->ent, src->hdr, d_ss, (uint32_t)n, (uint32_t*)ctx->sp_touched.p));
+		std::vector<uint32_t> merged(n);
+		HIP_TRY(ctx, hipMemcpyAsync(merged.data(), ctx->sp_touched.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+		uint64_t need = 0;
+		bool any_long = false;
+		for (uint64_t i = 0; i < n; i++) { need += merged[i]; any_long = any_long || src->hdr_host[src_slots[i]].nnz > sort_max; }
+		if (dst->ent_used + need > dst->ent_capacity)
+			return fail(ctx, MSC_ERR_OOM, "sparse set entry arena exhausted (%llu of %llu entries used, %llu needed)", (unsigned long long)dst->ent_used,
+			            (unsigned long long)dst->ent_capacity, (unsigned long long)need);
+		if (any_long && src->k > 13) return fail(ctx, MSC_ERR_UNSUPPORTED, "dense histograms support 1 <= k <= 13 (got %d): a list of more than %u entries goes through one", src->k, sort_max);
+		if (any_long && (r = revcomp_scratch_slot(ctx, src))) return r;
+		std::vector<uint32_t> s_ds, s_ss, longs;
+		std::vector<uint64_t> off;
+		uint64_t o = dst->ent_used;
+		uint32_t longest = 0;
+		for (uint64_t i = 0; i < n; i++) {
+			const uint32_t nnz = src->hdr_host[src_slots[i]].nnz;
+			if (nnz > sort_max) { longs.push_back((uint32_t)i); continue; }
+			s_ds.push_back(dst_slots[i]); s_ss.push_back(src_slots[i]); off.push_back(o);
+			o += merged[i];
+			longest = std::max(longest, nnz);
+		}
+		const uint64_t ns = s_ds.size();
+		if (ns) {
+			if ((r = ensure(ctx, ctx->sp_chunk_off, ns * sizeof(uint64_t))) || (r = ensure(ctx, ctx->sp_counts, ns * sizeof(MscSparseHdr)))) return r;
+			HIP_TRY(ctx, hipMemcpyAsync(ctx->slots.p, s_ds.data(), ns * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+			HIP_TRY(ctx, hipMemcpyAsync(ctx->pair_seg.p, s_ss.data(), ns * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+			HIP_TRY(ctx, hipMemcpyAsync(ctx->sp_chunk_off.p, off.data(), ns * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+			HIP_TRY(ctx, msc_launch_canonical_record(ctx->stream, dst->scalars, src->scalars, dst->scalar_stride, d_ds, d_ss, (uint32_t)ns));
+			HIP_TRY(ctx, msc_launch_sparse_canonical_sort(ctx->stream, src->k, src->dtype, src->L.nbins, src->ent, src->hdr, d_ds, d_ss, (const uint64_t*)ctx->sp_chunk_off.p, (uint32_t)ns,
+			                                              longest, dst->ent, dst->cum, dst->hdr, (MscSparseHdr*)ctx->sp_counts.p, dst->scalars, dst->scalar_stride));
+			std::vector<MscSparseHdr> hl(ns);          // the headers (the kernel's sub-range tables) for the host's mirror
+			HIP_TRY(ctx, hipMemcpyAsync(hl.data(), ctx->sp_counts.p, ns * sizeof(MscSparseHdr), hipMemcpyDeviceToHost, ctx->stream));
+			HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+			for (uint64_t i = 0; i < ns; i++) dst->hdr_host[s_ds[i]] = hl[i];
+			dst->ent_used = o;
+			ctx->last_kernel = "k_sparse_canonical_sort";
+		}
+		for (const uint32_t i : longs) {
+			if ((r = canonical_sparse_scratch(ctx, dst, dst_slots[i], src, src_slots[i]))) return r;
+			ctx->last_kernel = "k_sparse_canonical_scratch";
+		}
+		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+		lists_written(dst, lo, (uint64_t)hi + 1 - lo);
+		return refresh_bounds_list(ctx, dst, std::vector<uint32_t>(dst_slots, dst_slots + n));
+	}
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->slots.p, dst_slots, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->pair_seg.p, src_slots, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+	HIP_TRY(ctx, msc_launch_hist_canonical(ctx->stream, dst->L, dst->k, dst->dtype, dst->bins, dst->scalars, src->bins, src->scalars, d_ds, d_ss, (uint32_t)n));
+	{          // the sums, the magnitude, stddev and the tile prefixes of the new bins: msc_hist_upload's launch, per run of consecutive destination slots
+		std::vector<uint32_t> d(dst_slots, dst_slots + n);
+		std::sort(d.begin(), d.end());
+		for (size_t i = 0; i < d.size();) {
+			size_t j = i + 1;
+			while (j < d.size() && d[j] == d[j - 1] + 1) j++;
+			HIP_TRY(ctx, msc_launch_finalize(ctx->stream, dst->bins, dst->scalars, dst->L, dst->dtype, d[i], j - i, false));
+			i = j;
+		}
+	}
+	ctx->last_kernel = "k_hist_canonical";
+	return refresh_bounds_list(ctx, dst, std::vector<uint32_t>(dst_slots, dst_slots + n));          // (drains the stream: the caller's slot arrays may go away)
+}
+
 extern "C" int msc_hist_set_device_view(const msc_hist_set* set, void** bins, uint64_t* slot_bytes, void** scalars, uint64_t* scalar_bytes) {
 	if (!set || set->sparse) return MSC_ERR_INVALID_ARG;
 	if (bins) *bins = set->bins;

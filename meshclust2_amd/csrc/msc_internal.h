@@ -448,3 +448,17 @@ hipError_t msc_launch_sparse_revcomp_sort(hipStream_t st, int k, uint64_t nbins,
                                           const uint32_t* src_slots, const uint64_t* dst_off, uint32_t n, uint32_t longest, void* d_ent, uint32_t* d_cum, MscSparseHdr* d_hdr,
                                           MscSparseHdr* hdr_list);
 hipError_t msc_launch_sparse_revcomp_scatter(hipStream_t st, const MscLayout& L, int k, int dtype, void* scratch_bins, const void* ent, uint32_t n);
+// msc_canonical.hip: canon(D)[b] = clamp(D[b] + D[msc_rc_bin(b)] - 1, 0, max(T)) for slots, in place where a pair names one slot twice. Dense: the
+// record's words that do not follow from the bins (msc_launch_canonical_record: length, id, overflow, n_kmers, the 1-mers added up), then the bins,
+// which set the record's overflow word where a sum saturates; the sums and tile prefixes are msc_launch_finalize's, called by the API afterwards
+hipError_t msc_launch_canonical_record(hipStream_t st, uint8_t* dst_scalars, const uint8_t* src_scalars, uint64_t stride, const uint32_t* dst_slots, const uint32_t* src_slots,
+                                       uint32_t n);
+hipError_t msc_launch_hist_canonical(hipStream_t st, const MscLayout& L, int k, int dtype, uint8_t* dst_bins, uint8_t* dst_scalars, const uint8_t* src_bins,
+                                     const uint8_t* src_scalars, const uint32_t* dst_slots, const uint32_t* src_slots, uint32_t n);
+// sparse: counts[i] = the entries of the merged list of src_slots[i]; lists of at most msc_sparse_canonical_sort_max() entries merged and sorted in
+// LDS (list i of the launch goes to dst_off[i] of the arena; the record's sums are written too, after msc_launch_canonical_record)
+uint32_t msc_sparse_canonical_sort_max();
+hipError_t msc_launch_sparse_canonical_count(hipStream_t st, int k, const void* s_ent, const MscSparseHdr* s_hdr, const uint32_t* src_slots, uint32_t n, uint32_t* counts);
+hipError_t msc_launch_sparse_canonical_sort(hipStream_t st, int k, int dtype, uint64_t nbins, const void* s_ent, const MscSparseHdr* s_hdr, const uint32_t* dst_slots,
+                                            const uint32_t* src_slots, const uint64_t* dst_off, uint32_t n, uint32_t longest, void* d_ent, uint32_t* d_cum, MscSparseHdr* d_hdr,
+                                            MscSparseHdr* hdr_list, uint8_t* dst_scalars, uint64_t scalar_stride);

@@ -112,6 +112,12 @@ public:
 		if (dst.size() != src_slots.size()) throw Error(MSC_ERR_INVALID_ARG, "revcomp_batch: one source slot per destination slot");
 		ctx_.check(msc_hist_revcomp_batch(ctx_.get(), h_, dst.data(), src.h_, src_slots.data(), dst.size()));
 	}
+	// slot dst[i] of this set = the strand-neutral form of slot src_slots[i] of src (msc_hist_canonical_batch: bins'[b] = bins[b] + bins[rc(b)] - 1,
+	// clamped; a sequence and its reverse complement give the same slot); src may be this set and src_slots[i] == dst[i]: in place
+	void canonical_batch(const std::vector<uint32_t>& dst, const PointSet& src, const std::vector<uint32_t>& src_slots) {
+		if (dst.size() != src_slots.size()) throw Error(MSC_ERR_INVALID_ARG, "canonical_batch: one source slot per destination slot");
+		ctx_.check(msc_hist_canonical_batch(ctx_.get(), h_, dst.data(), src.h_, src_slots.data(), dst.size()));
+	}
 private:
 	Context& ctx_;
 	msc_hist_set* h_ = nullptr;

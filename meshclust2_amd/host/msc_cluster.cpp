@@ -13,7 +13,12 @@
 // 1 / WORLD_SIZE of the points and runs the same clustering logic over msc::ShardedBackend (msc_sharded.hpp): RCCL over xGMI between the
 // ranks (MSC_COMM=tcp: plain sockets + host staging, what the tests use when several ranks share one GPU: MSC_ONE_GPU=1).
 //   msc_cluster <input.fa> [--recover weights.txt] [--id 0.9] [--kmer K] [--datatype 8|16|32|64]   (no --recover: trains first)
-//               [--output output.clstr] [--delta 5] [--iterations 15] [--single-file] [--sparse] [--serial-update] [--no-ranges] [--device 0]
+//               [--output output.clstr] [--delta 5] [--iterations 15] [--single-file] [--sparse] [--serial-update] [--no-ranges] [--device 0] [--canonical]
+//
+// --canonical (one-process driver only): every histogram is made strand-neutral right after it is built (msc_hist_canonical_batch, in place: each
+// k-mer counted together with its reverse complement), so a sequence and its reverse complement are the same point and a read set of mixed
+// orientation clusters as if it had been oriented by hand. Training takes the same step, so a model trained with the flag is meant for runs with
+// the flag; the weights file is the reference's format and records nothing about it.
 #include <algorithm>
 #include <cctype>
 #include <chrono>
@@ -239,7 +244,14 @@ std::string mutate(const std::string& tmpl, double rate, SplitMix& rng) {
 }
 
 // cluster/CRunner.cpp:56-126: the narrowest type that holds the largest count (pseudocount included)
-int choose_datatype(msc::Context& ctx, int k, const std::vector<std::string>& seqs, bool sparse) {
+std::vector<uint32_t> iota_slots(size_t first, size_t n) {
+	std::vector<uint32_t> s(n);
+	for (size_t i = 0; i < n; i++) s[i] = (uint32_t)(first + i);
+	return s;
+}
+
+// (canonical: the counts of the strand-neutral histograms, which can be twice as large)
+int choose_datatype(msc::Context& ctx, int k, const std::vector<std::string>& seqs, bool sparse, bool canonical) {
 	auto largest = [&](int bits) {
 		uint64_t most = 0;          // (sparse layout: the probe's entry arena must hold the longest batch)
 		for (size_t off = 0; off < seqs.size(); off += 4096) {
@@ -249,9 +261,10 @@ int choose_datatype(msc::Context& ctx, int k, const std::vector<std::string>& se
 		}
 		uint64_t mx = 0;
 		for (size_t off = 0; off < seqs.size(); off += 4096) {
-			msc::PointSet probe(ctx, k, bits, 4096, sparse ? most + 1024 : 0);      // (a sparse arena is append-only: a fresh probe per batch)
+			msc::PointSet probe(ctx, k, bits, 4096, sparse ? (canonical ? 3 : 1) * most + 1024 : 0);      // (a sparse arena is append-only: a fresh probe per batch)
 			std::vector<std::string> part(seqs.begin() + (long)off, seqs.begin() + (long)std::min(seqs.size(), off + 4096));
 			probe.get_points(0, part);
+			if (canonical) { const std::vector<uint32_t> all = iota_slots(0, part.size()); probe.canonical_batch(all, probe, all); }
 			for (size_t i = 0; i < part.size(); i++) mx = std::max<uint64_t>(mx, probe.info(i).max_count);
 		}
 		return mx;
@@ -263,7 +276,7 @@ int choose_datatype(msc::Context& ctx, int k, const std::vector<std::string>& se
 }
 
 std::string train_model(msc::Context& ctx, int k, int dtype, double id, uint64_t feat_flags, int n_templates, int min_feat, int max_feat,
-                        const std::vector<std::string>& seqs, bool sparse) {
+                        const std::vector<std::string>& seqs, bool sparse, bool canonical) {
 	SplitMix rng{0xAAull};
 	std::vector<std::string> pts;
 	std::vector<uint32_t> first, second;
@@ -271,8 +284,13 @@ std::string train_model(msc::Context& ctx, int k, int dtype, double id, uint64_t
 	const double lo = std::max(0.35, id - 0.25);                 // negatives well below the cut-off (the reference's min_id, cluster/CRunner.h:41)
 	const size_t nt = std::min<size_t>((size_t)n_templates, seqs.size());
 	for (size_t t = 0; t < nt; t++) {
-		const std::string tmpl = acgt_only(seqs[t * seqs.size() / nt]);
+		std::string tmpl = acgt_only(seqs[t * seqs.size() / nt]);
 		if (tmpl.size() < 50) continue;
+		if (canonical) {          // the mutator reads a string: of a template and its reverse complement always the same one, so the input's orientation does not reach the model
+			std::string rc(tmpl.rbegin(), tmpl.rend());
+			for (char& c : rc) c = c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : 'A';
+			if (rc < tmpl) tmpl.swap(rc);
+		}
 		pts.push_back(tmpl);
 		const uint32_t ti = (uint32_t)pts.size() - 1;
 		for (int j = 0; j < 8; j++) {
@@ -288,9 +306,12 @@ std::string train_model(msc::Context& ctx, int k, int dtype, double id, uint64_t
 	}
 	uint64_t train_bases = 0;
 	for (const std::string& p_ : pts) train_bases += p_.size();
-	msc::PointSet set(ctx, k, dtype, pts.size(), sparse ? train_bases + 1024 : 0);      // (at k >= 13 a dense training set would not fit)
+	// (at k >= 13 a dense training set would not fit; canonical in place: a list of up to twice the entries behind the one it leaves in the arena)
+	msc::PointSet set(ctx, k, dtype, pts.size(), sparse ? (canonical ? 3 : 1) * train_bases + 1024 : 0);
 	for (size_t off = 0; off < pts.size(); off += 4096) {
-		set.get_points(off, pts.data() + off, std::min(pts.size(), off + 4096) - off);
+		const size_t nb = std::min(pts.size(), off + 4096) - off;
+		set.get_points(off, pts.data() + off, nb);
+		if (canonical) { const std::vector<uint32_t> s_ = iota_slots(off, nb); set.canonical_batch(s_, set, s_); }
 	}
 	const uint64_t n_train = first.size() / 2;
 	std::vector<char> text(1 << 16);
@@ -308,7 +329,7 @@ int main(int argc, char** argv) {
 	std::string weights, output = "output.clstr";
 	double similarity = 0.90;
 	int k = -1, dtype = 0, delta = 5, iterations = 15, device = 0;
-	bool single_file = false, sparse = false, serial_update = false, no_ranges = false;
+	bool single_file = false, sparse = false, serial_update = false, no_ranges = false, canonical = false;
 	int n_templates = 300, min_feat = 4, max_feat = 4;      // cluster/CRunner.h:33-35
 	uint64_t feat_flags = MSC_FEAT_FAST;                    // the CLI default (cluster/CRunner.h:51)
 	std::string dump = "weights.txt";
@@ -346,11 +367,14 @@ int main(int argc, char** argv) {
 		else if (a == "--serial-update") serial_update = true;
 		else if (a == "--no-ranges") no_ranges = true;   // get_close receives a slot list rebuilt on the host every step (the r02 form)
 		else if (a == "--sparse") sparse = true;         // sparse histogram layout (required for k >= 13)
+		else if (a == "--canonical") canonical = true;   // strand-neutral histograms (msc_hist_canonical_batch on every chunk of points)
 		else files.push_back(a);
 	}
 	if (files.empty()) {
-		std::fprintf(stderr, "usage: %s <input.fa> [--recover weights.txt] [--id 0.9] [--kmer K] [--datatype 8|16|32|64] [--output out.clstr] [--delta 5] [--iterations 15]\n"
-		                     "       without --recover a model is trained first (--feat fast|slow, --num-templates 300, --min-feat 4, --max-feat 4) and written to --dump (weights.txt)\n", argv[0]);
+		std::fprintf(stderr, "usage: %s <input.fa> [--recover weights.txt] [--id 0.9] [--kmer K] [--datatype 8|16|32|64] [--output out.clstr] [--delta 5] [--iterations 15] [--canonical]\n"
+		                     "       without --recover a model is trained first (--feat fast|slow, --num-templates 300, --min-feat 4, --max-feat 4) and written to --dump (weights.txt)\n"
+		                     "       --canonical counts every k-mer together with its reverse complement (a sequence and its reverse complement are one point); a model trained\n"
+		                     "       with the flag is meant for runs with the flag, and the weights file does not record it\n", argv[0]);
 		return 1;
 	}
 	const msc::CommEnv env = msc::CommEnv::from_environment();
@@ -358,6 +382,7 @@ int main(int argc, char** argv) {
 	// then runs on one GPU (the 1-GPU test of that code path)
 	const bool sharded = env.world > 1 || std::getenv("MSC_FORCE_SHARDED") != nullptr;
 	if (sharded && no_ranges) { std::fprintf(stderr, "--no-ranges is a switch of the one-process driver: the rank driver always scores position ranges\n"); return 1; }
+	if (sharded && canonical) { std::fprintf(stderr, "--canonical is a switch of the one-process driver: the rank driver does not build strand-neutral histograms\n"); return 1; }
 	if (sharded && !std::getenv("MSC_ONE_GPU")) device = env.local_rank;
 	try {
 		const auto t_start = std::chrono::steady_clock::now();
@@ -407,9 +432,9 @@ int main(int argc, char** argv) {
 				k = (int)std::ceil(std::log((double)length) / std::log(4.0)) - 1;
 				std::cout << "avg length: " << length << std::endl << "Recommended K: " << k << std::endl;
 			}
-			if (dtype == 0) { dtype = choose_datatype(ctx, k, seqs, sparse); std::cout << "Using " << dtype << " bit histograms" << std::endl; }
+			if (dtype == 0) { dtype = choose_datatype(ctx, k, seqs, sparse, canonical); std::cout << "Using " << dtype << " bit histograms" << std::endl; }
 			const double id = similarity > 1 ? similarity / 100.0 : similarity;
-			const std::string text = train_model(ctx, k, dtype, id, feat_flags, n_templates, min_feat, max_feat, seqs, sparse);
+			const std::string text = train_model(ctx, k, dtype, id, feat_flags, n_templates, min_feat, max_feat, seqs, sparse, canonical);
 			std::ofstream(dump.c_str()) << text;       // the reference always leaves weights.txt behind (cluster/Trainer.cpp:188-190)
 			weights = dump;
 			std::cout << "timestamp GLM " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count() << std::endl;
@@ -467,9 +492,14 @@ int main(int argc, char** argv) {
 				          << " | closest " << be.ops.closest << " update chunks " << be.ops.update_chunks << " set chunks " << be.ops.set_chunks << std::endl;
 			return 0;
 		}
-		msc::PointSet points(ctx, k, dtype, n, sparse ? total_bases + 1024 : 0);
+		// (--canonical on a sparse set: the strand-neutral list, up to twice the entries, is appended behind the list it replaces)
+		msc::PointSet points(ctx, k, dtype, n, sparse ? (canonical ? 3 : 1) * total_bases + 1024 : 0);
 		const size_t chunk = 8192;
-		for (size_t off = 0; off < n; off += chunk) points.get_points(off, seqs.data() + off, std::min(n, off + chunk) - off);
+		for (size_t off = 0; off < n; off += chunk) {
+			const size_t nb = std::min(n, off + chunk) - off;
+			points.get_points(off, seqs.data() + off, nb);
+			if (canonical) { const std::vector<uint32_t> s_ = iota_slots(off, nb); points.canonical_batch(s_, points, s_); }
+		}
 		if (std::getenv("MSC_CLUSTER_PROFILE"))
 			std::cout << "input profile: histograms built at " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count() << " s" << std::endl;
 		std::vector<msc::SeqRecord> records(n);
@@ -481,7 +511,7 @@ int main(int argc, char** argv) {
 		seqs.clear();
 		// (sparse centre store: room for every sequence as its own centre TWICE -- a round of the update stage appends the new list of
 		// every moved centre before the old ones are compacted away)
-		uint64_t centre_arena = sparse ? 2 * total_bases + 64 * longest + (1 << 20) : 0;
+		uint64_t centre_arena = sparse ? (canonical ? 2 : 1) * (2 * total_bases + 64 * longest) + (1 << 20) : 0;
 		if (const char* e = std::getenv("MSC_CLUSTER_CENTRE_ARENA")) {      // (tests: a snug arena, so that a small run compacts its store)
 			if (sparse && std::atoll(e) > 0) centre_arena = (uint64_t)std::atoll(e);
 		}

@@ -6,7 +6,12 @@
 // std::sort by length, bin_search, format_header and the output formatting follow fastcar/FC_Runner.cpp:389-471,
 // 560-611 at one thread (one output file "<prefix>0"); training is out of scope, a two-block weights file is required.
 //
-//   msc_fastcar <db.fa> --query <q.fa> --recover weights.txt [--output output] [--chunk 10000] [--no-format] [--device 0] [--div-cells] [--top N] [--both-strands]
+//   msc_fastcar <db.fa> --query <q.fa> --recover weights.txt [--output output] [--chunk 10000] [--no-format] [--device 0] [--div-cells] [--top N] [--both-strands] [--canonical]
+//
+// --canonical: database and query histograms are made strand-neutral right after they are built (msc_hist_canonical_batch, in place: each k-mer
+// counted together with its reverse complement), so a query and its reverse complement give the same lines; everything else is unchanged. The
+// model should have been trained on such histograms (msc_cluster --canonical). Not together with --both-strands: that flag compares the
+// query's two strands with the entry as stored and reports which one hit, a different definition of "both strands".
 //
 // --both-strands: every block of queries, single-member blocks included, goes through msc_search_pairs_strands: a hit is reported when the query
 // or its reverse complement is close to the database entry as stored, with the larger of the two similarities (a tie goes to the query as
@@ -86,10 +91,15 @@ std::string format_header(const std::string& hdr) {                             
 	return hdr.substr((size_t)b, (size_t)(len - b));
 }
 
-void load_chunk(msc::PointSet& set, const std::vector<Rec>& recs, size_t off, size_t n, std::vector<Pt>& pts) {
+void load_chunk(msc::PointSet& set, const std::vector<Rec>& recs, size_t off, size_t n, std::vector<Pt>& pts, bool canonical) {
 	std::vector<std::string> seqs;
 	for (size_t i = 0; i < n; i++) seqs.push_back(recs[off + i].seq);
 	set.get_points(0, seqs, /*strip=*/true);               // Loader<T>::get_point(header, base, ...): the string overload
+	if (canonical && n) {                                  // --canonical: the strand-neutral histograms, in place (lengths do not change)
+		std::vector<uint32_t> all(n);
+		for (size_t i = 0; i < n; i++) all[i] = (uint32_t)i;
+		set.canonical_batch(all, set, all);
+	}
 	pts.resize(n);
 	for (size_t i = 0; i < n; i++) pts[i] = Pt{recs[off + i].header, set.get_length(i), (uint32_t)i};
 }
@@ -117,7 +127,7 @@ int main(int argc, char** argv) {
 	std::vector<std::string> files, qfiles;
 	std::string weights, output = "output";
 	size_t chunk = 10000, qblock = 16, top = 0;
-	bool format = true, sparse = false, report_kernels = false, div_cells = false, sparse_matrix = false, both_strands = false;
+	bool format = true, sparse = false, report_kernels = false, div_cells = false, sparse_matrix = false, both_strands = false, canonical = false;
 	int device = 0;
 	for (int i = 1; i < argc; i++) {
 		std::string a = argv[i];
@@ -135,11 +145,16 @@ int main(int argc, char** argv) {
 		else if (a == "--sparse-matrix") sparse_matrix = true;  // msc_set_sparse_matrix_pass: with --sparse, the query blocks on the matrix-core route
 		else if (a == "--top") top = (size_t)std::max(0l, std::atol(need("--top").c_str()));          // each query's N best hits (0: all)
 		else if (a == "--both-strands") both_strands = true;          // msc_search_pairs_strands: the queries and their reverse complements
+		else if (a == "--canonical") canonical = true;          // msc_hist_canonical_batch on every chunk: strand-neutral histograms
 		else if (a == "--device") device = std::atoi(need("--device").c_str());
 		else files.push_back(a);
 	}
 	if (files.empty() || qfiles.empty() || weights.empty()) {
-		std::fprintf(stderr, "usage: %s <db.fa> --query <q.fa> --recover weights.txt [--output prefix] [--chunk 10000] [--no-format] [--sparse] [--sparse-matrix] [--div-cells] [--top N] [--both-strands]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s <db.fa> --query <q.fa> --recover weights.txt [--output prefix] [--chunk 10000] [--no-format] [--sparse] [--sparse-matrix] [--div-cells] [--top N] [--both-strands] [--canonical]\n", argv[0]);
+		return 1;
+	}
+	if (canonical && both_strands) {
+		std::fprintf(stderr, "--canonical and --both-strands cannot be combined: they are different definitions of a search on both strands\n");
 		return 1;
 	}
 	if (both_strands && top) {
@@ -169,7 +184,7 @@ int main(int argc, char** argv) {
 		// dense sets are refilled chunk after chunk; a sparse set's entry arena is append-only, so each chunk gets a fresh one
 		auto bases_of = [](const std::vector<Rec>& recs, size_t off, size_t n) { uint64_t t = 0; for (size_t i = 0; i < n; i++) t += recs[off + i].seq.size(); return t; };
 		auto make_set = [&](const std::vector<Rec>& recs, size_t off, size_t n) {
-			return std::unique_ptr<msc::PointSet>(new msc::PointSet(ctx, k, dtype, std::max<size_t>(1, n), sparse ? bases_of(recs, off, n) + 1024 : 0));
+			return std::unique_ptr<msc::PointSet>(new msc::PointSet(ctx, k, dtype, std::max<size_t>(1, n), sparse ? (canonical ? 3 : 1) * bases_of(recs, off, n) + 1024 : 0));          // (--canonical appends a list of up to twice the entries)
 		};
 		std::unique_ptr<msc::PointSet> qset_p = make_set(queries, 0, std::min(chunk, queries.size()));
 		std::unique_ptr<msc::PointSet> dset_p = make_set(db, 0, std::min(chunk, db.size()));
@@ -187,14 +202,14 @@ int main(int argc, char** argv) {
 			std::vector<Pt> qp;
 			if (sparse && qo) qset_p = make_set(queries, qo, std::min(chunk, queries.size() - qo));
 			msc::PointSet& qset = *qset_p;
-			load_chunk(qset, queries, qo, std::min(chunk, queries.size() - qo), qp);
+			load_chunk(qset, queries, qo, std::min(chunk, queries.size() - qo), qp, canonical);
 			std::vector<std::vector<Surv> > best(top ? qp.size() : 0);          // --top: each query's survivors over the database chunks so far
 			size_t n_dchunks = 0;
 			for (size_t d0 = 0; d0 < db.size(); d0 += chunk) {
 				std::vector<Pt> dp;
 				if (sparse && (d0 || qo)) dset_p = make_set(db, d0, std::min(chunk, db.size() - d0));
 				msc::PointSet& dset = *dset_p;
-				load_chunk(dset, db, d0, std::min(chunk, db.size() - d0), dp);
+				load_chunk(dset, db, d0, std::min(chunk, db.size() - d0), dp, canonical);
 				std::vector<Pt*> pts;
 				for (auto& p : dp) pts.push_back(&p);
 				std::sort(pts.begin(), pts.end(), [](Pt* a, Pt* b) { return a->length < b->length; });      // FC_Runner.cpp:590-592
