@@ -437,6 +437,30 @@ int msc_score_pair_list(msc_ctx* ctx, const msc_model* model,
                         uint64_t feat_mask, double* raw_out,
                         double* singles_out, double* combos_out, double* sum_out, double* csum_out, uint8_t* close_out);
 
+/* ------------------------------------------------------------------ the quantity every model here predicts: global-alignment identity
+ * Feature::align (predict/Feature.cpp:697-718, FEAT_ALIGN) over utility/GlobAlignE.cpp:123-292, for n_pairs listed pairs in one call: an
+ * affine-gap global alignment WITHOUT traceback whose every state carries its score, the alignment length so far and the identical columns
+ * so far. All integers, every tie in a fixed order: the triple (score, length, matches) is the reference's, bit for bit; identity =
+ * (double)matches / length is left to the caller. DESIGN.md 4.6e restates the recurrence.
+ *   sequence s = seqs[offsets[s] .. offsets[s+1]), host memory; pair p = (first[p], second[p]), first is GlobAlignE's seq1. Ties are NOT
+ *   symmetric in the two sequences: no pair is reordered, and both orders of a pair may differ. Bytes are compared for equality and nothing
+ *   else: no alphabet, no case folding, an N equals an N. A pair of a sequence with itself and repeated pairs are legal.
+ *   match, mismatch, gap_open, gap_continue: Feature::align passes 1, -1, 2, 1 (a gap of g columns costs gap_open + g * gap_continue).
+ *   The reference's finite stand-in for minus infinity ([-gap_open - |la - lb| * gap_continue, only if la != lb] + mismatch * min(la, lb) - 1),
+ *   its boundary row and column and its tie orders are reproduced as written; no banding, no approximation.
+ *   score / length / matches: n_pairs each, host memory, the caller's order.
+ * Checked on the host before anything is queued, MSC_ERR_INVALID_ARG with every output untouched otherwise: every LISTED sequence has
+ * 1 .. 32 767 bytes, the four parameters are at most 100 in absolute value, indices are below n_seqs. n_pairs == 0 is MSC_OK.
+ * One pair per wave, the anti-diagonals as a systolic array over the lanes; pairs are dealt longest first; the sequences are uploaded once per
+ * call. msc_last_kernel_info names the kernel, "k_align_pairs<carry in LDS>" or "k_align_pairs<carry in global memory>" (that of the call's
+ * last launch; queries_per_candidate_read = 0). Results do not depend on the order of the list, on the other pairs of a call or on the
+ * context's history. */
+int msc_align_pairs(msc_ctx* ctx,
+                    const uint8_t* seqs, const uint64_t* offsets, uint64_t n_seqs,
+                    const uint32_t* first, const uint32_t* second, uint64_t n_pairs,
+                    int match, int mismatch, int gap_open, int gap_continue,
+                    int32_t* score, int32_t* length, int32_t* matches);
+
 /* ------------------------------------------------------------------ a8/a9: Trainer operators */
 /* Trainer<T>::get_close (cluster/Trainer.cpp:23-71; caller cluster/ClusterFactory.cpp:566).
  * The window [istart, iend) is cand_slots[0..m). Candidates outside floor(len_q*cutoff) <= len <= floor(len_q/cutoff)

@@ -524,6 +524,36 @@ def score_pair_list(ctx, feat, a_set, a_slots, b_set, b_slots, order=ORDER_CAND_
     return dict(sum=s, csum=cs, close=close, singles=singles, combos=combos, raw=raw)
 
 
+def align_pairs(ctx, seqs, first, second, match=1, mismatch=-1, gap_open=2, gap_continue=1, out=None):
+    """The global-alignment identity of listed pairs (msc_align_pairs; the reference's GlobAlignE, what Feature::align computes with the
+    default parameters): pair p aligns seqs[first[p]] (the definition's sequence 1 -- ties are not symmetric) with seqs[second[p]]. seqs is a
+    list of bytes / str of 1 .. 32 767 bytes each; bytes are compared for equality and nothing else.
+    -> dict(score, length, matches: int32 [n_pairs]; identity: float64 [n_pairs] = matches / length), in the caller's order. `out` (a tuple
+    of three int32 arrays) receives the integers in place: a refused call leaves them as they were."""
+    raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs]
+    a = np.ascontiguousarray(first, dtype=np.uint32)
+    b = np.ascontiguousarray(second, dtype=np.uint32)
+    if a.ndim != 1 or a.shape != b.shape:
+        raise ValueError("first and second are one pair list: one dimension, equal lengths")
+    offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
+    np.cumsum([len(s) for s in raw], out=offsets[1:])
+    text = np.frombuffer(b"".join(raw) + b"\0", dtype=np.uint8)
+    if out is None:
+        out = tuple(np.zeros(a.size, dtype=np.int32) for _ in range(3))
+    score, length, matches = out
+    for o in out:
+        if o.dtype != np.int32 or o.shape != a.shape or not o.flags.c_contiguous:
+            raise ValueError("out: three contiguous int32 arrays of n_pairs")
+    lib = ctx.lib if ctx is not None else _capi.load_library()
+    rc = lib.msc_align_pairs(ctx.h if ctx is not None else None, _ptr(text), _ptr(offsets), len(raw), _ptr(a), _ptr(b), a.size, int(match), int(mismatch),
+                             int(gap_open), int(gap_continue), _ptr(score), _ptr(length), _ptr(matches))
+    if rc != 0:
+        raise MscError(rc, lib.msc_last_error(ctx.h).decode() if ctx is not None else "msc_align_pairs needs a Context (a gfx950 device): there is no CPU fallback")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        identity = matches.astype(np.float64) / length.astype(np.float64)
+    return dict(score=score, length=length, matches=matches, identity=identity)
+
+
 class Trainer:
     """The pair-scoring operators of cluster/Trainer.{h,cpp} (scoring half only; training is host work out of scope)."""
 

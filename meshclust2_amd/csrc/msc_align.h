@@ -1,0 +1,143 @@
+// msc_align.h -- the cell update, the boundaries and the per-lane step of msc_align_pairs, written once for the kernel
+// (msc_align.hip) and for host programs that replay its schedule (tests/align_schedule_check.cpp). Plain C++: no HIP type in here.
+//
+// The operator is the affine-gap global alignment WITHOUT traceback of the reference's GlobAlignE (utility/GlobAlignE.cpp:123-292): columns
+// i = 1 .. la run over the first sequence, rows j = 1 .. lb over the second, and every cell holds three states -- match (both bytes in a column
+// of the alignment), lower (a gap that consumes a byte of the first sequence; it moves along the row) and upper (a gap that consumes a byte of
+// the second; it moves down the column). A state is a score and, travelling with it, the length of the alignment so far and its identical
+// columns; the two counts share one word, length << 16 | count (a listed sequence has at most 32 767 bytes: length <= 65 534, count <= 32 767,
+// and the count never carries into the length).
+//
+//   upper(i, j) = max(match(i, j-1) - (open + cont), upper(i, j-1) - cont)            a tie goes to "opened from match"
+//   lower(i, j) = max(match(i-1, j) - (open + cont), lower(i-1, j) - cont)            likewise
+//   match(i, j) = s + max(match, lower, upper of (i-1, j-1)), s = match or mismatch    ties: match, then lower, then upper
+//   result      = max(match, lower, upper of (la, lb))                                 ties: match, then lower, then upper
+//
+// The reference has no true minus infinity: the value below, a finite number of the size of real scores, stands in for it, takes part in the
+// arithmetic (neg_inf - cont is a legal score) and in the ties (near the corners a true boundary score falls to it or below it).
+#pragma once
+#include <stdint.h>
+
+#include "msc_layout.h"
+
+constexpr int kAlignLanes = 64;                                  // lanes of the systolic array: one wave
+constexpr int kAlignCols = 4;                                    // consecutive columns a lane keeps in registers
+constexpr int kAlignStripe = kAlignLanes * kAlignCols;           // columns the wave covers in one sweep over the rows
+constexpr uint32_t kAlignMaxLen = 32767;                         // bytes of a listed sequence
+constexpr int kAlignMaxParam = 100;                              // |match|, |mismatch|, |gap_open|, |gap_continue|
+constexpr uint32_t kAlignSeqPad = 64;                            // zero bytes before and after the second sequence in LDS: a lane's row may lie up to 63 outside it
+
+struct MscAlignParams {
+	int32_t match, mismatch, open, cont, open_cont;
+	uint32_t w_eq, w_ne;          // what a diagonal step adds to length << 16 | count (the reference counts a column whose SCORE is `match`)
+};
+
+struct MscAlignState {
+	int32_t s;          // score
+	uint32_t w;         // length << 16 | identical columns
+};
+
+struct MscAlignTriple {
+	MscAlignState m, l, u;
+};
+
+MSC_HD MscAlignParams msc_align_params(int match, int mismatch, int gap_open, int gap_continue) {
+	MscAlignParams P;
+	P.match = match; P.mismatch = mismatch; P.open = gap_open; P.cont = gap_continue; P.open_cont = gap_open + gap_continue;
+	P.w_eq = (1u << 16) + 1u;
+	P.w_ne = (1u << 16) + (mismatch == match ? 1u : 0u);
+	return P;
+}
+
+MSC_HD int32_t msc_align_neg_inf(uint32_t la, uint32_t lb, const MscAlignParams& P) {
+	const int32_t shorter = (int32_t)(la < lb ? la : lb), diff = (int32_t)(la < lb ? lb - la : la - lb);
+	int32_t v = 0;
+	if (diff >= 1) v += -P.open - diff * P.cont;
+	return v + P.mismatch * shorter - 1;
+}
+
+// column i of row 0 (i = 0: the corner, as row 1 sees it on its diagonal)
+MSC_HD MscAlignTriple msc_align_row0(uint32_t i, int32_t neg_inf, const MscAlignParams& P) {
+	MscAlignTriple t;
+	const uint32_t w = i << 16;
+	t.m.s = i == 0 ? 0 : neg_inf;
+	t.u.s = i == 0 ? -P.open : neg_inf;
+	t.l.s = i == 0 ? neg_inf : -P.open - (int32_t)i * P.cont;
+	t.m.w = t.l.w = t.u.w = w;
+	return t;
+}
+
+// row r >= 1 of column 0: what column 1 reads to its left (match, lower) and, one row later, on its diagonal (all three)
+MSC_HD MscAlignTriple msc_align_col0(uint32_t r, int32_t neg_inf, const MscAlignParams& P) {
+	MscAlignTriple t;
+	t.m.s = t.l.s = neg_inf;
+	t.u.s = -P.open - (int32_t)r * P.cont;
+	t.m.w = t.l.w = t.u.w = r << 16;
+	return t;
+}
+
+MSC_HD MscAlignState msc_align_gap(const MscAlignState& from_match, const MscAlignState& from_gap, const MscAlignParams& P) {
+	const int32_t a = from_match.s - P.open_cont, b = from_gap.s - P.cont;
+	MscAlignState r;
+	r.s = a >= b ? a : b;
+	r.w = (a >= b ? from_match.w : from_gap.w) + (1u << 16);
+	return r;
+}
+
+MSC_HD MscAlignState msc_align_diag(const MscAlignTriple& d, bool eq, const MscAlignParams& P) {
+	const int32_t ml = d.m.s >= d.l.s ? d.m.s : d.l.s;
+	const uint32_t ml_w = d.m.s >= d.l.s ? d.m.w : d.l.w;
+	MscAlignState r;
+	r.s = (ml >= d.u.s ? ml : d.u.s) + (eq ? P.match : P.mismatch);
+	r.w = (ml >= d.u.s ? ml_w : d.u.w) + (eq ? P.w_eq : P.w_ne);
+	return r;
+}
+
+// col: the cell above (row j - 1) on entry, this cell (row j) on return. diag: column i - 1 at row j - 1. left: column i - 1 at row j (its
+// upper state is not read)
+MSC_HD void msc_align_cell(MscAlignTriple& col, const MscAlignTriple& diag, const MscAlignTriple& left, bool eq, const MscAlignParams& P) {
+	col.u = msc_align_gap(col.m, col.u, P);
+	col.m = msc_align_diag(diag, eq, P);
+	col.l = msc_align_gap(left.m, left.l, P);
+}
+
+MSC_HD MscAlignState msc_align_final(const MscAlignTriple& t) {
+	const MscAlignState ml = t.m.s >= t.l.s ? t.m : t.l;
+	return ml.s >= t.u.s ? ml : t.u;
+}
+
+// What a lane of the array holds: its kAlignCols columns at the row it finished last, the column to its left at that row (the diagonal
+// of its next row), and its columns' bytes of the first sequence, column c in bits [8c, 8c + 8)
+struct MscAlignLane {
+	MscAlignTriple col[kAlignCols];
+	MscAlignTriple prev;
+	uint32_t bytes;
+};
+
+// first_col: the 1-based index of the lane's first column
+MSC_HD void msc_align_lane_init(MscAlignLane& L, uint32_t first_col, uint32_t bytes, int32_t neg_inf, const MscAlignParams& P) {
+	L.prev = msc_align_row0(first_col - 1, neg_inf, P);
+	for (int c = 0; c < kAlignCols; c++) L.col[c] = msc_align_row0(first_col + c, neg_inf, P);
+	L.bytes = bytes;
+}
+
+// One row: recv = the column to the lane's left at THIS row, b = the row's byte of the second sequence. The lane's last column is what it
+// hands on
+MSC_HD void msc_align_lane_step(MscAlignLane& L, const MscAlignTriple& recv, uint32_t b, const MscAlignParams& P) {
+	MscAlignTriple diag = L.prev, left = recv;
+	for (int c = 0; c < kAlignCols; c++) {
+		const MscAlignTriple above = L.col[c];
+		msc_align_cell(L.col[c], diag, left, ((L.bytes >> (8 * c)) & 0xffu) == b, P);
+		diag = above;
+		left = L.col[c];
+	}
+	L.prev = recv;
+}
+
+// ---------------------------------------------------------------------------------------- the schedule's sizes
+MSC_HD uint32_t msc_align_stripes(uint32_t la) { return (la + kAlignStripe - 1) / kAlignStripe; }
+// LDS of one pair: the first sequence padded with zeros to whole stripes | pad, the second sequence, pad, rounded up to 8 bytes | where the
+// carry column lives in LDS, its rows 0 .. lb (24 bytes each; a single stripe has none)
+MSC_HD uint32_t msc_align_seq2_at(uint32_t la) { return msc_align_stripes(la) * kAlignStripe; }
+MSC_HD uint32_t msc_align_carry_at(uint32_t la, uint32_t lb) { return (msc_align_seq2_at(la) + 2 * kAlignSeqPad + lb + 7u) & ~7u; }
+MSC_HD uint32_t msc_align_carry_bytes(uint32_t la, uint32_t lb) { return msc_align_stripes(la) > 1 ? (lb + 1) * (uint32_t)sizeof(MscAlignTriple) : 0; }

@@ -1,0 +1,187 @@
+// msc_align.hip -- msc_align_pairs on the device: the global-alignment identity of listed pairs (the definition and the cell
+// update are msc_align.h's).
+//
+//   k_align_pairs<carry in LDS> : one pair per wave (a workgroup is one wave). The wave is a systolic array over the anti-diagonals: lane l keeps
+//       kAlignCols consecutive columns of the first sequence in registers and, at step t of a sweep, fills row t - l + 1 of them; its last column's
+//       three states (a score word and a length | count word each) reach lane l + 1 for the next step through six DPP wave shifts. A first
+//       sequence longer than kAlignStripe columns takes several sweeps: lane 63 writes its column row by row into the CARRY column, which lane 0
+//       of the next sweep reads back in place (row j is read 65 steps before it is written again). The carry lives in LDS behind the two
+//       sequences while the pair's total fits a workgroup's LDS, otherwise in the pair's own range of a scratch buffer the context owns.
+//       Both sequences are staged in LDS as bytes, the first padded with zeros to whole stripes (columns past its end are computed and
+//       never read), the second with kAlignSeqPad zeros on either side (a lane's row index runs up to 63 outside it).
+//   The host sorts the pairs by cells, longest first, inside classes of LDS need (a launch asks for its class's largest need, so short pairs
+//   keep their occupancy beside a few long ones); block b of a launch takes the b-th pair of its class. Results go to the pair's own index:
+//   no atomics, no reduction, nothing that depends on the order the waves run in.
+#include <algorithm>
+#include <vector>
+
+#include "msc_objects.h"
+#include "msc_align.h"
+
+namespace {
+
+struct AlignPair {
+	uint64_t off1, off2;          // byte offsets of the two sequences in the uploaded text
+	uint32_t la, lb;
+	uint32_t out;                 // the pair's index in the caller's list
+	uint32_t pad_;
+	uint64_t carry;               // offset of its carry range in the scratch buffer, in rows (global-carry launches)
+};
+
+__device__ __forceinline__ uint32_t wave_shr1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false); }          // wave_shr:1
+
+__device__ __forceinline__ MscAlignTriple shift_triple(const MscAlignTriple& t) {
+	MscAlignTriple r;
+	r.m.s = (int32_t)wave_shr1((uint32_t)t.m.s); r.m.w = wave_shr1(t.m.w);
+	r.l.s = (int32_t)wave_shr1((uint32_t)t.l.s); r.l.w = wave_shr1(t.l.w);
+	r.u.s = (int32_t)wave_shr1((uint32_t)t.u.s); r.u.w = wave_shr1(t.u.w);
+	return r;
+}
+
+template <bool kLdsCarry>
+__global__ void __launch_bounds__(kAlignLanes) k_align_pairs(const uint8_t* __restrict__ text, const AlignPair* __restrict__ pairs, MscAlignParams P, MscAlignTriple* scratch,
+                                                             int32_t* __restrict__ score, int32_t* __restrict__ length, int32_t* __restrict__ matches) {
+	extern __shared__ __attribute__((aligned(16))) unsigned char al_smem[];
+	const AlignPair pr = pairs[blockIdx.x];
+	const uint32_t lane = threadIdx.x, la = pr.la, lb = pr.lb;
+	const uint32_t stripes = msc_align_stripes(la), seq2_at = msc_align_seq2_at(la) + kAlignSeqPad;
+	uint8_t* s1 = al_smem;
+	uint8_t* s2 = al_smem + seq2_at;
+	MscAlignTriple* carry = kLdsCarry ? reinterpret_cast<MscAlignTriple*>(al_smem + msc_align_carry_at(la, lb)) : scratch + pr.carry;
+	for (uint32_t i = lane; i < stripes * kAlignStripe; i += kAlignLanes) s1[i] = i < la ? text[pr.off1 + i] : (uint8_t)0;
+	for (uint32_t i = lane; i < lb + 2 * kAlignSeqPad; i += kAlignLanes) s2[(int32_t)i - (int32_t)kAlignSeqPad] = i >= kAlignSeqPad && i < kAlignSeqPad + lb ? text[pr.off2 + i - kAlignSeqPad] : (uint8_t)0;
+	__syncthreads();
+	const int32_t neg_inf = msc_align_neg_inf(la, lb, P);
+	const uint32_t steps = lb + kAlignLanes - 1;
+	MscAlignLane L;
+	for (uint32_t s = 0; s < stripes; s++) {
+		const uint32_t first = s * kAlignStripe + lane * kAlignCols;          // 0-based index of the lane's first column
+		msc_align_lane_init(L, first + 1, *reinterpret_cast<const uint32_t*>(s1 + first), neg_inf, P);
+		const bool writes = lane == kAlignLanes - 1 && s + 1 < stripes;
+		MscAlignTriple out = L.col[kAlignCols - 1];
+		MscAlignTriple next = s ? carry[1] : msc_align_col0(1, neg_inf, P);          // what lane 0 receives at the coming step
+		for (uint32_t t = 0; t < steps; t++) {
+			MscAlignTriple recv = shift_triple(out);
+			if (lane == 0) recv = next;
+			const uint32_t ahead = t + 2 <= lb ? t + 2 : lb;                 // (one step ahead: the load is under way while this row is filled)
+			next = s ? carry[ahead] : msc_align_col0(ahead, neg_inf, P);
+			const int32_t row = (int32_t)t - (int32_t)lane;                     // 0-based
+			const uint32_t b = s2[row];
+			if (row >= 0 && row < (int32_t)lb) {
+				msc_align_lane_step(L, recv, b, P);
+				if (writes) carry[row + 1] = L.col[kAlignCols - 1];
+			}
+			out = L.col[kAlignCols - 1];
+		}
+		if (!kLdsCarry) __threadfence();          // the carry rows written in this sweep are read by another lane in the next
+	}
+	// every lane has ended on row lb: the lane that owns column la reports
+	const uint32_t at = (la - 1) % kAlignStripe;
+	if (lane == at / kAlignCols) {
+		MscAlignTriple t = L.col[0];
+#pragma unroll
+		for (int c = 1; c < kAlignCols; c++) if ((uint32_t)c == at % kAlignCols) t = L.col[c];
+		const MscAlignState r = msc_align_final(t);
+		score[pr.out] = r.s;
+		length[pr.out] = (int32_t)(r.w >> 16);
+		matches[pr.out] = (int32_t)(r.w & 0xffffu);
+	}
+}
+
+constexpr uint32_t kAlignLdsMax = 160 * 1024;                                       // of a workgroup
+constexpr uint32_t kAlignClassTop[] = {8 * 1024, 32 * 1024, 64 * 1024, kAlignLdsMax};          // LDS-carry classes; what needs more keeps its carry in global memory
+constexpr int kAlignClasses = 5;
+constexpr uint64_t kAlignScratchRows = (512ull << 20) / sizeof(MscAlignTriple);      // carry rows one global-carry launch may use
+
+}  // namespace
+
+extern "C" int msc_align_pairs(msc_ctx* ctx, const uint8_t* seqs, const uint64_t* offsets, uint64_t n_seqs, const uint32_t* first, const uint32_t* second, uint64_t n_pairs,
+                               int match, int mismatch, int gap_open, int gap_continue, int32_t* score, int32_t* length, int32_t* matches) {
+	if (!ctx) return MSC_ERR_INVALID_ARG;
+	if (n_pairs == 0) return MSC_OK;
+	if (!seqs || !offsets || !first || !second || !score || !length || !matches) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_align_pairs: a NULL argument");
+	if (n_pairs > 0xfffffff0ull) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_align_pairs: too many pairs in one call");
+	for (int v : {match, mismatch, gap_open, gap_continue})
+		if (v > kAlignMaxParam || v < -kAlignMaxParam) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_align_pairs: a scoring parameter of %d (at most %d in absolute value)", v, kAlignMaxParam);
+	std::vector<AlignPair> pairs(n_pairs);
+	for (uint64_t p = 0; p < n_pairs; p++) {
+		AlignPair& a = pairs[p];
+		for (uint32_t s : {first[p], second[p]}) {
+			if (s >= n_seqs) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_align_pairs: pair %llu names sequence %u of %llu", (unsigned long long)p, s, (unsigned long long)n_seqs);
+			if (offsets[s + 1] <= offsets[s] || offsets[s + 1] - offsets[s] > kAlignMaxLen)
+				return fail(ctx, MSC_ERR_INVALID_ARG, "msc_align_pairs: sequence %u has %lld bytes (1 .. %u)", s, (long long)(offsets[s + 1] - offsets[s]), kAlignMaxLen);
+		}
+		a.off1 = offsets[first[p]]; a.la = (uint32_t)(offsets[first[p] + 1] - a.off1);
+		a.off2 = offsets[second[p]]; a.lb = (uint32_t)(offsets[second[p] + 1] - a.off2);
+		a.out = (uint32_t)p; a.pad_ = 0; a.carry = 0;
+	}
+	uint64_t text_bytes = 0;          // the text up to the end of the last listed sequence
+	for (const AlignPair& a : pairs) text_bytes = std::max({text_bytes, a.off1 + a.la, a.off2 + a.lb});
+
+	// classes of LDS need, longest pairs first inside each
+	auto lds_need = [](const AlignPair& a) { return msc_align_carry_at(a.la, a.lb) + msc_align_carry_bytes(a.la, a.lb); };
+	auto class_of = [&](const AlignPair& a) {
+		const uint32_t need = lds_need(a);
+		for (int c = 0; c < kAlignClasses - 1; c++) if (need <= kAlignClassTop[c]) return c;
+		return kAlignClasses - 1;
+	};
+	std::stable_sort(pairs.begin(), pairs.end(), [&](const AlignPair& x, const AlignPair& y) {
+		const int cx = class_of(x), cy = class_of(y);
+		if (cx != cy) return cx < cy;
+		return (uint64_t)x.la * x.lb > (uint64_t)y.la * y.lb;
+	});
+	struct Launch { uint64_t at, n; uint32_t lds; bool lds_carry; uint64_t rows; };
+	std::vector<Launch> launches;
+	uint64_t scratch_rows = 0;
+	for (uint64_t i = 0; i < n_pairs;) {
+		const int c = class_of(pairs[i]);
+		Launch l{i, 0, 0, c < kAlignClasses - 1, 0};
+		for (; i < n_pairs && class_of(pairs[i]) == c; i++, l.n++) {
+			if (l.lds_carry) l.lds = std::max(l.lds, lds_need(pairs[i]));
+			else {
+				const uint64_t rows = pairs[i].lb + 1;
+				if (l.n && l.rows + rows > kAlignScratchRows) break;
+				pairs[i].carry = l.rows;
+				l.rows += rows;
+				l.lds = std::max(l.lds, msc_align_carry_at(pairs[i].la, pairs[i].lb));
+			}
+		}
+		scratch_rows = std::max(scratch_rows, l.rows);
+		launches.push_back(l);
+	}
+
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if (int r = ensure(ctx, ctx->align_text, text_bytes + 4)) return r;
+	if (int r = ensure(ctx, ctx->align_pairs, n_pairs * sizeof(AlignPair))) return r;
+	if (int r = ensure(ctx, ctx->align_out, 3 * n_pairs * sizeof(int32_t))) return r;
+	if (scratch_rows) if (int r = ensure(ctx, ctx->align_carry, scratch_rows * sizeof(MscAlignTriple))) return r;
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->align_text.p, seqs, text_bytes, hipMemcpyHostToDevice, ctx->stream));
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->align_pairs.p, pairs.data(), n_pairs * sizeof(AlignPair), hipMemcpyHostToDevice, ctx->stream));
+	static bool raised = false;
+	if (!raised) {
+		HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_align_pairs<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAlignLdsMax));
+		HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_align_pairs<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAlignLdsMax));
+		raised = true;
+	}
+	const MscAlignParams P = msc_align_params(match, mismatch, gap_open, gap_continue);
+	int32_t* d_out = (int32_t*)ctx->align_out.p;
+	const AlignPair* d_pairs = (const AlignPair*)ctx->align_pairs.p;
+	for (const Launch& l : launches) {
+		if (l.lds > kAlignLdsMax) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_align_pairs: a pair needs %u bytes of LDS", l.lds);          // (cannot happen within the length limit)
+		if (l.lds_carry)
+			k_align_pairs<true><<<dim3((unsigned)l.n), dim3(kAlignLanes), l.lds, ctx->stream>>>((const uint8_t*)ctx->align_text.p, d_pairs + l.at, P, nullptr, d_out, d_out + n_pairs, d_out + 2 * n_pairs);
+		else
+			k_align_pairs<false><<<dim3((unsigned)l.n), dim3(kAlignLanes), l.lds, ctx->stream>>>((const uint8_t*)ctx->align_text.p, d_pairs + l.at, P, (MscAlignTriple*)ctx->align_carry.p, d_out,
+			                                                                                    d_out + n_pairs, d_out + 2 * n_pairs);
+		HIP_TRY(ctx, hipGetLastError());
+	}
+	std::vector<int32_t> out(3 * n_pairs);          // (the caller's arrays stay untouched unless every launch went through)
+	HIP_TRY(ctx, hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	std::copy(out.begin(), out.begin() + n_pairs, score);
+	std::copy(out.begin() + n_pairs, out.begin() + 2 * n_pairs, length);
+	std::copy(out.begin() + 2 * n_pairs, out.end(), matches);
+	ctx->last_kernel = launches.back().lds_carry ? "k_align_pairs<carry in LDS>" : "k_align_pairs<carry in global memory>";
+	ctx->last_query_tile = 0;
+	return MSC_OK;
+}

@@ -329,4 +329,34 @@ private:
 	std::unique_ptr<Feature> cls_, reg_;
 };
 
+// The global-alignment identity of listed pairs (msc_align_pairs: the reference's GlobAlignE, what Feature::align computes with the default
+// parameters, predict/Feature.cpp:697-718): pair p aligns seqs[first[p]] -- the definition's sequence 1, ties are not symmetric -- with
+// seqs[second[p]]; sequences of 1 .. 32 767 bytes, compared byte by byte. identity[p] = matches[p] / length[p]; the caller's order.
+struct Alignments {
+	std::vector<int32_t> score, length, matches;
+	std::vector<double> identity;
+};
+inline Alignments align_pairs(const Context& ctx, const std::vector<std::string>& seqs, const std::vector<uint32_t>& first, const std::vector<uint32_t>& second, int match = 1,
+                              int mismatch = -1, int gap_open = 2, int gap_continue = 1) {
+	if (first.size() != second.size()) throw Error(MSC_ERR_INVALID_ARG, "align_pairs: first and second are one pair list");
+	std::string text;
+	std::vector<uint64_t> offsets(1, 0);
+	for (const std::string& s : seqs) { text += s; offsets.push_back(text.size()); }
+	text.push_back('\0');          // (never a null pointer, whatever the list holds)
+	Alignments a;
+	const size_t n = first.size();
+	a.score.resize(n); a.length.resize(n); a.matches.resize(n); a.identity.resize(n);
+	ctx.check(msc_align_pairs(ctx.get(), reinterpret_cast<const uint8_t*>(text.data()), offsets.data(), seqs.size(), first.data(), second.data(), n, match, mismatch, gap_open,
+	                          gap_continue, a.score.data(), a.length.data(), a.matches.data()));
+	for (size_t i = 0; i < n; i++) a.identity[i] = (double)a.matches[i] / a.length[i];
+	return a;
+}
+
+// the other strand of a sequence as a string: reversed, A <-> T and C <-> G, every other byte as it is
+inline std::string reverse_complement(const std::string& s) {
+	std::string rc(s.rbegin(), s.rend());
+	for (char& c : rc) c = c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c;
+	return rc;
+}
+
 }  // namespace msc

@@ -6,7 +6,14 @@
 // std::sort by length, bin_search, format_header and the output formatting follow fastcar/FC_Runner.cpp:389-471,
 // 560-611 at one thread (one output file "<prefix>0"); training is out of scope, a two-block weights file is required.
 //
-//   msc_fastcar <db.fa> --query <q.fa> --recover weights.txt [--output output] [--chunk 10000] [--no-format] [--device 0] [--div-cells] [--top N] [--both-strands] [--canonical]
+//   msc_fastcar <db.fa> --query <q.fa> --recover weights.txt [--output output] [--chunk 10000] [--no-format] [--device 0] [--div-cells] [--top N] [--both-strands] [--canonical] [--align]
+//
+// --align: one more column after the predicted identity (and after the strand column where there is one): the identity of the global alignment of
+// the reported pair, matches / length of msc_align_pairs with the default parameters (1, -1, 2, 1), the query as the first sequence -- the quantity
+// the column before it predicts -- printed the same way, 100 * identity. The hits of one (query chunk, database chunk) step are aligned in one
+// call, over the strings as read from the files (1 .. 32 767 bytes each); with --both-strands a `-` hit aligns the query's reverse complement
+// (the string reversed, A <-> T, C <-> G, any other byte kept). Not together with --canonical: a strand-neutral point has no orientation to
+// align. Without the flag the output is what it was.
 //
 // --canonical: database and query histograms are made strand-neutral right after they are built (msc_hist_canonical_batch, in place: each k-mer
 // counted together with its reverse complement), so a query and its reverse complement give the same lines; everything else is unchanged. The
@@ -105,7 +112,7 @@ void load_chunk(msc::PointSet& set, const std::vector<Rec>& recs, size_t off, si
 }
 
 // a hit that survived its database chunk's cut; `chunk` and `cand` give its place in the output without --top
-struct Surv { size_t chunk, cand; double sim; std::string header; };
+struct Surv { size_t chunk, cand; double sim; std::string header; double aln; };
 
 // the rule of msc_search_pairs_top on the host: the n of largest similarity (compared as doubles), ties to the earlier entry, order kept
 template <class T>
@@ -127,7 +134,7 @@ int main(int argc, char** argv) {
 	std::vector<std::string> files, qfiles;
 	std::string weights, output = "output";
 	size_t chunk = 10000, qblock = 16, top = 0;
-	bool format = true, sparse = false, report_kernels = false, div_cells = false, sparse_matrix = false, both_strands = false, canonical = false;
+	bool format = true, sparse = false, report_kernels = false, div_cells = false, sparse_matrix = false, both_strands = false, canonical = false, align = false;
 	int device = 0;
 	for (int i = 1; i < argc; i++) {
 		std::string a = argv[i];
@@ -146,15 +153,20 @@ int main(int argc, char** argv) {
 		else if (a == "--top") top = (size_t)std::max(0l, std::atol(need("--top").c_str()));          // each query's N best hits (0: all)
 		else if (a == "--both-strands") both_strands = true;          // msc_search_pairs_strands: the queries and their reverse complements
 		else if (a == "--canonical") canonical = true;          // msc_hist_canonical_batch on every chunk: strand-neutral histograms
+		else if (a == "--align") align = true;          // msc_align_pairs on every reported pair: a column with the alignment identity
 		else if (a == "--device") device = std::atoi(need("--device").c_str());
 		else files.push_back(a);
 	}
 	if (files.empty() || qfiles.empty() || weights.empty()) {
-		std::fprintf(stderr, "usage: %s <db.fa> --query <q.fa> --recover weights.txt [--output prefix] [--chunk 10000] [--no-format] [--sparse] [--sparse-matrix] [--div-cells] [--top N] [--both-strands] [--canonical]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s <db.fa> --query <q.fa> --recover weights.txt [--output prefix] [--chunk 10000] [--no-format] [--sparse] [--sparse-matrix] [--div-cells] [--top N] [--both-strands] [--canonical] [--align]\n", argv[0]);
 		return 1;
 	}
 	if (canonical && both_strands) {
 		std::fprintf(stderr, "--canonical and --both-strands cannot be combined: they are different definitions of a search on both strands\n");
+		return 1;
+	}
+	if (canonical && align) {
+		std::fprintf(stderr, "--align and --canonical cannot be combined: a strand-neutral point has no orientation to align\n");
 		return 1;
 	}
 	if (both_strands && top) {
@@ -218,7 +230,7 @@ int main(int argc, char** argv) {
 				// work() (:426-471) for every query of the chunk. Queries are taken in blocks of `qblock` neighbours in LENGTH order, so
 				// their length windows nearly coincide and one Q x M pass over the union window serves the block; each query then
 				// keeps only its own window, and the lines are written in the reference's order (query order, then window order).
-				struct Hit { size_t cand; double sim; uint8_t strand; };
+				struct Hit { size_t cand; double sim; uint8_t strand; double aln; };
 				std::vector<std::vector<Hit> > hits(qp.size());
 				std::vector<size_t> win_start(qp.size()), win_end(qp.size());
 				for (size_t qi = 0; qi < qp.size(); qi++) {
@@ -256,7 +268,7 @@ int main(int argc, char** argv) {
 						note_kernel();
 						const size_t before = hits[members[0]].size();
 						for (size_t i = win_start[members[0]]; i < win_end[members[0]]; i++)
-							if (close[i - lo]) hits[members[0]].push_back(Hit{i, sim[i - lo], 0});
+							if (close[i - lo]) hits[members[0]].push_back(Hit{i, sim[i - lo], 0, 0.0});
 						num_pred_pos += hits[members[0]].size() - before;
 						cut_top(hits[members[0]], top);
 						continue;
@@ -274,11 +286,31 @@ int main(int argc, char** argv) {
 					note_kernel();
 					for (size_t j = 0; j < members.size(); j++) num_pred_pos += top ? counts[j] : offsets[j + 1] - offsets[j];
 					for (size_t j = 0; j < members.size(); j++)
-						for (uint64_t p = offsets[j]; p < offsets[j + 1]; p++) hits[members[j]].push_back(Hit{lo + idx[p], sim[p], both_strands ? strand[p] : (uint8_t)0});
+						for (uint64_t p = offsets[j]; p < offsets[j + 1]; p++) hits[members[j]].push_back(Hit{lo + idx[p], sim[p], both_strands ? strand[p] : (uint8_t)0, 0.0});
+				}
+				if (align) {          // --align: the step's reported pairs in one call, over the strings of the two chunks; sequence 1 = the query (reversed for a `-` hit)
+					std::vector<std::string> text;
+					std::vector<uint32_t> first, second;
+					std::vector<long> q_at(2 * qp.size(), -1), d_at(pts.size(), -1);          // where a query (by strand) / an entry sits in `text`
+					std::vector<Hit*> listed;
+					for (size_t qi = 0; qi < qp.size(); qi++)
+						for (Hit& h : hits[qi]) {
+							if (!(h.sim > 0)) continue;
+							long& qa = q_at[2 * qi + (h.strand ? 1 : 0)];
+							if (qa < 0) { qa = (long)text.size(); text.push_back(h.strand ? msc::reverse_complement(queries[qo + qp[qi].slot].seq) : queries[qo + qp[qi].slot].seq); }
+							long& da = d_at[h.cand];
+							if (da < 0) { da = (long)text.size(); text.push_back(db[d0 + pts[h.cand]->slot].seq); }
+							first.push_back((uint32_t)qa);
+							second.push_back((uint32_t)da);
+							listed.push_back(&h);
+						}
+					const msc::Alignments al = msc::align_pairs(ctx, text, first, second);
+					note_kernel();
+					for (size_t i = 0; i < listed.size(); i++) listed[i]->aln = al.identity[i];
 				}
 				if (top) {          // the chunk's survivors behind those of the chunks before, cut again: ties stay with the earlier chunk
 					for (size_t qi = 0; qi < qp.size(); qi++) {
-						for (const Hit& h : hits[qi]) best[qi].push_back(Surv{dchunk, h.cand, h.sim, pts[h.cand]->header});
+						for (const Hit& h : hits[qi]) best[qi].push_back(Surv{dchunk, h.cand, h.sim, pts[h.cand]->header, h.aln});
 						cut_top(best[qi], top);
 					}
 					continue;
@@ -290,6 +322,7 @@ int main(int argc, char** argv) {
 							if (format) out << format_header(query.header) << delim << format_header(pts[h.cand]->header) << delim << 100 * h.sim;
 							else out << query.header << delim << pts[h.cand]->header << delim << 100 * h.sim;
 							if (both_strands) out << delim << (h.strand ? '-' : '+');
+							if (align) out << delim << 100 * h.aln;
 							out << std::endl;
 						}
 					}
@@ -302,8 +335,10 @@ int main(int argc, char** argv) {
 						for (; at[qi] < best[qi].size() && best[qi][at[qi]].chunk == dc; at[qi]++) {
 							const Surv& h = best[qi][at[qi]];
 							if (!(h.sim > 0)) continue;
-							if (format) out << format_header(qp[qi].header) << delim << format_header(h.header) << delim << 100 * h.sim << std::endl;
-							else out << qp[qi].header << delim << h.header << delim << 100 * h.sim << std::endl;
+							if (format) out << format_header(qp[qi].header) << delim << format_header(h.header) << delim << 100 * h.sim;
+							else out << qp[qi].header << delim << h.header << delim << 100 * h.sim;
+							if (align) out << delim << 100 * h.aln;
+							out << std::endl;
 						}
 			}
 		}
