@@ -461,6 +461,40 @@ int msc_align_pairs(msc_ctx* ctx,
                     int match, int mismatch, int gap_open, int gap_continue,
                     int32_t* score, int32_t* length, int32_t* matches);
 
+/* ------------------------------------------------------------------ the same integers over a band of diagonals, with a proof per pair
+ * For SIMILAR pairs (the hits of msc_fastcar --align, a cluster's members against its centre) the optimal path stays near the corner-to-corner
+ * line, and filling the whole grid is wasted work. Both calls below take the lists, the parameters, the limits and the refusals of
+ * msc_align_pairs (1 .. 32 767 bytes, parameters at most 100 in absolute value, indices below n_seqs, MSC_ERR_INVALID_ARG with every output
+ * untouched otherwise, n_pairs == 0 is MSC_OK, results in the caller's order). DESIGN.md 4.6f has the definition and the proof.
+ *
+ * msc_align_pairs_banded: the recurrence over the diagonals min(0, la - lb) - band .. max(0, la - lb) + band of the grid only (cell (i, j)
+ *   lies on diagonal i - j); every state outside them is the constant (-2^30, 0). Any uint32 is a legal band; one of min(la, lb) or more
+ *   covers the grid. The triple is a function of (pair, parameters, band) alone, certified or not.
+ *   certified[p] = 1: the pair's triple is PROVEN to be msc_align_pairs's, bit for bit -- by an integer test on the banded score (it exceeds
+ *   every score a path through a cell outside the band can reach), or because the band covers the grid. 0: not proven; the triple may or may
+ *   not be the full one. The test is offered only where gap_open >= 0, gap_continue >= 0 and max(match, mismatch) + 2 * gap_continue >= 0;
+ *   under other parameters only a covering band certifies.
+ * msc_align_pairs_auto: msc_align_pairs's triples, always and under every parameter set, with fewer cells filled for similar pairs. Every
+ *   pair starts at first_band (0: the library's default, 64) and is rerun with its band doubled while it is not certified; a pair whose
+ *   band's row window (diagonals + 64 * columns a lane - 1 rows) would exceed half of its rows, and every pair under parameters without a
+ *   certificate, goes through k_align_pairs instead. band_used (may be NULL): the band that certified pair p, 0xffffffff where the full
+ *   kernel ran. Worth it from about 1 000 bytes a sequence at 97 % identity and from 5 000 bytes at 85 - 95 % (profiles/align_band.md);
+ *   below that it costs what msc_align_pairs costs, plus a round that certified nothing.
+ * One pair per wave, the systolic sweep of k_align_pairs over the rows each stripe of columns has in band; the sequences are uploaded once
+ * per call, each round of msc_align_pairs_auto launches only the pairs still open, each at its own band. msc_last_kernel_info names
+ * "k_align_band<C column(s) a lane, carry in LDS | global memory>" (of the call's last banded launch; k_align_pairs's name where
+ * msc_align_pairs_auto ran no banded round). */
+int msc_align_pairs_banded(msc_ctx* ctx,
+                           const uint8_t* seqs, const uint64_t* offsets, uint64_t n_seqs,
+                           const uint32_t* first, const uint32_t* second, uint64_t n_pairs,
+                           int match, int mismatch, int gap_open, int gap_continue, uint32_t band,
+                           int32_t* score, int32_t* length, int32_t* matches, uint8_t* certified);
+int msc_align_pairs_auto(msc_ctx* ctx,
+                         const uint8_t* seqs, const uint64_t* offsets, uint64_t n_seqs,
+                         const uint32_t* first, const uint32_t* second, uint64_t n_pairs,
+                         int match, int mismatch, int gap_open, int gap_continue, uint32_t first_band,
+                         int32_t* score, int32_t* length, int32_t* matches, uint32_t* band_used);
+
 /* ------------------------------------------------------------------ a8/a9: Trainer operators */
 /* Trainer<T>::get_close (cluster/Trainer.cpp:23-71; caller cluster/ClusterFactory.cpp:566).
  * The window [istart, iend) is cand_slots[0..m). Candidates outside floor(len_q*cutoff) <= len <= floor(len_q/cutoff)

@@ -554,6 +554,52 @@ def align_pairs(ctx, seqs, first, second, match=1, mismatch=-1, gap_open=2, gap_
     return dict(score=score, length=length, matches=matches, identity=identity)
 
 
+def _align_over_a_band(name, ctx, seqs, first, second, band, params, out, last):
+    """msc_align_pairs_banded / msc_align_pairs_auto: align_pairs's arguments, a band between the parameters and the outputs and a fourth
+    output (`last`: uint8 flags or uint32 bands)"""
+    raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs]
+    a = np.ascontiguousarray(first, dtype=np.uint32)
+    b = np.ascontiguousarray(second, dtype=np.uint32)
+    if a.ndim != 1 or a.shape != b.shape:
+        raise ValueError("first and second are one pair list: one dimension, equal lengths")
+    if not 0 <= int(band) <= 0xffffffff:
+        raise ValueError("a band is a uint32")
+    offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
+    np.cumsum([len(s) for s in raw], out=offsets[1:])
+    text = np.frombuffer(b"".join(raw) + b"\0", dtype=np.uint8)
+    if out is None:
+        out = tuple(np.zeros(a.size, dtype=np.int32) for _ in range(3)) + (np.zeros(a.size, dtype=last),)
+    if len(out) != 4 or any(o.dtype != (np.int32 if i < 3 else last) or o.shape != a.shape or not o.flags.c_contiguous for i, o in enumerate(out)):
+        raise ValueError("out: three contiguous int32 arrays of n_pairs and one of %s" % np.dtype(last).name)
+    lib = ctx.lib if ctx is not None else _capi.load_library()
+    rc = getattr(lib, name)(ctx.h if ctx is not None else None, _ptr(text), _ptr(offsets), len(raw), _ptr(a), _ptr(b), a.size, *[int(v) for v in params], int(band),
+                            *[_ptr(o) for o in out])
+    if rc != 0:
+        raise MscError(rc, lib.msc_last_error(ctx.h).decode() if ctx is not None else name + " needs a Context (a gfx950 device): there is no CPU fallback")
+    score, length, matches = out[:3]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        identity = matches.astype(np.float64) / length.astype(np.float64)
+    return dict(score=score, length=length, matches=matches, identity=identity), out[3]
+
+
+def align_pairs_banded(ctx, seqs, first, second, band, match=1, mismatch=-1, gap_open=2, gap_continue=1, out=None):
+    """align_pairs over the diagonals within `band` of the corner-to-corner ones only (msc_align_pairs_banded).
+    -> align_pairs's dict and certified: uint8 [n_pairs], 1 where the pair's integers are proven to be align_pairs's. `out`: a tuple of three
+    int32 arrays and a uint8 one, left as they were by a refused call."""
+    r, flags = _align_over_a_band("msc_align_pairs_banded", ctx, seqs, first, second, band, (match, mismatch, gap_open, gap_continue), out, np.uint8)
+    r["certified"] = flags
+    return r
+
+
+def align_pairs_auto(ctx, seqs, first, second, match=1, mismatch=-1, gap_open=2, gap_continue=1, first_band=0, out=None):
+    """align_pairs's integers, computed over a band that is doubled per pair until the pair is certified (msc_align_pairs_auto; first_band 0:
+    the library's default). -> align_pairs's dict and band_used: uint32 [n_pairs], the band that certified the pair, 0xffffffff where the
+    full grid was filled. `out`: a tuple of three int32 arrays and a uint32 one, left as they were by a refused call."""
+    r, bands = _align_over_a_band("msc_align_pairs_auto", ctx, seqs, first, second, first_band, (match, mismatch, gap_open, gap_continue), out, np.uint32)
+    r["band_used"] = bands
+    return r
+
+
 class Trainer:
     """The pair-scoring operators of cluster/Trainer.{h,cpp} (scoring half only; training is host work out of scope)."""
 

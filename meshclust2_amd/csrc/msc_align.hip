@@ -17,16 +17,9 @@
 
 #include "msc_objects.h"
 #include "msc_align.h"
+#include "msc_align_host.h"
 
 namespace {
-
-struct AlignPair {
-	uint64_t off1, off2;          // byte offsets of the two sequences in the uploaded text
-	uint32_t la, lb;
-	uint32_t out;                 // the pair's index in the caller's list
-	uint32_t pad_;
-	uint64_t carry;               // offset of its carry range in the scratch buffer, in rows (global-carry launches)
-};
 
 __device__ __forceinline__ uint32_t wave_shr1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false); }          // wave_shr:1
 
@@ -88,36 +81,35 @@ __global__ void __launch_bounds__(kAlignLanes) k_align_pairs(const uint8_t* __re
 	}
 }
 
-constexpr uint32_t kAlignLdsMax = 160 * 1024;                                       // of a workgroup
-constexpr uint32_t kAlignClassTop[] = {8 * 1024, 32 * 1024, 64 * 1024, kAlignLdsMax};          // LDS-carry classes; what needs more keeps its carry in global memory
-constexpr int kAlignClasses = 5;
-constexpr uint64_t kAlignScratchRows = (512ull << 20) / sizeof(MscAlignTriple);      // carry rows one global-carry launch may use
-
 }  // namespace
 
-extern "C" int msc_align_pairs(msc_ctx* ctx, const uint8_t* seqs, const uint64_t* offsets, uint64_t n_seqs, const uint32_t* first, const uint32_t* second, uint64_t n_pairs,
-                               int match, int mismatch, int gap_open, int gap_continue, int32_t* score, int32_t* length, int32_t* matches) {
-	if (!ctx) return MSC_ERR_INVALID_ARG;
-	if (n_pairs == 0) return MSC_OK;
-	if (!seqs || !offsets || !first || !second || !score || !length || !matches) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_align_pairs: a NULL argument");
-	if (n_pairs > 0xfffffff0ull) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_align_pairs: too many pairs in one call");
+// The checks every alignment call makes on the host before anything is queued, and the pair records in the caller's order
+int msc_align_list(msc_ctx* ctx, const char* who, const uint64_t* offsets, uint64_t n_seqs, const uint32_t* first, const uint32_t* second, uint64_t n_pairs, int match, int mismatch,
+                   int gap_open, int gap_continue, std::vector<AlignPair>& pairs, uint64_t& text_bytes) {
+	if (n_pairs > 0xfffffff0ull) return fail(ctx, MSC_ERR_INVALID_ARG, "%s: too many pairs in one call", who);
 	for (int v : {match, mismatch, gap_open, gap_continue})
-		if (v > kAlignMaxParam || v < -kAlignMaxParam) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_align_pairs: a scoring parameter of %d (at most %d in absolute value)", v, kAlignMaxParam);
-	std::vector<AlignPair> pairs(n_pairs);
+		if (v > kAlignMaxParam || v < -kAlignMaxParam) return fail(ctx, MSC_ERR_INVALID_ARG, "%s: a scoring parameter of %d (at most %d in absolute value)", who, v, kAlignMaxParam);
+	pairs.resize(n_pairs);
 	for (uint64_t p = 0; p < n_pairs; p++) {
 		AlignPair& a = pairs[p];
 		for (uint32_t s : {first[p], second[p]}) {
-			if (s >= n_seqs) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_align_pairs: pair %llu names sequence %u of %llu", (unsigned long long)p, s, (unsigned long long)n_seqs);
+			if (s >= n_seqs) return fail(ctx, MSC_ERR_INVALID_ARG, "%s: pair %llu names sequence %u of %llu", who, (unsigned long long)p, s, (unsigned long long)n_seqs);
 			if (offsets[s + 1] <= offsets[s] || offsets[s + 1] - offsets[s] > kAlignMaxLen)
-				return fail(ctx, MSC_ERR_INVALID_ARG, "msc_align_pairs: sequence %u has %lld bytes (1 .. %u)", s, (long long)(offsets[s + 1] - offsets[s]), kAlignMaxLen);
+				return fail(ctx, MSC_ERR_INVALID_ARG, "%s: sequence %u has %lld bytes (1 .. %u)", who, s, (long long)(offsets[s + 1] - offsets[s]), kAlignMaxLen);
 		}
 		a.off1 = offsets[first[p]]; a.la = (uint32_t)(offsets[first[p] + 1] - a.off1);
 		a.off2 = offsets[second[p]]; a.lb = (uint32_t)(offsets[second[p] + 1] - a.off2);
-		a.out = (uint32_t)p; a.pad_ = 0; a.carry = 0;
+		a.out = (uint32_t)p; a.band = 0; a.carry = 0;
 	}
-	uint64_t text_bytes = 0;          // the text up to the end of the last listed sequence
+	text_bytes = 0;          // the text up to the end of the last listed sequence
 	for (const AlignPair& a : pairs) text_bytes = std::max({text_bytes, a.off1 + a.la, a.off2 + a.lb});
+	return MSC_OK;
+}
 
+// Queues k_align_pairs for `pairs` (reordered here) over the uploaded text: pair p's integers go to d_out[p.out], d_out[n_out + p.out] and
+// d_out[2 * n_out + p.out]
+int msc_align_queue_full(msc_ctx* ctx, std::vector<AlignPair>& pairs, const uint8_t* d_text, const MscAlignParams& P, int32_t* d_out, uint64_t n_out) {
+	const uint64_t n_pairs = pairs.size();
 	// classes of LDS need, longest pairs first inside each
 	auto lds_need = [](const AlignPair& a) { return msc_align_carry_at(a.la, a.lb) + msc_align_carry_bytes(a.la, a.lb); };
 	auto class_of = [&](const AlignPair& a) {
@@ -149,13 +141,8 @@ extern "C" int msc_align_pairs(msc_ctx* ctx, const uint8_t* seqs, const uint64_t
 		scratch_rows = std::max(scratch_rows, l.rows);
 		launches.push_back(l);
 	}
-
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	if (int r = ensure(ctx, ctx->align_text, text_bytes + 4)) return r;
 	if (int r = ensure(ctx, ctx->align_pairs, n_pairs * sizeof(AlignPair))) return r;
-	if (int r = ensure(ctx, ctx->align_out, 3 * n_pairs * sizeof(int32_t))) return r;
 	if (scratch_rows) if (int r = ensure(ctx, ctx->align_carry, scratch_rows * sizeof(MscAlignTriple))) return r;
-	HIP_TRY(ctx, hipMemcpyAsync(ctx->align_text.p, seqs, text_bytes, hipMemcpyHostToDevice, ctx->stream));
 	HIP_TRY(ctx, hipMemcpyAsync(ctx->align_pairs.p, pairs.data(), n_pairs * sizeof(AlignPair), hipMemcpyHostToDevice, ctx->stream));
 	static bool raised = false;
 	if (!raised) {
@@ -163,25 +150,39 @@ extern "C" int msc_align_pairs(msc_ctx* ctx, const uint8_t* seqs, const uint64_t
 		HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_align_pairs<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAlignLdsMax));
 		raised = true;
 	}
-	const MscAlignParams P = msc_align_params(match, mismatch, gap_open, gap_continue);
-	int32_t* d_out = (int32_t*)ctx->align_out.p;
 	const AlignPair* d_pairs = (const AlignPair*)ctx->align_pairs.p;
 	for (const Launch& l : launches) {
 		if (l.lds > kAlignLdsMax) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_align_pairs: a pair needs %u bytes of LDS", l.lds);          // (cannot happen within the length limit)
 		if (l.lds_carry)
-			k_align_pairs<true><<<dim3((unsigned)l.n), dim3(kAlignLanes), l.lds, ctx->stream>>>((const uint8_t*)ctx->align_text.p, d_pairs + l.at, P, nullptr, d_out, d_out + n_pairs, d_out + 2 * n_pairs);
+			k_align_pairs<true><<<dim3((unsigned)l.n), dim3(kAlignLanes), l.lds, ctx->stream>>>(d_text, d_pairs + l.at, P, nullptr, d_out, d_out + n_out, d_out + 2 * n_out);
 		else
-			k_align_pairs<false><<<dim3((unsigned)l.n), dim3(kAlignLanes), l.lds, ctx->stream>>>((const uint8_t*)ctx->align_text.p, d_pairs + l.at, P, (MscAlignTriple*)ctx->align_carry.p, d_out,
-			                                                                                    d_out + n_pairs, d_out + 2 * n_pairs);
+			k_align_pairs<false><<<dim3((unsigned)l.n), dim3(kAlignLanes), l.lds, ctx->stream>>>(d_text, d_pairs + l.at, P, (MscAlignTriple*)ctx->align_carry.p, d_out, d_out + n_out, d_out + 2 * n_out);
 		HIP_TRY(ctx, hipGetLastError());
 	}
+	ctx->last_kernel = launches.back().lds_carry ? "k_align_pairs<carry in LDS>" : "k_align_pairs<carry in global memory>";
+	ctx->last_query_tile = 0;
+	return MSC_OK;
+}
+
+extern "C" int msc_align_pairs(msc_ctx* ctx, const uint8_t* seqs, const uint64_t* offsets, uint64_t n_seqs, const uint32_t* first, const uint32_t* second, uint64_t n_pairs,
+                               int match, int mismatch, int gap_open, int gap_continue, int32_t* score, int32_t* length, int32_t* matches) {
+	if (!ctx) return MSC_ERR_INVALID_ARG;
+	if (n_pairs == 0) return MSC_OK;
+	if (!seqs || !offsets || !first || !second || !score || !length || !matches) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_align_pairs: a NULL argument");
+	std::vector<AlignPair> pairs;
+	uint64_t text_bytes = 0;
+	if (int r = msc_align_list(ctx, "msc_align_pairs", offsets, n_seqs, first, second, n_pairs, match, mismatch, gap_open, gap_continue, pairs, text_bytes)) return r;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if (int r = ensure(ctx, ctx->align_text, text_bytes + 4)) return r;
+	if (int r = ensure(ctx, ctx->align_out, 3 * n_pairs * sizeof(int32_t))) return r;
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->align_text.p, seqs, text_bytes, hipMemcpyHostToDevice, ctx->stream));
+	int32_t* d_out = (int32_t*)ctx->align_out.p;
+	if (int r = msc_align_queue_full(ctx, pairs, (const uint8_t*)ctx->align_text.p, msc_align_params(match, mismatch, gap_open, gap_continue), d_out, n_pairs)) return r;
 	std::vector<int32_t> out(3 * n_pairs);          // (the caller's arrays stay untouched unless every launch went through)
 	HIP_TRY(ctx, hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	std::copy(out.begin(), out.begin() + n_pairs, score);
 	std::copy(out.begin() + n_pairs, out.begin() + 2 * n_pairs, length);
 	std::copy(out.begin() + 2 * n_pairs, out.end(), matches);
-	ctx->last_kernel = launches.back().lds_carry ? "k_align_pairs<carry in LDS>" : "k_align_pairs<carry in global memory>";
-	ctx->last_query_tile = 0;
 	return MSC_OK;
 }

@@ -352,6 +352,52 @@ inline Alignments align_pairs(const Context& ctx, const std::vector<std::string>
 	return a;
 }
 
+// The same integers over a band of diagonals (msc_align_pairs_banded, msc_align_pairs_auto). align_pairs_banded fills the
+// diagonals within `band` of the corner-to-corner ones and says per pair whether its integers are PROVEN to be align_pairs's (certified[p]
+// = 1); align_pairs_auto doubles each pair's band from first_band (0: the library's default) until it is, and always returns align_pairs's
+// integers -- band_used[p] is the band that certified the pair, no_band where the full grid was filled.
+struct BandedAlignments {
+	enum : uint32_t { no_band = 0xffffffffu };
+	std::vector<int32_t> score, length, matches;
+	std::vector<double> identity;
+	std::vector<uint8_t> certified;          // align_pairs_banded
+	std::vector<uint32_t> band_used;         // align_pairs_auto
+};
+namespace detail {
+inline BandedAlignments align_over_a_band(const Context& ctx, bool automatic, const std::vector<std::string>& seqs, const std::vector<uint32_t>& first, const std::vector<uint32_t>& second,
+                                          uint32_t band, int match, int mismatch, int gap_open, int gap_continue) {
+	if (first.size() != second.size()) throw Error(MSC_ERR_INVALID_ARG, "align_pairs: first and second are one pair list");
+	std::string text;
+	std::vector<uint64_t> offsets(1, 0);
+	for (const std::string& s : seqs) { text += s; offsets.push_back(text.size()); }
+	text.push_back('\0');
+	BandedAlignments a;
+	const size_t n = first.size();
+	a.score.resize(n); a.length.resize(n); a.matches.resize(n); a.identity.resize(n);
+	const uint8_t* bytes = reinterpret_cast<const uint8_t*>(text.data());
+	if (automatic) {
+		a.band_used.resize(n + 1);          // (never a null pointer: NULL means "not wanted")
+		ctx.check(msc_align_pairs_auto(ctx.get(), bytes, offsets.data(), seqs.size(), first.data(), second.data(), n, match, mismatch, gap_open, gap_continue, band, a.score.data(),
+		                               a.length.data(), a.matches.data(), a.band_used.data()));
+		a.band_used.resize(n);
+	} else {
+		a.certified.resize(n);
+		ctx.check(msc_align_pairs_banded(ctx.get(), bytes, offsets.data(), seqs.size(), first.data(), second.data(), n, match, mismatch, gap_open, gap_continue, band, a.score.data(),
+		                                 a.length.data(), a.matches.data(), a.certified.data()));
+	}
+	for (size_t i = 0; i < n; i++) a.identity[i] = (double)a.matches[i] / a.length[i];
+	return a;
+}
+}  // namespace detail
+inline BandedAlignments align_pairs_banded(const Context& ctx, const std::vector<std::string>& seqs, const std::vector<uint32_t>& first, const std::vector<uint32_t>& second, uint32_t band,
+                                           int match = 1, int mismatch = -1, int gap_open = 2, int gap_continue = 1) {
+	return detail::align_over_a_band(ctx, false, seqs, first, second, band, match, mismatch, gap_open, gap_continue);
+}
+inline BandedAlignments align_pairs_auto(const Context& ctx, const std::vector<std::string>& seqs, const std::vector<uint32_t>& first, const std::vector<uint32_t>& second,
+                                         uint32_t first_band = 0, int match = 1, int mismatch = -1, int gap_open = 2, int gap_continue = 1) {
+	return detail::align_over_a_band(ctx, true, seqs, first, second, first_band, match, mismatch, gap_open, gap_continue);
+}
+
 // the other strand of a sequence as a string: reversed, A <-> T and C <-> G, every other byte as it is
 inline std::string reverse_complement(const std::string& s) {
 	std::string rc(s.rbegin(), s.rend());

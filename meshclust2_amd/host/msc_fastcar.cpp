@@ -6,7 +6,7 @@
 // std::sort by length, bin_search, format_header and the output formatting follow fastcar/FC_Runner.cpp:389-471,
 // 560-611 at one thread (one output file "<prefix>0"); training is out of scope, a two-block weights file is required.
 //
-//   msc_fastcar <db.fa> --query <q.fa> --recover weights.txt [--output output] [--chunk 10000] [--no-format] [--device 0] [--div-cells] [--top N] [--both-strands] [--canonical] [--align]
+//   msc_fastcar <db.fa> --query <q.fa> --recover weights.txt [--output output] [--chunk 10000] [--no-format] [--device 0] [--div-cells] [--top N] [--both-strands] [--canonical] [--align] [--align-band W]
 //
 // --align: one more column after the predicted identity (and after the strand column where there is one): the identity of the global alignment of
 // the reported pair, matches / length of msc_align_pairs with the default parameters (1, -1, 2, 1), the query as the first sequence -- the quantity
@@ -14,6 +14,8 @@
 // call, over the strings as read from the files (1 .. 32 767 bytes each); with --both-strands a `-` hit aligns the query's reverse complement
 // (the string reversed, A <-> T, C <-> G, any other byte kept). Not together with --canonical: a strand-neutral point has no orientation to
 // align. Without the flag the output is what it was.
+// --align-band W (with --align): the same column through msc_align_pairs_auto, which fills a band of diagonals per pair (first half-width W, 0 = the
+// library's default, doubled until the pair is certified) and returns msc_align_pairs's integers: the output is byte for byte that of --align.
 //
 // --canonical: database and query histograms are made strand-neutral right after they are built (msc_hist_canonical_batch, in place: each k-mer
 // counted together with its reverse complement), so a query and its reverse complement give the same lines; everything else is unchanged. The
@@ -134,7 +136,8 @@ int main(int argc, char** argv) {
 	std::vector<std::string> files, qfiles;
 	std::string weights, output = "output";
 	size_t chunk = 10000, qblock = 16, top = 0;
-	bool format = true, sparse = false, report_kernels = false, div_cells = false, sparse_matrix = false, both_strands = false, canonical = false, align = false;
+	bool format = true, sparse = false, report_kernels = false, div_cells = false, sparse_matrix = false, both_strands = false, canonical = false, align = false, align_band = false;
+	uint32_t first_band = 0;
 	int device = 0;
 	for (int i = 1; i < argc; i++) {
 		std::string a = argv[i];
@@ -154,11 +157,12 @@ int main(int argc, char** argv) {
 		else if (a == "--both-strands") both_strands = true;          // msc_search_pairs_strands: the queries and their reverse complements
 		else if (a == "--canonical") canonical = true;          // msc_hist_canonical_batch on every chunk: strand-neutral histograms
 		else if (a == "--align") align = true;          // msc_align_pairs on every reported pair: a column with the alignment identity
+		else if (a == "--align-band") { align_band = true; first_band = (uint32_t)std::max(0l, std::atol(need("--align-band").c_str())); }          // --align through msc_align_pairs_auto
 		else if (a == "--device") device = std::atoi(need("--device").c_str());
 		else files.push_back(a);
 	}
 	if (files.empty() || qfiles.empty() || weights.empty()) {
-		std::fprintf(stderr, "usage: %s <db.fa> --query <q.fa> --recover weights.txt [--output prefix] [--chunk 10000] [--no-format] [--sparse] [--sparse-matrix] [--div-cells] [--top N] [--both-strands] [--canonical] [--align]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s <db.fa> --query <q.fa> --recover weights.txt [--output prefix] [--chunk 10000] [--no-format] [--sparse] [--sparse-matrix] [--div-cells] [--top N] [--both-strands] [--canonical] [--align] [--align-band W]\n", argv[0]);
 		return 1;
 	}
 	if (canonical && both_strands) {
@@ -167,6 +171,10 @@ int main(int argc, char** argv) {
 	}
 	if (canonical && align) {
 		std::fprintf(stderr, "--align and --canonical cannot be combined: a strand-neutral point has no orientation to align\n");
+		return 1;
+	}
+	if (align_band && !align) {
+		std::fprintf(stderr, "--align-band needs --align: it chooses how the alignment column is computed\n");
 		return 1;
 	}
 	if (both_strands && top) {
@@ -304,9 +312,9 @@ int main(int argc, char** argv) {
 							second.push_back((uint32_t)da);
 							listed.push_back(&h);
 						}
-					const msc::Alignments al = msc::align_pairs(ctx, text, first, second);
+					const std::vector<double> identity = align_band ? msc::align_pairs_auto(ctx, text, first, second, first_band).identity : msc::align_pairs(ctx, text, first, second).identity;
 					note_kernel();
-					for (size_t i = 0; i < listed.size(); i++) listed[i]->aln = al.identity[i];
+					for (size_t i = 0; i < listed.size(); i++) listed[i]->aln = identity[i];
 				}
 				if (top) {          // the chunk's survivors behind those of the chunks before, cut again: ties stay with the earlier chunk
 					for (size_t qi = 0; qi < qp.size(); qi++) {
