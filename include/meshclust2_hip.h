@@ -495,6 +495,37 @@ int msc_align_pairs_auto(msc_ctx* ctx,
                          int match, int mismatch, int gap_open, int gap_continue, uint32_t first_band,
                          int32_t* score, int32_t* length, int32_t* matches, uint32_t* band_used);
 
+/* ------------------------------------------------------------------ the same three calls for LONG sequences
+ * msc_align_pairs_long, msc_align_pairs_long_banded and msc_align_pairs_long_auto take the arguments of their namesakes above and return
+ * what they return -- the same recurrence, boundaries, finite "minus infinity" and tie orders, the same band, out-of-band constant -2^30 and
+ * certificate, `first` is sequence 1, int32 score, length and matches -- for listed sequences of 1 .. 1 048 575 bytes (kAlignLongMaxLen,
+ * 2^20 - 1: every score the recurrence forms stays inside int32 and every real score above anything derived from -2^30, proven in 4.6g).
+ * Parameters are at most 100 in absolute value; the other checks are msc_align_pairs's, made before anything is queued; a refusal returns
+ * MSC_ERR_INVALID_ARG with every output untouched; n_pairs == 0 is MSC_OK. The three calls above keep their limit of 32 767 bytes.
+ *   A pair with both sequences within 32 767 bytes goes through the queueing of the calls above, so through k_align_pairs / k_align_band<>,
+ *   and comes out bit for bit as from them. Every other pair is cut into tiles of 256 columns by H rows (256; MSC_ALIGN_TILE_ROWS=n) that
+ *   k_align_tiles fills one wave a tile, launch after launch along the anti-diagonals of the tile grid, with states whose length and count have
+ *   a word each; MSC_ALIGN_LONG_ALL=1 sends every pair there. Both switches are read on every call. Results come back in the caller's order.
+ *   msc_align_pairs_long_auto: first_band (0: the library's default, 64), doubled per uncertified pair, one group of launches a round; a
+ *   pair that a band no longer helps goes to the full grid; band_used (may be NULL) as above, 0xffffffff for the full grid.
+ * msc_last_kernel_info names "k_align_tiles<wide states, H rows a tile>" whenever one of its launches ran in the call, otherwise what the
+ * namesake would name. */
+int msc_align_pairs_long(msc_ctx* ctx,
+                         const uint8_t* seqs, const uint64_t* offsets, uint64_t n_seqs,
+                         const uint32_t* first, const uint32_t* second, uint64_t n_pairs,
+                         int match, int mismatch, int gap_open, int gap_continue,
+                         int32_t* score, int32_t* length, int32_t* matches);
+int msc_align_pairs_long_banded(msc_ctx* ctx,
+                                const uint8_t* seqs, const uint64_t* offsets, uint64_t n_seqs,
+                                const uint32_t* first, const uint32_t* second, uint64_t n_pairs,
+                                int match, int mismatch, int gap_open, int gap_continue, uint32_t band,
+                                int32_t* score, int32_t* length, int32_t* matches, uint8_t* certified);
+int msc_align_pairs_long_auto(msc_ctx* ctx,
+                              const uint8_t* seqs, const uint64_t* offsets, uint64_t n_seqs,
+                              const uint32_t* first, const uint32_t* second, uint64_t n_pairs,
+                              int match, int mismatch, int gap_open, int gap_continue, uint32_t first_band,
+                              int32_t* score, int32_t* length, int32_t* matches, uint32_t* band_used);
+
 /* ------------------------------------------------------------------ a8/a9: Trainer operators */
 /* Trainer<T>::get_close (cluster/Trainer.cpp:23-71; caller cluster/ClusterFactory.cpp:566).
  * The window [istart, iend) is cand_slots[0..m). Candidates outside floor(len_q*cutoff) <= len <= floor(len_q/cutoff)

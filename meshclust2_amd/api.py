@@ -524,12 +524,9 @@ def score_pair_list(ctx, feat, a_set, a_slots, b_set, b_slots, order=ORDER_CAND_
     return dict(sum=s, csum=cs, close=close, singles=singles, combos=combos, raw=raw)
 
 
-def align_pairs(ctx, seqs, first, second, match=1, mismatch=-1, gap_open=2, gap_continue=1, out=None):
-    """The global-alignment identity of listed pairs (msc_align_pairs; the reference's GlobAlignE, what Feature::align computes with the
-    default parameters): pair p aligns seqs[first[p]] (the definition's sequence 1 -- ties are not symmetric) with seqs[second[p]]. seqs is a
-    list of bytes / str of 1 .. 32 767 bytes each; bytes are compared for equality and nothing else.
-    -> dict(score, length, matches: int32 [n_pairs]; identity: float64 [n_pairs] = matches / length), in the caller's order. `out` (a tuple
-    of three int32 arrays) receives the integers in place: a refused call leaves them as they were."""
+def _align_full(name, ctx, seqs, first, second, params, out):
+    """msc_align_pairs / msc_align_pairs_long: the arguments and the outputs of align_pairs"""
+    match, mismatch, gap_open, gap_continue = params
     raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs]
     a = np.ascontiguousarray(first, dtype=np.uint32)
     b = np.ascontiguousarray(second, dtype=np.uint32)
@@ -545,13 +542,28 @@ def align_pairs(ctx, seqs, first, second, match=1, mismatch=-1, gap_open=2, gap_
         if o.dtype != np.int32 or o.shape != a.shape or not o.flags.c_contiguous:
             raise ValueError("out: three contiguous int32 arrays of n_pairs")
     lib = ctx.lib if ctx is not None else _capi.load_library()
-    rc = lib.msc_align_pairs(ctx.h if ctx is not None else None, _ptr(text), _ptr(offsets), len(raw), _ptr(a), _ptr(b), a.size, int(match), int(mismatch),
-                             int(gap_open), int(gap_continue), _ptr(score), _ptr(length), _ptr(matches))
+    rc = getattr(lib, name)(ctx.h if ctx is not None else None, _ptr(text), _ptr(offsets), len(raw), _ptr(a), _ptr(b), a.size, int(match), int(mismatch),
+                            int(gap_open), int(gap_continue), _ptr(score), _ptr(length), _ptr(matches))
     if rc != 0:
-        raise MscError(rc, lib.msc_last_error(ctx.h).decode() if ctx is not None else "msc_align_pairs needs a Context (a gfx950 device): there is no CPU fallback")
+        raise MscError(rc, lib.msc_last_error(ctx.h).decode() if ctx is not None else name + " needs a Context (a gfx950 device): there is no CPU fallback")
     with np.errstate(divide="ignore", invalid="ignore"):
         identity = matches.astype(np.float64) / length.astype(np.float64)
     return dict(score=score, length=length, matches=matches, identity=identity)
+
+
+def align_pairs(ctx, seqs, first, second, match=1, mismatch=-1, gap_open=2, gap_continue=1, out=None):
+    """The global-alignment identity of listed pairs (msc_align_pairs; the reference's GlobAlignE, what Feature::align computes with the
+    default parameters): pair p aligns seqs[first[p]] (the definition's sequence 1 -- ties are not symmetric) with seqs[second[p]]. seqs is a
+    list of bytes / str of 1 .. 32 767 bytes each; bytes are compared for equality and nothing else.
+    -> dict(score, length, matches: int32 [n_pairs]; identity: float64 [n_pairs] = matches / length), in the caller's order. `out` (a tuple
+    of three int32 arrays) receives the integers in place: a refused call leaves them as they were."""
+    return _align_full("msc_align_pairs", ctx, seqs, first, second, (match, mismatch, gap_open, gap_continue), out)
+
+
+def align_pairs_long(ctx, seqs, first, second, match=1, mismatch=-1, gap_open=2, gap_continue=1, out=None):
+    """align_pairs for sequences of 1 .. 1 048 575 bytes each (msc_align_pairs_long): the same integers, the same dict; pairs
+    within align_pairs's limit run on its kernels, longer ones tile by tile."""
+    return _align_full("msc_align_pairs_long", ctx, seqs, first, second, (match, mismatch, gap_open, gap_continue), out)
 
 
 def _align_over_a_band(name, ctx, seqs, first, second, band, params, out, last):
@@ -596,6 +608,21 @@ def align_pairs_auto(ctx, seqs, first, second, match=1, mismatch=-1, gap_open=2,
     the library's default). -> align_pairs's dict and band_used: uint32 [n_pairs], the band that certified the pair, 0xffffffff where the
     full grid was filled. `out`: a tuple of three int32 arrays and a uint32 one, left as they were by a refused call."""
     r, bands = _align_over_a_band("msc_align_pairs_auto", ctx, seqs, first, second, first_band, (match, mismatch, gap_open, gap_continue), out, np.uint32)
+    r["band_used"] = bands
+    return r
+
+
+def align_pairs_long_banded(ctx, seqs, first, second, band, match=1, mismatch=-1, gap_open=2, gap_continue=1, out=None):
+    """align_pairs_banded for sequences of 1 .. 1 048 575 bytes each (msc_align_pairs_long_banded): the same dict."""
+    r, flags = _align_over_a_band("msc_align_pairs_long_banded", ctx, seqs, first, second, band, (match, mismatch, gap_open, gap_continue), out, np.uint8)
+    r["certified"] = flags
+    return r
+
+
+def align_pairs_long_auto(ctx, seqs, first, second, match=1, mismatch=-1, gap_open=2, gap_continue=1, first_band=0, out=None):
+    """align_pairs_auto for sequences of 1 .. 1 048 575 bytes each (msc_align_pairs_long_auto): the same dict; a long pair's
+    band is doubled up to its shorter length."""
+    r, bands = _align_over_a_band("msc_align_pairs_long_auto", ctx, seqs, first, second, first_band, (match, mismatch, gap_open, gap_continue), out, np.uint32)
     r["band_used"] = bands
     return r
 

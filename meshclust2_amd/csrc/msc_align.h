@@ -6,7 +6,8 @@
 // of the alignment), lower (a gap that consumes a byte of the first sequence; it moves along the row) and upper (a gap that consumes a byte of
 // the second; it moves down the column). A state is a score and, travelling with it, the length of the alignment so far and its identical
 // columns; the two counts share one word, length << 16 | count (a listed sequence has at most 32 767 bytes: length <= 65 534, count <= 32 767,
-// and the count never carries into the length).
+// and the count never carries into the length). msc_align_pairs_long keeps the two counts in a word each, MscAlignWide:
+// everything below is a template over that count word W, uint32_t for the packed pair, and is written once for both.
 //
 //   upper(i, j) = max(match(i, j-1) - (open + cont), upper(i, j-1) - cont)            a tie goes to "opened from match"
 //   lower(i, j) = max(match(i-1, j) - (open + cont), lower(i-1, j) - cont)            likewise
@@ -32,14 +33,22 @@ struct MscAlignParams {
 	uint32_t w_eq, w_ne;          // what a diagonal step adds to length << 16 | count (the reference counts a column whose SCORE is `match`)
 };
 
-struct MscAlignState {
-	int32_t s;          // score
-	uint32_t w;         // length << 16 | identical columns
+struct MscAlignWide {
+	uint32_t len, cnt;  // length | identical columns, a word each: sequences of up to kAlignLongMaxLen bytes (msc_align_long.h)
 };
 
-struct MscAlignTriple {
-	MscAlignState m, l, u;
+template <class W>
+struct MscAlignStateT {
+	int32_t s;          // score
+	W w;                // length << 16 | identical columns (uint32_t), or the two apart (MscAlignWide)
 };
+using MscAlignState = MscAlignStateT<uint32_t>;
+
+template <class W>
+struct MscAlignTripleT {
+	MscAlignStateT<W> m, l, u;
+};
+using MscAlignTriple = MscAlignTripleT<uint32_t>;
 
 MSC_HD MscAlignParams msc_align_params(int match, int mismatch, int gap_open, int gap_continue) {
 	MscAlignParams P;
@@ -49,6 +58,24 @@ MSC_HD MscAlignParams msc_align_params(int match, int mismatch, int gap_open, in
 	return P;
 }
 
+// What the recurrence does to a count word: a boundary state's word, one more column of a gap, one more diagonal column, and the two counts
+// as the caller gets them
+template <class W> struct MscAlignCount;
+template <> struct MscAlignCount<uint32_t> {
+	static MSC_HD uint32_t of_length(uint32_t len) { return len << 16; }
+	static MSC_HD uint32_t gap(uint32_t w) { return w + (1u << 16); }
+	static MSC_HD uint32_t diag(uint32_t w, bool eq, const MscAlignParams& P) { return w + (eq ? P.w_eq : P.w_ne); }
+	static MSC_HD uint32_t length(uint32_t w) { return w >> 16; }
+	static MSC_HD uint32_t matches(uint32_t w) { return w & 0xffffu; }
+};
+template <> struct MscAlignCount<MscAlignWide> {
+	static MSC_HD MscAlignWide of_length(uint32_t len) { return MscAlignWide{len, 0}; }
+	static MSC_HD MscAlignWide gap(MscAlignWide w) { return MscAlignWide{w.len + 1, w.cnt}; }
+	static MSC_HD MscAlignWide diag(MscAlignWide w, bool eq, const MscAlignParams& P) { return MscAlignWide{w.len + 1, w.cnt + (eq ? 1u : P.w_ne & 1u)}; }
+	static MSC_HD uint32_t length(MscAlignWide w) { return w.len; }
+	static MSC_HD uint32_t matches(MscAlignWide w) { return w.cnt; }
+};
+
 MSC_HD int32_t msc_align_neg_inf(uint32_t la, uint32_t lb, const MscAlignParams& P) {
 	const int32_t shorter = (int32_t)(la < lb ? la : lb), diff = (int32_t)(la < lb ? lb - la : la - lb);
 	int32_t v = 0;
@@ -57,9 +84,10 @@ MSC_HD int32_t msc_align_neg_inf(uint32_t la, uint32_t lb, const MscAlignParams&
 }
 
 // column i of row 0 (i = 0: the corner, as row 1 sees it on its diagonal)
-MSC_HD MscAlignTriple msc_align_row0(uint32_t i, int32_t neg_inf, const MscAlignParams& P) {
-	MscAlignTriple t;
-	const uint32_t w = i << 16;
+template <class W = uint32_t>
+MSC_HD MscAlignTripleT<W> msc_align_row0(uint32_t i, int32_t neg_inf, const MscAlignParams& P) {
+	MscAlignTripleT<W> t;
+	const W w = MscAlignCount<W>::of_length(i);
 	t.m.s = i == 0 ? 0 : neg_inf;
 	t.u.s = i == 0 ? -P.open : neg_inf;
 	t.l.s = i == 0 ? neg_inf : -P.open - (int32_t)i * P.cont;
@@ -68,41 +96,46 @@ MSC_HD MscAlignTriple msc_align_row0(uint32_t i, int32_t neg_inf, const MscAlign
 }
 
 // row r >= 1 of column 0: what column 1 reads to its left (match, lower) and, one row later, on its diagonal (all three)
-MSC_HD MscAlignTriple msc_align_col0(uint32_t r, int32_t neg_inf, const MscAlignParams& P) {
-	MscAlignTriple t;
+template <class W = uint32_t>
+MSC_HD MscAlignTripleT<W> msc_align_col0(uint32_t r, int32_t neg_inf, const MscAlignParams& P) {
+	MscAlignTripleT<W> t;
 	t.m.s = t.l.s = neg_inf;
 	t.u.s = -P.open - (int32_t)r * P.cont;
-	t.m.w = t.l.w = t.u.w = r << 16;
+	t.m.w = t.l.w = t.u.w = MscAlignCount<W>::of_length(r);
 	return t;
 }
 
-MSC_HD MscAlignState msc_align_gap(const MscAlignState& from_match, const MscAlignState& from_gap, const MscAlignParams& P) {
+template <class W>
+MSC_HD MscAlignStateT<W> msc_align_gap(const MscAlignStateT<W>& from_match, const MscAlignStateT<W>& from_gap, const MscAlignParams& P) {
 	const int32_t a = from_match.s - P.open_cont, b = from_gap.s - P.cont;
-	MscAlignState r;
+	MscAlignStateT<W> r;
 	r.s = a >= b ? a : b;
-	r.w = (a >= b ? from_match.w : from_gap.w) + (1u << 16);
+	r.w = MscAlignCount<W>::gap(a >= b ? from_match.w : from_gap.w);
 	return r;
 }
 
-MSC_HD MscAlignState msc_align_diag(const MscAlignTriple& d, bool eq, const MscAlignParams& P) {
+template <class W>
+MSC_HD MscAlignStateT<W> msc_align_diag(const MscAlignTripleT<W>& d, bool eq, const MscAlignParams& P) {
 	const int32_t ml = d.m.s >= d.l.s ? d.m.s : d.l.s;
-	const uint32_t ml_w = d.m.s >= d.l.s ? d.m.w : d.l.w;
-	MscAlignState r;
+	const W ml_w = d.m.s >= d.l.s ? d.m.w : d.l.w;
+	MscAlignStateT<W> r;
 	r.s = (ml >= d.u.s ? ml : d.u.s) + (eq ? P.match : P.mismatch);
-	r.w = (ml >= d.u.s ? ml_w : d.u.w) + (eq ? P.w_eq : P.w_ne);
+	r.w = MscAlignCount<W>::diag(ml >= d.u.s ? ml_w : d.u.w, eq, P);
 	return r;
 }
 
 // col: the cell above (row j - 1) on entry, this cell (row j) on return. diag: column i - 1 at row j - 1. left: column i - 1 at row j (its
 // upper state is not read)
-MSC_HD void msc_align_cell(MscAlignTriple& col, const MscAlignTriple& diag, const MscAlignTriple& left, bool eq, const MscAlignParams& P) {
+template <class W>
+MSC_HD void msc_align_cell(MscAlignTripleT<W>& col, const MscAlignTripleT<W>& diag, const MscAlignTripleT<W>& left, bool eq, const MscAlignParams& P) {
 	col.u = msc_align_gap(col.m, col.u, P);
 	col.m = msc_align_diag(diag, eq, P);
 	col.l = msc_align_gap(left.m, left.l, P);
 }
 
-MSC_HD MscAlignState msc_align_final(const MscAlignTriple& t) {
-	const MscAlignState ml = t.m.s >= t.l.s ? t.m : t.l;
+template <class W>
+MSC_HD MscAlignStateT<W> msc_align_final(const MscAlignTripleT<W>& t) {
+	const MscAlignStateT<W> ml = t.m.s >= t.l.s ? t.m : t.l;
 	return ml.s >= t.u.s ? ml : t.u;
 }
 

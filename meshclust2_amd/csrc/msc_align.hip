@@ -85,7 +85,7 @@ __global__ void __launch_bounds__(kAlignLanes) k_align_pairs(const uint8_t* __re
 
 // The checks every alignment call makes on the host before anything is queued, and the pair records in the caller's order
 int msc_align_list(msc_ctx* ctx, const char* who, const uint64_t* offsets, uint64_t n_seqs, const uint32_t* first, const uint32_t* second, uint64_t n_pairs, int match, int mismatch,
-                   int gap_open, int gap_continue, std::vector<AlignPair>& pairs, uint64_t& text_bytes) {
+                   int gap_open, int gap_continue, std::vector<AlignPair>& pairs, uint64_t& text_bytes, uint32_t max_len) {
 	if (n_pairs > 0xfffffff0ull) return fail(ctx, MSC_ERR_INVALID_ARG, "%s: too many pairs in one call", who);
 	for (int v : {match, mismatch, gap_open, gap_continue})
 		if (v > kAlignMaxParam || v < -kAlignMaxParam) return fail(ctx, MSC_ERR_INVALID_ARG, "%s: a scoring parameter of %d (at most %d in absolute value)", who, v, kAlignMaxParam);
@@ -94,8 +94,8 @@ int msc_align_list(msc_ctx* ctx, const char* who, const uint64_t* offsets, uint6
 		AlignPair& a = pairs[p];
 		for (uint32_t s : {first[p], second[p]}) {
 			if (s >= n_seqs) return fail(ctx, MSC_ERR_INVALID_ARG, "%s: pair %llu names sequence %u of %llu", who, (unsigned long long)p, s, (unsigned long long)n_seqs);
-			if (offsets[s + 1] <= offsets[s] || offsets[s + 1] - offsets[s] > kAlignMaxLen)
-				return fail(ctx, MSC_ERR_INVALID_ARG, "%s: sequence %u has %lld bytes (1 .. %u)", who, s, (long long)(offsets[s + 1] - offsets[s]), kAlignMaxLen);
+			if (offsets[s + 1] <= offsets[s] || offsets[s + 1] - offsets[s] > max_len)
+				return fail(ctx, MSC_ERR_INVALID_ARG, "%s: sequence %u has %lld bytes (1 .. %u)", who, s, (long long)(offsets[s + 1] - offsets[s]), max_len);
 		}
 		a.off1 = offsets[first[p]]; a.la = (uint32_t)(offsets[first[p] + 1] - a.off1);
 		a.off2 = offsets[second[p]]; a.lb = (uint32_t)(offsets[second[p] + 1] - a.off2);

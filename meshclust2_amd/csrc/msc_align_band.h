@@ -5,7 +5,8 @@
 //
 // For a half-width w the diagonals lo .. hi of the grid are IN BAND, lo = min(0, la - lb) - w, hi = max(0, la - lb) + w (cell (i, j) lies on
 // diagonal i - j). In-band cells hold what 4.6e gives them from their three neighbours; every state of every out-of-band cell, boundary cells
-// included, is the constant (kAlignDeep, 0).
+// included, is the constant (kAlignDeep, 0). As msc_align.h, the lane's step and the boundaries are templates over the count word W, so that
+// msc_align_pairs_long_banded runs the same lines over wide states.
 #pragma once
 #include "msc_align.h"
 
@@ -39,6 +40,16 @@ MSC_HD MscAlignTriple msc_align_deep() {
 	t.m.w = t.l.w = t.u.w = 0;
 	return t;
 }
+// (the same constant over another count word. As an instantiation of this template the packed one costs k_align_band<4 columns> six VGPRs and a
+// wave of occupancy, so the packed one stays a plain function; the overload below picks it)
+template <class W>
+MSC_HD MscAlignTripleT<W> msc_align_deep(const W*) {
+	MscAlignTripleT<W> t;
+	t.m.s = t.l.s = t.u.s = kAlignDeep;
+	t.m.w = t.l.w = t.u.w = MscAlignCount<W>::of_length(0);
+	return t;
+}
+MSC_HD MscAlignTriple msc_align_deep(const uint32_t*) { return msc_align_deep(); }
 
 // ---------------------------------------------------------------------------------------- the certificate
 // true: the banded score s_w proves that the banded triple is the full one. Never true where they differ; it may be
@@ -99,37 +110,46 @@ MSC_HD uint32_t msc_align_band_carry_at(uint32_t la, uint32_t lb, uint32_t strip
 MSC_HD uint32_t msc_align_band_carry_rows(uint32_t la, uint32_t lb, uint32_t w, uint32_t stripe) { return msc_align_band_stripes(la, stripe) > 1 ? msc_align_band_ring(la, lb, w, stripe) : 0; }
 
 // ---------------------------------------------------------------------------------------- a lane of the array
-template <int C>
-struct MscAlignBandLane {
-	MscAlignTriple col[C];          // its C columns at the row it finished last
-	MscAlignTriple prev;            // the column to its left at that row
+template <int C, class W>
+struct MscAlignBandLaneT {
+	MscAlignTripleT<W> col[C];      // its C columns at the row it finished last
+	MscAlignTripleT<W> prev;        // the column to its left at that row
 	uint32_t bytes;                 // its columns' bytes of the first sequence, column c in bits [8c, 8c + 8)
 };
+template <int C>
+using MscAlignBandLane = MscAlignBandLaneT<C, uint32_t>;
 
 // cell (i, r0 - 1), the row above a stripe's window: a boundary cell of row 0 where the window starts at row 1, out of band otherwise (the
 // one exception, the column to the left of the stripe, comes from the carry: `from_carry`)
 MSC_HD MscAlignTriple msc_align_band_above(const MscAlignBand& b, uint32_t i, uint32_t r0, int32_t neg_inf, const MscAlignParams& P) {
 	return r0 == 1 && (int32_t)i <= b.hi ? msc_align_row0(i, neg_inf, P) : msc_align_deep();
 }
+template <class W>
+MSC_HD MscAlignTripleT<W> msc_align_band_above(const MscAlignBand& b, uint32_t i, uint32_t r0, int32_t neg_inf, const MscAlignParams& P, const W* word) {
+	return r0 == 1 && (int32_t)i <= b.hi ? msc_align_row0<W>(i, neg_inf, P) : msc_align_deep(word);
+}
+MSC_HD MscAlignTriple msc_align_band_above(const MscAlignBand& b, uint32_t i, uint32_t r0, int32_t neg_inf, const MscAlignParams& P, const uint32_t*) {
+	return msc_align_band_above(b, i, r0, neg_inf, P);
+}
 
 // first_col: the 1-based index of the lane's first column; from_carry: cell (first_col - 1, r0 - 1) for the stripe's first lane where r0 > 1
-template <int C>
-MSC_HD void msc_align_band_lane_init(MscAlignBandLane<C>& L, const MscAlignBand& b, uint32_t first_col, uint32_t bytes, uint32_t r0, bool first_lane, const MscAlignTriple& from_carry,
+template <int C, class W>
+MSC_HD void msc_align_band_lane_init(MscAlignBandLaneT<C, W>& L, const MscAlignBand& b, uint32_t first_col, uint32_t bytes, uint32_t r0, bool first_lane, const MscAlignTripleT<W>& from_carry,
                                      int32_t neg_inf, const MscAlignParams& P) {
-	L.prev = first_lane && r0 > 1 ? from_carry : msc_align_band_above(b, first_col - 1, r0, neg_inf, P);
-	for (int c = 0; c < C; c++) L.col[c] = msc_align_band_above(b, first_col + c, r0, neg_inf, P);
+	L.prev = first_lane && r0 > 1 ? from_carry : msc_align_band_above(b, first_col - 1, r0, neg_inf, P, (const W*)nullptr);
+	for (int c = 0; c < C; c++) L.col[c] = msc_align_band_above(b, first_col + c, r0, neg_inf, P, (const W*)nullptr);
 	L.bytes = bytes;
 }
 
 // One row: recv = the column to the lane's left at THIS row, byte = the row's byte of the second sequence
-template <int C>
-MSC_HD void msc_align_band_lane_step(MscAlignBandLane<C>& L, const MscAlignBand& b, uint32_t first_col, uint32_t row, const MscAlignTriple& recv, uint32_t byte, const MscAlignParams& P) {
-	MscAlignTriple diag = L.prev, left = recv;
+template <int C, class W>
+MSC_HD void msc_align_band_lane_step(MscAlignBandLaneT<C, W>& L, const MscAlignBand& b, uint32_t first_col, uint32_t row, const MscAlignTripleT<W>& recv, uint32_t byte, const MscAlignParams& P) {
+	MscAlignTripleT<W> diag = L.prev, left = recv;
 	const int32_t on = (int32_t)first_col - (int32_t)row;          // the diagonal of the lane's first column
 	for (int c = 0; c < C; c++) {
-		const MscAlignTriple above = L.col[c];
+		const MscAlignTripleT<W> above = L.col[c];
 		msc_align_cell(L.col[c], diag, left, ((L.bytes >> (8 * c)) & 0xffu) == byte, P);
-		if (on + c < b.lo || on + c > b.hi) L.col[c] = msc_align_deep();
+		if (on + c < b.lo || on + c > b.hi) L.col[c] = msc_align_deep((const W*)nullptr);
 		diag = above;
 		left = L.col[c];
 	}
@@ -138,7 +158,8 @@ MSC_HD void msc_align_band_lane_step(MscAlignBandLane<C>& L, const MscAlignBand&
 
 // What the stripe's first lane receives for row `row` (>= 1) of the column to the stripe's left (column c0 - 1): boundary column 0 for the
 // first stripe, the carry otherwise (`stored`, read only where the row is in band), out of band past read_hi
-MSC_HD MscAlignTriple msc_align_band_left(const MscAlignWindow& win, bool first_stripe, uint32_t row, const MscAlignTriple& stored, int32_t neg_inf, const MscAlignParams& P) {
-	if ((int32_t)row > win.read_hi) return msc_align_deep();
-	return first_stripe ? msc_align_col0(row, neg_inf, P) : stored;
+template <class W>
+MSC_HD MscAlignTripleT<W> msc_align_band_left(const MscAlignWindow& win, bool first_stripe, uint32_t row, const MscAlignTripleT<W>& stored, int32_t neg_inf, const MscAlignParams& P) {
+	if ((int32_t)row > win.read_hi) return msc_align_deep((const W*)nullptr);
+	return first_stripe ? msc_align_col0<W>(row, neg_inf, P) : stored;
 }

@@ -109,9 +109,11 @@ void launch_band(bool lds_carry, unsigned n, uint32_t lds, hipStream_t stream, c
 	else k_align_band<C, false><<<dim3(n), dim3(kAlignLanes), lds, stream>>>(d_text, d_pairs, P, scratch, d_out, d_out + n_out, d_out + 2 * n_out, d_out + 3 * n_out);
 }
 
+}  // namespace
+
 // Queues k_align_band for `pairs` (reordered here), each at its own half-width: pair p's integers and its flag go to d_out[p.out],
 // d_out[n_out + p.out], d_out[2 * n_out + p.out] and d_out[3 * n_out + p.out]
-int queue_banded(msc_ctx* ctx, std::vector<AlignPair>& pairs, const uint8_t* d_text, const MscAlignParams& P, int32_t* d_out, uint64_t n_out) {
+int msc_align_queue_banded(msc_ctx* ctx, std::vector<AlignPair>& pairs, const uint8_t* d_text, const MscAlignParams& P, int32_t* d_out, uint64_t n_out) {
 	const uint64_t n_pairs = pairs.size();
 	// groups: columns per lane, then classes of LDS need (the last class keeps its ring in global memory), most band cells first inside each
 	auto lds_need = [](const AlignPair& a) { return (uint64_t)lds_base(a) + ring_rows(a) * sizeof(MscAlignTriple); };
@@ -172,8 +174,6 @@ int queue_banded(msc_ctx* ctx, std::vector<AlignPair>& pairs, const uint8_t* d_t
 	return MSC_OK;
 }
 
-}  // namespace
-
 extern "C" int msc_align_pairs_banded(msc_ctx* ctx, const uint8_t* seqs, const uint64_t* offsets, uint64_t n_seqs, const uint32_t* first, const uint32_t* second, uint64_t n_pairs,
                                       int match, int mismatch, int gap_open, int gap_continue, uint32_t band, int32_t* score, int32_t* length, int32_t* matches, uint8_t* certified) {
 	if (!ctx) return MSC_ERR_INVALID_ARG;
@@ -188,7 +188,7 @@ extern "C" int msc_align_pairs_banded(msc_ctx* ctx, const uint8_t* seqs, const u
 	if (int r = ensure(ctx, ctx->align_out, 4 * n_pairs * sizeof(int32_t))) return r;
 	HIP_TRY(ctx, hipMemcpyAsync(ctx->align_text.p, seqs, text_bytes, hipMemcpyHostToDevice, ctx->stream));
 	int32_t* d_out = (int32_t*)ctx->align_out.p;
-	if (int r = queue_banded(ctx, pairs, (const uint8_t*)ctx->align_text.p, msc_align_params(match, mismatch, gap_open, gap_continue), d_out, n_pairs)) return r;
+	if (int r = msc_align_queue_banded(ctx, pairs, (const uint8_t*)ctx->align_text.p, msc_align_params(match, mismatch, gap_open, gap_continue), d_out, n_pairs)) return r;
 	std::vector<int32_t> out(4 * n_pairs);          // (the caller's arrays stay untouched unless every launch went through)
 	HIP_TRY(ctx, hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -226,7 +226,7 @@ extern "C" int msc_align_pairs_auto(msc_ctx* ctx, const uint8_t* seqs, const uin
 	bool banded = false;
 	char name[sizeof(ctx->last_kernel_buf)];
 	while (!open.empty()) {
-		if (int r = queue_banded(ctx, open, d_text, P, d_out, n_pairs)) return r;
+		if (int r = msc_align_queue_banded(ctx, open, d_text, P, d_out, n_pairs)) return r;
 		HIP_TRY(ctx, hipMemcpyAsync(flags.data(), d_out + 3 * n_pairs, n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 		banded = true;

@@ -1,5 +1,6 @@
 // msc_align_host.h -- what the alignment entry points (msc_align.hip: msc_align_pairs; msc_align_band.hip: msc_align_pairs_banded,
-// msc_align_pairs_auto) share on the host: the pair record, the checks of a call and the queueing of the full-grid kernel.
+// msc_align_pairs_auto; msc_align_long.hip: their _long namesakes) share on the host: the pair record, the checks of a call and the queueing
+// of the full-grid and of the banded kernel.
 #pragma once
 #include <vector>
 
@@ -11,7 +12,7 @@ struct AlignPair {
 	uint32_t la, lb;
 	uint32_t out;                 // the pair's index in the caller's list
 	uint32_t band;                // its half-width (k_align_band; k_align_pairs does not read it)
-	uint64_t carry;               // offset of its carry range in the scratch buffer, in rows (global-carry launches)
+	uint64_t carry;               // offset of its carry range in the scratch buffer, in rows (global-carry launches; k_align_tiles: of its borders)
 };
 
 constexpr uint32_t kAlignLdsMax = 160 * 1024;                                       // of a workgroup
@@ -20,5 +21,6 @@ constexpr int kAlignClasses = 5;
 constexpr uint64_t kAlignScratchRows = (512ull << 20) / sizeof(MscAlignTriple);      // carry rows one global-carry launch may use
 
 int msc_align_list(msc_ctx* ctx, const char* who, const uint64_t* offsets, uint64_t n_seqs, const uint32_t* first, const uint32_t* second, uint64_t n_pairs, int match, int mismatch,
-                   int gap_open, int gap_continue, std::vector<AlignPair>& pairs, uint64_t& text_bytes);
+                   int gap_open, int gap_continue, std::vector<AlignPair>& pairs, uint64_t& text_bytes, uint32_t max_len = kAlignMaxLen);
 int msc_align_queue_full(msc_ctx* ctx, std::vector<AlignPair>& pairs, const uint8_t* d_text, const MscAlignParams& P, int32_t* d_out, uint64_t n_out);
+int msc_align_queue_banded(msc_ctx* ctx, std::vector<AlignPair>& pairs, const uint8_t* d_text, const MscAlignParams& P, int32_t* d_out, uint64_t n_out);

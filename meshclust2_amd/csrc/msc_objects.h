@@ -132,6 +132,7 @@ struct msc_ctx {
 	// msc_align_pairs (msc_align.hip): the sequences of a call, its sorted pair records, the three result arrays, and the carry columns of the pairs
 	// too long for LDS
 	DevBuf align_text, align_pairs, align_out, align_carry, align_band_pairs;          // (align_band_pairs: the records of msc_align_band.hip's rounds)
+	DevBuf align_long_pairs, align_long_tiles, align_long_borders;          // msc_align_long.hip: a round's pair records, its tile table, the pairs' borders
 	// MSC_PROFILE_CALLS: host wall clock of the 1 x M scoring calls, split into preparing + queueing the slot list, issuing the
 	// launches, and waiting for the stream (printed by msc_destroy)
 	double prof_prep = 0, prof_issue = 0, prof_wait = 0;

@@ -336,8 +336,9 @@ struct Alignments {
 	std::vector<int32_t> score, length, matches;
 	std::vector<double> identity;
 };
-inline Alignments align_pairs(const Context& ctx, const std::vector<std::string>& seqs, const std::vector<uint32_t>& first, const std::vector<uint32_t>& second, int match = 1,
-                              int mismatch = -1, int gap_open = 2, int gap_continue = 1) {
+namespace detail {
+inline Alignments align_full(const Context& ctx, bool long_entry, const std::vector<std::string>& seqs, const std::vector<uint32_t>& first, const std::vector<uint32_t>& second, int match,
+                             int mismatch, int gap_open, int gap_continue) {
 	if (first.size() != second.size()) throw Error(MSC_ERR_INVALID_ARG, "align_pairs: first and second are one pair list");
 	std::string text;
 	std::vector<uint64_t> offsets(1, 0);
@@ -346,10 +347,26 @@ inline Alignments align_pairs(const Context& ctx, const std::vector<std::string>
 	Alignments a;
 	const size_t n = first.size();
 	a.score.resize(n); a.length.resize(n); a.matches.resize(n); a.identity.resize(n);
-	ctx.check(msc_align_pairs(ctx.get(), reinterpret_cast<const uint8_t*>(text.data()), offsets.data(), seqs.size(), first.data(), second.data(), n, match, mismatch, gap_open,
-	                          gap_continue, a.score.data(), a.length.data(), a.matches.data()));
+	const uint8_t* bytes = reinterpret_cast<const uint8_t*>(text.data());
+	if (long_entry)
+		ctx.check(msc_align_pairs_long(ctx.get(), bytes, offsets.data(), seqs.size(), first.data(), second.data(), n, match, mismatch, gap_open, gap_continue, a.score.data(), a.length.data(),
+		                               a.matches.data()));
+	else
+		ctx.check(msc_align_pairs(ctx.get(), bytes, offsets.data(), seqs.size(), first.data(), second.data(), n, match, mismatch, gap_open, gap_continue, a.score.data(), a.length.data(),
+		                          a.matches.data()));
 	for (size_t i = 0; i < n; i++) a.identity[i] = (double)a.matches[i] / a.length[i];
 	return a;
+}
+}  // namespace detail
+inline Alignments align_pairs(const Context& ctx, const std::vector<std::string>& seqs, const std::vector<uint32_t>& first, const std::vector<uint32_t>& second, int match = 1,
+                              int mismatch = -1, int gap_open = 2, int gap_continue = 1) {
+	return detail::align_full(ctx, false, seqs, first, second, match, mismatch, gap_open, gap_continue);
+}
+// align_pairs for sequences of 1 .. 1 048 575 bytes (msc_align_pairs_long): the same integers; pairs within align_pairs's limit
+// run on its kernels
+inline Alignments align_pairs_long(const Context& ctx, const std::vector<std::string>& seqs, const std::vector<uint32_t>& first, const std::vector<uint32_t>& second, int match = 1,
+                                   int mismatch = -1, int gap_open = 2, int gap_continue = 1) {
+	return detail::align_full(ctx, true, seqs, first, second, match, mismatch, gap_open, gap_continue);
 }
 
 // The same integers over a band of diagonals (msc_align_pairs_banded, msc_align_pairs_auto). align_pairs_banded fills the
@@ -365,7 +382,7 @@ struct BandedAlignments {
 };
 namespace detail {
 inline BandedAlignments align_over_a_band(const Context& ctx, bool automatic, const std::vector<std::string>& seqs, const std::vector<uint32_t>& first, const std::vector<uint32_t>& second,
-                                          uint32_t band, int match, int mismatch, int gap_open, int gap_continue) {
+                                          uint32_t band, int match, int mismatch, int gap_open, int gap_continue, bool long_entry = false) {
 	if (first.size() != second.size()) throw Error(MSC_ERR_INVALID_ARG, "align_pairs: first and second are one pair list");
 	std::string text;
 	std::vector<uint64_t> offsets(1, 0);
@@ -377,13 +394,21 @@ inline BandedAlignments align_over_a_band(const Context& ctx, bool automatic, co
 	const uint8_t* bytes = reinterpret_cast<const uint8_t*>(text.data());
 	if (automatic) {
 		a.band_used.resize(n + 1);          // (never a null pointer: NULL means "not wanted")
-		ctx.check(msc_align_pairs_auto(ctx.get(), bytes, offsets.data(), seqs.size(), first.data(), second.data(), n, match, mismatch, gap_open, gap_continue, band, a.score.data(),
-		                               a.length.data(), a.matches.data(), a.band_used.data()));
+		if (long_entry)
+			ctx.check(msc_align_pairs_long_auto(ctx.get(), bytes, offsets.data(), seqs.size(), first.data(), second.data(), n, match, mismatch, gap_open, gap_continue, band, a.score.data(),
+			                                    a.length.data(), a.matches.data(), a.band_used.data()));
+		else
+			ctx.check(msc_align_pairs_auto(ctx.get(), bytes, offsets.data(), seqs.size(), first.data(), second.data(), n, match, mismatch, gap_open, gap_continue, band, a.score.data(),
+			                               a.length.data(), a.matches.data(), a.band_used.data()));
 		a.band_used.resize(n);
 	} else {
 		a.certified.resize(n);
-		ctx.check(msc_align_pairs_banded(ctx.get(), bytes, offsets.data(), seqs.size(), first.data(), second.data(), n, match, mismatch, gap_open, gap_continue, band, a.score.data(),
-		                                 a.length.data(), a.matches.data(), a.certified.data()));
+		if (long_entry)
+			ctx.check(msc_align_pairs_long_banded(ctx.get(), bytes, offsets.data(), seqs.size(), first.data(), second.data(), n, match, mismatch, gap_open, gap_continue, band, a.score.data(),
+			                                      a.length.data(), a.matches.data(), a.certified.data()));
+		else
+			ctx.check(msc_align_pairs_banded(ctx.get(), bytes, offsets.data(), seqs.size(), first.data(), second.data(), n, match, mismatch, gap_open, gap_continue, band, a.score.data(),
+			                                 a.length.data(), a.matches.data(), a.certified.data()));
 	}
 	for (size_t i = 0; i < n; i++) a.identity[i] = (double)a.matches[i] / a.length[i];
 	return a;
@@ -396,6 +421,15 @@ inline BandedAlignments align_pairs_banded(const Context& ctx, const std::vector
 inline BandedAlignments align_pairs_auto(const Context& ctx, const std::vector<std::string>& seqs, const std::vector<uint32_t>& first, const std::vector<uint32_t>& second,
                                          uint32_t first_band = 0, int match = 1, int mismatch = -1, int gap_open = 2, int gap_continue = 1) {
 	return detail::align_over_a_band(ctx, true, seqs, first, second, first_band, match, mismatch, gap_open, gap_continue);
+}
+// both for sequences of 1 .. 1 048 575 bytes (msc_align_pairs_long_banded, msc_align_pairs_long_auto)
+inline BandedAlignments align_pairs_long_banded(const Context& ctx, const std::vector<std::string>& seqs, const std::vector<uint32_t>& first, const std::vector<uint32_t>& second,
+                                                uint32_t band, int match = 1, int mismatch = -1, int gap_open = 2, int gap_continue = 1) {
+	return detail::align_over_a_band(ctx, false, seqs, first, second, band, match, mismatch, gap_open, gap_continue, true);
+}
+inline BandedAlignments align_pairs_long_auto(const Context& ctx, const std::vector<std::string>& seqs, const std::vector<uint32_t>& first, const std::vector<uint32_t>& second,
+                                              uint32_t first_band = 0, int match = 1, int mismatch = -1, int gap_open = 2, int gap_continue = 1) {
+	return detail::align_over_a_band(ctx, true, seqs, first, second, first_band, match, mismatch, gap_open, gap_continue, true);
 }
 
 // the other strand of a sequence as a string: reversed, A <-> T and C <-> G, every other byte as it is

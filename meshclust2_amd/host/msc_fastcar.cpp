@@ -9,13 +9,13 @@
 //   msc_fastcar <db.fa> --query <q.fa> --recover weights.txt [--output output] [--chunk 10000] [--no-format] [--device 0] [--div-cells] [--top N] [--both-strands] [--canonical] [--align] [--align-band W]
 //
 // --align: one more column after the predicted identity (and after the strand column where there is one): the identity of the global alignment of
-// the reported pair, matches / length of msc_align_pairs with the default parameters (1, -1, 2, 1), the query as the first sequence -- the quantity
+// the reported pair, matches / length of msc_align_pairs_long with the default parameters (1, -1, 2, 1), the query as the first sequence -- the quantity
 // the column before it predicts -- printed the same way, 100 * identity. The hits of one (query chunk, database chunk) step are aligned in one
-// call, over the strings as read from the files (1 .. 32 767 bytes each); with --both-strands a `-` hit aligns the query's reverse complement
+// call, over the strings as read from the files (1 .. 1 048 575 bytes each; pairs within 32 767 bytes run on msc_align_pairs's kernels); with --both-strands a `-` hit aligns the query's reverse complement
 // (the string reversed, A <-> T, C <-> G, any other byte kept). Not together with --canonical: a strand-neutral point has no orientation to
 // align. Without the flag the output is what it was.
-// --align-band W (with --align): the same column through msc_align_pairs_auto, which fills a band of diagonals per pair (first half-width W, 0 = the
-// library's default, doubled until the pair is certified) and returns msc_align_pairs's integers: the output is byte for byte that of --align.
+// --align-band W (with --align): the same column through msc_align_pairs_long_auto, which fills a band of diagonals per pair (first half-width W, 0 = the
+// library's default, doubled until the pair is certified) and returns msc_align_pairs_long's integers: the output is byte for byte that of --align.
 //
 // --canonical: database and query histograms are made strand-neutral right after they are built (msc_hist_canonical_batch, in place: each k-mer
 // counted together with its reverse complement), so a query and its reverse complement give the same lines; everything else is unchanged. The
@@ -156,8 +156,8 @@ int main(int argc, char** argv) {
 		else if (a == "--top") top = (size_t)std::max(0l, std::atol(need("--top").c_str()));          // each query's N best hits (0: all)
 		else if (a == "--both-strands") both_strands = true;          // msc_search_pairs_strands: the queries and their reverse complements
 		else if (a == "--canonical") canonical = true;          // msc_hist_canonical_batch on every chunk: strand-neutral histograms
-		else if (a == "--align") align = true;          // msc_align_pairs on every reported pair: a column with the alignment identity
-		else if (a == "--align-band") { align_band = true; first_band = (uint32_t)std::max(0l, std::atol(need("--align-band").c_str())); }          // --align through msc_align_pairs_auto
+		else if (a == "--align") align = true;          // msc_align_pairs_long on every reported pair: a column with the alignment identity
+		else if (a == "--align-band") { align_band = true; first_band = (uint32_t)std::max(0l, std::atol(need("--align-band").c_str())); }          // --align through msc_align_pairs_long_auto
 		else if (a == "--device") device = std::atoi(need("--device").c_str());
 		else files.push_back(a);
 	}
@@ -312,7 +312,7 @@ int main(int argc, char** argv) {
 							second.push_back((uint32_t)da);
 							listed.push_back(&h);
 						}
-					const std::vector<double> identity = align_band ? msc::align_pairs_auto(ctx, text, first, second, first_band).identity : msc::align_pairs(ctx, text, first, second).identity;
+					const std::vector<double> identity = align_band ? msc::align_pairs_long_auto(ctx, text, first, second, first_band).identity : msc::align_pairs_long(ctx, text, first, second).identity;
 					note_kernel();
 					for (size_t i = 0; i < listed.size(); i++) listed[i]->aln = identity[i];
 				}
