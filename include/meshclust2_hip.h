@@ -526,6 +526,40 @@ int msc_align_pairs_long_auto(msc_ctx* ctx,
                               int match, int mismatch, int gap_open, int gap_continue, uint32_t first_band,
                               int32_t* score, int32_t* length, int32_t* matches, uint32_t* band_used);
 
+/* ------------------------------------------------------------------ the alignment itself: a CIGAR per pair
+ * msc_align_pairs_trace takes the lists, the parameters, the limits and the refusals of msc_align_pairs (sequences of 1 .. 32 767 bytes,
+ * parameters at most 100 in absolute value, indices below n_seqs, checked before anything is queued: MSC_ERR_INVALID_ARG with every output
+ * untouched; n_pairs == 0 is MSC_OK, with op_offsets[0] = 0 where the pointer is given) and returns msc_align_pairs's triples, bit for bit,
+ * together with the path they were counted along.
+ *   The path is a function of (pair, parameters) alone: it starts at the corner (la, lb) in the state the result's maximum picks (match, then
+ *   lower, then upper) and follows the winners of the recurrence back, with its tie orders -- a match state leaves a diagonal column and goes
+ *   to the state that won its maximum; a lower (upper) state leaves a column that consumes a byte of sequence 1 (2) and goes to match where
+ *   the gap opened, else stays -- until it reaches row 0 or column 0, where the i (j) columns left consume sequence 1 (2).
+ *   Encoding: the columns in forward order, run-length encoded, one uint32 per run, run << 4 | op, with BAM's op numbers; `first`
+ *   (sequence 1, msc_fastcar's query) is the query and `second` the reference: 7 '=' a diagonal column whose bytes are equal, 8 'X' one
+ *   whose bytes differ, 1 'I' a column that consumes sequence 1 only, 2 'D' one that consumes sequence 2 only. Adjacent runs never share an op.
+ *   op_offsets: n_pairs + 1 words, host memory; pair p's runs are words op_offsets[p] .. op_offsets[p + 1] of the list, the caller's order.
+ *   The list stays on the device until the next msc_align_pairs_trace on ctx or msc_destroy; msc_align_pairs_trace_fetch copies words
+ *   first_word .. first_word + n_words of it to host memory; a range past its end is MSC_ERR_INVALID_ARG.
+ * Invariants (proven in 4.6h): (1) the columns of a pair's runs number `length`, under every parameter set; (2) its '=' columns
+ * number `matches` whenever match != mismatch (with match == mismatch the reference counts every diagonal column); (3) where the walk ends on a
+ * boundary state that is not the reference's finite "minus infinity" (a REAL path: every related pair), the affine score of the runs -- match
+ * or mismatch per diagonal column, -(gap_open + g * gap_continue) per gap run of g columns -- is `score`. For the other paths only (1) and
+ * (2) are promised.
+ * k_align_pairs's schedule with one 16-bit word of back pointers stored per lane and step (4 bits a cell: ceil(la / 256) * (lb + 63) * 128
+ * bytes a pair), then one lane per pair walks them twice: to count the runs and, behind a scan, to write them. The pairs are dealt in the
+ * caller's order into groups whose back pointers fit 2 GiB (kAlignTraceBytes; MSC_ALIGN_TRACE_BYTES=n overrides it, read on every call; a pair
+ * above the cap is a group of its own); results do not depend on the grouping, the order of the list, the other pairs or the context's
+ * history. msc_last_kernel_info names "k_align_pairs_dirs<carry in LDS>" or "k_align_pairs_dirs<carry in global memory>" (of the call's last
+ * forward launch); msc_last_kernel_ms gives the forward launches (tiles_ms) and the call's whole span on the device. Banded and long
+ * (> 32 767 bytes) traceback are not offered. */
+int msc_align_pairs_trace(msc_ctx* ctx,
+                          const uint8_t* seqs, const uint64_t* offsets, uint64_t n_seqs,
+                          const uint32_t* first, const uint32_t* second, uint64_t n_pairs,
+                          int match, int mismatch, int gap_open, int gap_continue,
+                          int32_t* score, int32_t* length, int32_t* matches, uint64_t* op_offsets);
+int msc_align_pairs_trace_fetch(msc_ctx* ctx, uint64_t first_word, uint64_t n_words, uint32_t* ops);
+
 /* ------------------------------------------------------------------ a8/a9: Trainer operators */
 /* Trainer<T>::get_close (cluster/Trainer.cpp:23-71; caller cluster/ClusterFactory.cpp:566).
  * The window [istart, iend) is cand_slots[0..m). Candidates outside floor(len_q*cutoff) <= len <= floor(len_q/cutoff)

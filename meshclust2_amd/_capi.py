@@ -112,6 +112,8 @@ PROTOTYPES = {
     "msc_align_pairs_long": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _int, _int, _int, _int, _vp, _vp, _vp]),
     "msc_align_pairs_long_banded": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _int, _int, _int, _int, _u32, _vp, _vp, _vp, _vp]),
     "msc_align_pairs_long_auto": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _int, _int, _int, _int, _u32, _vp, _vp, _vp, _vp]),
+    "msc_align_pairs_trace": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _int, _int, _int, _int, _vp, _vp, _vp, _vp]),
+    "msc_align_pairs_trace_fetch": (_int, [_vp, _u64, _u64, _vp]),
     "msc_get_close": (_int, [_vp, _vp, _dbl, _vp, _vp, _u64, _vp, _u64, _vp, _pi64, _pdbl, C.POINTER(_int)]),
     "msc_filter": (_int, [_vp, _vp, _dbl, _vp, _u64, _vp, _vp, _u64, _vp, _pu64]),
     "msc_merge": (_int, [_vp, _vp, _dbl, _vp, _vp, _u64, _i64, _i64, _i64, _pi64]),

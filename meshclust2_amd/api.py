@@ -566,6 +566,51 @@ def align_pairs_long(ctx, seqs, first, second, match=1, mismatch=-1, gap_open=2,
     return _align_full("msc_align_pairs_long", ctx, seqs, first, second, (match, mismatch, gap_open, gap_continue), out)
 
 
+def align_pairs_trace(ctx, seqs, first, second, match=1, mismatch=-1, gap_open=2, gap_continue=1, out=None):
+    """align_pairs's integers and the alignment itself (msc_align_pairs_trace): the path the winners of the recurrence point
+    along from the corner, run-length encoded, one uint32 per run = run << 4 | op with BAM's op numbers (7 '=', 8 'X', 1 'I' consumes
+    seqs[first[p]], the query, 2 'D' consumes seqs[second[p]], the reference). Sequences of 1 .. 32 767 bytes.
+    -> align_pairs's dict and op_offsets: uint64 [n_pairs + 1], ops: uint32 [op_offsets[-1]], the whole list; pair p's runs are
+    ops[op_offsets[p]:op_offsets[p + 1]] (cigar_string turns them into text). `out`: a tuple of three int32 arrays of n_pairs and a uint64
+    one of n_pairs + 1, left as they were by a refused call."""
+    raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs]
+    a = np.ascontiguousarray(first, dtype=np.uint32)
+    b = np.ascontiguousarray(second, dtype=np.uint32)
+    if a.ndim != 1 or a.shape != b.shape:
+        raise ValueError("first and second are one pair list: one dimension, equal lengths")
+    offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
+    np.cumsum([len(s) for s in raw], out=offsets[1:])
+    text = np.frombuffer(b"".join(raw) + b"\0", dtype=np.uint8)
+    if out is None:
+        out = tuple(np.zeros(a.size, dtype=np.int32) for _ in range(3)) + (np.zeros(a.size + 1, dtype=np.uint64),)
+    if len(out) != 4 or any(o.dtype != (np.int32 if i < 3 else np.uint64) or o.shape != (a.size + (i == 3),) or not o.flags.c_contiguous for i, o in enumerate(out)):
+        raise ValueError("out: three contiguous int32 arrays of n_pairs and a uint64 one of n_pairs + 1")
+    score, length, matches, op_offsets = out
+    name = "msc_align_pairs_trace"
+    lib = ctx.lib if ctx is not None else _capi.load_library()
+    rc = lib.msc_align_pairs_trace(ctx.h if ctx is not None else None, _ptr(text), _ptr(offsets), len(raw), _ptr(a), _ptr(b), a.size, int(match), int(mismatch), int(gap_open),
+                                   int(gap_continue), _ptr(score), _ptr(length), _ptr(matches), _ptr(op_offsets))
+    if rc != 0:
+        raise MscError(rc, lib.msc_last_error(ctx.h).decode() if ctx is not None else name + " needs a Context (a gfx950 device): there is no CPU fallback")
+    ops = align_trace_fetch(ctx, 0, int(op_offsets[-1]))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        identity = matches.astype(np.float64) / length.astype(np.float64)
+    return dict(score=score, length=length, matches=matches, identity=identity, op_offsets=op_offsets, ops=ops)
+
+
+def align_trace_fetch(ctx, first_word, n_words):
+    """words first_word .. first_word + n_words of the op list the last align_pairs_trace on ctx left on the device (msc_align_pairs_trace_fetch)
+    -> uint32 [n_words]; a range past the list's end is refused"""
+    ops = np.zeros(int(n_words), dtype=np.uint32)
+    ctx.check(ctx.lib.msc_align_pairs_trace_fetch(ctx.h, int(first_word), int(n_words), _ptr(ops)))
+    return ops
+
+
+def cigar_string(ops):
+    """the runs of one pair (uint32, run << 4 | op) as text, such as "120=1X3I": BAM's letters for the op numbers"""
+    return "".join("%d%s" % (int(w) >> 4, "MIDNSHP=X"[int(w) & 15]) for w in np.asarray(ops, dtype=np.uint32))
+
+
 def _align_over_a_band(name, ctx, seqs, first, second, band, params, out, last):
     """msc_align_pairs_banded / msc_align_pairs_auto: align_pairs's arguments, a band between the parameters and the outputs and a fourth
     output (`last`: uint8 flags or uint32 bands)"""

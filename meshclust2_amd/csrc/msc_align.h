@@ -167,6 +167,67 @@ MSC_HD void msc_align_lane_step(MscAlignLane& L, const MscAlignTriple& recv, uin
 	L.prev = recv;
 }
 
+// ---------------------------------------------------------------------------------------- the same update, and what it decided
+// msc_align_pairs_trace: siblings of the functions above that also return the three `>=` decisions of a cell, its back
+// pointers, as a nibble -- bits 0-1 the state that won the diagonal (kAlignFromMatch / Lower / Upper), bit 2 lower CONTINUED (it did not open
+// from match), bit 3 upper continued. The states they compute are those of their namesakes, expression for expression.
+constexpr uint32_t kAlignFromMatch = 0, kAlignFromLower = 1, kAlignFromUpper = 2;
+constexpr uint32_t kAlignLowerCont = 4, kAlignUpperCont = 8;
+
+template <class W>
+MSC_HD MscAlignStateT<W> msc_align_gap_dir(const MscAlignStateT<W>& from_match, const MscAlignStateT<W>& from_gap, const MscAlignParams& P, bool& continued) {
+	const int32_t a = from_match.s - P.open_cont, b = from_gap.s - P.cont;
+	MscAlignStateT<W> r;
+	r.s = a >= b ? a : b;
+	r.w = MscAlignCount<W>::gap(a >= b ? from_match.w : from_gap.w);
+	continued = !(a >= b);
+	return r;
+}
+
+template <class W>
+MSC_HD MscAlignStateT<W> msc_align_diag_dir(const MscAlignTripleT<W>& d, bool eq, const MscAlignParams& P, uint32_t& from) {
+	const int32_t ml = d.m.s >= d.l.s ? d.m.s : d.l.s;
+	const W ml_w = d.m.s >= d.l.s ? d.m.w : d.l.w;
+	MscAlignStateT<W> r;
+	r.s = (ml >= d.u.s ? ml : d.u.s) + (eq ? P.match : P.mismatch);
+	r.w = MscAlignCount<W>::diag(ml >= d.u.s ? ml_w : d.u.w, eq, P);
+	from = ml >= d.u.s ? (d.m.s >= d.l.s ? kAlignFromMatch : kAlignFromLower) : kAlignFromUpper;
+	return r;
+}
+
+// msc_align_cell, returning the cell's nibble
+template <class W>
+MSC_HD uint32_t msc_align_cell_dir(MscAlignTripleT<W>& col, const MscAlignTripleT<W>& diag, const MscAlignTripleT<W>& left, bool eq, const MscAlignParams& P) {
+	bool upper_cont, lower_cont;
+	uint32_t from;
+	col.u = msc_align_gap_dir(col.m, col.u, P, upper_cont);
+	col.m = msc_align_diag_dir(diag, eq, P, from);
+	col.l = msc_align_gap_dir(left.m, left.l, P, lower_cont);
+	return from | (lower_cont ? kAlignLowerCont : 0u) | (upper_cont ? kAlignUpperCont : 0u);
+}
+
+// msc_align_final, and the state it picked
+template <class W>
+MSC_HD MscAlignStateT<W> msc_align_final_dir(const MscAlignTripleT<W>& t, uint32_t& from) {
+	const MscAlignStateT<W> ml = t.m.s >= t.l.s ? t.m : t.l;
+	from = ml.s >= t.u.s ? (t.m.s >= t.l.s ? kAlignFromMatch : kAlignFromLower) : kAlignFromUpper;
+	return ml.s >= t.u.s ? ml : t.u;
+}
+
+// msc_align_lane_step, returning the nibbles of the lane's kAlignCols cells of the row: column c in bits [4c, 4c + 4)
+MSC_HD uint32_t msc_align_lane_step_dir(MscAlignLane& L, const MscAlignTriple& recv, uint32_t b, const MscAlignParams& P) {
+	MscAlignTriple diag = L.prev, left = recv;
+	uint32_t dirs = 0;
+	for (int c = 0; c < kAlignCols; c++) {
+		const MscAlignTriple above = L.col[c];
+		dirs |= msc_align_cell_dir(L.col[c], diag, left, ((L.bytes >> (8 * c)) & 0xffu) == b, P) << (4 * c);
+		diag = above;
+		left = L.col[c];
+	}
+	L.prev = recv;
+	return dirs;
+}
+
 // ---------------------------------------------------------------------------------------- the schedule's sizes
 MSC_HD uint32_t msc_align_stripes(uint32_t la) { return (la + kAlignStripe - 1) / kAlignStripe; }
 // LDS of one pair: the first sequence padded with zeros to whole stripes | pad, the second sequence, pad, rounded up to 8 bytes | where the

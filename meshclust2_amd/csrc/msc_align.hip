@@ -106,9 +106,7 @@ int msc_align_list(msc_ctx* ctx, const char* who, const uint64_t* offsets, uint6
 	return MSC_OK;
 }
 
-// Queues k_align_pairs for `pairs` (reordered here) over the uploaded text: pair p's integers go to d_out[p.out], d_out[n_out + p.out] and
-// d_out[2 * n_out + p.out]
-int msc_align_queue_full(msc_ctx* ctx, std::vector<AlignPair>& pairs, const uint8_t* d_text, const MscAlignParams& P, int32_t* d_out, uint64_t n_out) {
+void msc_align_plan_full(std::vector<AlignPair>& pairs, std::vector<AlignLaunch>& launches, uint64_t& scratch_rows) {
 	const uint64_t n_pairs = pairs.size();
 	// classes of LDS need, longest pairs first inside each
 	auto lds_need = [](const AlignPair& a) { return msc_align_carry_at(a.la, a.lb) + msc_align_carry_bytes(a.la, a.lb); };
@@ -122,12 +120,11 @@ int msc_align_queue_full(msc_ctx* ctx, std::vector<AlignPair>& pairs, const uint
 		if (cx != cy) return cx < cy;
 		return (uint64_t)x.la * x.lb > (uint64_t)y.la * y.lb;
 	});
-	struct Launch { uint64_t at, n; uint32_t lds; bool lds_carry; uint64_t rows; };
-	std::vector<Launch> launches;
-	uint64_t scratch_rows = 0;
+	launches.clear();
+	scratch_rows = 0;
 	for (uint64_t i = 0; i < n_pairs;) {
 		const int c = class_of(pairs[i]);
-		Launch l{i, 0, 0, c < kAlignClasses - 1, 0};
+		AlignLaunch l{i, 0, 0, c < kAlignClasses - 1, 0};
 		for (; i < n_pairs && class_of(pairs[i]) == c; i++, l.n++) {
 			if (l.lds_carry) l.lds = std::max(l.lds, lds_need(pairs[i]));
 			else {
@@ -141,6 +138,15 @@ int msc_align_queue_full(msc_ctx* ctx, std::vector<AlignPair>& pairs, const uint
 		scratch_rows = std::max(scratch_rows, l.rows);
 		launches.push_back(l);
 	}
+}
+
+// Queues k_align_pairs for `pairs` (reordered here) over the uploaded text: pair p's integers go to d_out[p.out], d_out[n_out + p.out] and
+// d_out[2 * n_out + p.out]
+int msc_align_queue_full(msc_ctx* ctx, std::vector<AlignPair>& pairs, const uint8_t* d_text, const MscAlignParams& P, int32_t* d_out, uint64_t n_out) {
+	const uint64_t n_pairs = pairs.size();
+	std::vector<AlignLaunch> launches;
+	uint64_t scratch_rows = 0;
+	msc_align_plan_full(pairs, launches, scratch_rows);
 	if (int r = ensure(ctx, ctx->align_pairs, n_pairs * sizeof(AlignPair))) return r;
 	if (scratch_rows) if (int r = ensure(ctx, ctx->align_carry, scratch_rows * sizeof(MscAlignTriple))) return r;
 	HIP_TRY(ctx, hipMemcpyAsync(ctx->align_pairs.p, pairs.data(), n_pairs * sizeof(AlignPair), hipMemcpyHostToDevice, ctx->stream));
@@ -151,7 +157,7 @@ int msc_align_queue_full(msc_ctx* ctx, std::vector<AlignPair>& pairs, const uint
 		raised = true;
 	}
 	const AlignPair* d_pairs = (const AlignPair*)ctx->align_pairs.p;
-	for (const Launch& l : launches) {
+	for (const AlignLaunch& l : launches) {
 		if (l.lds > kAlignLdsMax) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_align_pairs: a pair needs %u bytes of LDS", l.lds);          // (cannot happen within the length limit)
 		if (l.lds_carry)
 			k_align_pairs<true><<<dim3((unsigned)l.n), dim3(kAlignLanes), l.lds, ctx->stream>>>(d_text, d_pairs + l.at, P, nullptr, d_out, d_out + n_out, d_out + 2 * n_out);

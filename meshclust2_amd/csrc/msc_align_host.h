@@ -1,6 +1,6 @@
 // msc_align_host.h -- what the alignment entry points (msc_align.hip: msc_align_pairs; msc_align_band.hip: msc_align_pairs_banded,
-// msc_align_pairs_auto; msc_align_long.hip: their _long namesakes) share on the host: the pair record, the checks of a call and the queueing
-// of the full-grid and of the banded kernel.
+// msc_align_pairs_auto; msc_align_long.hip: their _long namesakes; msc_align_trace.hip: msc_align_pairs_trace) share on the host: the pair
+// record, the checks of a call, the plan of the full-grid launches and the queueing of the full-grid and of the banded kernel.
 #pragma once
 #include <vector>
 
@@ -22,5 +22,11 @@ constexpr uint64_t kAlignScratchRows = (512ull << 20) / sizeof(MscAlignTriple); 
 
 int msc_align_list(msc_ctx* ctx, const char* who, const uint64_t* offsets, uint64_t n_seqs, const uint32_t* first, const uint32_t* second, uint64_t n_pairs, int match, int mismatch,
                    int gap_open, int gap_continue, std::vector<AlignPair>& pairs, uint64_t& text_bytes, uint32_t max_len = kAlignMaxLen);
+// One launch of the full-grid kernel: pairs [at, at + n) of the sorted list, the dynamic LDS it asks for, where its carry lives and (global
+// carry) the rows of the scratch buffer it uses
+struct AlignLaunch { uint64_t at, n; uint32_t lds; bool lds_carry; uint64_t rows; };
+// Sorts `pairs` into the classes of LDS need, longest first inside each, sets their carry offsets and lists the launches (msc_align_queue_full
+// and msc_align_pairs_trace queue the same plan)
+void msc_align_plan_full(std::vector<AlignPair>& pairs, std::vector<AlignLaunch>& launches, uint64_t& scratch_rows);
 int msc_align_queue_full(msc_ctx* ctx, std::vector<AlignPair>& pairs, const uint8_t* d_text, const MscAlignParams& P, int32_t* d_out, uint64_t n_out);
 int msc_align_queue_banded(msc_ctx* ctx, std::vector<AlignPair>& pairs, const uint8_t* d_text, const MscAlignParams& P, int32_t* d_out, uint64_t n_out);

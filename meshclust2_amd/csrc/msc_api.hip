@@ -161,7 +161,8 @@ extern "C" void msc_destroy(msc_ctx* ctx) {
 	                  &ctx->sp_cumbase, &ctx->sp_acc, &ctx->sp_chunk_off, &ctx->sp_chunk_cum, &ctx->sp_partials, &ctx->grp_pairs, &ctx->grp_self,
 	                  &ctx->tile_scratch, &ctx->reduce_parts, &ctx->sp_touched, &ctx->sp_acc_batch, &ctx->ps_idx, &ctx->ps_sim, &ctx->ps_m_idx, &ctx->ps_m_sim,
 	                  &ctx->pl_strand, &ctx->ps_off, &ctx->ps_only, &ctx->ps_counts, &ctx->align_text, &ctx->align_pairs, &ctx->align_out, &ctx->align_carry, &ctx->align_band_pairs,
-	                  &ctx->align_long_pairs, &ctx->align_long_tiles, &ctx->align_long_borders};
+	                  &ctx->align_long_pairs, &ctx->align_long_tiles, &ctx->align_long_borders, &ctx->align_trace_dirs, &ctx->align_trace_at, &ctx->align_trace_idx,
+	                  &ctx->align_trace_ops};
 	for (DevBuf* b : bufs) release(*b);
 	for (hipEvent_t e : pipe.ev_pool) (void)hipEventDestroy(e);
 	for (hipEvent_t e : {ctx->ev_tiles0, ctx->ev_tiles1, ctx->ev_all0, ctx->ev_all1, pipe.ev_call}) (void)hipEventDestroy(e);

@@ -133,6 +133,10 @@ struct msc_ctx {
 	// too long for LDS
 	DevBuf align_text, align_pairs, align_out, align_carry, align_band_pairs;          // (align_band_pairs: the records of msc_align_band.hip's rounds)
 	DevBuf align_long_pairs, align_long_tiles, align_long_borders;          // msc_align_long.hip: a round's pair records, its tile table, the pairs' borders
+	// msc_align_pairs_trace (msc_align_trace.hip): a group's back pointers, where each of its pairs' start, the call's range ends and run counts,
+	// and the op list of the last call (align_trace_n words), kept until the next call
+	DevBuf align_trace_dirs, align_trace_at, align_trace_idx, align_trace_ops;
+	uint64_t align_trace_n = 0;
 	// MSC_PROFILE_CALLS: host wall clock of the 1 x M scoring calls, split into preparing + queueing the slot list, issuing the
 	// launches, and waiting for the stream (printed by msc_destroy)
 	double prof_prep = 0, prof_issue = 0, prof_wait = 0;

@@ -369,6 +369,37 @@ inline Alignments align_pairs_long(const Context& ctx, const std::vector<std::st
 	return detail::align_full(ctx, true, seqs, first, second, match, mismatch, gap_open, gap_continue);
 }
 
+// align_pairs's integers and the alignment itself (msc_align_pairs_trace): pair p's runs are ops[op_offsets[p]] ..
+// ops[op_offsets[p + 1]), the columns in forward order, one word per run = run << 4 | op with BAM's op numbers -- 7 '=', 8 'X', 1 'I' (consumes
+// seqs[first[p]], the query), 2 'D' (consumes seqs[second[p]], the reference). Sequences of 1 .. 32 767 bytes.
+struct Traces : Alignments {
+	std::vector<uint64_t> op_offsets;
+	std::vector<uint32_t> ops;
+	std::string cigar(size_t p) const {          // such as "120=1X3I"
+		std::string s;
+		for (uint64_t k = op_offsets.at(p); k < op_offsets.at(p + 1); k++) { s += std::to_string(ops[k] >> 4); s += "MIDNSHP=X*******"[ops[k] & 15u]; }
+		return s;
+	}
+};
+inline Traces align_pairs_trace(const Context& ctx, const std::vector<std::string>& seqs, const std::vector<uint32_t>& first, const std::vector<uint32_t>& second, int match = 1,
+                                int mismatch = -1, int gap_open = 2, int gap_continue = 1) {
+	if (first.size() != second.size()) throw Error(MSC_ERR_INVALID_ARG, "align_pairs_trace: first and second are one pair list");
+	std::string text;
+	std::vector<uint64_t> offsets(1, 0);
+	for (const std::string& s : seqs) { text += s; offsets.push_back(text.size()); }
+	text.push_back('\0');          // (never a null pointer, whatever the list holds)
+	Traces a;
+	const size_t n = first.size();
+	a.score.resize(n); a.length.resize(n); a.matches.resize(n); a.identity.resize(n);
+	a.op_offsets.assign(n + 1, 0);
+	ctx.check(msc_align_pairs_trace(ctx.get(), reinterpret_cast<const uint8_t*>(text.data()), offsets.data(), seqs.size(), first.data(), second.data(), n, match, mismatch, gap_open,
+	                                gap_continue, a.score.data(), a.length.data(), a.matches.data(), a.op_offsets.data()));
+	a.ops.resize(a.op_offsets[n]);
+	ctx.check(msc_align_pairs_trace_fetch(ctx.get(), 0, a.ops.size(), a.ops.data()));
+	for (size_t i = 0; i < n; i++) a.identity[i] = (double)a.matches[i] / a.length[i];
+	return a;
+}
+
 // The same integers over a band of diagonals (msc_align_pairs_banded, msc_align_pairs_auto). align_pairs_banded fills the
 // diagonals within `band` of the corner-to-corner ones and says per pair whether its integers are PROVEN to be align_pairs's (certified[p]
 // = 1); align_pairs_auto doubles each pair's band from first_band (0: the library's default) until it is, and always returns align_pairs's

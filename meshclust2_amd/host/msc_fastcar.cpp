@@ -6,7 +6,7 @@
 // std::sort by length, bin_search, format_header and the output formatting follow fastcar/FC_Runner.cpp:389-471,
 // 560-611 at one thread (one output file "<prefix>0"); training is out of scope, a two-block weights file is required.
 //
-//   msc_fastcar <db.fa> --query <q.fa> --recover weights.txt [--output output] [--chunk 10000] [--no-format] [--device 0] [--div-cells] [--top N] [--both-strands] [--canonical] [--align] [--align-band W]
+//   msc_fastcar <db.fa> --query <q.fa> --recover weights.txt [--output output] [--chunk 10000] [--no-format] [--device 0] [--div-cells] [--top N] [--both-strands] [--canonical] [--align] [--align-band W] [--cigar]
 //
 // --align: one more column after the predicted identity (and after the strand column where there is one): the identity of the global alignment of
 // the reported pair, matches / length of msc_align_pairs_long with the default parameters (1, -1, 2, 1), the query as the first sequence -- the quantity
@@ -16,6 +16,10 @@
 // align. Without the flag the output is what it was.
 // --align-band W (with --align): the same column through msc_align_pairs_long_auto, which fills a band of diagonals per pair (first half-width W, 0 = the
 // library's default, doubled until the pair is certified) and returns msc_align_pairs_long's integers: the output is byte for byte that of --align.
+// --cigar (with --align, not beside --align-band): one more last column, the alignment itself as a CIGAR string such as 120=1X3I (msc_align_pairs_trace,
+// = equal bytes, X different bytes, I consumes the query, D consumes the database entry; the query is the CIGAR's query, reversed
+// for a `-` hit as --align aligns it). A hit with a sequence longer than 32 767 bytes prints * there; its identity column still comes from
+// msc_align_pairs_long. Without --cigar every output byte is what it was.
 //
 // --canonical: database and query histograms are made strand-neutral right after they are built (msc_hist_canonical_batch, in place: each k-mer
 // counted together with its reverse complement), so a query and its reverse complement give the same lines; everything else is unchanged. The
@@ -114,7 +118,7 @@ void load_chunk(msc::PointSet& set, const std::vector<Rec>& recs, size_t off, si
 }
 
 // a hit that survived its database chunk's cut; `chunk` and `cand` give its place in the output without --top
-struct Surv { size_t chunk, cand; double sim; std::string header; double aln; };
+struct Surv { size_t chunk, cand; double sim; std::string header; double aln; std::string cigar; };
 
 // the rule of msc_search_pairs_top on the host: the n of largest similarity (compared as doubles), ties to the earlier entry, order kept
 template <class T>
@@ -136,7 +140,7 @@ int main(int argc, char** argv) {
 	std::vector<std::string> files, qfiles;
 	std::string weights, output = "output";
 	size_t chunk = 10000, qblock = 16, top = 0;
-	bool format = true, sparse = false, report_kernels = false, div_cells = false, sparse_matrix = false, both_strands = false, canonical = false, align = false, align_band = false;
+	bool format = true, sparse = false, report_kernels = false, div_cells = false, sparse_matrix = false, both_strands = false, canonical = false, align = false, align_band = false, cigar = false;
 	uint32_t first_band = 0;
 	int device = 0;
 	for (int i = 1; i < argc; i++) {
@@ -158,11 +162,12 @@ int main(int argc, char** argv) {
 		else if (a == "--canonical") canonical = true;          // msc_hist_canonical_batch on every chunk: strand-neutral histograms
 		else if (a == "--align") align = true;          // msc_align_pairs_long on every reported pair: a column with the alignment identity
 		else if (a == "--align-band") { align_band = true; first_band = (uint32_t)std::max(0l, std::atol(need("--align-band").c_str())); }          // --align through msc_align_pairs_long_auto
+		else if (a == "--cigar") cigar = true;          // with --align: msc_align_pairs_trace, a last column with the hit's CIGAR string
 		else if (a == "--device") device = std::atoi(need("--device").c_str());
 		else files.push_back(a);
 	}
 	if (files.empty() || qfiles.empty() || weights.empty()) {
-		std::fprintf(stderr, "usage: %s <db.fa> --query <q.fa> --recover weights.txt [--output prefix] [--chunk 10000] [--no-format] [--sparse] [--sparse-matrix] [--div-cells] [--top N] [--both-strands] [--canonical] [--align] [--align-band W]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s <db.fa> --query <q.fa> --recover weights.txt [--output prefix] [--chunk 10000] [--no-format] [--sparse] [--sparse-matrix] [--div-cells] [--top N] [--both-strands] [--canonical] [--align] [--align-band W] [--cigar]\n", argv[0]);
 		return 1;
 	}
 	if (canonical && both_strands) {
@@ -175,6 +180,10 @@ int main(int argc, char** argv) {
 	}
 	if (align_band && !align) {
 		std::fprintf(stderr, "--align-band needs --align: it chooses how the alignment column is computed\n");
+		return 1;
+	}
+	if (cigar && (!align || align_band)) {
+		std::fprintf(stderr, "--cigar needs --align and cannot be combined with --align-band: the CIGAR is the full-grid alignment's\n");
 		return 1;
 	}
 	if (both_strands && top) {
@@ -238,7 +247,7 @@ int main(int argc, char** argv) {
 				// work() (:426-471) for every query of the chunk. Queries are taken in blocks of `qblock` neighbours in LENGTH order, so
 				// their length windows nearly coincide and one Q x M pass over the union window serves the block; each query then
 				// keeps only its own window, and the lines are written in the reference's order (query order, then window order).
-				struct Hit { size_t cand; double sim; uint8_t strand; double aln; };
+				struct Hit { size_t cand; double sim; uint8_t strand; double aln; std::string cigar; };
 				std::vector<std::vector<Hit> > hits(qp.size());
 				std::vector<size_t> win_start(qp.size()), win_end(qp.size());
 				for (size_t qi = 0; qi < qp.size(); qi++) {
@@ -276,7 +285,7 @@ int main(int argc, char** argv) {
 						note_kernel();
 						const size_t before = hits[members[0]].size();
 						for (size_t i = win_start[members[0]]; i < win_end[members[0]]; i++)
-							if (close[i - lo]) hits[members[0]].push_back(Hit{i, sim[i - lo], 0, 0.0});
+							if (close[i - lo]) hits[members[0]].push_back(Hit{i, sim[i - lo], 0, 0.0, std::string()});
 						num_pred_pos += hits[members[0]].size() - before;
 						cut_top(hits[members[0]], top);
 						continue;
@@ -294,7 +303,7 @@ int main(int argc, char** argv) {
 					note_kernel();
 					for (size_t j = 0; j < members.size(); j++) num_pred_pos += top ? counts[j] : offsets[j + 1] - offsets[j];
 					for (size_t j = 0; j < members.size(); j++)
-						for (uint64_t p = offsets[j]; p < offsets[j + 1]; p++) hits[members[j]].push_back(Hit{lo + idx[p], sim[p], both_strands ? strand[p] : (uint8_t)0, 0.0});
+						for (uint64_t p = offsets[j]; p < offsets[j + 1]; p++) hits[members[j]].push_back(Hit{lo + idx[p], sim[p], both_strands ? strand[p] : (uint8_t)0, 0.0, std::string()});
 				}
 				if (align) {          // --align: the step's reported pairs in one call, over the strings of the two chunks; sequence 1 = the query (reversed for a `-` hit)
 					std::vector<std::string> text;
@@ -315,10 +324,24 @@ int main(int argc, char** argv) {
 					const std::vector<double> identity = align_band ? msc::align_pairs_long_auto(ctx, text, first, second, first_band).identity : msc::align_pairs_long(ctx, text, first, second).identity;
 					note_kernel();
 					for (size_t i = 0; i < listed.size(); i++) listed[i]->aln = identity[i];
+					if (cigar) {          // --cigar: the listed pairs within msc_align_pairs_trace's limit in one more call; the others print *
+						std::vector<uint32_t> short_first, short_second;
+						std::vector<Hit*> traced;
+						for (size_t i = 0; i < listed.size(); i++) {
+							listed[i]->cigar = "*";
+							if (text[first[i]].size() > 32767 || text[second[i]].size() > 32767) continue;
+							short_first.push_back(first[i]);
+							short_second.push_back(second[i]);
+							traced.push_back(listed[i]);
+						}
+						const msc::Traces tr = msc::align_pairs_trace(ctx, text, short_first, short_second);
+						note_kernel();
+						for (size_t i = 0; i < traced.size(); i++) traced[i]->cigar = tr.cigar(i);
+					}
 				}
 				if (top) {          // the chunk's survivors behind those of the chunks before, cut again: ties stay with the earlier chunk
 					for (size_t qi = 0; qi < qp.size(); qi++) {
-						for (const Hit& h : hits[qi]) best[qi].push_back(Surv{dchunk, h.cand, h.sim, pts[h.cand]->header, h.aln});
+						for (const Hit& h : hits[qi]) best[qi].push_back(Surv{dchunk, h.cand, h.sim, pts[h.cand]->header, h.aln, h.cigar});
 						cut_top(best[qi], top);
 					}
 					continue;
@@ -331,6 +354,7 @@ int main(int argc, char** argv) {
 							else out << query.header << delim << pts[h.cand]->header << delim << 100 * h.sim;
 							if (both_strands) out << delim << (h.strand ? '-' : '+');
 							if (align) out << delim << 100 * h.aln;
+							if (cigar) out << delim << h.cigar;
 							out << std::endl;
 						}
 					}
@@ -346,6 +370,7 @@ int main(int argc, char** argv) {
 							if (format) out << format_header(qp[qi].header) << delim << format_header(h.header) << delim << 100 * h.sim;
 							else out << qp[qi].header << delim << h.header << delim << 100 * h.sim;
 							if (align) out << delim << 100 * h.aln;
+							if (cigar) out << delim << h.cigar;
 							out << std::endl;
 						}
 			}
