@@ -669,12 +669,19 @@ int msc_search_pairs_fetch_strands(msc_ctx* ctx, uint64_t first, uint64_t n, uin
  *     would mark, ascending; they DIE with the call -- the loop removes marked points next (remove_available,
  *     cluster/ClusterFactory.cpp:598). best_pos = POSITION of the arg-max, -1 if nothing passed the length filter.
  *   msc_window_kill: positions that leave the store otherwise (bvec::erase of the next seed :589, bvec::pop :593).
- *   msc_window_alive: alive positions in [first, end), from the host-side count the library keeps (no device read-back). */
+ *   msc_window_alive: alive positions in [first, end), from the host-side count the library keeps (no device read-back).
+ *   msc_window_last_compaction: the grid of the compaction launch of the last msc_get_close_window on this window -- (1, 1024): one
+ *     workgroup; (n, 256) / (n, 1024): the multi-block form; (0, 0): the call returned before launching (nothing alive in the range).
+ *   msc_window_last_close_blocks: the workgroups of the close pass that call launched as a kernel of its own; 0 where the pass rode in
+ *     the fused epilogue + reduce kernel (the default for histograms of up to four tiles) or the call returned early. Both are host
+ *     bookkeeping for tests: they tell which form of a step ran, and read no device memory. */
 typedef struct msc_window msc_window;
 int      msc_window_create(msc_ctx* ctx, const msc_hist_set* set, const uint32_t* slots, uint64_t n, msc_window** out);
 void     msc_window_destroy(msc_window* w);
 uint64_t msc_window_alive(const msc_window* w, uint64_t first, uint64_t end);
 int      msc_window_kill(msc_ctx* ctx, msc_window* w, const uint32_t* positions, uint64_t n);
+void     msc_window_last_compaction(const msc_window* w, uint32_t* blocks, uint32_t* threads);
+uint32_t msc_window_last_close_blocks(const msc_window* w);
 int      msc_get_close_window(msc_ctx* ctx, const msc_model* model, double cutoff, msc_window* w, uint64_t first, uint64_t end,
                               const msc_hist_set* qset, uint64_t q_slot, const uint32_t** close_pos, uint64_t* n_close,
                               int64_t* best_pos, double* best_sim, int* is_min);

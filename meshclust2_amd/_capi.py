@@ -152,6 +152,8 @@ PROTOTYPES = {
     "msc_window_destroy": (None, [_vp]),
     "msc_window_alive": (_u64, [_vp, _u64, _u64]),
     "msc_window_kill": (_int, [_vp, _vp, _vp, _u64]),
+    "msc_window_last_compaction": (None, [_vp, _pu32, _pu32]),
+    "msc_window_last_close_blocks": (_u32, [_vp]),
     "msc_get_close_window": (_int, [_vp, _vp, _dbl, _vp, _u64, _u64, _vp, _u64, C.POINTER(_pu32), _pu64, _pi64, _pdbl, C.POINTER(_int)]),
 }
 

@@ -767,6 +767,16 @@ class Window:
         p = np.ascontiguousarray(positions, dtype=np.uint32)
         self.ctx.check(self.ctx.lib.msc_window_kill(self.ctx.h, self.h, _ptr(p), p.size))
 
+    def last_compaction(self):
+        """(blocks, threads) of the compaction launch of the last get_close; (0, 0): it returned before launching"""
+        b, t = C.c_uint32(), C.c_uint32()
+        self.ctx.lib.msc_window_last_compaction(self.h, C.byref(b), C.byref(t))
+        return b.value, t.value
+
+    def last_close_blocks(self):
+        """workgroups of the last get_close's close pass as a kernel of its own; 0: it rode in the fused epilogue + reduce kernel"""
+        return self.ctx.lib.msc_window_last_close_blocks(self.h)
+
     def get_close(self, trainer, first, end, qset, q_slot):
         """Trainer::get_close over the alive positions of [first, end) -> (close positions (ascending; they die), best position, best_sim, is_min)"""
         lst = C.POINTER(C.c_uint32)()

@@ -36,6 +36,9 @@ struct msc_window {
 	uint32_t* d_kill = nullptr;       // page-locked host memory the kill kernel reads
 	uint64_t d_kill_cap = 0;
 	hipEvent_t ev_kill = nullptr;     // behind the last kill kernel: the list is rewritten only once that kernel is through
+	// host-only, for the tests: the grid of the last msc_get_close_window's compaction launch (0, 0: it returned before launching) and of
+	// its k_window_close launch (0: none -- the close pass rode in the fused epilogue + reduce kernel, or the call returned early)
+	uint32_t last_blocks = 0, last_threads = 0, last_close_blocks = 0;
 };
 
 namespace {
@@ -194,6 +197,13 @@ extern "C" uint64_t msc_window_alive(const msc_window* w, uint64_t first, uint64
 	return fen_prefix(w->fen, end) - fen_prefix(w->fen, first);
 }
 
+extern "C" void msc_window_last_compaction(const msc_window* w, uint32_t* blocks, uint32_t* threads) {
+	if (blocks) *blocks = w ? w->last_blocks : 0;
+	if (threads) *threads = w ? w->last_threads : 0;
+}
+
+extern "C" uint32_t msc_window_last_close_blocks(const msc_window* w) { return w ? w->last_close_blocks : 0; }
+
 extern "C" int msc_window_kill(msc_ctx* ctx, msc_window* w, const uint32_t* positions, uint64_t n) {
 	if (!ctx || !w || w->ctx != ctx || (!positions && n)) return MSC_ERR_INVALID_ARG;
 	if (n == 0) return MSC_OK;
@@ -253,6 +263,7 @@ extern "C" int msc_get_close_window(msc_ctx* ctx, const msc_model* model, double
 	*n_close = 0; *best_pos = -1; *is_min = 1;
 	if (best_sim) *best_sim = -1.0;
 	if (close_pos) *close_pos = nullptr;
+	w->last_blocks = w->last_threads = w->last_close_blocks = 0;
 	const uint64_t m = msc_window_alive(w, first, end);
 	if (m == 0) return MSC_OK;
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -267,6 +278,7 @@ extern "C" int msc_get_close_window(msc_ctx* ctx, const msc_model* model, double
 	// r04_notes.md); from a few thousand positions on, many small workgroups count their tiles and claim their places (k_window_compact)
 	if (range <= 4 * kWinBlock) {
 		k_window_compact_one<<<dim3(1), dim3(kWinBlock), 0, ctx->stream>>>(w->d_alive, w->d_order, (uint32_t)first, range, w->d_slots, w->d_pos, w->d_counts + kMaxBlocks, kills);
+		w->last_blocks = 1; w->last_threads = kWinBlock;
 	} else {
 		const uint32_t tb = range <= 64 * kWinTile ? 256 : kWinBlock, tile = tb * kWinPer;
 		const uint32_t blocks = (range + tile - 1) / tile;
@@ -274,6 +286,7 @@ extern "C" int msc_get_close_window(msc_ctx* ctx, const msc_model* model, double
 		uint32_t *claim = w->d_counts + (w->turn & 1u), *claim_next = w->d_counts + ((w->turn & 1u) ^ 1u);
 		w->turn++;
 		k_window_compact<<<dim3(blocks), dim3(tb), 0, ctx->stream>>>(w->d_alive, w->d_order, (uint32_t)first, range, w->d_slots, w->d_pos, w->d_counts + kMaxBlocks, claim, claim_next, kills);
+		w->last_blocks = blocks; w->last_threads = tb;
 	}
 	HIP_TRY(ctx, hipGetLastError());
 	if (kills_on_file) {          // (the list is rewritten only once this kernel is through)
@@ -301,6 +314,7 @@ extern "C" int msc_get_close_window(msc_ctx* ctx, const msc_model* model, double
 	rq.reduce_host = &ro;
 	rq.after_reduce = [&](const MscReduceOut* d_rec) -> hipError_t {
 		k_window_close<<<dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream>>>(w->d_flags, w->d_pos, (uint32_t)m, w->d_alive, counter, d_rec, d_out);
+		w->last_close_blocks = (uint32_t)((m + 255) / 256);
 		return hipGetLastError();
 	};
 	rq.close_list = MscCloseList{w->d_pos, w->d_alive, counter, d_out, w->h_close};

@@ -2087,8 +2087,10 @@ def test_bench_two_ranks_row_shards(tmp_path):
 def test_get_close_over_a_device_window_equals_get_close_over_a_slot_list(ctx, dtype, k, wts, sparse, n):
     """msc_get_close_window (the accumulate loop's window kept on the device: cluster/ClusterFactory.cpp:553-610 over
     cluster/Trainer.cpp:23-71) against msc_get_close on the slot list of the same alive positions: the same close set, arg-max and
-    is_min on random ranges while positions die (close ones by themselves, others through msc_window_kill), single-block and
-    multi-block compaction, a `--feat slow` model, dense and sparse sets."""
+    is_min on random ranges while positions die (close ones by themselves, others through msc_window_kill), a `--feat slow` model,
+    dense and sparse sets. Ranges of up to 4 096 positions take the single-block compaction, longer ones the multi-block form with
+    256 threads; the edges of the forms, the 1 024-thread form above 524 288 positions, ties and the CPU oracle as the reference are
+    tests/test_gpu_window.py's."""
     rng = np.random.default_rng(5 + k)
     seqs, _ = synth.families(900 + k, n, 1000, family=25, length_jitter=120)
     hs = api.HistogramSet(ctx, k, dtype, n, sparse_entries=(sum(len(s) for s in seqs) + 4096) if sparse else 0)
@@ -2104,7 +2106,7 @@ def test_get_close_over_a_device_window_equals_get_close_over_a_slot_list(ctx, d
         q = int(rng.integers(n))
         a, b = sorted(int(x) for x in rng.integers(0, n + 1, 2))
         if step % 7 == 0:
-            a, b = 0, n          # the whole store: more than 128 * 1024 positions take the multi-block compaction (the 140 000-point case)
+            a, b = 0, n          # the whole store: more than 4 096 positions take the multi-block compaction (here only the 140 000-point case)
         pos = a + np.flatnonzero(alive[a:b])
         assert win.alive(a, b) == pos.size
         flags, bp, bs, im = trn.get_close(hs, order[pos], hs, q) if pos.size else (np.zeros(0, dtype=np.uint8), -1, -1.0, True)

@@ -3,6 +3,8 @@ kernel of run_score (k_pair_tiles, k_pair_tiles_wide, the merge kernels, k_pair_
 sums and of the group statistics, the switches that are read on every call, the window call, m = 0 and a slot list of two chunks -- and prints
 per call the kernel it named, its launches, its status and a SHA-256 of each output array. tests/golden/score_routes.json holds those lines as
 the library printed them before run_score became a route chosen in one place and one function per stage: a fresh run must print the same.
+(The last two lines, the window call over a small dense set with the fused and the unfused reduce, were recorded when those cases joined the
+table; the 91 lines in front of them are the earlier table's, byte for byte.)
 (A process of its own: the rank lists of a set are built at the third pass that asks for them, so the table is reproducible only from a fresh
 context. Outputs that hold the two FP64 divergence sums are not in the table; tests/test_gpu_ranks_pass.py and tests/test_gpu_parity.py hold
 them to the oracle.)"""

@@ -8,8 +8,8 @@ per stage, and tests/test_gpu_score_routes.py compares a fresh run with them.
 The table, in one fixed order (the rank lists of a set are built at the third pass that asks for them, so the order is part of a case):
 dense sets without a list form (32-bit k = 6, 8-bit k = 3), the 64-bit range (k_pair_tiles_wide), a dense set with a sparse mirror (32-bit
 k = 9: merge kernels, then the rank kernels, the streaming kernel behind msc_set_mirror_pass(0)), a sparse set (16-bit k = 9: whole-list
-kernel, merge-path parts, rank kernels, the window call), the generic merge kernel (a count >= 2^16; 64-bit k = 13), and a slot list one
-entry longer than a chunk of the partial records. Outputs that hold the two FP64 divergence sums are not hashed: --dump DIR writes them
+kernel, merge-path parts, rank kernels, the window call), the generic merge kernel (a count >= 2^16; 64-bit k = 13), a slot list one
+entry longer than a chunk of the partial records, and the window call over a small dense set, fused and unfused. Outputs that hold the two FP64 divergence sums are not hashed: --dump DIR writes them
 as .npy files to be compared bit for bit between two builds."""
 import argparse
 import hashlib
@@ -260,6 +260,21 @@ def main():
     call("two chunks k7 raw", raw(hs, slots, 1))
     call("two chunks k7 compute", compute(model(fast9, 7), hs, slots, 2))
     ctx.set_mirror_pass(True)
+    hs.close()
+
+    # ---- the window call over a small dense set (16-bit k = 5: the streaming kernel): 9 000 positions that name 40 slots over and over, the
+    # multi-block compaction, the fused epilogue + reduce kernel and -- MSC_NO_FUSED_REDUCE -- epilogue, keyed reduce and k_window_close
+    hs = api.HistogramSet(ctx, 5, 16, len(seqs6))
+    hs.build(seqs6)
+    trn5 = api.Trainer(ctx, api.Feature.from_text(ctx, open(os.path.join(GOLDEN, "weights_k5_u16.txt")).read(), 0), 0.9)
+    order = ((np.arange(9000, dtype=np.uint64) * 7919) % 40).astype(np.uint32)
+    win = api.Window(ctx, hs, order)
+    call("window get_close", window(win, trn5, 100, 8900, hs, 3))
+    win.close()
+    win = api.Window(ctx, hs, order)
+    with env("MSC_NO_FUSED_REDUCE"):
+        call("window get_close unfused", window(win, trn5, 100, 8900, hs, 3))
+    win.close()
     hs.close()
     ctx.close()
     print("\n".join(lines))
