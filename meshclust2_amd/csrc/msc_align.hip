@@ -9,27 +9,19 @@
 //       sequences while the pair's total fits a workgroup's LDS, otherwise in the pair's own range of a scratch buffer the context owns.
 //       Both sequences are staged in LDS as bytes, the first padded with zeros to whole stripes (columns past its end are computed and
 //       never read), the second with kAlignSeqPad zeros on either side (a lane's row index runs up to 63 outside it).
-//   The host sorts the pairs by cells, longest first, inside classes of LDS need (a launch asks for its class's largest need, so short pairs
-//   keep their occupancy beside a few long ones); block b of a launch takes the b-th pair of its class. Results go to the pair's own index:
-//   no atomics, no reduction, nothing that depends on the order the waves run in.
+//   The host sorts the pairs by cells, longest first, inside classes of LDS need (msc_align_plan.h: msc_align_plan_full; a launch asks for its
+//   class's largest need, so short pairs keep their occupancy beside a few long ones); block b of a launch takes the b-th pair of its class.
+//   Results go to the pair's own index: no atomics, no reduction, nothing that depends on the order the waves run in.
+//   This file holds the kernel and msc_align_queue_full; the entry point, msc_align_pairs, is msc_align_api.hip's.
 #include <algorithm>
 #include <vector>
 
 #include "msc_objects.h"
 #include "msc_align.h"
 #include "msc_align_host.h"
+#include "msc_align_wave.h"
 
 namespace {
-
-__device__ __forceinline__ uint32_t wave_shr1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false); }          // wave_shr:1
-
-__device__ __forceinline__ MscAlignTriple shift_triple(const MscAlignTriple& t) {
-	MscAlignTriple r;
-	r.m.s = (int32_t)wave_shr1((uint32_t)t.m.s); r.m.w = wave_shr1(t.m.w);
-	r.l.s = (int32_t)wave_shr1((uint32_t)t.l.s); r.l.w = wave_shr1(t.l.w);
-	r.u.s = (int32_t)wave_shr1((uint32_t)t.u.s); r.u.w = wave_shr1(t.u.w);
-	return r;
-}
 
 template <bool kLdsCarry>
 __global__ void __launch_bounds__(kAlignLanes) k_align_pairs(const uint8_t* __restrict__ text, const AlignPair* __restrict__ pairs, MscAlignParams P, MscAlignTriple* scratch,
@@ -83,70 +75,12 @@ __global__ void __launch_bounds__(kAlignLanes) k_align_pairs(const uint8_t* __re
 
 }  // namespace
 
-// The checks every alignment call makes on the host before anything is queued, and the pair records in the caller's order
-int msc_align_list(msc_ctx* ctx, const char* who, const uint64_t* offsets, uint64_t n_seqs, const uint32_t* first, const uint32_t* second, uint64_t n_pairs, int match, int mismatch,
-                   int gap_open, int gap_continue, std::vector<AlignPair>& pairs, uint64_t& text_bytes, uint32_t max_len) {
-	if (n_pairs > 0xfffffff0ull) return fail(ctx, MSC_ERR_INVALID_ARG, "%s: too many pairs in one call", who);
-	for (int v : {match, mismatch, gap_open, gap_continue})
-		if (v > kAlignMaxParam || v < -kAlignMaxParam) return fail(ctx, MSC_ERR_INVALID_ARG, "%s: a scoring parameter of %d (at most %d in absolute value)", who, v, kAlignMaxParam);
-	pairs.resize(n_pairs);
-	for (uint64_t p = 0; p < n_pairs; p++) {
-		AlignPair& a = pairs[p];
-		for (uint32_t s : {first[p], second[p]}) {
-			if (s >= n_seqs) return fail(ctx, MSC_ERR_INVALID_ARG, "%s: pair %llu names sequence %u of %llu", who, (unsigned long long)p, s, (unsigned long long)n_seqs);
-			if (offsets[s + 1] <= offsets[s] || offsets[s + 1] - offsets[s] > max_len)
-				return fail(ctx, MSC_ERR_INVALID_ARG, "%s: sequence %u has %lld bytes (1 .. %u)", who, s, (long long)(offsets[s + 1] - offsets[s]), max_len);
-		}
-		a.off1 = offsets[first[p]]; a.la = (uint32_t)(offsets[first[p] + 1] - a.off1);
-		a.off2 = offsets[second[p]]; a.lb = (uint32_t)(offsets[second[p] + 1] - a.off2);
-		a.out = (uint32_t)p; a.band = 0; a.carry = 0;
-	}
-	text_bytes = 0;          // the text up to the end of the last listed sequence
-	for (const AlignPair& a : pairs) text_bytes = std::max({text_bytes, a.off1 + a.la, a.off2 + a.lb});
-	return MSC_OK;
-}
-
-void msc_align_plan_full(std::vector<AlignPair>& pairs, std::vector<AlignLaunch>& launches, uint64_t& scratch_rows) {
-	const uint64_t n_pairs = pairs.size();
-	// classes of LDS need, longest pairs first inside each
-	auto lds_need = [](const AlignPair& a) { return msc_align_carry_at(a.la, a.lb) + msc_align_carry_bytes(a.la, a.lb); };
-	auto class_of = [&](const AlignPair& a) {
-		const uint32_t need = lds_need(a);
-		for (int c = 0; c < kAlignClasses - 1; c++) if (need <= kAlignClassTop[c]) return c;
-		return kAlignClasses - 1;
-	};
-	std::stable_sort(pairs.begin(), pairs.end(), [&](const AlignPair& x, const AlignPair& y) {
-		const int cx = class_of(x), cy = class_of(y);
-		if (cx != cy) return cx < cy;
-		return (uint64_t)x.la * x.lb > (uint64_t)y.la * y.lb;
-	});
-	launches.clear();
-	scratch_rows = 0;
-	for (uint64_t i = 0; i < n_pairs;) {
-		const int c = class_of(pairs[i]);
-		AlignLaunch l{i, 0, 0, c < kAlignClasses - 1, 0};
-		for (; i < n_pairs && class_of(pairs[i]) == c; i++, l.n++) {
-			if (l.lds_carry) l.lds = std::max(l.lds, lds_need(pairs[i]));
-			else {
-				const uint64_t rows = pairs[i].lb + 1;
-				if (l.n && l.rows + rows > kAlignScratchRows) break;
-				pairs[i].carry = l.rows;
-				l.rows += rows;
-				l.lds = std::max(l.lds, msc_align_carry_at(pairs[i].la, pairs[i].lb));
-			}
-		}
-		scratch_rows = std::max(scratch_rows, l.rows);
-		launches.push_back(l);
-	}
-}
-
 // Queues k_align_pairs for `pairs` (reordered here) over the uploaded text: pair p's integers go to d_out[p.out], d_out[n_out + p.out] and
 // d_out[2 * n_out + p.out]
 int msc_align_queue_full(msc_ctx* ctx, std::vector<AlignPair>& pairs, const uint8_t* d_text, const MscAlignParams& P, int32_t* d_out, uint64_t n_out) {
 	const uint64_t n_pairs = pairs.size();
 	std::vector<AlignLaunch> launches;
-	uint64_t scratch_rows = 0;
-	msc_align_plan_full(pairs, launches, scratch_rows);
+	const uint64_t scratch_rows = msc_align_plan_full(pairs, launches);
 	if (int r = ensure(ctx, ctx->align_pairs, n_pairs * sizeof(AlignPair))) return r;
 	if (scratch_rows) if (int r = ensure(ctx, ctx->align_carry, scratch_rows * sizeof(MscAlignTriple))) return r;
 	HIP_TRY(ctx, hipMemcpyAsync(ctx->align_pairs.p, pairs.data(), n_pairs * sizeof(AlignPair), hipMemcpyHostToDevice, ctx->stream));
@@ -167,28 +101,5 @@ int msc_align_queue_full(msc_ctx* ctx, std::vector<AlignPair>& pairs, const uint
 	}
 	ctx->last_kernel = launches.back().lds_carry ? "k_align_pairs<carry in LDS>" : "k_align_pairs<carry in global memory>";
 	ctx->last_query_tile = 0;
-	return MSC_OK;
-}
-
-extern "C" int msc_align_pairs(msc_ctx* ctx, const uint8_t* seqs, const uint64_t* offsets, uint64_t n_seqs, const uint32_t* first, const uint32_t* second, uint64_t n_pairs,
-                               int match, int mismatch, int gap_open, int gap_continue, int32_t* score, int32_t* length, int32_t* matches) {
-	if (!ctx) return MSC_ERR_INVALID_ARG;
-	if (n_pairs == 0) return MSC_OK;
-	if (!seqs || !offsets || !first || !second || !score || !length || !matches) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_align_pairs: a NULL argument");
-	std::vector<AlignPair> pairs;
-	uint64_t text_bytes = 0;
-	if (int r = msc_align_list(ctx, "msc_align_pairs", offsets, n_seqs, first, second, n_pairs, match, mismatch, gap_open, gap_continue, pairs, text_bytes)) return r;
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	if (int r = ensure(ctx, ctx->align_text, text_bytes + 4)) return r;
-	if (int r = ensure(ctx, ctx->align_out, 3 * n_pairs * sizeof(int32_t))) return r;
-	HIP_TRY(ctx, hipMemcpyAsync(ctx->align_text.p, seqs, text_bytes, hipMemcpyHostToDevice, ctx->stream));
-	int32_t* d_out = (int32_t*)ctx->align_out.p;
-	if (int r = msc_align_queue_full(ctx, pairs, (const uint8_t*)ctx->align_text.p, msc_align_params(match, mismatch, gap_open, gap_continue), d_out, n_pairs)) return r;
-	std::vector<int32_t> out(3 * n_pairs);          // (the caller's arrays stay untouched unless every launch went through)
-	HIP_TRY(ctx, hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-	std::copy(out.begin(), out.begin() + n_pairs, score);
-	std::copy(out.begin() + n_pairs, out.begin() + 2 * n_pairs, length);
-	std::copy(out.begin() + 2 * n_pairs, out.end(), matches);
 	return MSC_OK;
 }

@@ -12,6 +12,8 @@
 //   The half-width travels in the pair record, so one call serves pairs of different bands: msc_align_pairs_auto reruns the pairs a round left
 //   uncertified with their band doubled, in one group of launches a round, and hands those that a band no longer helps to k_align_pairs.
 //   Results go to the pair's own index: no atomics, nothing that depends on the order the waves run in.
+//   This file holds the kernel and msc_align_queue_banded, which launches what msc_align_plan_banded (msc_align_plan.h) lists; the entry
+//   points and the loop of msc_align_pairs_auto are msc_align_api.hip's.
 #include <algorithm>
 #include <cstdio>
 #include <vector>
@@ -19,18 +21,9 @@
 #include "msc_objects.h"
 #include "msc_align_band.h"
 #include "msc_align_host.h"
+#include "msc_align_wave.h"
 
 namespace {
-
-__device__ __forceinline__ uint32_t wave_shr1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false); }          // wave_shr:1
-
-__device__ __forceinline__ MscAlignTriple shift_triple(const MscAlignTriple& t) {
-	MscAlignTriple r;
-	r.m.s = (int32_t)wave_shr1((uint32_t)t.m.s); r.m.w = wave_shr1(t.m.w);
-	r.l.s = (int32_t)wave_shr1((uint32_t)t.l.s); r.l.w = wave_shr1(t.l.w);
-	r.u.s = (int32_t)wave_shr1((uint32_t)t.u.s); r.u.w = wave_shr1(t.u.w);
-	return r;
-}
 
 template <int C, bool kLdsCarry>
 __global__ void __launch_bounds__(kAlignLanes) k_align_band(const uint8_t* __restrict__ text, const AlignPair* __restrict__ pairs, MscAlignParams P, MscAlignTriple* scratch,
@@ -98,10 +91,6 @@ __global__ void __launch_bounds__(kAlignLanes) k_align_band(const uint8_t* __res
 	}
 }
 
-int cols_of(const AlignPair& a) { return msc_align_band_cols(msc_align_band_diagonals(a.la, a.lb, a.band)); }
-uint32_t lds_base(const AlignPair& a) { return msc_align_band_carry_at(a.la, a.lb, (uint32_t)(kAlignLanes * cols_of(a))); }
-uint64_t ring_rows(const AlignPair& a) { return msc_align_band_carry_rows(a.la, a.lb, a.band, (uint32_t)(kAlignLanes * cols_of(a))); }
-
 template <int C>
 void launch_band(bool lds_carry, unsigned n, uint32_t lds, hipStream_t stream, const uint8_t* d_text, const AlignPair* d_pairs, const MscAlignParams& P, MscAlignTriple* scratch, int32_t* d_out,
                  uint64_t n_out) {
@@ -115,39 +104,8 @@ void launch_band(bool lds_carry, unsigned n, uint32_t lds, hipStream_t stream, c
 // d_out[n_out + p.out], d_out[2 * n_out + p.out] and d_out[3 * n_out + p.out]
 int msc_align_queue_banded(msc_ctx* ctx, std::vector<AlignPair>& pairs, const uint8_t* d_text, const MscAlignParams& P, int32_t* d_out, uint64_t n_out) {
 	const uint64_t n_pairs = pairs.size();
-	// groups: columns per lane, then classes of LDS need (the last class keeps its ring in global memory), most band cells first inside each
-	auto lds_need = [](const AlignPair& a) { return (uint64_t)lds_base(a) + ring_rows(a) * sizeof(MscAlignTriple); };
-	auto class_of = [&](const AlignPair& a) {
-		const uint64_t need = lds_need(a);
-		int c = 0;
-		while (c < kAlignClasses - 1 && need > kAlignClassTop[c]) c++;
-		return cols_of(a) * kAlignClasses + c;
-	};
-	auto cells = [](const AlignPair& a) { return (uint64_t)a.la * msc_align_band_rows(a.la, a.lb, a.band); };
-	std::stable_sort(pairs.begin(), pairs.end(), [&](const AlignPair& x, const AlignPair& y) {
-		const int cx = class_of(x), cy = class_of(y);
-		if (cx != cy) return cx < cy;
-		return cells(x) > cells(y);
-	});
-	struct Launch { uint64_t at, n; uint32_t lds; int cols; bool lds_carry; uint64_t rows; };
-	std::vector<Launch> launches;
-	uint64_t scratch_rows = 0;
-	for (uint64_t i = 0; i < n_pairs;) {
-		const int c = class_of(pairs[i]);
-		Launch l{i, 0, 0, cols_of(pairs[i]), c % kAlignClasses < kAlignClasses - 1, 0};
-		for (; i < n_pairs && class_of(pairs[i]) == c; i++, l.n++) {
-			if (l.lds_carry) l.lds = std::max(l.lds, (uint32_t)lds_need(pairs[i]));
-			else {
-				const uint64_t rows = ring_rows(pairs[i]);
-				if (l.n && l.rows + rows > kAlignScratchRows) break;
-				pairs[i].carry = l.rows;
-				l.rows += rows;
-				l.lds = std::max(l.lds, lds_base(pairs[i]));
-			}
-		}
-		scratch_rows = std::max(scratch_rows, l.rows);
-		launches.push_back(l);
-	}
+	std::vector<AlignLaunch> launches;
+	const uint64_t scratch_rows = msc_align_plan_banded(pairs, launches);
 	if (int r = ensure(ctx, ctx->align_band_pairs, n_pairs * sizeof(AlignPair))) return r;
 	if (scratch_rows) if (int r = ensure(ctx, ctx->align_carry, scratch_rows * sizeof(MscAlignTriple))) return r;
 	HIP_TRY(ctx, hipMemcpyAsync(ctx->align_band_pairs.p, pairs.data(), n_pairs * sizeof(AlignPair), hipMemcpyHostToDevice, ctx->stream));
@@ -159,7 +117,7 @@ int msc_align_queue_banded(msc_ctx* ctx, std::vector<AlignPair>& pairs, const ui
 		raised = true;
 	}
 	const AlignPair* d_pairs = (const AlignPair*)ctx->align_band_pairs.p;
-	for (const Launch& l : launches) {
+	for (const AlignLaunch& l : launches) {
 		if (l.lds > kAlignLdsMax) return fail(ctx, MSC_ERR_INVALID_ARG, "k_align_band: a pair needs %u bytes of LDS", l.lds);          // (cannot happen within the length limit)
 		MscAlignTriple* scratch = (MscAlignTriple*)ctx->align_carry.p;
 		if (l.cols == 1) launch_band<1>(l.lds_carry, (unsigned)l.n, l.lds, ctx->stream, d_text, d_pairs + l.at, P, scratch, d_out, n_out);
@@ -171,85 +129,5 @@ int msc_align_queue_banded(msc_ctx* ctx, std::vector<AlignPair>& pairs, const ui
 	         launches.back().lds_carry ? "LDS" : "global memory");
 	ctx->last_kernel = ctx->last_kernel_buf;
 	ctx->last_query_tile = 0;
-	return MSC_OK;
-}
-
-extern "C" int msc_align_pairs_banded(msc_ctx* ctx, const uint8_t* seqs, const uint64_t* offsets, uint64_t n_seqs, const uint32_t* first, const uint32_t* second, uint64_t n_pairs,
-                                      int match, int mismatch, int gap_open, int gap_continue, uint32_t band, int32_t* score, int32_t* length, int32_t* matches, uint8_t* certified) {
-	if (!ctx) return MSC_ERR_INVALID_ARG;
-	if (n_pairs == 0) return MSC_OK;
-	if (!seqs || !offsets || !first || !second || !score || !length || !matches || !certified) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_align_pairs_banded: a NULL argument");
-	std::vector<AlignPair> pairs;
-	uint64_t text_bytes = 0;
-	if (int r = msc_align_list(ctx, "msc_align_pairs_banded", offsets, n_seqs, first, second, n_pairs, match, mismatch, gap_open, gap_continue, pairs, text_bytes)) return r;
-	for (AlignPair& a : pairs) a.band = band;
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	if (int r = ensure(ctx, ctx->align_text, text_bytes + 4)) return r;
-	if (int r = ensure(ctx, ctx->align_out, 4 * n_pairs * sizeof(int32_t))) return r;
-	HIP_TRY(ctx, hipMemcpyAsync(ctx->align_text.p, seqs, text_bytes, hipMemcpyHostToDevice, ctx->stream));
-	int32_t* d_out = (int32_t*)ctx->align_out.p;
-	if (int r = msc_align_queue_banded(ctx, pairs, (const uint8_t*)ctx->align_text.p, msc_align_params(match, mismatch, gap_open, gap_continue), d_out, n_pairs)) return r;
-	std::vector<int32_t> out(4 * n_pairs);          // (the caller's arrays stay untouched unless every launch went through)
-	HIP_TRY(ctx, hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-	std::copy(out.begin(), out.begin() + n_pairs, score);
-	std::copy(out.begin() + n_pairs, out.begin() + 2 * n_pairs, length);
-	std::copy(out.begin() + 2 * n_pairs, out.begin() + 3 * n_pairs, matches);
-	for (uint64_t p = 0; p < n_pairs; p++) certified[p] = out[3 * n_pairs + p] ? 1 : 0;
-	return MSC_OK;
-}
-
-extern "C" int msc_align_pairs_auto(msc_ctx* ctx, const uint8_t* seqs, const uint64_t* offsets, uint64_t n_seqs, const uint32_t* first, const uint32_t* second, uint64_t n_pairs,
-                                    int match, int mismatch, int gap_open, int gap_continue, uint32_t first_band, int32_t* score, int32_t* length, int32_t* matches, uint32_t* band_used) {
-	if (!ctx) return MSC_ERR_INVALID_ARG;
-	if (n_pairs == 0) return MSC_OK;
-	if (!seqs || !offsets || !first || !second || !score || !length || !matches) return fail(ctx, MSC_ERR_INVALID_ARG, "msc_align_pairs_auto: a NULL argument");
-	std::vector<AlignPair> all;
-	uint64_t text_bytes = 0;
-	if (int r = msc_align_list(ctx, "msc_align_pairs_auto", offsets, n_seqs, first, second, n_pairs, match, mismatch, gap_open, gap_continue, all, text_bytes)) return r;
-	const MscAlignParams P = msc_align_params(match, mismatch, gap_open, gap_continue);
-	const uint32_t w0 = first_band ? first_band : kAlignBandDefault;
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	if (int r = ensure(ctx, ctx->align_text, text_bytes + 4)) return r;
-	if (int r = ensure(ctx, ctx->align_out, 4 * n_pairs * sizeof(int32_t))) return r;
-	HIP_TRY(ctx, hipMemcpyAsync(ctx->align_text.p, seqs, text_bytes, hipMemcpyHostToDevice, ctx->stream));
-	const uint8_t* d_text = (const uint8_t*)ctx->align_text.p;
-	int32_t* d_out = (int32_t*)ctx->align_out.p;
-	std::vector<uint32_t> used(n_pairs, kAlignBandNone);
-	std::vector<AlignPair> open, full;          // the pairs of the coming banded round, each at its own band | those a band does not help
-	const bool offered = msc_align_band_offered(P);
-	for (AlignPair a : all) {
-		a.band = w0;
-		(offered && msc_align_band_worth(a.la, a.lb, a.band) ? open : full).push_back(a);
-	}
-	std::vector<int32_t> flags(n_pairs);
-	bool banded = false;
-	char name[sizeof(ctx->last_kernel_buf)];
-	while (!open.empty()) {
-		if (int r = msc_align_queue_banded(ctx, open, d_text, P, d_out, n_pairs)) return r;
-		HIP_TRY(ctx, hipMemcpyAsync(flags.data(), d_out + 3 * n_pairs, n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-		banded = true;
-		snprintf(name, sizeof(name), "%s", ctx->last_kernel_buf);
-		std::vector<AlignPair> again;
-		for (AlignPair a : open) {
-			if (flags[a.out]) { used[a.out] = a.band; continue; }
-			a.band *= 2;          // (at most 2 * 32 767 here: a band is worth it only below the shorter length)
-			(msc_align_band_worth(a.la, a.lb, a.band) ? again : full).push_back(a);
-		}
-		open.swap(again);
-	}
-	if (!full.empty()) if (int r = msc_align_queue_full(ctx, full, d_text, P, d_out, n_pairs)) return r;
-	std::vector<int32_t> out(3 * n_pairs);          // (the caller's arrays stay untouched unless every launch went through)
-	HIP_TRY(ctx, hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-	std::copy(out.begin(), out.begin() + n_pairs, score);
-	std::copy(out.begin() + n_pairs, out.begin() + 2 * n_pairs, length);
-	std::copy(out.begin() + 2 * n_pairs, out.end(), matches);
-	if (band_used) std::copy(used.begin(), used.end(), band_used);
-	if (banded) {          // the call's kernel is the banded one wherever a round ran
-		snprintf(ctx->last_kernel_buf, sizeof(ctx->last_kernel_buf), "%s", name);
-		ctx->last_kernel = ctx->last_kernel_buf;
-	}
 	return MSC_OK;
 }

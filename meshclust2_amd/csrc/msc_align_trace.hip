@@ -12,6 +12,8 @@
 //   read on every call; a pair above the cap is a group of its own) and runs per group: the forward launches (msc_align_plan_full's classes,
 //   longest first), the count, an exclusive scan on the host, the write. The op list of all groups is one device list in the caller's order,
 //   kept by the context until the next call. No atomics; a pair's words depend on the pair and the parameters alone.
+//   The checks of the call (msc_align_list) and the fan-out of the three integers (msc_align_download) are msc_align_api.hip's, the plan of a
+//   group's forward launches msc_align_plan.h's; the group loop, with its own buffers and its timing events, stays here.
 #include <algorithm>
 #include <cstdlib>
 #include <vector>
@@ -20,18 +22,9 @@
 #include "msc_align.h"
 #include "msc_align_trace.h"
 #include "msc_align_host.h"
+#include "msc_align_wave.h"
 
 namespace {
-
-__device__ __forceinline__ uint32_t wave_shr1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false); }          // wave_shr:1
-
-__device__ __forceinline__ MscAlignTriple shift_triple(const MscAlignTriple& t) {
-	MscAlignTriple r;
-	r.m.s = (int32_t)wave_shr1((uint32_t)t.m.s); r.m.w = wave_shr1(t.m.w);
-	r.l.s = (int32_t)wave_shr1((uint32_t)t.l.s); r.l.w = wave_shr1(t.l.w);
-	r.u.s = (int32_t)wave_shr1((uint32_t)t.u.s); r.u.w = wave_shr1(t.u.w);
-	return r;
-}
 
 // dirs_at[blockIdx.x]: where the pair's directions start in `dirs`, in 16-bit words. start[pr.out]: the state the walk starts in
 template <bool kLdsCarry>
@@ -181,8 +174,7 @@ extern "C" int msc_align_pairs_trace(msc_ctx* ctx, const uint8_t* seqs, const ui
 		uint64_t words = 0;
 		for (uint64_t k = 0; k < n; k++) { at_of[k] = words; words += msc_align_trace_words(pairs[k].la, pairs[k].lb); }
 		std::vector<AlignLaunch> launches;
-		uint64_t scratch_rows = 0;
-		msc_align_plan_full(pairs, launches, scratch_rows);
+		const uint64_t scratch_rows = msc_align_plan_full(pairs, launches);
 		for (uint64_t k = 0; k < n; k++) at[k] = at_of[pairs[k].out - g0];
 		if (scratch_rows) if (int r = ensure(ctx, ctx->align_carry, scratch_rows * sizeof(MscAlignTriple))) return r;
 		HIP_TRY(ctx, hipMemcpyAsync(ctx->align_pairs.p, pairs.data(), n * sizeof(AlignPair), hipMemcpyHostToDevice, ctx->stream));
@@ -222,12 +214,7 @@ extern "C" int msc_align_pairs_trace(msc_ctx* ctx, const uint8_t* seqs, const ui
 		HIP_TRY(ctx, hipGetLastError());
 	}
 	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_all1, ctx->stream));
-	std::vector<int32_t> out(3 * n_pairs);          // (the caller's arrays stay untouched unless every launch went through)
-	HIP_TRY(ctx, hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-	std::copy(out.begin(), out.begin() + n_pairs, score);
-	std::copy(out.begin() + n_pairs, out.begin() + 2 * n_pairs, length);
-	std::copy(out.begin() + 2 * n_pairs, out.end(), matches);
+	if (int r = msc_align_download(ctx, d_out, n_pairs, score, length, matches, nullptr)) return r;
 	std::copy(ends.begin(), ends.end(), op_offsets);
 	ctx->align_trace_n = ends[n_pairs];
 	ctx->last_kernel = lds_carry_last ? "k_align_pairs_dirs<carry in LDS>" : "k_align_pairs_dirs<carry in global memory>";

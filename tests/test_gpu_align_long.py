@@ -240,6 +240,38 @@ def test_an_empty_list_and_the_refusals(ctx):
         api.align_pairs(ctx, [b"A" * 32768, b"AC"], [0], [1])
 
 
+def test_the_short_entries_ignore_the_switches(ctx):
+    """the short entries share the driver of the _long ones with the tile route shut: the two switches must not reach them"""
+    lens = [(1, 1), (1, 600), (600, 1), (63, 64), (255, 300), (256, 256), (256, 17), (257, 257), (257, 599), (511, 130), (513, 40), (600, 600), (300, 256)]
+    seqs, first, second = [], [], []
+    for k, (la, lb) in enumerate(lens):
+        t = synth.template(301 + k, 0, 700)
+        seqs += [synth.to_ascii(t[:la]), synth.to_ascii((synth.member(301 + k, 0, 0, t) if k % 3 else synth.template(301 + k, 1, 600))[:lb])]
+        first.append(2 * k)
+        second.append(2 * k + 1)
+    assert all(len(seqs[2 * k]) == la and len(seqs[2 * k + 1]) == lb for k, (la, lb) in enumerate(lens))
+    calls = ((api.align_pairs, {}, "k_align_pairs<"), (api.align_pairs_banded, dict(band=17), "k_align_band<"), (api.align_pairs_auto, {}, None))
+    with switches():
+        want = [call(ctx, seqs, first, second, **kw) for call, kw, _ in calls]
+        auto_kernel = ctx.last_kernel_info()[0]
+    assert auto_kernel.startswith("k_align_band<") or auto_kernel.startswith("k_align_pairs<"), auto_kernel
+    with switches(long_all=1, tile_rows=16):
+        for (call, kw, kernel), w in zip(calls, want):
+            got = call(ctx, seqs, first, second, **kw)
+            name = ctx.last_kernel_info()[0]
+            assert name.startswith("k_align_pairs<") or name.startswith("k_align_band<"), (call.__name__, name)
+            assert name == auto_kernel if kernel is None else name.startswith(kernel), (call.__name__, name)
+            assert sorted(got) == sorted(w)
+            for key in w:
+                assert np.array_equal(got[key], w[key]), (call.__name__, key, got[key].tolist(), w[key].tolist())
+        # and they keep their limit: a 32 768-byte sequence is refused by name
+        for call, kw, _ in calls:
+            with pytest.raises(api.MscError) as e:
+                call(ctx, [b"A" * 32768, b"AC"], [0], [1], **kw)
+            assert e.value.code == -1, e.value          # MSC_ERR_INVALID_ARG
+            assert call.__name__.replace("align", "msc_align") in str(e.value) and "32767" in str(e.value), str(e.value)
+
+
 def test_fastcar_align_reports_a_40_kb_hit(tmp_path, ctx):
     db, h = synth.families(41, 30, 1000, family=10, length_jitter=150)
     q, hq = synth.families(41, 4, 1000, family=10, length_jitter=150)
