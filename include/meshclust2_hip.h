@@ -183,6 +183,13 @@ int         msc_set_fold_screen(msc_ctx* ctx, int fold);
  * built for up to `cap` consecutive full blocks in one set of launches, a group ahead of the blocks that read it (default 32; 0 at start with
  * MSC_NO_QUERY_GROUPS in the environment). cap = 0 or 1: block by block. Identical results. cap < 0: MSC_ERR_INVALID_ARG. */
 int         msc_set_query_groups(msc_ctx* ctx, int cap);
+/* The folded blocks of msc_score_multi (msc_set_fold_screen) run what follows their product -- the screen, the listed pairs' exact counts, walk and FP64
+ * evaluation, the close counts, the flags' copy home -- once for up to `cap` consecutive full blocks of one query group (default 8; 0 at start with
+ * MSC_NO_TAIL_GROUPS in the environment). The call's final groups halve down to one block (MSC_TAIL_NO_RAMP in the environment: full groups to the end).
+ * cap = 0 or 1: block by block. Identical results and counters. cap < 0: MSC_ERR_INVALID_ARG. */
+int         msc_set_tail_groups(msc_ctx* ctx, int cap);
+/* What the last msc_score_multi call did about it: the tail groups of two blocks and more it ran, and the blocks in them. Any pointer may be null. */
+int         msc_last_tail_groups(const msc_ctx* ctx, uint64_t* groups, uint64_t* grouped_blocks);
 /* What the last msc_score_multi call did about it: the fold used (0: none), the blocks whose product was folded, and those of them that fell
  * back to the true product. Any pointer may be null. */
 int         msc_last_fold_screen(const msc_ctx* ctx, uint64_t* fold, uint64_t* folded_blocks, uint64_t* fell_back);

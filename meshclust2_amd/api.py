@@ -101,6 +101,17 @@ class Context:
         block by block (0 or 1); identical results"""
         self.check(self.lib.msc_set_query_groups(self.h, int(cap)))
 
+    def set_tail_groups(self, cap):
+        """score_multi's folded blocks: what follows the product of up to `cap` consecutive full blocks of one query group in one set of
+        launches (default 8), or block by block (0 or 1); identical results and counters"""
+        self.check(self.lib.msc_set_tail_groups(self.h, int(cap)))
+
+    def last_tail_groups(self):
+        """(groups, grouped_blocks) of the last score_multi call: the tail groups of two blocks and more it ran, and the blocks in them"""
+        v = [C.c_uint64(0) for _ in range(2)]
+        self.check(self.lib.msc_last_tail_groups(self.h, C.byref(v[0]), C.byref(v[1])))
+        return tuple(int(x.value) for x in v)
+
     def last_fold_screen(self):
         """(fold, folded_blocks, fell_back) of the last score_multi call: the fold used (0: none), the blocks whose product was folded and
         those of them whose list of open pairs overflowed and were scored again with the true product"""

@@ -111,6 +111,8 @@ extern "C" int msc_create(int device, msc_ctx** out) {
 		for (hipEvent_t* e : {&pipe.side[i].ev_head, &pipe.side[i].ev_product, &pipe.side[i].ev_tail, &pipe.side[i].ev_prep, &pipe.ev_scored[i], &pipe.ev_copied[i]})
 			ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
 	for (int i = 0; i < 2; i++) ok = ok && hipEventCreateWithFlags(&pipe.arena[i].ev_ready, hipEventDisableTiming) == hipSuccess;
+	for (int i = 0; i < 2; i++)
+		for (hipEvent_t* e : {&pipe.gside[i].ev_product, &pipe.gside[i].ev_tail, &pipe.gside[i].ev_copied}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
 	if (!ok || hipEventCreateWithFlags(&pipe.ev_call, hipEventDisableTiming) != hipSuccess) {
 		delete ctx;
 		return fail(nullptr, MSC_ERR_HIP, "msc_create: stream/event creation failed");
@@ -120,6 +122,8 @@ extern "C" int msc_create(int device, msc_ctx** out) {
 	ctx->emd_bounds = getenv("MSC_NO_EMD_BOUNDS") == nullptr;
 	ctx->fold_screen = getenv("MSC_NO_FOLD") == nullptr ? 16 : 0;
 	ctx->query_groups = getenv("MSC_NO_QUERY_GROUPS") == nullptr ? 32 : 0;
+	ctx->tail_groups = getenv("MSC_NO_TAIL_GROUPS") == nullptr ? 8 : 0;
+	ctx->tail_ramp = getenv("MSC_TAIL_NO_RAMP") == nullptr;
 	*out = ctx;
 	return MSC_OK;
 }
@@ -171,6 +175,8 @@ extern "C" void msc_destroy(msc_ctx* ctx) {
 		for (DevBuf* b : {&sd.qT, &sd.min, &sd.diff, &sd.anib, &sd.hot, &sd.hot_idx, &pipe.close_pp[i], &pipe.arena[i].buf}) release(*b);
 		if (pipe.arena[i].ev_ready) (void)hipEventDestroy(pipe.arena[i].ev_ready);
 		for (hipEvent_t e : {sd.ev_head, sd.ev_product, sd.ev_tail, sd.ev_prep, pipe.ev_scored[i], pipe.ev_copied[i]}) (void)hipEventDestroy(e);
+		release(pipe.gside[i].buf);
+		for (hipEvent_t e : {pipe.gside[i].ev_product, pipe.gside[i].ev_tail, pipe.gside[i].ev_copied}) if (e) (void)hipEventDestroy(e);
 	}
 	for (hipStream_t s : {pipe.copy_stream, pipe.tail_stream, pipe.prep_stream}) (void)hipStreamDestroy(s);
 	(void)hipStreamDestroy(ctx->stream);
@@ -206,6 +212,19 @@ extern "C" int msc_set_emd_bounds(msc_ctx* ctx, int on) {
 extern "C" int msc_set_query_groups(msc_ctx* ctx, int cap) {
 	if (!ctx || cap < 0) return MSC_ERR_INVALID_ARG;
 	ctx->query_groups = (uint32_t)cap;
+	return MSC_OK;
+}
+
+extern "C" int msc_set_tail_groups(msc_ctx* ctx, int cap) {
+	if (!ctx || cap < 0) return MSC_ERR_INVALID_ARG;
+	ctx->tail_groups = (uint32_t)cap;
+	return MSC_OK;
+}
+
+extern "C" int msc_last_tail_groups(const msc_ctx* ctx, uint64_t* groups, uint64_t* grouped_blocks) {
+	if (!ctx) return MSC_ERR_INVALID_ARG;
+	if (groups) *groups = ctx->tail_group_runs;
+	if (grouped_blocks) *grouped_blocks = ctx->tail_group_blocks;
 	return MSC_OK;
 }
 

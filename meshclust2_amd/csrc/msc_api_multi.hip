@@ -133,6 +133,10 @@ struct MultiCall {
 	// its group (-1: the block builds its own queries' side)
 	std::vector<MscQueryGroup> groups;
 	std::vector<int> group_arena, group_of;
+	// msc_set_tail_groups: the tail groups of two blocks and more (msc_tail_groups), the side of the pipe each took (-1: not yet), and per block of the plan
+	// its tail group (-1: the block runs its own tail)
+	std::vector<MscTailGroup> tgroups;
+	std::vector<int> tgroup_side, tgroup_of;
 };
 
 // one block of the call: its queries, its rows of the caller's arrays, and what its route's steps hand one another while it runs
@@ -176,6 +180,7 @@ int flush_deferred(MultiCall& c) {
 		if (e == hipSuccess) e = e2;
 		pipe.tail_used = false;
 		for (BlockPipe::Side& s : pipe.side) s.tail_busy = s.product_busy = false;          // (every product waited for its queries' side: the prep stream is idle too)
+		for (BlockPipe::GroupSide& s : pipe.gside) s.tail_busy = s.product_busy = false;
 	}
 	for (BlockPipe::Arena& a : pipe.arena) a.busy = false;          // (what read them is through; a group built ahead of its blocks stays as it is)
 	for (size_t i = 0; i + 1 < pipe.ev_used; i += 2) {
@@ -558,6 +563,8 @@ int run_streamed(MultiCall& c, Block& b, const BlockRoute& rt) {
 // A flags-only block whose distance comes from the ranks mirrors runs no walk beside the product: its tail is the bound screen, the walk and the FP64 evaluation of
 // the listed pairs, then the dense walk and the two older epilogue kernels predicated on the list's overflow word (msc_emd_list.hip).
 // Such a block in one chunk runs its product over bits folded F-to-1 where both sets carry the folded mirror (msc_fold.h).
+// Consecutive FOLDED blocks of one such group share ONE tail too (plan_tail_groups, tail_group_slot, group_tail; msc_set_tail_groups): their products stay one launch per block,
+// each into its slot of one of two group sides, and the group's last block issues every kernel behind them once, blockIdx.y the block.
 // Consecutive piped blocks of 128 rows share ONE build of the queries' side (plan_query_groups, group_side; msc_set_query_groups): a group's images and lists lie in one of
 // two arenas, built on the prep stream a group ahead of the blocks that read them; such a block's qT, anib and hot list are views into the arena.
 // What a block decides is plain arithmetic (msc_matrix_stages, msc_multi_plan.h) over facts gathered in one place (matrix_facts); run_matrix is the order of the
@@ -630,6 +637,39 @@ void plan_query_groups(MultiCall& c) {
 	c.group_arena.assign(c.groups.size(), -1);
 }
 
+// msc_set_tail_groups: the tail groups of the call's plan (msc_tail_groups, msc_multi_plan.h), inside its query groups -- a block joins on the stage decisions
+// it will take when it runs, as above. MSC_TAIL_NO_RAMP (read when the context is made) keeps full groups to the call's end.
+constexpr uint64_t kTailSideBudget = 1024ull << 20;
+void plan_tail_groups(MultiCall& c) {
+	msc_ctx* ctx = c.ctx;
+	c.tgroups.clear(); c.tgroup_side.clear(); c.tgroup_of.clear();
+	if (ctx->tail_groups < 2 || c.groups.empty()) return;
+	std::vector<MscTailBlock> tb(c.blocks.size(), MscTailBlock{false, -1, 0});
+	size_t next_taken = 0;
+	uint32_t slices_f = 0;
+	for (size_t i = 0; i < c.blocks.size(); i++) {
+		if (!c.blocks[i].matrix) continue;
+		const BlockRoute& rt = c.taken[next_taken++];
+		if (c.group_of[i] < 0) continue;
+		Block b = block_of(c, i);
+		const uint32_t rows = settle_matrix_block(c, b);
+		const MscMatrixStages st = msc_matrix_stages(matrix_facts(c, b, rt, false));
+		const bool joins = st.piped && rows == 128 && b.chunk == c.m && b.close && msc_matrix_chunk(st, b.nq, c.m).tail == MSC_TAIL_FOLDED;
+		tb[i] = MscTailBlock{joins, c.group_of[i], rt.n_hot};
+		if (joins && !slices_f) slices_f = msc_pair_gemm_slices(c.cands->L.nbins / st.fold, (uint32_t)b.chunk, rows, ctx->num_cus);          // (one for all: the blocks of a query group agree on the fold)
+	}
+	if (!slices_f) return;
+	std::vector<MscTailGroup> all;
+	msc_tail_groups(tb, c.m, slices_f, ctx->tail_groups, kTailSideBudget, ctx->tail_ramp, all);
+	c.tgroup_of.assign(c.blocks.size(), -1);
+	for (const MscTailGroup& g : all) {
+		if (g.n < 2) continue;          // (a group of one block: the per-block path)
+		for (size_t i = g.first; i < g.first + g.n; i++) c.tgroup_of[i] = (int)c.tgroups.size();
+		c.tgroups.push_back(g);
+	}
+	c.tgroup_side.assign(c.tgroups.size(), -1);
+}
+
 // a block on the matrix cores: what is settled before anything of it is issued, and what its stages hand one another
 struct MatrixBlock {
 	MscMatrixStages st;                               // the decisions
@@ -643,6 +683,8 @@ struct MatrixBlock {
 	int group = -1;                                   // the block's group of the call (-1: none: the images below are its side's own)
 	const uint8_t *qT = nullptr, *anib = nullptr;     // the queries' images and the entries of the hot list: the side's buffers, or views into the group's arena
 	const void* hot_entries = nullptr;
+	int tgroup = -1;                                  // the block's tail group of the call (-1: none: it runs its own tail, and the arrays below are its side's own)
+	int32_t *out_min = nullptr, *out_diff = nullptr;  // where the product writes P1 and P2: the side's arrays, or the block's slot of its tail group's side
 };
 // a chunk's tail: the epilogue's arguments, and the one of the two buffers its close flags go into
 struct Tail { MscEpilogueArgs ea; int pp = 0; uint8_t* d_close = nullptr; };
@@ -676,6 +718,31 @@ int wait_side_free(msc_ctx* ctx, const MatrixBlock& p) {
 			if (p.prep != ctx->stream && p.group < 0) HIP_TRY(ctx, hipStreamWaitEvent(p.prep, pipe.side[i].ev_tail, 0));          // (it rewrites the transposed image that epilogue read; a grouped block's image is its arena's)
 			if (!p.st.piped) pipe.side[i].tail_busy = false;
 		}
+	for (BlockPipe::GroupSide& g : pipe.gside)          // (the tails of the tail groups are epilogues in flight like any other)
+		if (g.tail_busy && !p.st.piped) { HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, g.ev_tail, 0)); g.tail_busy = false; }
+	return MSC_OK;
+}
+
+// A block of a tail group takes its slot of the group's side. The group's first block takes the side whose turn it is, has the product's stream wait -- once
+// for the group -- for the tail that last read that side, and clears the P2 of all the group's blocks in one call.
+int tail_group_slot(MultiCall& c, const Block& b, MatrixBlock& p) {
+	msc_ctx* ctx = c.ctx;
+	BlockPipe& pipe = ctx->pipe;
+	const MscTailGroup& T = c.tgroups[p.tgroup];
+	int r;
+	if (b.idx == T.first) {
+		const int si = (int)(pipe.gside_next++ & 1);
+		BlockPipe::GroupSide& g = pipe.gside[si];
+		if ((r = ensure(ctx, g.buf, T.bytes))) return r;
+		if (g.tail_busy) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, g.ev_tail, 0));
+		if (T.diff_stride) HIP_TRY(ctx, hipMemsetAsync((uint8_t*)g.buf.p + T.diff_off, 0, T.n * T.diff_stride, ctx->stream));
+		c.tgroup_side[p.tgroup] = si;
+	}
+	BlockPipe::GroupSide& g = pipe.gside[c.tgroup_side[p.tgroup]];
+	const uint64_t j = b.idx - T.first;
+	p.s = &g;
+	p.out_min = (int32_t*)((uint8_t*)g.buf.p + T.min_off + j * T.min_stride);
+	p.out_diff = T.diff_stride ? (int32_t*)((uint8_t*)g.buf.p + T.diff_off + j * T.diff_stride) : nullptr;
 	return MSC_OK;
 }
 
@@ -768,15 +835,17 @@ int group_side(MultiCall& c, const Block& b, MatrixBlock& p) {
 int product_stage(const MultiCall& c, const Block& b, const MatrixBlock& p, const Chunk& k, hipEvent_t ev_t0, hipEvent_t ev_t1) {
 	msc_ctx* ctx = c.ctx;
 	BlockPipe::Side& s = *p.s;
-	if (p.st.piped) {          // everything the tail needs from this stream so far (slot lists, the cleared error word) is behind this mark
+	const bool grouped = p.tgroup >= 0;          // (a tail group's tail waits for its last product, which is behind every such mark: no ev_head)
+	const bool last_of_group = grouped && b.idx + 1 == c.tgroups[p.tgroup].first + c.tgroups[p.tgroup].n;
+	if (p.st.piped && !grouped) {          // everything the tail needs from this stream so far (slot lists, the cleared error word) is behind this mark
 		HIP_TRY(ctx, hipEventRecord(s.ev_head, ctx->stream));
 		HIP_TRY(ctx, hipStreamWaitEvent(b.tail, s.ev_head, 0));
 	}
 	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ev_t0, ctx->stream));
-	HIP_TRY(ctx, msc_launch_pair_gemm(ctx->stream, p.nbins_f, p.st.fold ? c.cands->kbf : c.cands->kb, k.d_slots, k.off, k.mc, p.rows, p.slices_f, p.hot.ptr, p.hot_entries, (int32_t*)s.min.p,
-	                                  (int32_t*)s.diff.p, p.anib));
+	HIP_TRY(ctx, msc_launch_pair_gemm(ctx->stream, p.nbins_f, p.st.fold ? c.cands->kbf : c.cands->kb, k.d_slots, k.off, k.mc, p.rows, p.slices_f, p.hot.ptr, p.hot_entries, p.out_min,
+	                                  p.out_diff, p.anib, grouped));
 	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ev_t1, ctx->stream));
-	if (p.st.piped) { HIP_TRY(ctx, hipEventRecord(s.ev_product, ctx->stream)); s.product_busy = true; }
+	if (p.st.piped && (!grouped || last_of_group)) { HIP_TRY(ctx, hipEventRecord(s.ev_product, ctx->stream)); s.product_busy = true; }
 	return MSC_OK;
 }
 
@@ -902,6 +971,68 @@ void count_chunk(msc_ctx* ctx, const MscMatrixStages& st, const MscMatrixChunk& 
 	if (ck.tail == MSC_TAIL_FOLDED) { ctx->fold_used = st.fold; ctx->fold_blocks++; }
 }
 
+// The folded tail of a whole tail group, issued by its last block b: behind ONE wait for that block's product (the stream ran the group's products in order), the
+// kernels of tail_folded once, blockIdx.y the block of the group (the first block's arguments and the strides of the group's side and of its query group's arena);
+// the lists are closed in block order, the close counts run over the group's rows, and the group's flags -- rows q0 .. of consecutive blocks, contiguous on
+// both sides -- go home in one copy on the copy stream. Lists, their words and the fold_over words stay per block: rerun_overflowed sees what it always saw.
+int group_tail(MultiCall& c, const Block& b, const MatrixBlock& p, const Chunk& k, uint32_t open_cap) {
+	msc_ctx* ctx = c.ctx;
+	BlockPipe& pipe = ctx->pipe;
+	const msc_hist_set *cands = c.cands, *qset = c.qset;
+	const MscLayout& L = cands->L;
+	const MscTailGroup& T = c.tgroups[p.tgroup];
+	const MscQueryGroup& G = c.groups[p.group];
+	BlockPipe::GroupSide& g = pipe.gside[c.tgroup_side[p.tgroup]];
+	hipStream_t tail = pipe.tail_stream;
+	uint8_t* base = (uint8_t*)g.buf.p;
+	if (open_cap != T.list_cap || open_cap > T.list_stride) return fail(ctx, MSC_ERR_HIP, "a tail group's lists are not of the capacity it was planned with");
+	Block b0 = block_of(c, T.first);
+	b0.dq_slots = (const uint32_t*)ctx->qslots_all.p + b0.q0;
+	uint32_t* words = (uint32_t*)(base + T.words_off);
+	if (g.copy_busy) HIP_TRY(ctx, hipStreamWaitEvent(tail, g.ev_copied, 0));          // (the flags of the group that had this side before are home)
+	HIP_TRY(ctx, hipStreamWaitEvent(tail, g.ev_product, 0));
+	HIP_TRY(ctx, hipMemsetAsync(words, 0, T.n * T.words_stride * sizeof(uint32_t), tail));
+	MscEpilogueArgs ea;
+	fill_block_args(c, b0, b0.dq_slots, k, L.S, ea);
+	ea.kb_min = (const int32_t*)(base + T.min_off);
+	ea.kb_diff = T.diff_stride ? (const int32_t*)(base + T.diff_off) : nullptr;
+	ea.kb_slices = p.slices_f; ea.kb_qn = p.rows; ea.kb_first = c.cand_slots ? 0 : k.off;
+	ea.kb_c_mb = cands->mb; ea.kb_c_mb_n = cands->mb_n; ea.kb_c_pitch = cands->mb_pitch;
+	ea.kb_q_mb = qset->mb; ea.kb_q_mb_n = qset->mb_n; ea.kb_q_pitch = qset->mb_pitch;
+	ea.kb_qT = p.qT - (b.idx - T.first) * G.qt_stride;
+	ea.emd_stride = p.rows;
+	ea.cq_group = 16;
+	ea.close_soa = base + T.flags_off;
+	ea.screen = p.st.screen;
+	ea.rk_c_sum = cands->rk_sum; ea.rk_c_dev = cands->rk_dev; ea.rk_q_sum = qset->rk_sum; ea.rk_q_dev = qset->rk_dev;
+	ea.open_list = (uint32_t*)(base + T.list_off); ea.open_words = words; ea.open_cap = open_cap; ea.emd_list = (const uint64_t*)(base + T.emd_off);
+	ea.fold_x_c = cands->kbf_x; ea.fold_x_q = qset->kbf_x;
+	ea.tg_blocks = (uint32_t)T.n;
+	ea.tg_min_stride = T.min_stride; ea.tg_diff_stride = T.diff_stride; ea.tg_qt_stride = G.qt_stride; ea.tg_flags_stride = T.flags_stride;
+	ea.tg_list_stride = T.list_stride; ea.tg_q_stride = 128; ea.tg_words_stride = (uint32_t)T.words_stride;
+	const MscListGroup lg{(uint32_t)T.n, 128, (uint32_t)T.words_stride, T.list_stride, G.qt_stride, T.min_stride, T.diff_stride};
+	const bool u16 = cands->ranks16 && qset->ranks16;
+	HIP_TRY(ctx, msc_launch_epilogue_bound(tail, ea));
+	const MscFoldExact fx{cands->ranks, cands->rk_pitch, L.nbins, L.E, L.R, k.d_slots, k.off, k.mc, b0.dq_slots, ea.open_list, words, open_cap, ea.kb_qT, p.rows,
+	                      qset->mb, qset->mb_n, qset->mb_pitch, (int32_t*)(base + T.min_off), ea.kb_slices, T.diff_stride ? (int32_t*)(base + T.diff_off) : nullptr};
+	HIP_TRY(ctx, msc_launch_fold_exact_list(tail, fx, ctx->num_cus, &lg));
+	HIP_TRY(ctx, msc_launch_emd_ranks_list(tail, u16, u16 ? (const void*)cands->ranks16 : (const void*)cands->ranks, u16 ? (const void*)qset->ranks16 : (const void*)qset->ranks,
+	                                       cands->rk_pitch, k.d_slots, k.off, k.mc, b0.dq_slots, ea.open_list, words, open_cap, (uint64_t*)(base + T.emd_off), ctx->num_cus, &lg));
+	HIP_TRY(ctx, msc_launch_epilogue_list(tail, ea, ctx->num_cus));
+	HIP_TRY(ctx, msc_launch_emd_list_close(tail, words, open_cap, (uint64_t*)((uint32_t*)ctx->open_words.p + 2), (uint32_t*)ctx->fold_over.p + T.first, (uint32_t)T.n, (uint32_t)T.words_stride));
+	if (ctx->close_counts_n) HIP_TRY(ctx, msc_launch_close_counts(tail, ea.close_soa, (uint32_t)(T.n * 128), k.mc, (uint64_t*)ctx->close_counts.p + b0.q0));
+	HIP_TRY(ctx, hipEventRecord(g.ev_tail, tail));
+	g.tail_busy = true;
+	pipe.tail_used = true;
+	HIP_TRY(ctx, hipStreamWaitEvent(pipe.copy_stream, g.ev_tail, 0));
+	HIP_TRY(ctx, hipMemcpyAsync(b0.close, ea.close_soa, T.n * T.flags_stride, hipMemcpyDeviceToHost, pipe.copy_stream));
+	HIP_TRY(ctx, hipEventRecord(g.ev_copied, pipe.copy_stream));
+	g.copy_busy = true;
+	pipe.copy_pending = true;
+	ctx->tail_group_runs++; ctx->tail_group_blocks += T.n;
+	return MSC_OK;
+}
+
 // candidates [off, off + b.chunk) of the block: the product, one of the three tails, the results' way home
 int matrix_chunk(MultiCall& c, Block& b, const MatrixBlock& p, uint64_t off) {
 	msc_ctx* ctx = c.ctx;
@@ -915,6 +1046,13 @@ int matrix_chunk(MultiCall& c, Block& b, const MatrixBlock& p, uint64_t off) {
 	if ((r = product_stage(c, b, p, k, ev_t0, ev_t1))) return r;
 	const MscMatrixChunk ck = msc_matrix_chunk(p.st, b.nq, k.mc);
 	count_chunk(ctx, p.st, ck);
+	if (p.tgroup >= 0) {          // the tail is its group's: issued behind the product of the group's last block
+		const MscTailGroup& T = c.tgroups[p.tgroup];
+		if (b.idx + 1 == T.first + T.n && (r = group_tail(c, b, p, k, ck.open_cap))) return r;
+		if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_all1, ctx->stream));
+		ctx->tiles_launches++;
+		return MSC_OK;
+	}
 	Tail t;
 	switch (ck.tail) {
 		case MSC_TAIL_SCORED: r = tail_scored(c, b, p, k, t); break;
@@ -947,14 +1085,19 @@ int run_matrix(MultiCall& c, Block& b, const BlockRoute& rt, bool second_run = f
 	MatrixBlock p = plan_matrix(c, b, rt, rows, second_run);
 	p.group = second_run || c.group_of.empty() ? -1 : c.group_of[b.idx];
 	if (p.group >= 0 && (!p.st.piped || rows != 128 || p.st.fold != c.groups[p.group].fold)) return fail(ctx, MSC_ERR_HIP, "a grouped block's stages are not those its group was planned with");
-	if ((r = wait_side_free(ctx, p))) return r;
+	p.tgroup = p.group < 0 || c.tgroup_of.empty() ? -1 : c.tgroup_of[b.idx];
+	if (p.tgroup >= 0 && (msc_matrix_chunk(p.st, b.nq, c.m).tail != MSC_TAIL_FOLDED || b.chunk != c.m)) return fail(ctx, MSC_ERR_HIP, "a block's tail is not the one its tail group was planned with");
+	if (p.tgroup < 0 && (r = wait_side_free(ctx, p))) return r;
 	// (a folded block passes the true bin count and the larger of the two slice counts)
-	if (p.group >= 0) {
+	if (p.tgroup >= 0) {
+		if ((r = tail_group_slot(c, b, p)) || (r = group_side(c, b, p))) return r;
+	} else if (p.group >= 0) {
 		if ((r = ensure_products(ctx, *p.s, rows, std::max(p.slices, p.slices_f), b.chunk, rt.n_hot)) || (r = group_side(c, b, p))) return r;
 	} else {
 		if ((r = ensure_side(ctx, *p.s, nbins, rows, std::max(p.slices, p.slices_f), b.chunk, rt.n_hot, &p.hot)) || (r = queries_side(c, b, p))) return r;
 		p.qT = (const uint8_t*)p.s->qT.p; p.anib = (const uint8_t*)p.s->anib.p; p.hot_entries = p.s->hot.p;
 	}
+	if (p.tgroup < 0) { p.out_min = (int32_t*)p.s->min.p; p.out_diff = (int32_t*)p.s->diff.p; }
 	if (rt.emd_ranks && (r = ensure(ctx, ctx->emd_out, b.chunk * rows * sizeof(uint64_t)))) return r;
 	name_matrix_kernel(ctx, rows, rt.emd_ranks, c.cells, c.cands->sparse, p.st.fold);
 	ctx->last_query_tile = (int)b.nq;
@@ -1012,6 +1155,7 @@ int rerun_overflowed(MultiCall& c, const std::vector<BlockRoute>& route_of) {
 // The call's counters (msc_last_emd_walk, msc_last_fold_screen) start from zero ...
 void clear_call_counters(msc_ctx* ctx) {
 	ctx->walk_listed = ctx->walk_dense = ctx->walk_blocks = ctx->walk_bound_blocks = ctx->fold_used = ctx->fold_blocks = ctx->fold_fell_back = 0;
+	ctx->tail_group_runs = ctx->tail_group_blocks = 0;
 }
 
 // ... and take the totals of the bound pass when the call is through (every stream of the call is idle: the error word has been read)
@@ -1100,6 +1244,7 @@ int score_multi(MultiCall& c) {
 	}, c.blocks);
 	if (err) return err;
 	plan_query_groups(c);
+	plan_tail_groups(c);
 	size_t next_taken = 0;
 	std::vector<BlockRoute> route_of(c.blocks.size());
 	for (size_t i = 0; i < c.blocks.size(); i++) {
@@ -1147,7 +1292,7 @@ extern "C" int msc_score_multi(msc_ctx* ctx, const msc_model* model, const msc_h
 	if (ctx && r == MSC_OK) r = read_call_totals(ctx, model);
 	if (ctx && ctx->pipe.copy_pending) {          // the flag copies of the last blocks (issued beside the kernels that followed them)
 		const hipError_t e = hipStreamSynchronize(ctx->pipe.copy_stream);
-		ctx->pipe.copy_pending = ctx->pipe.close_pp_busy[0] = ctx->pipe.close_pp_busy[1] = false;
+		ctx->pipe.copy_pending = ctx->pipe.close_pp_busy[0] = ctx->pipe.close_pp_busy[1] = ctx->pipe.gside[0].copy_busy = ctx->pipe.gside[1].copy_busy = false;
 		if (e != hipSuccess && r == MSC_OK) return fail(ctx, MSC_ERR_HIP, "copy of the close flags failed: %s", hipGetErrorString(e));
 	}
 	return r;

@@ -50,7 +50,9 @@ __global__ void __launch_bounds__(256) k_rank_moments(const uint32_t* __restrict
 template <bool kU16>
 __global__ void __launch_bounds__(256) k_emd_ranks_list(const void* __restrict__ c_rk, const void* __restrict__ q_rk, uint64_t pitch, const uint32_t* __restrict__ cand_slots, uint64_t first,
                                                         uint32_t m_per_query, const uint32_t* __restrict__ q_slots, const uint32_t* __restrict__ list, const uint32_t* __restrict__ words,
-                                                        uint32_t cap, uint64_t* __restrict__ emd_list) {
+                                                        uint32_t cap, uint64_t* __restrict__ emd_list, const MscListGroup g) {
+	// (a group of blocks, msc_tail_groups: blockIdx.y is the block; its query slots, list, words and distances lie that many strides on -- all 0 for one block)
+	q_slots += (uint64_t)blockIdx.y * g.q_stride; list += blockIdx.y * g.list_stride; words += (uint64_t)blockIdx.y * g.words_stride; emd_list += blockIdx.y * g.list_stride;
 	if (words[1]) return;
 	const uint32_t n = words[0] < cap ? words[0] : cap;
 	const uint32_t lane = threadIdx.x & 63;
@@ -99,7 +101,12 @@ __global__ void __launch_bounds__(256) k_emd_ranks_list(const void* __restrict__
 // mirror -- its k-mers as LOGICAL bins in order, a bin repeated per copy, padded with 4^k --, takes each distinct bin once, reads the query's two
 // bits at the bin's physical position from the transposed planes (plane 0: the query holds the k-mer; plane 1: more than once, and its own list
 // of large bins has the count), and stores P1 into slice 0 of the product's output (zeros into the other slices) and P2 beside it.
-__global__ void __launch_bounds__(256) k_fold_exact_list(const MscFoldExact a) {
+__global__ void __launch_bounds__(256) k_fold_exact_list(const MscFoldExact a_, const MscListGroup g) {
+	MscFoldExact a = a_;          // (a group of blocks, as k_emd_ranks_list takes it: the block's offsets once, wave-uniform)
+	a.q_slots += (uint64_t)blockIdx.y * g.q_stride; a.list += blockIdx.y * g.list_stride; a.words += (uint64_t)blockIdx.y * g.words_stride;
+	a.qT += blockIdx.y * g.qt_stride;
+	a.out_min = reinterpret_cast<int32_t*>(reinterpret_cast<uint8_t*>(a.out_min) + blockIdx.y * g.min_stride);
+	if (a.out_diff) a.out_diff = reinterpret_cast<int32_t*>(reinterpret_cast<uint8_t*>(a.out_diff) + blockIdx.y * g.diff_stride);
 	if (a.words[1]) return;
 	const uint32_t n = a.words[0] < a.cap ? a.words[0] : a.cap;
 	const uint32_t lane = threadIdx.x & 63;
@@ -132,16 +139,27 @@ __global__ void __launch_bounds__(256) k_fold_exact_list(const MscFoldExact a) {
 // blocks whose list overflowed) and are cleared for the next block.
 // fold_flag: the block's product was folded (msc_api_multi.hip). An overflow of ITS list is no dense block: totals[2] counts it and the flag tells the
 // host, when the call's blocks are through, to score the block again with the true product.
-__global__ void k_emd_list_close(uint32_t* __restrict__ words, uint32_t cap, unsigned long long* __restrict__ totals, uint32_t* __restrict__ fold_flag) {
+// n_blocks > 1: the lists of a group's blocks (msc_tail_groups), one after the other in block order, so that the totals add up in the order of per-block launches.
+__global__ void k_emd_list_close(uint32_t* __restrict__ words, uint32_t cap, unsigned long long* __restrict__ totals, uint32_t* __restrict__ fold_flag, uint32_t n_blocks,
+                                 uint32_t words_stride) {
 	if (threadIdx.x || blockIdx.x) return;
-	if (fold_flag && words[1]) { totals[2] += 1; *fold_flag = 1; }
-	else if (words[1]) totals[1] += 1;
-	else totals[0] += words[0] < cap ? words[0] : cap;
-	words[0] = 0;
-	words[1] = 0;
+	for (uint32_t j = 0; j < n_blocks; j++, words += words_stride) {
+		if (fold_flag && words[1]) { totals[2] += 1; fold_flag[j] = 1; }
+		else if (words[1]) totals[1] += 1;
+		else totals[0] += words[0] < cap ? words[0] : cap;
+		words[0] = 0;
+		words[1] = 0;
+	}
 }
 
 }  // namespace
+
+// one wave per listed pair: four to a workgroup, at most num_cus * 8 workgroups. A group of blocks takes that many for its TOTAL capacity, shared out over
+// blockIdx.y -- not a block's grid times the group
+static dim3 list_grid(uint32_t cap, uint32_t n_blocks, int num_cus) {
+	const uint64_t n = std::max<uint32_t>(n_blocks, 1), all = std::min<uint64_t>(n * (((uint64_t)cap + 3) / 4), (uint64_t)num_cus * 8);
+	return dim3((unsigned)std::max<uint64_t>(1, (all + n - 1) / n), (unsigned)n);
+}
 
 // the two moments of slots [first_slot, first_slot + n_slots) from their 32-bit ranks
 hipError_t msc_launch_rank_moments(hipStream_t st, uint64_t nbins, const uint32_t* ranks, uint64_t pitch, uint64_t first_slot, uint64_t n_slots, uint64_t* rk_sum, uint64_t* rk_dev) {
@@ -152,24 +170,26 @@ hipError_t msc_launch_rank_moments(hipStream_t st, uint64_t nbins, const uint32_
 
 // emd_list[i] = the distance of listed pair i, i < min(words[0], cap); two sets of one pitch. u16: both rows are the 16-bit form
 hipError_t msc_launch_emd_ranks_list(hipStream_t st, bool u16, const void* c_ranks, const void* q_ranks, uint64_t pitch, const uint32_t* cand_slots, uint64_t first, uint32_t m_per_query,
-                                     const uint32_t* q_slots_dev, const uint32_t* list, const uint32_t* words, uint32_t cap, uint64_t* emd_list, int num_cus) {
+                                     const uint32_t* q_slots_dev, const uint32_t* list, const uint32_t* words, uint32_t cap, uint64_t* emd_list, int num_cus,
+                                     const MscListGroup* grp) {
 	if (cap == 0) return hipSuccess;
 	if (pitch % (u16 ? 1024 : 256) || m_per_query == 0) return hipErrorInvalidValue;
-	const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)cap + 3) / 4, (uint64_t)num_cus * 8);
-	if (u16) k_emd_ranks_list<true><<<dim3(grid), dim3(256), 0, st>>>(c_ranks, q_ranks, pitch, cand_slots, first, m_per_query, q_slots_dev, list, words, cap, emd_list);
-	else k_emd_ranks_list<false><<<dim3(grid), dim3(256), 0, st>>>(c_ranks, q_ranks, pitch, cand_slots, first, m_per_query, q_slots_dev, list, words, cap, emd_list);
+	const MscListGroup g = grp ? *grp : MscListGroup{1, 0, 0, 0, 0, 0, 0};
+	const dim3 grid = list_grid(cap, g.n_blocks, num_cus);
+	if (u16) k_emd_ranks_list<true><<<grid, dim3(256), 0, st>>>(c_ranks, q_ranks, pitch, cand_slots, first, m_per_query, q_slots_dev, list, words, cap, emd_list, g);
+	else k_emd_ranks_list<false><<<grid, dim3(256), 0, st>>>(c_ranks, q_ranks, pitch, cand_slots, first, m_per_query, q_slots_dev, list, words, cap, emd_list, g);
 	return hipGetLastError();
 }
 
-hipError_t msc_launch_fold_exact_list(hipStream_t st, const MscFoldExact& a, int num_cus) {
+hipError_t msc_launch_fold_exact_list(hipStream_t st, const MscFoldExact& a, int num_cus, const MscListGroup* grp) {
 	if (a.cap == 0) return hipSuccess;
 	if (a.m_per_query == 0 || a.slices == 0 || a.slices > 64 || !a.c_ranks || !a.qT || !a.out_min) return hipErrorInvalidValue;
-	const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)a.cap + 3) / 4, (uint64_t)num_cus * 8);
-	k_fold_exact_list<<<dim3(grid), dim3(256), 0, st>>>(a);
+	const MscListGroup g = grp ? *grp : MscListGroup{1, 0, 0, 0, 0, 0, 0};
+	k_fold_exact_list<<<list_grid(a.cap, g.n_blocks, num_cus), dim3(256), 0, st>>>(a, g);
 	return hipGetLastError();
 }
 
-hipError_t msc_launch_emd_list_close(hipStream_t st, uint32_t* words, uint32_t cap, uint64_t* totals, uint32_t* fold_flag) {
-	k_emd_list_close<<<dim3(1), dim3(64), 0, st>>>(words, cap, (unsigned long long*)totals, fold_flag);
+hipError_t msc_launch_emd_list_close(hipStream_t st, uint32_t* words, uint32_t cap, uint64_t* totals, uint32_t* fold_flag, uint32_t n_blocks, uint32_t words_stride) {
+	k_emd_list_close<<<dim3(1), dim3(64), 0, st>>>(words, cap, (unsigned long long*)totals, fold_flag, n_blocks, words_stride);
 	return hipGetLastError();
 }

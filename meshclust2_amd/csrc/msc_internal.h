@@ -161,6 +161,11 @@ struct MscEpilogueArgs {
 	// k_pair_epilogue_bits_bound on a FOLDED block (msc_fold.h): kb_min / kb_diff then hold P1' / P2' of the folded product, upper bounds of P1 / P2
 	// with each slot's own collisions added (fold_x_c: by candidate slot, fold_x_q: by query slot); null: the product was exact
 	const uint32_t *fold_x_c, *fold_x_q;
+	// k_pair_epilogue_bits_bound / _list over a GROUP of blocks of 128 query rows (msc_tail_groups, msc_multi_plan.h): blockIdx.y is the block of the group,
+	// and its kb_min, kb_diff, kb_qT, close_soa (bytes), q_slots, open_list and emd_list (entries), open_words (words) lie that many strides behind the
+	// first block's; tg_blocks is their number, the launch's gridDim.y. All 0: a launch over one block
+	uint64_t tg_min_stride, tg_diff_stride, tg_qt_stride, tg_flags_stride, tg_list_stride;
+	uint32_t tg_q_stride, tg_words_stride, tg_blocks;
 };
 
 // ---------------------------------------------------------------- launchers (defined in the .hip kernel files)
@@ -237,10 +242,16 @@ hipError_t msc_launch_emd_ranks16(hipStream_t st, uint64_t nbins, const uint16_t
 // msc_emd_list.hip: two moments per slot of the ranks mirror that bound the distance of a pair, the exact distances of a device list of pairs, and the
 // bookkeeping of that list (words = {pairs appended, overflow}; totals = {pairs walked, blocks that overflowed} of a call)
 hipError_t msc_launch_rank_moments(hipStream_t st, uint64_t nbins, const uint32_t* ranks, uint64_t pitch, uint64_t first_slot, uint64_t n_slots, uint64_t* rk_sum, uint64_t* rk_dev);
+// The list kernels over a GROUP of blocks of 128 query rows (msc_tail_groups, msc_multi_plan.h): blockIdx.y is the block of the group, whose query slots, list,
+// emd_list (entries), words, transposed planes, P1 and P2 (bytes) lie that many strides behind the first block's. The grid is sized for the group's
+// total capacity. n_blocks 0 or 1 with every stride 0: a launch over one block
+struct MscListGroup { uint32_t n_blocks, q_stride, words_stride; uint64_t list_stride, qt_stride, min_stride, diff_stride; };
 hipError_t msc_launch_emd_ranks_list(hipStream_t st, bool u16, const void* c_ranks, const void* q_ranks, uint64_t pitch, const uint32_t* cand_slots, uint64_t first, uint32_t m_per_query,
-                                     const uint32_t* q_slots_dev, const uint32_t* list, const uint32_t* words, uint32_t cap, uint64_t* emd_list, int num_cus);
+                                     const uint32_t* q_slots_dev, const uint32_t* list, const uint32_t* words, uint32_t cap, uint64_t* emd_list, int num_cus,
+                                     const MscListGroup* grp = nullptr);
 // (fold_flag: null, or the word of a FOLDED block: set when its list overflowed, which totals[2] counts instead of totals[1])
-hipError_t msc_launch_emd_list_close(hipStream_t st, uint32_t* words, uint32_t cap, uint64_t* totals, uint32_t* fold_flag = nullptr);
+// n_blocks > 1: the lists of a group's blocks, closed in block order in one launch -- block j's words at words + j * words_stride, its flag at fold_flag + j
+hipError_t msc_launch_emd_list_close(hipStream_t st, uint32_t* words, uint32_t cap, uint64_t* totals, uint32_t* fold_flag = nullptr, uint32_t n_blocks = 1, uint32_t words_stride = 0);
 // the exact P1 / P2 of the listed pairs of a folded block, from the candidate's row of the 32-bit ranks mirror and the queries' transposed planes
 struct MscFoldExact {
 	const uint32_t* c_ranks; uint64_t pitch; uint64_t nbins; uint32_t E, R;
@@ -250,7 +261,7 @@ struct MscFoldExact {
 	const void* q_mb; const uint32_t* q_mb_n; uint32_t q_pitch;
 	int32_t* out_min; uint32_t slices; int32_t* out_diff;
 };
-hipError_t msc_launch_fold_exact_list(hipStream_t st, const MscFoldExact& a, int num_cus);
+hipError_t msc_launch_fold_exact_list(hipStream_t st, const MscFoldExact& a, int num_cus, const MscListGroup* grp = nullptr);
 // the r04 form of that pass (msc_pair_gemm.hip): presence-bit mirror + lists of large bins, the queries' side of a block, the product
 uint64_t msc_kb_bytes(const MscLayout& L, uint64_t capacity);
 hipError_t msc_launch_kb_build(hipStream_t st, const MscLayout& L, int dtype, const uint8_t* bins, uint8_t* kb, uint64_t first_slot, uint64_t n_slots, void* mb,
@@ -296,7 +307,7 @@ hipError_t msc_launch_pair_gemm_queries(hipStream_t st, uint64_t nbins, const ui
                                         const uint32_t* q_slots_dev, uint32_t n_q, uint32_t qn, uint8_t* qT, uint64_t n_hot, void* hot, uint32_t* hot_ptr,
                                         uint32_t* hot_cursor, uint32_t* hot_cnt, uint8_t* anib);
 hipError_t msc_launch_pair_gemm(hipStream_t st, uint64_t nbins, const uint8_t* cand_kb, const uint32_t* cand_slots, uint64_t first, uint32_t m, uint32_t qn,
-                                uint32_t k_slices, const uint32_t* hot_ptr, const void* hot, int32_t* out_min, int32_t* out_diff, const uint8_t* anib);
+                                uint32_t k_slices, const uint32_t* hot_ptr, const void* hot, int32_t* out_min, int32_t* out_diff, const uint8_t* anib, bool diff_zeroed = false);
 // the folded mirror of a set (msc_fold.h) and the two parts of the queries' side on their own
 hipError_t msc_launch_kb_fold(hipStream_t st, uint64_t nbins, uint32_t fold, const uint8_t* kb, uint8_t* kbf, uint32_t* x, uint64_t first_slot, uint64_t n_slots);
 hipError_t msc_launch_kb_gather(hipStream_t st, uint64_t nbins, const uint8_t* q_kb, const uint32_t* q_slots_dev, uint32_t n_q, uint32_t qn, uint8_t* qT, uint8_t* anib);

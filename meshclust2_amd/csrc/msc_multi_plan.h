@@ -141,3 +141,69 @@ inline void msc_query_groups(const std::vector<MscGroupBlock>& blocks, uint64_t 
 		i += g.n;
 	}
 }
+
+// ---- the folded tail of several blocks in one set of launches (msc_set_tail_groups; group_tail, msc_api_multi.hip). The products stay one launch per
+// block; what runs behind them -- bound screen, the listed pairs' exact counts, walk and FP64 evaluation, the closing kernel, the close counts, the
+// flags' copy home -- runs once for a TAIL GROUP: a run of consecutive blocks that each `joins` (piped, 128 query rows, in a query group, not a second
+// run, one chunk, the folded tail) and lie in ONE query group (their qT sit at one stride in its arena). A group's arrays lie in one buffer (two such
+// sides take turns), region by region, block j at a region's offset + j strides:
+//   min     P1 of the product, every slice                    slices x m x 128 int32
+//   diff    P2 (only where a block of the group has a hot list)        m x 128 int32
+//   flags   the close flags, query-major: the group's rows are contiguous, here and at the caller's        128 x m bytes
+//   list, emd   the open pairs and their distances            128 m / 64 entries each (the stride rounded up to 4 entries)
+//   words   {count, overflow} of a block's list               4 words a block (two used)
+// Size of a group: at most `cap` blocks, at most what `budget` bytes hold, at most what keeps n x 128 x m pairs within msc_list_pairs_fit (never
+// fewer than one block: a group of one is left to the per-block path, as is every block with cap < 2). Every offset and stride is a multiple of 16 bytes.
+// ramp: a group's flags leave on the copy stream under the NEXT group's kernels, so the last group's copy is exposed. The call's final `cap` blocks
+// are therefore cut cap/2, cap/4, ..., 1 and the one left over alone: no group crosses a point where cap, cap/2, cap/4, ..., 1 blocks of the call remain.
+struct MscTailBlock { bool joins; int qgroup; uint64_t n_hot; };          // qgroup: the block's query group of the call (-1: none, and then it does not join)
+struct MscTailGroup {
+	size_t first = 0, n = 0;                 // blocks [first, first + n) of the plan
+	uint32_t list_cap = 0;                   // entries a block's list holds: 128 m / 64
+	uint64_t min_stride = 0, diff_stride = 0, flags_stride = 0;          // bytes (diff_stride 0: no block of the group has a hot list)
+	uint64_t list_stride = 0, words_stride = 0;                          // entries of list and emd; words
+	uint64_t min_off = 0, diff_off = 0, flags_off = 0, list_off = 0, emd_off = 0, words_off = 0, bytes = 0;          // byte offsets of the regions; the side's size
+};
+
+inline uint64_t msc_tail_list_stride(uint64_t m) { return (128 * m / 64 + 3) / 4 * 4; }
+inline uint64_t msc_tail_block_bytes(uint64_t m, uint32_t slices, bool diff) {
+	return (uint64_t)slices * m * 128 * sizeof(int32_t) + (diff ? m * 128 * sizeof(int32_t) : 0) + 128 * m + msc_tail_list_stride(m) * (sizeof(uint32_t) + sizeof(uint64_t)) + 4 * sizeof(uint32_t);
+}
+
+inline void msc_tail_groups(const std::vector<MscTailBlock>& blocks, uint64_t m, uint32_t slices, uint32_t cap, uint64_t budget, bool ramp, std::vector<MscTailGroup>& out) {
+	out.clear();
+	if (m == 0 || slices == 0) return;
+	const size_t total = blocks.size();
+	const uint64_t pairs_fit = 0xffffffffull / (128 * m);          // blocks whose pairs the 32-bit row arithmetic of one launch holds
+	for (size_t i = 0; i < total;) {
+		if (!blocks[i].joins || blocks[i].qgroup < 0) { i++; continue; }
+		uint64_t limit = std::max<uint32_t>(cap, 1);
+		if (ramp && cap >= 2) {          // the nearest of the points cap, cap/2, ..., 1, 0 (blocks that remain) ahead of this block
+			const uint64_t left = total - i;
+			uint64_t stop = cap;
+			while (stop >= left) stop /= 2;
+			limit = std::min<uint64_t>(limit, left - stop);
+		}
+		size_t end = i;
+		while (end < total && end - i < limit && blocks[end].joins && blocks[end].qgroup == blocks[i].qgroup) end++;
+		auto any_hot = [&](size_t n) { for (size_t j = i; j < i + n; j++) if (blocks[j].n_hot) return true; return false; };
+		const uint64_t fit = budget / msc_tail_block_bytes(m, slices, any_hot(end - i));          // (with P2 if any block of the run has a hot list: a shorter group needs no more)
+		MscTailGroup g;
+		g.first = i;
+		g.n = (size_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(end - i, fit), pairs_fit));
+		g.list_cap = (uint32_t)(128 * m / 64);
+		g.min_stride = (uint64_t)slices * m * 128 * sizeof(int32_t);
+		g.diff_stride = any_hot(g.n) ? m * 128 * sizeof(int32_t) : 0;
+		g.flags_stride = 128 * m;
+		g.list_stride = msc_tail_list_stride(m); g.words_stride = 4;
+		g.min_off = 0;
+		g.diff_off = g.min_off + g.n * g.min_stride;
+		g.flags_off = g.diff_off + g.n * g.diff_stride;
+		g.list_off = g.flags_off + g.n * g.flags_stride;
+		g.emd_off = g.list_off + g.n * g.list_stride * sizeof(uint32_t);
+		g.words_off = g.emd_off + g.n * g.list_stride * sizeof(uint64_t);
+		g.bytes = g.words_off + g.n * g.words_stride * sizeof(uint32_t);
+		out.push_back(g);
+		i += g.n;
+	}
+}

@@ -41,6 +41,16 @@ struct BlockPipe {
 		bool busy = false;
 	} arena[2];
 	uint32_t arena_next = 0;               // the arena the next group takes (its low bit)
+	// The folded tail of a TAIL GROUP of blocks in one set of launches (msc_set_tail_groups; msc_tail_groups in msc_multi_plan.h lays a side out): P1, P2, flags,
+	// lists and list words of the group's blocks in one buffer, two such sides taking turns. A block of the group issues its product into its slot; the
+	// group's last block issues the tail on tail_stream and the flags' copy home on copy_stream. The events are a Side's: ev_product the last product
+	// issued into the side, ev_tail the tail that read it; ev_copied the flags' copy
+	struct GroupSide : Side {
+		DevBuf buf;
+		hipEvent_t ev_copied = nullptr;
+		bool copy_busy = false;
+	} gside[2];
+	uint32_t gside_next = 0;               // the side the next tail group takes (its low bit)
 	hipStream_t tail_stream = nullptr, prep_stream = nullptr, copy_stream = nullptr;
 	hipEvent_t ev_call = nullptr;          // the call's query slots are on the device
 	// the close flags of a block go back to the host on copy_stream, under the next block's kernels: two device buffers take turns, and
@@ -97,6 +107,9 @@ struct msc_ctx {
 	BlockPipe pipe;                        // msc_pair_gemm.hip: the queries' side of a block and the streams its stages run on
 	bool block_pipe = true;                // msc_set_block_pipe: the blocks of msc_score_multi on three streams
 	uint32_t query_groups = 32;            // msc_set_query_groups / MSC_NO_QUERY_GROUPS: most blocks whose queries' side one set of launches builds (0, 1: block by block)
+	uint32_t tail_groups = 8;              // msc_set_tail_groups / MSC_NO_TAIL_GROUPS: most folded blocks whose tail one set of launches runs (0, 1: block by block)
+	uint64_t tail_group_runs = 0, tail_group_blocks = 0;          // msc_last_tail_groups: the last call's
+	bool tail_ramp = true;                 // ... the call's final groups halve down to one block (MSC_TAIL_NO_RAMP: full groups to the end, for A/B runs)
 	bool pairs_div_cells = false;          // msc_set_pairs_div_cells: msc_search_pairs keeps divergence-statistic models on the matrix-core route
 	bool multi_div_cells = false;          // msc_set_multi_div_cells: msc_score_multi keeps blocks that want a divergence statistic on the matrix-core route, no merge pass
 	bool sparse_matrix_pass = false;       // msc_set_sparse_matrix_pass: two sparse sets may take the matrix-core Q x M route (mirrors built from their lists)

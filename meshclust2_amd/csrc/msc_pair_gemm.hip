@@ -732,11 +732,12 @@ hipError_t msc_launch_query_group(hipStream_t st, uint64_t nbins, uint32_t fold,
 
 // P1 [k_slices][m][qn] and, with a hot list, P2 [m][qn] (zeroed here) of the block's queries against m candidates (slot list, or slots
 // first .. first + m - 1) of the mirror cand_kb (a folded block: of the folded mirror, nbins = its bin count)
+// diff_zeroed: the caller has cleared out_diff on this stream (a tail group clears the P2 of all its blocks in one call)
 hipError_t msc_launch_pair_gemm(hipStream_t st, uint64_t nbins, const uint8_t* cand_kb, const uint32_t* cand_slots, uint64_t first, uint32_t m, uint32_t qn,
-                                uint32_t k_slices, const uint32_t* hot_ptr, const void* hot, int32_t* out_min, int32_t* out_diff, const uint8_t* anib) {
+                                uint32_t k_slices, const uint32_t* hot_ptr, const void* hot, int32_t* out_min, int32_t* out_diff, const uint8_t* anib, bool diff_zeroed) {
 	if (m == 0) return hipSuccess;
 	if (k_slices == 0 || nbins % ((uint64_t)k_slices * 2 * kStep)) return hipErrorInvalidValue;
-	if (hot_ptr) {
+	if (hot_ptr && !diff_zeroed) {
 		const hipError_t e = hipMemsetAsync(out_diff, 0, (size_t)m * qn * sizeof(int32_t), st);
 		if (e != hipSuccess) return e;
 	}

@@ -1582,8 +1582,26 @@ __global__ void __launch_bounds__(kBlock, 5) k_pair_epilogue_bits_open(const Msc
 // bits_pair_totals forms the corner P1 = P2 = 0; the other corner adds U1 -- cut to min(sum e_c, sum e_q) less the lists' part of sum min, which
 // sum min cannot pass -- to sum min and U1 + P2' to the sum of products -- cut to (sq_c + sq_q) / 2, which sum c_i q_i cannot pass --, and
 // screen_close<true, true> evaluates every statistic at both (screen_raw_box). The open pairs get their exact P1 / P2 from k_fold_exact_list.
+// A launch over a GROUP of blocks of 128 query rows (msc_tail_groups, msc_multi_plan.h): blockIdx.y is the block, and the arrays that are a block's own lie
+// that many strides behind the first block's. Added once at the kernel's head, wave-uniform (a wave's 64 queries lie in one block); every stride is 0 and
+// blockIdx.y is 0 in a launch over one block.
+__device__ __forceinline__ MscEpilogueArgs group_block_args(const MscEpilogueArgs& a_) {
+	MscEpilogueArgs a = a_;
+	const uint64_t g = blockIdx.y;
+	a.kb_min = reinterpret_cast<const int32_t*>(reinterpret_cast<const uint8_t*>(a.kb_min) + g * a.tg_min_stride);
+	if (a.kb_diff) a.kb_diff = reinterpret_cast<const int32_t*>(reinterpret_cast<const uint8_t*>(a.kb_diff) + g * a.tg_diff_stride);
+	a.kb_qT += g * a.tg_qt_stride;
+	a.close_soa += g * a.tg_flags_stride;
+	a.q_slots += g * a.tg_q_stride;
+	a.open_list += g * a.tg_list_stride;
+	a.emd_list += g * a.tg_list_stride;
+	a.open_words += g * a.tg_words_stride;
+	return a;
+}
+
 template <uint32_t kScreenChunk, bool kFold>
-__global__ void __launch_bounds__(kBlock, 4) k_pair_epilogue_bits_bound(const MscEpilogueArgs a) {
+__global__ void __launch_bounds__(kBlock, 4) k_pair_epilogue_bits_bound(const MscEpilogueArgs a_) {
+	const MscEpilogueArgs a = group_block_args(a_);
 	const uint32_t lane = threadIdx.x & 63;
 	const uint32_t groups = (a.n_queries + 63) / 64;
 	const uint32_t chunks = (a.m_per_query + kScreenChunk - 1) / kScreenChunk;
@@ -1677,7 +1695,8 @@ __global__ void __launch_bounds__(kBlock, 4) k_pair_epilogue_bits_bound(const Ms
 // Behind k_pair_epilogue_bits_bound and k_emd_ranks_list (msc_emd_list.hip): one thread per listed pair forms the pair's integer reductions as
 // k_pair_epilogue_bits_open does, takes the exact distance from emd_list and evaluates in FP64 (epilogue_eval writes the flag). Nothing to do
 // when the list overflowed. (96 registers, for the reason given at k_pair_epilogue_bits_open.)
-__global__ void __launch_bounds__(kBlock, 5) k_pair_epilogue_bits_list(const MscEpilogueArgs a) {
+__global__ void __launch_bounds__(kBlock, 5) k_pair_epilogue_bits_list(const MscEpilogueArgs a_) {
+	const MscEpilogueArgs a = group_block_args(a_);
 	if (a.open_words[1]) return;
 	const uint32_t n = a.open_words[0] < a.open_cap ? a.open_words[0] : a.open_cap;
 	const uint32_t ns = a.kb_slices;
@@ -2499,10 +2518,12 @@ hipError_t msc_launch_epilogue_bound(hipStream_t st, const MscEpilogueArgs& a) {
 		return hipErrorInvalidValue;
 	constexpr uint32_t chunk = 4;          // (as the screen of msc_launch_epilogue)
 	const uint64_t cw = (uint64_t)((a.m_per_query + chunk - 1) / chunk) * ((a.n_queries + 63) / 64);
+	const unsigned n_blocks = a.tg_blocks ? a.tg_blocks : 1;          // (a group of blocks: blockIdx.y)
+	if (n_blocks > 65535) return hipErrorInvalidValue;
 	if (a.fold_x_c || a.fold_x_q) {
 		if (!a.fold_x_c || !a.fold_x_q) return hipErrorInvalidValue;
-		hipLaunchKernelGGL((k_pair_epilogue_bits_bound<chunk, true>), dim3((unsigned)((cw + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, st, a);
-	} else hipLaunchKernelGGL((k_pair_epilogue_bits_bound<chunk, false>), dim3((unsigned)((cw + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, st, a);
+		hipLaunchKernelGGL((k_pair_epilogue_bits_bound<chunk, true>), dim3((unsigned)((cw + kWavesPerBlock - 1) / kWavesPerBlock), n_blocks), dim3(kBlock), 0, st, a);
+	} else hipLaunchKernelGGL((k_pair_epilogue_bits_bound<chunk, false>), dim3((unsigned)((cw + kWavesPerBlock - 1) / kWavesPerBlock), n_blocks), dim3(kBlock), 0, st, a);
 	return hipGetLastError();
 }
 
@@ -2510,8 +2531,11 @@ hipError_t msc_launch_epilogue_bound(hipStream_t st, const MscEpilogueArgs& a) {
 hipError_t msc_launch_epilogue_list(hipStream_t st, const MscEpilogueArgs& a, int num_cus) {
 	if (a.m == 0 || a.open_cap == 0) return hipSuccess;
 	if (!a.kb_min || !a.open_list || !a.open_words || !a.emd_list || !a.close_soa) return hipErrorInvalidValue;
-	const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)a.open_cap + kBlock - 1) / kBlock, (uint64_t)num_cus * 4);
-	hipLaunchKernelGGL(k_pair_epilogue_bits_list, dim3(grid), dim3(kBlock), 0, st, a);
+	// (a group of blocks: the grid of the group's TOTAL capacity, shared out over blockIdx.y)
+	const uint64_t n_blocks = a.tg_blocks ? a.tg_blocks : 1;
+	const uint64_t all = std::min<uint64_t>(n_blocks * (((uint64_t)a.open_cap + kBlock - 1) / kBlock), (uint64_t)num_cus * 4);
+	const unsigned grid = (unsigned)std::max<uint64_t>(1, (all + n_blocks - 1) / n_blocks);
+	hipLaunchKernelGGL(k_pair_epilogue_bits_list, dim3(grid, (unsigned)n_blocks), dim3(kBlock), 0, st, a);
 	return hipGetLastError();
 }
 
