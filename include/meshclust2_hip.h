@@ -170,7 +170,9 @@ int         msc_set_multi_div_cells(msc_ctx* ctx, int on);
 int         msc_set_emd_bounds(msc_ctx* ctx, int on);
 /* What the last msc_score_multi call did about the earth mover's distance of its close-flag blocks (those the switch above is about):
  * blocks = such blocks, dense_blocks = those whose every pair had its rank lists walked (switch off, a remembered model, sets of
- * different list pitch, an overflowed list), listed_pairs = pairs walked one by one from the lists of the others. Any pointer may be null. */
+ * different list pitch, an overflowed list), listed_pairs = pairs walked one by one from the lists of the others. A block whose candidates
+ * run in several chunks (one launch's scratch is capped) counts once PER CHUNK in blocks and dense_blocks: each chunk has a list of its own,
+ * 1/64 of the chunk's pairs, and overflows or not by itself; the rule that remembers a model counts chunks on both sides. Any pointer may be null. */
 int         msc_last_emd_walk(const msc_ctx* ctx, uint64_t* listed_pairs, uint64_t* dense_blocks, uint64_t* blocks);
 /* The blocks the switch above is about multiply presence bits of every pair of a block on the matrix cores to count its shared k-mers, which
  * all but the related pairs' flags do not need exactly. fold = 8, 16 or 32 (default 16; 0 at start with MSC_NO_FOLD in the environment): the

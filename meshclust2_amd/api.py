@@ -85,7 +85,7 @@ class Context:
 
     def last_emd_walk(self):
         """(listed_pairs, dense_blocks, blocks) of the last score_multi call: pairs whose rank lists were walked one by one, close-flag
-        blocks whose every pair was walked, and such blocks in all"""
+        blocks whose every pair was walked, and such blocks in all (a block whose candidates run in several chunks counts once per chunk)"""
         v = [C.c_uint64(0) for _ in range(3)]
         self.check(self.lib.msc_last_emd_walk(self.h, C.byref(v[0]), C.byref(v[1]), C.byref(v[2])))
         return tuple(int(x.value) for x in v)
