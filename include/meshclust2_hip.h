@@ -195,6 +195,14 @@ int         msc_last_tail_groups(const msc_ctx* ctx, uint64_t* groups, uint64_t*
 /* What the last msc_score_multi call did about it: the fold used (0: none), the blocks whose product was folded, and those of them that fell
  * back to the true product. Any pointer may be null. */
 int         msc_last_fold_screen(const msc_ctx* ctx, uint64_t* fold, uint64_t* folded_blocks, uint64_t* fell_back);
+/* A folded block decides most of its pairs without an evaluation: per query row an integer cut T(q) is PROVEN once per block (csrc/msc_fold_reject.h: for
+ * every candidate within the ranges of the candidates' set whose folded product output P1' + P2' is at most T(q), an upper bound of the model's sum
+ * lies below 0), and the screen evaluates only the waves that hold a pair above the cut or a row without one. on = 1 (default; 0 at start with
+ * MSC_NO_FOLD_REJECT in the environment). The flags are those of on = 0, pair for pair. */
+int         msc_set_fold_reject(msc_ctx* ctx, int on);
+/* What the last msc_score_multi call did about it: the pairs of its folded blocks the cut rejected, and the query rows of those blocks that got no cut.
+ * Any pointer may be null. */
+int         msc_last_fold_reject(const msc_ctx* ctx, uint64_t* rejected_pairs, uint64_t* rows_without_cut);
 /* The fold map: the folded bin of `bin` of a histogram of nbins = 4^k bins, bin mod (nbins / fold); fold a power of two (0, 1: bin). */
 uint64_t    msc_fold_bin(uint64_t bin, uint64_t nbins, uint32_t fold);
 /* A Q x M call over two SPARSE sets (msc_score_multi, msc_search_pairs) runs one 1 x M pass per query over the lists: the matrix-core

@@ -63,6 +63,8 @@ PROTOTYPES = {
     "msc_set_tail_groups": (_int, [_vp, _int]),
     "msc_last_tail_groups": (_int, [_vp, _pu64, _pu64]),
     "msc_last_fold_screen": (_int, [_vp, _pu64, _pu64, _pu64]),
+    "msc_set_fold_reject": (_int, [_vp, _int]),
+    "msc_last_fold_reject": (_int, [_vp, _pu64, _pu64]),
     "msc_fold_bin": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint32]),
     "msc_set_sparse_matrix_pass": (_int, [_vp, _int]),
     "msc_last_kernel_launches": (_int, [_vp]),

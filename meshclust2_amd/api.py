@@ -119,6 +119,18 @@ class Context:
         self.check(self.lib.msc_last_fold_screen(self.h, C.byref(v[0]), C.byref(v[1]), C.byref(v[2])))
         return tuple(int(x.value) for x in v)
 
+    def set_fold_reject(self, on):
+        """score_multi's folded blocks: an integer cut per query row, proven once per block, decides the pairs whose folded product output
+        lies under it without an evaluation (default), or every pair goes through the screen; the same flags"""
+        self.check(self.lib.msc_set_fold_reject(self.h, 1 if on else 0))
+
+    def last_fold_reject(self):
+        """(rejected_pairs, rows_without_cut) of the last score_multi call: the pairs of its folded blocks the cut rejected, and the query
+        rows of those blocks that got no cut"""
+        v = [C.c_uint64(0) for _ in range(2)]
+        self.check(self.lib.msc_last_fold_reject(self.h, C.byref(v[0]), C.byref(v[1])))
+        return tuple(int(x.value) for x in v)
+
     def set_sparse_matrix_pass(self, on):
         """score_multi / search_pairs over two sparse sets: the matrix-core route over mirrors built from the lists (on) or one 1 x M pass
         per query (default); identical results"""

@@ -123,6 +123,7 @@ extern "C" int msc_create(int device, msc_ctx** out) {
 	ctx->fold_screen = getenv("MSC_NO_FOLD") == nullptr ? 16 : 0;
 	ctx->query_groups = getenv("MSC_NO_QUERY_GROUPS") == nullptr ? 32 : 0;
 	ctx->tail_groups = getenv("MSC_NO_TAIL_GROUPS") == nullptr ? 8 : 0;
+	ctx->fold_reject = getenv("MSC_NO_FOLD_REJECT") == nullptr;
 	ctx->tail_ramp = getenv("MSC_TAIL_NO_RAMP") == nullptr;
 	*out = ctx;
 	return MSC_OK;
@@ -161,7 +162,7 @@ extern "C" void msc_destroy(msc_ctx* ctx) {
 	                  &ctx->seq_meta, &ctx->qslots_all, &ctx->shard_payload, &ctx->shard_hdrs, &ctx->rk_q, &ctx->rk_acc, &ctx->rk_counters,
 	                  &ctx->rk_tables, &ctx->rk_items, &ctx->rk_big, &ctx->pl_idx, &ctx->pl_sim, &ctx->pl_stage_idx, &ctx->pl_stage_sim, &ctx->pl_flags,
 	                  &ctx->pl_counts, &ctx->pl_offsets, &ctx->pl_seg, &ctx->pl_dst, &ctx->pl_qslots, &ctx->pl_win, &ctx->pl_qcount, &ctx->pl_words,
-	                  &ctx->emd_out, &ctx->open_list, &ctx->emd_list, &ctx->open_words, &ctx->fold_over, &ctx->close_counts, &ctx->rk_bad, &ctx->prof_nnz, &ctx->segs, &ctx->pair_seg, &ctx->dist, &ctx->sp_counts,
+	                  &ctx->emd_out, &ctx->open_list, &ctx->emd_list, &ctx->open_words, &ctx->fold_over, &ctx->reject_cut, &ctx->close_counts, &ctx->rk_bad, &ctx->prof_nnz, &ctx->segs, &ctx->pair_seg, &ctx->dist, &ctx->sp_counts,
 	                  &ctx->sp_cumbase, &ctx->sp_acc, &ctx->sp_chunk_off, &ctx->sp_chunk_cum, &ctx->sp_partials, &ctx->grp_pairs, &ctx->grp_self,
 	                  &ctx->tile_scratch, &ctx->reduce_parts, &ctx->sp_touched, &ctx->sp_acc_batch, &ctx->ps_idx, &ctx->ps_sim, &ctx->ps_m_idx, &ctx->ps_m_sim,
 	                  &ctx->pl_strand, &ctx->ps_off, &ctx->ps_only, &ctx->ps_counts, &ctx->align_text, &ctx->align_pairs, &ctx->align_out, &ctx->align_carry, &ctx->align_band_pairs,
@@ -239,6 +240,19 @@ extern "C" int msc_last_fold_screen(const msc_ctx* ctx, uint64_t* fold, uint64_t
 	if (fold) *fold = ctx->fold_used;
 	if (folded_blocks) *folded_blocks = ctx->fold_blocks;
 	if (fell_back) *fell_back = ctx->fold_fell_back;
+	return MSC_OK;
+}
+
+extern "C" int msc_set_fold_reject(msc_ctx* ctx, int on) {
+	if (!ctx) return MSC_ERR_INVALID_ARG;
+	ctx->fold_reject = on != 0;
+	return MSC_OK;
+}
+
+extern "C" int msc_last_fold_reject(const msc_ctx* ctx, uint64_t* rejected_pairs, uint64_t* rows_without_cut) {
+	if (!ctx) return MSC_ERR_INVALID_ARG;
+	if (rejected_pairs) *rejected_pairs = ctx->reject_pairs;
+	if (rows_without_cut) *rows_without_cut = ctx->reject_rows_none;
 	return MSC_OK;
 }
 

@@ -90,8 +90,9 @@ namespace {
 
 // ---- msc_score_multi: the call, its blocks, a route per block
 // ctx->open_words: {count, overflow} of a block's list of open pairs, then the call's three totals (pairs walked, blocks that overflowed, folded blocks
-// that fell back)
-constexpr size_t kOpenWordsBytes = 2 * sizeof(uint32_t) + 3 * sizeof(uint64_t);
+// that fell back), then the two words of the integer cut (msc_fold_reject.h): {pairs evaluated in rows with a cut, rows without a cut}
+constexpr size_t kOpenWordsBytes = 2 * sizeof(uint32_t) + 5 * sizeof(uint64_t);
+constexpr size_t kRejectWordsAt = 2 * sizeof(uint32_t) + 3 * sizeof(uint64_t);
 enum Route { R_MATRIX, R_DIGEST, R_RING, R_TILES, R_SPARSE_QUEUED, R_PER_QUERY };
 
 // what pick_route decides for one block
@@ -119,6 +120,7 @@ struct MultiCall {
 	bool mirrors_settled = false; // c_sp / q_sp, grp_dense and simple are what the older routes need (with cells: not before a block falls back)
 	bool grp_dense = false;       // the group passes read the dense slots
 	bool kb_fit = false;          // the matrix cores can take the call's blocks
+	bool reject = false;          // msc_set_fold_reject: the call's folded blocks may cut their rows (flags only, a model with an f32 image, every candidate slot holds a histogram)
 	bool simple = false;          // dense sets: a block of two or more runs on one of the Q x M kernels
 	uint64_t mc_ = 0, ms_ = 0;    // largest count / sum of either set
 	bool compact = false, excess16 = false;
@@ -936,6 +938,23 @@ int tail_bounds(MultiCall& c, Block& b, const MatrixBlock& p, const Chunk& k, ui
 	return MSC_OK;
 }
 
+// The integer cut of a folded tail's rows (msc_fold_reject.h), ahead of its screen: T for rows [q0, q0 + n_out) of the call -- those past n_rows get none --
+// into ctx->reject_cut, from the queries' records, moments, collisions and lists, the ranges of the candidates' set (run_matrix has brought them up to date on the
+// context's stream, ahead of the product this tail waits for) and the model. e: the screen's arguments, which take the cuts and the counter.
+int cut_rows(const MultiCall& c, hipStream_t tail, const uint32_t* dq_slots, uint64_t q0, uint32_t n_rows, uint32_t n_out, uint32_t mc, MscEpilogueArgs& e) {
+	msc_ctx* ctx = c.ctx;
+	const msc_hist_set *cands = c.cands, *qset = c.qset;
+	if (!c.reject || !cands->rj_ranges) return MSC_OK;
+	int32_t* out = (int32_t*)ctx->reject_cut.p + q0;
+	unsigned long long* words = (unsigned long long*)((uint8_t*)ctx->open_words.p + kRejectWordsAt);
+	const MscFoldRejectCut a{c.model->d, cands->rj_ranges, cands->L.nbins, cands->dtype, c.order, dq_slots, n_rows, n_out, qset->scalars, qset->scalar_stride, qset->rk_dev, qset->kbf_x,
+	                         qset->mb, qset->mb_n, qset->mb_pitch, out, words};
+	HIP_TRY(ctx, msc_launch_fold_reject_cut(tail, a));
+	e.fold_cut = out; e.fold_cut_words = words;
+	ctx->reject_seen += (uint64_t)n_rows * mc; ctx->reject_m = c.m;
+	return MSC_OK;
+}
+
 // The folded tail: the screen over intervals, the listed pairs' exact counts, their walk and FP64 evaluation. Should ITS list overflow -- every related pair is
 // on it, the lower bound of P1 being 0 --, k_emd_list_close raises the block's word of ctx->fold_over and rerun_overflowed, once the call's blocks are through,
 // scores the block again with the true product (no host wait here, and nothing queued for the case that did not arise)
@@ -946,6 +965,7 @@ int tail_folded(MultiCall& c, Block& b, const MatrixBlock& p, const Chunk& k, ui
 	if ((r = ensure_open_list(ctx, open_cap)) || (r = tail_ready(c, b, p, k, t))) return r;
 	MscEpilogueArgs ef = bound_args(c, t.ea, open_cap);
 	ef.kb_slices = p.slices_f; ef.fold_x_c = c.cands->kbf_x; ef.fold_x_q = c.qset->kbf_x;
+	if ((r = cut_rows(c, b.tail, b.dq_slots, b.q0, (uint32_t)b.nq, (uint32_t)b.nq, k.mc, ef))) return r;
 	if ((r = list_stage(c, b, p, k, ef, open_cap))) return r;
 	HIP_TRY(ctx, msc_launch_emd_list_close(b.tail, open_words, open_cap, (uint64_t*)(open_words + 2), (uint32_t*)ctx->fold_over.p + b.idx));
 	return MSC_OK;
@@ -1012,6 +1032,8 @@ int group_tail(MultiCall& c, const Block& b, const MatrixBlock& p, const Chunk& 
 	ea.tg_list_stride = T.list_stride; ea.tg_q_stride = 128; ea.tg_words_stride = (uint32_t)T.words_stride;
 	const MscListGroup lg{(uint32_t)T.n, 128, (uint32_t)T.words_stride, T.list_stride, G.qt_stride, T.min_stride, T.diff_stride};
 	const bool u16 = cands->ranks16 && qset->ranks16;
+	int r;
+	if ((r = cut_rows(c, tail, b0.dq_slots, b0.q0, (uint32_t)std::min<uint64_t>(T.n * 128, c.n_q - b0.q0), (uint32_t)(T.n * 128), k.mc, ea))) return r;
 	HIP_TRY(ctx, msc_launch_epilogue_bound(tail, ea));
 	const MscFoldExact fx{cands->ranks, cands->rk_pitch, L.nbins, L.E, L.R, k.d_slots, k.off, k.mc, b0.dq_slots, ea.open_list, words, open_cap, ea.kb_qT, p.rows,
 	                      qset->mb, qset->mb_n, qset->mb_pitch, (int32_t*)(base + T.min_off), ea.kb_slices, T.diff_stride ? (int32_t*)(base + T.diff_off) : nullptr};
@@ -1102,6 +1124,7 @@ int run_matrix(MultiCall& c, Block& b, const BlockRoute& rt, bool second_run = f
 	name_matrix_kernel(ctx, rows, rt.emd_ranks, c.cells, c.cands->sparse, p.st.fold);
 	ctx->last_query_tile = (int)b.nq;
 	if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev_all0, ctx->stream));
+	if (c.reject && p.st.fold && (r = ensure_reject_ranges(ctx, c.cands))) return r;          // (ahead of the product: the tail that reads them waits for it)
 	for (uint64_t off = 0; off < c.m; off += b.chunk)
 		if ((r = matrix_chunk(c, b, p, off))) return r;
 	return rt.queued ? MSC_OK : read_error_word(ctx);
@@ -1156,12 +1179,13 @@ int rerun_overflowed(MultiCall& c, const std::vector<BlockRoute>& route_of) {
 void clear_call_counters(msc_ctx* ctx) {
 	ctx->walk_listed = ctx->walk_dense = ctx->walk_blocks = ctx->walk_bound_blocks = ctx->fold_used = ctx->fold_blocks = ctx->fold_fell_back = 0;
 	ctx->tail_group_runs = ctx->tail_group_blocks = 0;
+	ctx->reject_seen = ctx->reject_m = ctx->reject_pairs = ctx->reject_rows_none = 0;
 }
 
 // ... and take the totals of the bound pass when the call is through (every stream of the call is idle: the error word has been read)
 int read_call_totals(msc_ctx* ctx, const msc_model* model) {
 	if (!ctx->walk_bound_blocks) return MSC_OK;
-	uint64_t totals[3] = {0, 0, 0};
+	uint64_t totals[5] = {0, 0, 0, 0, 0};          // (a folded block is a bound block: the cut's two words come home in the same copy)
 	const hipError_t e = hipMemcpy(totals, (const uint8_t*)ctx->open_words.p + 2 * sizeof(uint32_t), sizeof totals, hipMemcpyDeviceToHost);
 	if (e != hipSuccess) return fail(ctx, MSC_ERR_HIP, "copy of the pair list's totals failed: %s", hipGetErrorString(e));
 	ctx->walk_listed = totals[0];
@@ -1171,6 +1195,10 @@ int read_call_totals(msc_ctx* ctx, const msc_model* model) {
 	// ... nor, a model whose related pairs are too many for the list, the folded stage
 	ctx->fold_fell_back = totals[2];
 	if (totals[2] * 2 > ctx->fold_blocks) model->fold_overflows = true;
+	if (ctx->reject_seen) {          // msc_last_fold_reject: the pairs of the rows that had a cut, less those the screen evaluated all the same
+		ctx->reject_rows_none = totals[4];
+		ctx->reject_pairs = ctx->reject_seen - totals[4] * ctx->reject_m - totals[3];
+	}
 	return MSC_OK;
 }
 
@@ -1188,6 +1216,9 @@ int clear_call_words(MultiCall& c) {
 		const size_t over_bytes = ((n_q + 63) / 64 + 1) * sizeof(uint32_t);          // (a plan's blocks are of 64 queries or more, but for the last)
 		if ((r = ensure(ctx, ctx->fold_over, over_bytes))) return r;
 		HIP_TRY(ctx, hipMemsetAsync(ctx->fold_over.p, 0, over_bytes, ctx->stream));
+	}
+	if (c.reject) {          // the cut of every query row of the call (whole blocks of 128); its two counters are words of open_words, cleared above
+		if ((r = ensure(ctx, ctx->reject_cut, (n_q + 127) / 128 * 128 * sizeof(int32_t)))) return r;
 	}
 	if (c.close_out) {
 		if ((r = ensure(ctx, ctx->close_counts, n_q * sizeof(uint64_t)))) return r;
@@ -1225,6 +1256,7 @@ int score_multi(MultiCall& c) {
 		const bool flags_only = c.model && c.close_out && !c.sum_out && !c.csum_out && !c.raw_out && c.need_emd && !c.want_div && !c.want_grp;
 		if ((r = ensure_kb(ctx, cands, flags_only)) || (r = ensure_kb(ctx, qset, flags_only))) return r;
 		c.kb_fit = cands->kb && qset->kb && !cands->kb_has_zero && !qset->kb_has_zero;
+		c.reject = ctx->fold_reject && flags_only && c.kb_fit && c.model->h.screen_ok && reject_ranges_cover(cands, c.cand_slots, m);
 	}
 	c.cells = div_cells && c.kb_fit;
 	if ((r = clear_call_words(c))) return r;

@@ -61,6 +61,8 @@ int batch_div_pass(msc_ctx* ctx, const msc_hist_set* cands, const msc_hist_set* 
 int ensure_digest(msc_ctx* ctx, const msc_hist_set* set);      // the digest mirror of a dense set (set->digest null: unavailable)
 int ensure_kb(msc_ctx* ctx, const msc_hist_set* set, bool want_fold = false);          // the presence-bit mirror and lists of large bins of a set, from its bins or its lists (set->kb null: unavailable); want_fold: and its folded form
 int ensure_ranks(msc_ctx* ctx, const msc_hist_set* set);       // the ranks mirror, likewise (set->ranks null: unavailable)
+int ensure_reject_ranges(msc_ctx* ctx, const msc_hist_set* set);          // the ranges of the slots' scalars, moments and lists behind the cut of a folded block (set->rj_ranges null: unavailable)
+bool reject_ranges_cover(const msc_hist_set* set, const uint32_t* slots, uint64_t m);          // ... and whether they cover the m candidates of a call
 bool kb_route_fits(const msc_hist_set* cands, const msc_hist_set* qset, bool need_emd);          // host-side bounds of the matrix-core pass
 void mark_stale(msc_hist_set* s, uint64_t first, uint64_t n);  // slots [first, first + n) were written: the mirrors the set has are stale there
 void free_mirrors(const msc_hist_set* set);                    // msc_hist_set_destroy

@@ -161,6 +161,10 @@ struct MscEpilogueArgs {
 	// k_pair_epilogue_bits_bound on a FOLDED block (msc_fold.h): kb_min / kb_diff then hold P1' / P2' of the folded product, upper bounds of P1 / P2
 	// with each slot's own collisions added (fold_x_c: by candidate slot, fold_x_q: by query slot); null: the product was exact
 	const uint32_t *fold_x_c, *fold_x_q;
+	// ... and the integer cut of its rows (msc_fold_reject.h, k_fold_reject_cut): fold_cut[q] = T(q), or negative: none. A candidate whose P1' + P2' is at most
+	// the cut in every lane of a wave is "not close" without an evaluation. fold_cut_words[0] counts the pairs evaluated in rows that have a cut. null: no cuts
+	const int32_t* fold_cut;
+	unsigned long long* fold_cut_words;
 	// k_pair_epilogue_bits_bound / _list over a GROUP of blocks of 128 query rows (msc_tail_groups, msc_multi_plan.h): blockIdx.y is the block of the group,
 	// and its kb_min, kb_diff, kb_qT, close_soa (bytes), q_slots, open_list and emd_list (entries), open_words (words) lie that many strides behind the
 	// first block's; tg_blocks is their number, the launch's gridDim.y. All 0: a launch over one block
@@ -262,6 +266,19 @@ struct MscFoldExact {
 	int32_t* out_min; uint32_t slices; int32_t* out_diff;
 };
 hipError_t msc_launch_fold_exact_list(hipStream_t st, const MscFoldExact& a, int num_cus, const MscListGroup* grp = nullptr);
+// msc_fold_reject.hip: the ranges of a set's slots the cut's certificate reads (ten words in the order of MscRejectRanges, msc_fold_reject.h: atomic min / max
+// into what they hold), and the cut of every query row of a block or of a tail group's blocks: out[0 .. n_out), rows past n_rows without a cut;
+// words[1] += the rows without a cut (null: not counted)
+hipError_t msc_launch_fold_reject_ranges(hipStream_t st, const uint8_t* scalars, uint64_t scalar_stride, const void* mb, const uint32_t* mb_n, uint32_t pitch, const uint64_t* rk_dev,
+                                         uint64_t first, uint64_t n, uint64_t* ranges);
+struct MscFoldRejectCut {
+	const MscDevModel* model; const uint64_t* ranges; uint64_t nbins; int32_t dtype, order;
+	const uint32_t* q_slots; uint32_t n_rows, n_out;
+	const uint8_t* q_scalars; uint64_t q_scalar_stride; const uint64_t* q_rk_dev; const uint32_t* q_x;
+	const void* q_mb; const uint32_t* q_mb_n; uint32_t q_pitch;
+	int32_t* out; unsigned long long* words;
+};
+hipError_t msc_launch_fold_reject_cut(hipStream_t st, const MscFoldRejectCut& a);
 // the r04 form of that pass (msc_pair_gemm.hip): presence-bit mirror + lists of large bins, the queries' side of a block, the product
 uint64_t msc_kb_bytes(const MscLayout& L, uint64_t capacity);
 hipError_t msc_launch_kb_build(hipStream_t st, const MscLayout& L, int dtype, const uint8_t* bins, uint8_t* kb, uint64_t first_slot, uint64_t n_slots, void* mb,

@@ -8,6 +8,7 @@
 
 #include "msc_internal.h"
 #include "msc_fold.h"
+#include "msc_fold_reject.h"
 
 #include "msc_objects.h"
 #include "msc_api_private.h"
@@ -19,6 +20,7 @@ void mark_stale(msc_hist_set* s, uint64_t first, uint64_t n) {
 	if (s->sp_mirror) s->sm_stale.add(first, n);
 	if (s->kb) s->kb_stale.add(first, n);
 	if (s->ranks) s->rk_stale.add(first, n);
+	if (s->rj_ranges) s->rj_stale.add(first, n);
 }
 
 // the presence bits, the lists of large bins and the folded form beside them: freed together (ensure_kb, when one of them cannot be had)
@@ -39,6 +41,8 @@ void free_mirrors(const msc_hist_set* set) {
 	if (set->ranks16) (void)hipFree(set->ranks16);
 	if (set->rk_n) (void)hipFree(set->rk_n);
 	if (set->rk_sum) (void)hipFree(set->rk_sum);          // (rk_dev is its second half)
+	if (set->rj_ranges) (void)hipFree(set->rj_ranges);
+	set->rj_ranges = nullptr;
 	set->digest = nullptr; set->ranks = nullptr; set->ranks16 = nullptr; set->rk_n = nullptr; set->rk_sum = set->rk_dev = nullptr;
 }
 
@@ -183,6 +187,7 @@ int ensure_ranks(msc_ctx* ctx, const msc_hist_set* set) {
 		set->rk_n = (uint32_t*)pn;
 		set->rk_pitch = pitch;
 		set->rk_stale.all(set->capacity);
+		if (set->rj_ranges) set->rj_stale.all(set->capacity);          // (every slot's moment is taken again at the new pitch: the ranges behind the cut start over)
 		if (!set->rk_sum) {          // the two moments per slot (msc_emd_list.hip), built with the rows below; without them the close flags take the dense walk
 			void* pm = nullptr;
 			if (hipMalloc(&pm, 2 * sizeof(uint64_t) * set->capacity) != hipSuccess) (void)hipGetLastError();
@@ -235,6 +240,47 @@ int ensure_ranks(msc_ctx* ctx, const msc_hist_set* set) {
 		}
 	}
 	return MSC_OK;
+}
+
+// The ranges the cut of a folded block reads of its candidates (msc_fold_reject.h): minima and maxima of the scalar records' four, the largest second rank
+// moment and the largest sum of (e - 1) over a list of large bins, over the slots that hold a histogram -- beside the mirrors they are read from (the lists of
+// ensure_kb, the moments of ensure_ranks: both stand when this is called), once per range of slots written since. A slot written again adds its new values
+// to the ranges and its old ones stay: wider ranges certify less and never wrongly -- for the values of ONE ranks pitch. The moments depend on the pitch, so
+// when ensure_ranks lays the mirror out again it marks every slot stale here, and a stale range that covers the whole set starts the ranges from empty (which
+// also lets a set that once held an outlier have its cuts back after a full rewrite). MSC_OK with set->rj_ranges == nullptr when they cannot be had.
+int ensure_reject_ranges(msc_ctx* ctx, const msc_hist_set* set) {
+	if (!set->mb || !set->mb_n || !set->rk_dev) return MSC_OK;
+	if (!set->rj_ranges) {
+		void* p = nullptr;
+		if (hipMalloc(&p, sizeof(MscRejectRanges)) != hipSuccess) { (void)hipGetLastError(); return MSC_OK; }
+		set->rj_ranges = (uint64_t*)p;
+		set->rj_stale.all(set->capacity);
+	}
+	if (set->rj_stale.any()) {
+		if (set->rj_stale.lo == 0 && set->rj_stale.hi >= set->capacity) {
+			static const MscRejectRanges empty{~0ull, 0, ~0ull, 0, ~0ull, 0, ~0ull, 0, 0, 0};
+			HIP_TRY(ctx, hipMemcpyAsync(set->rj_ranges, &empty, sizeof empty, hipMemcpyHostToDevice, ctx->stream));
+		}
+		const uint64_t lo = set->rj_stale.lo, hi = std::min<uint64_t>(set->rj_stale.hi, set->sparse ? set->hdr_host.size() : set->written.size());
+		const int r = for_each_run(lo, hi, [&](uint64_t i) { return set->sparse ? set->hdr_host[i].nnz != 0 : set->written[i] != 0; }, [&](uint64_t first, uint64_t n) {
+			HIP_TRY(ctx, msc_launch_fold_reject_ranges(ctx->stream, set->scalars, set->scalar_stride, set->mb, set->mb_n, set->mb_pitch, set->rk_dev, first, n, set->rj_ranges));
+			return (int)MSC_OK;
+		});
+		if (r) return r;
+		set->rj_stale.clear();
+	}
+	return MSC_OK;
+}
+
+// whether every one of the m candidates of a call (slots, or 0 .. m - 1) holds a histogram: the ranges above cover no other slot
+bool reject_ranges_cover(const msc_hist_set* set, const uint32_t* slots, uint64_t m) {
+	if (!set->sparse && !slots) {          // slots 0 .. m - 1 of a dense set: the leading run of written slots only grows, so it is walked once
+		while (set->written_run < set->written.size() && set->written[set->written_run]) set->written_run++;
+		return m <= set->written_run;
+	}
+	auto holds = [&](uint64_t i) { return set->sparse ? i < set->hdr_host.size() && set->hdr_host[i].nnz != 0 : i < set->written.size() && set->written[i] != 0; };
+	for (uint64_t i = 0; i < m; i++) if (!holds(slots ? slots[i] : i)) return false;
+	return true;
 }
 
 // Whether the pass on the matrix cores (msc_pair_gemm.hip) can take a Q x M call over these sets -- host-side bounds only: dense 8/16/32-bit

@@ -141,6 +141,12 @@ struct msc_ctx {
 	// fold, its blocks whose product was folded, and those of them whose list overflowed (scored again with the true product)
 	uint32_t fold_screen = 16;
 	uint64_t fold_used = 0, fold_blocks = 0, fold_fell_back = 0;
+	// msc_set_fold_reject / MSC_NO_FOLD_REJECT (msc_fold_reject.h): the integer cut of a folded block's rows. reject_cut: T per query row of the call in progress;
+	// its two counters {pairs evaluated in rows with a cut, rows without a cut} are the last words of open_words, on the device until the call ends; reject_seen: the pairs of the folded
+	// blocks that ran with cuts; msc_last_fold_reject: the last call's pairs the cut rejected and rows without a cut
+	bool fold_reject = true;
+	DevBuf reject_cut;
+	uint64_t reject_seen = 0, reject_m = 0, reject_pairs = 0, reject_rows_none = 0;          // (reject_m: the candidates of the call)
 	msc_hist_set* shard_gather = nullptr;
 	// msc_align_pairs (msc_align.hip): the sequences of a call, its sorted pair records, the three result arrays, and the carry columns of the pairs
 	// too long for LDS
@@ -224,6 +230,11 @@ struct msc_hist_set {
 	mutable uint64_t rk_pitch = 0;
 	mutable StaleRange rk_stale;
 	mutable bool ranks_unavailable = false;
+	// the ranges the cut of a folded block reads of its candidates (msc_fold_reject.h, MscRejectRanges: ten words on the device), over every slot the
+	// mirrors have been built for; rj_stale: the slots written since (ensure_reject_ranges, msc_mirrors.hip). They only widen, until every slot is stale: then they start over
+	mutable uint64_t* rj_ranges = nullptr;
+	mutable StaleRange rj_stale;
+	mutable uint64_t written_run = 0;          // dense sets: slots [0, written_run) are known to hold a histogram (reject_ranges_cover; `written` is never cleared)
 	// ... and their 16-bit form (rank - floor(t * 4^k / pitch) + 32768; msc_emd_ranks.hip, k_emd_ranks16), kept while every slot's reduced
 	// ranks fit and the pitch is a multiple of 1 024; rk16_off: a slot did not fit (or the allocation failed): the 32-bit walk stays
 	mutable uint16_t* ranks16 = nullptr;

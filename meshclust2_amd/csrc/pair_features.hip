@@ -1596,6 +1596,7 @@ __device__ __forceinline__ MscEpilogueArgs group_block_args(const MscEpilogueArg
 	a.open_list += g * a.tg_list_stride;
 	a.emd_list += g * a.tg_list_stride;
 	a.open_words += g * a.tg_words_stride;
+	if (a.fold_cut) a.fold_cut += g * a.tg_q_stride;
 	return a;
 }
 
@@ -1618,6 +1619,10 @@ __global__ void __launch_bounds__(kBlock, 4) k_pair_epilogue_bits_bound(const Ms
 	const uint32_t ns = a.kb_slices;
 	uint32_t x_q = 0;
 	if constexpr (kFold) x_q = a.fold_x_q[q_slot];
+	// the row's integer cut (msc_fold_reject.h): negative = none; a lane past the block's rows never keeps a candidate
+	int32_t cut = -1;
+	uint32_t kept = 0;          // pairs evaluated in rows that have a cut (wave-uniform)
+	if constexpr (kFold) if (a.fold_cut) cut = live ? a.fold_cut[qq] : 0x7fffffff;
 	uint32_t fl[4] = {0, 0, 0, 0};
 	auto totals_of = [&](uint32_t ci, int64_t min_e, int64_t diff_e, Side& cand, PairTotals& t, PairTotals& t1) {
 		const uint32_t slot_rel = a.cand_slots ? a.cand_slots[ci] : ci;
@@ -1658,6 +1663,14 @@ __global__ void __launch_bounds__(kBlock, 4) k_pair_epilogue_bits_bound(const Ms
 #pragma unroll
 		for (uint32_t j = 0; j < 4; j++) {
 			if (j0 + j >= nc) break;
+			if constexpr (kFold) {
+				// P1' + P2' at most the cut in every lane: "not close" is proven for the whole wave's pairs, the flag bytes stay 0 -- no candidate record,
+				// no list walk, no evaluation. Any other candidate runs the code below for the whole wave, its verdicts what they always were
+				if (a.fold_cut) {
+					if (!__ballot(cut < 0 || min4[j] + diff4[j] > (int64_t)cut)) continue;
+					kept += (uint32_t)__popcll(__ballot(live && cut >= 0));
+				}
+			}
 			Side cand;
 			PairTotals t{0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.f}, t1;
 			totals_of(c0 + j0 + j, min4[j], diff4[j], cand, t, t1);
@@ -1686,6 +1699,7 @@ __global__ void __launch_bounds__(kBlock, 4) k_pair_epilogue_bits_bound(const Ms
 			}
 		}
 	}
+	if constexpr (kFold) if (kept && lane == 0) atomicAdd(a.fold_cut_words, (unsigned long long)kept);          // (one add per wave that evaluated anything under a cut: the few that hold a related pair)
 	if (!live) return;
 	uint8_t* row = a.close_soa + (uint64_t)q * a.m_per_query + c0;
 	if (kScreenChunk == 4 && nc == kScreenChunk && ((uintptr_t)row & 3) == 0) *reinterpret_cast<uint32_t*>(row) = fl[0];

@@ -49,6 +49,8 @@ public:
 	// the queries' side of up to cap consecutive full blocks of a Q x M call in one set of launches (0, 1: block by block; identical results)
 	void set_query_groups(int cap) { check(msc_set_query_groups(h_, cap)); }
 	void set_tail_groups(int cap) { check(msc_set_tail_groups(h_, cap)); }
+	// a folded block's rows get an integer cut: pairs whose folded product output lies under it are "not close" without an evaluation (identical flags)
+	void set_fold_reject(bool on) { check(msc_set_fold_reject(h_, on ? 1 : 0)); }
 	// Q x M calls over two sparse sets on the matrix-core route, mirrors built from their lists (identical results)
 	void set_sparse_matrix_pass(bool on) { check(msc_set_sparse_matrix_pass(h_, on ? 1 : 0)); }
 	void check(int rc) const { if (rc != MSC_OK) throw Error(rc, msc_last_error(h_)); }
